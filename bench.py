@@ -10,16 +10,26 @@ configs[1], "C2"): 8 scenes per GPU, 4 StreetView views @512 px + aerial tile,
 pose samples x 8 retries.  Scenes are independent: N GPUs = N ranks, each with its
 own 8-scene batch, no data-path collective ("weak" scaling).
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings),
-including ``roofline`` (dominant kernel, HIP-event timed inside the timed region)
-and ``cpu_baseline`` (the numpy oracle timed on the host cores on a bounded sample).
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings).  A plain run
+sets up, warms up, times the K steps, writes ``--dump-outputs DIR`` if asked and prints the
+line.  ``--full`` adds everything else: ``roofline`` and ``kernels`` (HIP events around every
+launch of the last timed step, which then runs alone), the short extra legs (one batch at a
+time, f32_exact, volume_materialized, train_c3, train_c3_fp16, c4, c5) and ``cpu_baseline``
+(the numpy oracle timed on the host cores).
+
+``--dump-outputs DIR`` writes what the last timed step returned as ``DIR/<name>.npy`` (float32,
+or float64 for float64 / 32- and 64-bit integer outputs; a fixed, seeded sample of the larger
+ones, at most 64 MB in all) plus ``DIR/manifest.json`` (shape, dtype and sampling of each).
 """
 import argparse
 import contextlib
+import dataclasses
 import json
 import os
+import re
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -220,6 +230,69 @@ def _sync(device):
     torch.cuda.synchronize()
 
 
+DUMP_BYTES = 60 * 1000 * 1000      # (the .npy files; 64 MB with headers and manifest to spare)
+DUMP_ELEMS = 1 << 20               # elements kept of one output before it is sampled
+
+
+def _output_leaves(tree, name=''):
+  """(name, tensor) of every array in an output pytree, names sorted.  A lazy feature volume that
+  was never read contributes its mask only: reading ``features`` would run the unfused chain."""
+  from snap_amd.models import types
+  sub = (lambda k: f'{name}.{k}' if name else str(k))
+  if isinstance(tree, torch.Tensor):
+    yield name, tree
+  elif isinstance(tree, (bool, int, float, np.ndarray, np.generic)):
+    yield name, torch.as_tensor(np.asarray(tree))
+  elif isinstance(tree, dict):
+    for k in sorted(tree, key=str):
+      yield from _output_leaves(tree[k], sub(k))
+  elif isinstance(tree, (list, tuple)):
+    for k, v in enumerate(tree):
+      yield from _output_leaves(v, sub(k))
+  elif isinstance(tree, types.LazyFeatureVolume):
+    if tree.materialized:
+      yield from _output_leaves(tree.features, sub('features'))
+    yield from _output_leaves(tree.valid, sub('valid'))
+  elif dataclasses.is_dataclass(tree):
+    for f in dataclasses.fields(tree):
+      yield from _output_leaves(getattr(tree, f.name), sub(f.name))
+  elif hasattr(tree, '_fields'):     # (utils.geometry structs: Transform2D, Camera, ...)
+    for k in tree._fields:
+      yield from _output_leaves(getattr(tree, k), sub(k))
+
+
+def dump_outputs(tree, out_dir):
+  """Write the arrays of `tree` as out_dir/<name>.npy: float64 for float64 and 32 / 64-bit integer
+  tensors (exact), float32 otherwise.  An output of more than DUMP_ELEMS elements is replaced by the
+  elements at a fixed sample of flat indices (seeded by its name and size, sorted, drawn with
+  replacement), so that two builds given the same arguments write comparable files."""
+  leaves = [(n, t) for n, t in _output_leaves(tree) if t.numel() > 0]
+  wide = (torch.float64, torch.int32, torch.int64)
+  cap = DUMP_ELEMS
+  while cap > 1 and sum(min(t.numel(), cap) * (8 if t.dtype in wide else 4) for _, t in leaves) > DUMP_BYTES:
+    cap //= 2
+  os.makedirs(out_dir, exist_ok=True)
+  manifest = {}
+  for name, t in leaves:
+    fname = re.sub(r'[^A-Za-z0-9_.+-]', '_', name) or 'output'
+    entry = {'shape': list(t.shape), 'dtype': str(t.dtype).replace('torch.', '')}
+    flat = t.detach().reshape(-1)
+    if flat.numel() > cap:
+      seed = zlib.crc32(f'{name}:{flat.numel()}'.encode())
+      g = torch.Generator(device='cpu').manual_seed(seed)
+      idx = torch.randint(0, flat.numel(), (cap,), generator=g).sort().values
+      flat = flat[idx.to(flat.device)]
+      entry['sample'] = {'elements': cap, 'seed': seed,
+                         'index': 'sorted torch.randint(0, numel, (elements,)) of a CPU generator seeded with seed'}
+    arr = flat.cpu().to(torch.float64 if t.dtype in wide else torch.float32).numpy()
+    if 'sample' not in entry:
+      arr = arr.reshape(tuple(t.shape))
+    np.save(os.path.join(out_dir, fname + '.npy'), arr)
+    manifest[fname] = entry
+  with open(os.path.join(out_dir, 'manifest.json'), 'w') as f:
+    json.dump(manifest, f, indent=1)
+
+
 def cpu_baseline_full_scene(cfg, meta, workload):
   """The numpy oracle on ONE WHOLE scene of the workload, end to end (encoders, lift, fusion MLP,
   pooling, fusion, similarity, scoring of all P hypotheses): no extrapolation.  ~23 s on the 256
@@ -369,10 +442,17 @@ def main(argv=None, emit=True):
   ap.add_argument('--warmup', type=int, default=5)
   ap.add_argument('--workload', default='c2', choices=sorted(WORKLOADS))
   ap.add_argument('--device', default='cuda')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
-  ap.add_argument('--dump', default=None, help='write the per-launch HIP-event timings of the profiled step (JSON)')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure what the headline does not need: per-kernel HIP-event times of the last timed '
+                       'step and the roofline figures, the extra legs and the CPU baseline')
+  ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                  help='after the timed steps, write what the last one returned as DIR/<name>.npy (+ manifest.json)')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+  ap.add_argument('--dump', default=None,
+                  help='write the per-launch HIP-event timings of the profiled step (JSON; profiles the last step '
+                       'without --full too)')
   ap.add_argument('--no-extra-legs', action='store_true',
-                  help='skip the short extra legs (f32_exact, volume_materialized, train_c3, c4, c5)')
+                  help='--full: skip the short extra legs (f32_exact, volume_materialized, train_c3, c4, c5)')
   ap.add_argument('--dist-backend', default=None,
                   help='testing only: override the process-group backend (default nccl = RCCL)')
   ap.add_argument('--share-gpu', action='store_true',
@@ -512,6 +592,8 @@ def main(argv=None, emit=True):
   ring = pipeline.BatchesInFlight(nfl, device)
   preds = [None] * nfl
   digests = []
+  dump = args.dump or os.environ.get('SNAP_BENCH_DUMP')
+  profile = use_cuda and rank == 0 and (args.full or bool(dump))
 
   def run_step(slot, i, mark=None):
     with ring.slot(slot):
@@ -541,7 +623,7 @@ def main(argv=None, emit=True):
                        # (tools/host_time_probe2.py: the same on an idle GPU = the pure enqueue cost, C2 7.4 ms, C5 8.4, C4 0.44)
   for i in range(args.steps):
     th0 = time.perf_counter()
-    if use_cuda and rank == 0 and i == args.steps - 1:
+    if profile and i == args.steps - 1:
       if nfl > 1:
         torch.cuda.synchronize(device)  # the profiled step runs ALONE (its events time single launches)
       prof = ops.KernelProfiler()   # HIP events around every launch of the last step
@@ -567,6 +649,8 @@ def main(argv=None, emit=True):
   elapsed = time.perf_counter() - t0
   gc.enable()
   pred = preds[(args.steps - 1) % nfl]
+  if args.dump_outputs and rank == 0:
+    dump_outputs(pred if args.mode == 'infer' else {'logs': pred, 'params': state.params}, args.dump_outputs)
   # (N batches in flight: a mark is a step's START on its own stream; the period of a stream / N is
   #  the per-step time while N batches share the GPU -- the drained last step is left out)
   if nfl == 1:
@@ -753,11 +837,10 @@ def main(argv=None, emit=True):
               'kernel': 'exhaustive_voting', 'bound': 'hbm', 'achieved': round(gbs, 1), 'peak': PEAK_HBM_GBS,
               'unit': 'GB/s', 'frac': round(gbs / PEAK_HBM_GBS, 5), 'algorithmic_bytes': c4_algo['voting_bytes'],
               'note': 'algorithmic bytes of SURVEY 8(d); only a frequency-domain formulation is HBM-bound'}
-      dump = args.dump or os.environ.get('SNAP_BENCH_DUMP')
       if dump:
         with open(dump, 'w') as f:
           json.dump({n: prof.launches(n) for n in summ}, f)
-    if (args.mode == 'infer' and not is_c4 and use_cuda and world == 1 and not args.no_extra_legs
+    if (args.full and args.mode == 'infer' and not is_c4 and use_cuda and world == 1 and not args.no_extra_legs
         and args.math == 'bf16x3' and not args.materialize_volume):
       # The headline configuration is the split-bf16 engine without the dense feature volume.  The
       # same workload in the two reference-shaped configurations, timed here (short legs, same
@@ -823,7 +906,7 @@ def main(argv=None, emit=True):
         torch.cuda.empty_cache()
         t1 = time.perf_counter()
         try:
-          r = main(leg_args + ['--no-cpu-baseline', '--no-extra-legs'], emit=False)
+          r = main(leg_args + ['--full', '--no-cpu-baseline', '--no-extra-legs'], emit=False)
           out[key] = {
               'ms_per_step': r['ms_per_step'], 'scenes_per_sec': r['value'], 'metric': r['metric'],
               'steps': r['steps'], 'warmup': r['warmup'], 'dtype': r['dtype'],
@@ -843,7 +926,7 @@ def main(argv=None, emit=True):
         os.environ['SNAP_BENCH_DUMP'] = dump_env
     if args.mode == 'train':
       out['train_logs'] = {k: (round(v, 6) if isinstance(v, float) else v) for k, v in last_logs.items()}
-    if (world == 1 and not args.no_cpu_baseline and not WORKLOADS[args.workload]['tiny']
+    if (args.full and world == 1 and not args.no_cpu_baseline and not WORKLOADS[args.workload]['tiny']
         and not WORKLOADS[args.workload].get('vit') and args.mode == 'infer' and not is_c4):
       try:
         # a whole scene where the host is big enough to finish it in ~20-30 s (the GPU box: 256

@@ -1,14 +1,15 @@
 #!/bin/bash
 # Tuning experiments: bench under env-knob variants; prints conv time per variant.
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+O=${OUT_DIR:-gpu_results}   # output folder, relative to the repository root
+mkdir -p $O
 for v in "$@"; do
-  env $v timeout 600 python bench.py --steps 6 --warmup 2 --no-cpu-baseline > gpurun_out/exp.log 2>&1
-  python - "$v" <<'PY'
+  env $v timeout 600 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $O/exp.log 2>&1
+  python - "$v" "$O/exp.log" <<'PY'
 import json, sys
-line = [l for l in open('gpurun_out/exp.log') if l.startswith('{')]
+line = [l for l in open(sys.argv[2]) if l.startswith('{')]
 if not line:
-    print(sys.argv[1], 'FAILED'); print(open('gpurun_out/exp.log').read()[-800:])
+    print(sys.argv[1], 'FAILED'); print(open(sys.argv[2]).read()[-800:])
 else:
     r = json.loads(line[-1])
     k = r['kernels']

@@ -8,7 +8,7 @@ export TMPDIR=/tmp PYTHONPATH=.
 timeout 1500 python -m pytest tests -m gpu -q -x 2>&1 | tail -30 > $O/tests.log
 cat $O/tests.log | tail -15
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 | tee $O/smoke.log
-timeout 900 python bench.py > $O/bench_c2.log 2>$O/bench_c2.err
+timeout 900 python bench.py --full > $O/bench_c2.log 2>$O/bench_c2.err
 tail -1 $O/bench_c2.log > $O/r05_c2_bench.json
 python - <<'PY'
 import json

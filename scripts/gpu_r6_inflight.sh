@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp PYTHONPATH=.
 O=gpurun_out/r6if; rm -rf $O; mkdir -p $O
 timeout 600 python -m pytest tests/test_gpu_model.py -m gpu -q -x -k "in_flight or evaluator" 2>&1 | tail -4
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python - <<PY
 import json
 d=json.loads(open('$O/bench_default.json').read().strip().splitlines()[-1])

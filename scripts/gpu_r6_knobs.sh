@@ -4,7 +4,7 @@ set -u
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp PYTHONPATH=.
 O=gpurun_out/r6kn; rm -rf $O; mkdir -p $O
-run() { tag=$1; shift; timeout 300 python bench.py --no-cpu-baseline --no-extra-legs --steps 30 --warmup 3 "$@" 2> $O/$tag.err | tail -1 > $O/$tag.json; python - <<PY
+run() { tag=$1; shift; timeout 300 python bench.py --full --no-cpu-baseline --no-extra-legs --steps 30 --warmup 3 "$@" 2> $O/$tag.err | tail -1 > $O/$tag.json; python - <<PY
 import json
 try:
     d=json.loads(open('$O/$tag.json').read())

@@ -11,7 +11,7 @@ cat $O/tests.log
 for rep in 1 2; do
 for lib in "" ${ALTS:-snap_amd/lib/alt_vfold/libsnap_hip.so}; do
   echo "== lib=${lib:-default}"
-  SNAP_HIP_LIB=${lib:+$PWD/$lib} timeout 300 python bench.py --workload c4 --steps 12 --warmup 3 --digest 2>/dev/null | tail -1 | python -c "
+  SNAP_HIP_LIB=${lib:+$PWD/$lib} timeout 300 python bench.py --full --workload c4 --steps 12 --warmup 3 --digest 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], (d.get('step_digests') or [None])[0], {n:round(v['ms'],3) for n,v in d.get('kernels',{}).items()})"
 done; done 2>&1 | tee $O/ab.log

@@ -7,13 +7,13 @@ rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 R=$PWD
 # 1. bench lines (the default engine with the CPU baseline; the other two engines without)
-SNAP_BENCH_DUMP=$O/launches_bf16x3.json timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_bf16x3.log 2>&1
+SNAP_BENCH_DUMP=$O/launches_bf16x3.json timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_bf16x3.log 2>&1
 tail -1 $O/bench_bf16x3.log > $O/r02_c2_bench_bf16x3.json
 for m in bf16x6 f32; do
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --math $m 2>/dev/null | tail -1 > $O/r02_c2_bench_$m.json
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --math $m 2>/dev/null | tail -1 > $O/r02_c2_bench_$m.json
 done
 # (the default engine with the dense feature volume written: the unfused MLP -> fill -> pool chain)
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --materialize-volume 2>/dev/null | tail -1 > $O/r02_c2_bench_bf16x3_volume.json
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --materialize-volume 2>/dev/null | tail -1 > $O/r02_c2_bench_bf16x3_volume.json
 # 2. rocprofv3 kernel stats of the same command
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof" -o snap -- \
   python "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline) > $O/prof.log 2>&1
@@ -42,7 +42,7 @@ json.dump(a, open('$O/r02_c2_pmc_summary.json', 'w'), indent=1)
 PY
 # 5. C4 (eval path) on the f32 and the default engine + kernel stats
 for m in f32 bf16x3; do
-  timeout 300 python bench.py --workload c4 --steps 5 --warmup 2 --math $m 2>/dev/null | tail -1 > $O/r02_c4_bench_$m.json
+  timeout 300 python bench.py --full --workload c4 --steps 5 --warmup 2 --math $m 2>/dev/null | tail -1 > $O/r02_c4_bench_$m.json
 done
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_c4" -o snap -- \
   python "$R/bench.py" --workload c4 --steps 2 --warmup 1) > $O/prof_c4.log 2>&1
@@ -51,10 +51,10 @@ cp $O/prof_c4/snap_kernel_stats.csv $O/r02_c4_kernel_stats.csv 2>/dev/null
 timeout 400 python tools/fullsize_parity.py --math f32,bf16x6,bf16x3,bf16x3+plane --out $O/r02_c2_fullsize_parity.json > $O/parity.log 2>&1
 timeout 400 python tools/fullsize_parity.py --math bf16x3+plane --eval --out $O/r02_c2_fullsize_parity_eval.json > $O/parity_eval.log 2>&1
 # 7. training step (C3) and the ViT workload (C5)
-timeout 300 python bench.py --mode train --workload c3 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r02_c3_train_bench.json
-timeout 300 python bench.py --mode train --workload c3 --precision bf16 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r02_c3_train_bf16_bench.json
-timeout 300 python bench.py --mode train --workload c3 --precision bf16x3 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r02_c3_train_bf16x3_bench.json
-timeout 300 python bench.py --workload c5 --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/r02_c5_vit_bench.json
+timeout 300 python bench.py --full --mode train --workload c3 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r02_c3_train_bench.json
+timeout 300 python bench.py --full --mode train --workload c3 --precision bf16 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r02_c3_train_bf16_bench.json
+timeout 300 python bench.py --full --mode train --workload c3 --precision bf16x3 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r02_c3_train_bf16x3_bench.json
+timeout 300 python bench.py --full --workload c5 --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/r02_c5_vit_bench.json
 rm -rf $O/prof $O/prof_c4 $O/pmcs1 $O/pmcs2 $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE
 ls -la $O
 head -c 600 $O/r02_c2_bench_bf16x3.json; echo

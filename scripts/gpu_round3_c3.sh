@@ -6,8 +6,8 @@ O=gpurun_out/r03p
 mkdir -p $O
 export TMPDIR=/tmp PYTHONPATH=.
 R=$PWD
-timeout 300 python bench.py --mode train --workload c3 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r03_c3_train_bench.json
-SNAP_BENCH_DUMP=$O/r03_c3_train_bf16_launches.json timeout 300 python bench.py --mode train --workload c3 --precision bf16 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r03_c3_train_bf16_bench.json
+timeout 300 python bench.py --full --mode train --workload c3 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r03_c3_train_bench.json
+SNAP_BENCH_DUMP=$O/r03_c3_train_bf16_launches.json timeout 300 python bench.py --full --mode train --workload c3 --precision bf16 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r03_c3_train_bf16_bench.json
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_c3" -o snap -- \
   python "$R/bench.py" --mode train --workload c3 --precision bf16 --steps 3 --warmup 1) > $O/prof_c3.log 2>&1
 cp $O/prof_c3/snap_kernel_stats.csv $O/r03_c3_train_bf16_kernel_stats.csv 2>/dev/null

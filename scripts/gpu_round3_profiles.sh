@@ -7,7 +7,7 @@ rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp PYTHONPATH=.
 R=$PWD
 # 1. the headline line exactly as the driver runs it (default flags: CPU baseline + the two extra legs)
-SNAP_BENCH_DUMP=$O/r03_c2_launches.json timeout 900 python bench.py > $O/bench_c2.log 2>&1
+SNAP_BENCH_DUMP=$O/r03_c2_launches.json timeout 900 python bench.py --full > $O/bench_c2.log 2>&1
 tail -1 $O/bench_c2.log > $O/r03_c2_bench.json
 # 2. rocprofv3 kernel stats of the same workload (1 warm-up + 3 timed steps, no extra legs)
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof" -o snap -- \
@@ -39,18 +39,18 @@ except Exception as e:
   print('pmc summary failed', e)
 PY
 # 5. C4 (eval path): the pre-split GEMM engine behind the exhaustive voting + kernel stats
-SNAP_BENCH_DUMP=$O/r03_c4_launches.json timeout 300 python bench.py --workload c4 --steps 5 --warmup 2 2>/dev/null | tail -1 > $O/r03_c4_bench.json
-timeout 300 python bench.py --workload c4 --steps 5 --warmup 2 --math f32 2>/dev/null | tail -1 > $O/r03_c4_bench_f32.json
+SNAP_BENCH_DUMP=$O/r03_c4_launches.json timeout 300 python bench.py --full --workload c4 --steps 5 --warmup 2 2>/dev/null | tail -1 > $O/r03_c4_bench.json
+timeout 300 python bench.py --full --workload c4 --steps 5 --warmup 2 --math f32 2>/dev/null | tail -1 > $O/r03_c4_bench_f32.json
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_c4" -o snap -- \
   python "$R/bench.py" --workload c4 --steps 2 --warmup 1) > $O/prof_c4.log 2>&1
 cp $O/prof_c4/snap_kernel_stats.csv $O/r03_c4_kernel_stats.csv 2>/dev/null
 # 6. training step (C3): f32 / bf16 lines, kernel stats of the bf16 step
-timeout 300 python bench.py --mode train --workload c3 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r03_c3_train_bench.json
-SNAP_BENCH_DUMP=$O/r03_c3_train_bf16_launches.json timeout 300 python bench.py --mode train --workload c3 --precision bf16 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r03_c3_train_bf16_bench.json
+timeout 300 python bench.py --full --mode train --workload c3 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r03_c3_train_bench.json
+SNAP_BENCH_DUMP=$O/r03_c3_train_bf16_launches.json timeout 300 python bench.py --full --mode train --workload c3 --precision bf16 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r03_c3_train_bf16_bench.json
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_c3" -o snap -- \
   python "$R/bench.py" --mode train --workload c3 --precision bf16 --steps 3 --warmup 1) > $O/prof_c3.log 2>&1
 cp $O/prof_c3/snap_kernel_stats.csv $O/r03_c3_train_bf16_kernel_stats.csv 2>/dev/null
-timeout 300 python bench.py --workload c5 --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/r03_c5_vit_bench.json
+timeout 300 python bench.py --full --workload c5 --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/r03_c5_vit_bench.json
 # 7. unit benches: the row-stationary 1x1 kernel against the tiled body, the pre-split GEMM shapes
 timeout 200 python tools/rs_bench.py > $O/r03_rs_bench.jsonl 2>/dev/null
 timeout 300 python tools/ps_gemm_bench.py > $O/r03_ps_gemm_bench.log 2>&1

@@ -24,7 +24,7 @@ SNAP_GIT_HEAD=${SNAP_GIT_HEAD:-unknown} python tools/make_hbm_traffic.py $O/pmc_
 # 1. the headline line exactly as the driver runs it (default flags: CPU baseline + the extra legs), AFTER the
 #    traffic record of these sources exists (bench.py reads profiles/r06_c2_hbm_traffic.json: traffic_stale false)
 cp $O/r06_c2_hbm_traffic.json profiles/r06_c2_hbm_traffic.json 2>/dev/null
-SNAP_BENCH_DUMP=$O/r06_c2_launches.json timeout 900 python bench.py > $O/bench_c2.log 2>&1
+SNAP_BENCH_DUMP=$O/r06_c2_launches.json timeout 900 python bench.py --full > $O/bench_c2.log 2>&1
 tail -1 $O/bench_c2.log > $O/r06_c2_bench.json
 # 4. utilisation counters
 i=0
@@ -46,20 +46,20 @@ except Exception as e:
   print('pmc summary failed', e)
 PY
 # 5. C4 (eval path): the pre-split GEMM engine behind the exhaustive voting + kernel stats
-SNAP_BENCH_DUMP=$O/r06_c4_launches.json timeout 300 python bench.py --workload c4 --steps 12 --warmup 2 2>/dev/null | tail -1 > $O/r06_c4_bench.json
-timeout 300 python bench.py --workload c4 --steps 12 --warmup 2 --in-flight 1 2>/dev/null | tail -1 > $O/r06_c4_bench_one_at_a_time.json
-timeout 300 python bench.py --workload c4 --steps 5 --warmup 2 --voting direct 2>/dev/null | tail -1 > $O/r06_c4_bench_direct.json
+SNAP_BENCH_DUMP=$O/r06_c4_launches.json timeout 300 python bench.py --full --workload c4 --steps 12 --warmup 2 2>/dev/null | tail -1 > $O/r06_c4_bench.json
+timeout 300 python bench.py --full --workload c4 --steps 12 --warmup 2 --in-flight 1 2>/dev/null | tail -1 > $O/r06_c4_bench_one_at_a_time.json
+timeout 300 python bench.py --full --workload c4 --steps 5 --warmup 2 --voting direct 2>/dev/null | tail -1 > $O/r06_c4_bench_direct.json
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_c4" -o snap -- \
   python "$R/bench.py" --workload c4 --steps 2 --warmup 1 --in-flight 1) > $O/prof_c4.log 2>&1
 cp $O/prof_c4/snap_kernel_stats.csv $O/r06_c4_kernel_stats.csv 2>/dev/null
 # 6. training step (C3): f32 / bf16 lines, kernel stats of the bf16 step
-timeout 300 python bench.py --mode train --workload c3 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r06_c3_train_bench.json
-SNAP_BENCH_DUMP=$O/r06_c3_train_bf16_launches.json timeout 300 python bench.py --mode train --workload c3 --precision bf16 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r06_c3_train_bf16_bench.json
+timeout 300 python bench.py --full --mode train --workload c3 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r06_c3_train_bench.json
+SNAP_BENCH_DUMP=$O/r06_c3_train_bf16_launches.json timeout 300 python bench.py --full --mode train --workload c3 --precision bf16 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r06_c3_train_bf16_bench.json
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_c3" -o snap -- \
   python "$R/bench.py" --mode train --workload c3 --precision bf16 --steps 3 --warmup 1) > $O/prof_c3.log 2>&1
 cp $O/prof_c3/snap_kernel_stats.csv $O/r06_c3_train_bf16_kernel_stats.csv 2>/dev/null
-timeout 300 python bench.py --workload c5 --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/r06_c5_vit_bench.json
-timeout 300 python bench.py --mode train --workload c3 --precision fp16 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r06_c3_train_fp16_bench.json
+timeout 300 python bench.py --full --workload c5 --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/r06_c5_vit_bench.json
+timeout 300 python bench.py --full --mode train --workload c3 --precision fp16 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/r06_c3_train_fp16_bench.json
 python tools/family_table.py $O/r06_c3_train_bf16_launches.json > $O/r06_c3_train_bf16_layers.txt 2>&1
 timeout 200 python tools/wgrad_bench.py 2>/dev/null | tail -1 > $O/r06_wgrad_bench.json
 # 7. the operand path's own ceiling (global -> LDS by LDS-DMA, no compute): tools/lds_dma_probe.hip
