@@ -292,6 +292,39 @@ int snap_interpolate_nd_f32(const float* array, const int32_t* size, int32_t n, 
                             float* values, uint8_t* valid, void* stream);
 int snap_expectation_nd_f32(const float* pdf, int64_t rows, const int32_t* size, int32_t n,
                             float* out, void* stream);
+/* OccupancyNet query path (snap/models/occupancy_net.py).  Point source: rays when `hits` is
+ * non-NULL -- hits / origins [B, num_rays, 3], ray_mask [B, num_rays] -- sampled as
+ * sample_queries_from_rays (:34-60): P = num_samples * num_rays points per scene, element
+ * k * num_rays + n, k = 0 the hit (label 1), k >= 1 origin + linspace(0, 1, S - 1)[k - 1] * dir with
+ * dir = (hit - origin) * (|d| - margin) / max(|d|, 1) (label 0); otherwise explicit `points`
+ * [B, num_points, 3] (data['occupancy_queries'], :91-105).  out_points [B, P, 3], out_labels /
+ * out_ray_valid [B, P] are optional (NULL: not written).  The volume is [B, X, Y, Z, D] with an
+ * optional volume_valid [B, X, Y, Z]; each point is sampled as interpolate_nd(volume,
+ * point / cell_size, volume_valid) (:107-111, grids.py:116-137), bitwise the arithmetic of
+ * snap_interpolate_nd_f32.
+ * snap_occupancy_ray_features_f32 -> features [B * P, D], valid [B * P]. */
+int snap_occupancy_ray_features_f32(const float* hits, const float* origins, const uint8_t* ray_mask,
+                                    int64_t num_rays, int32_t num_samples, float margin, const float* points,
+                                    int64_t num_points, int32_t B, const float* volume,
+                                    const uint8_t* volume_valid, int32_t X, int32_t Y, int32_t Z, int32_t D,
+                                    float cell_size, float* out_points, uint8_t* out_labels,
+                                    uint8_t* out_ray_valid, float* features, uint8_t* valid, void* stream);
+/* 1 when snap_occupancy_head_f32 takes D -> h1 [-> h2] -> 1 (every width a multiple of 32, at most
+ * 256; h2 = 0: one hidden layer), else 0: the caller runs the producer + the Dense engine. */
+int32_t snap_occupancy_head_supported(int32_t D, int32_t h1, int32_t h2);
+/* The whole query chain of occupancy_net.py:84-116 in one launch: samples -> trilinear gather ->
+ * MLP(occupancy_mlp) (layers.py:55-78: Dense + ReLU between layers, kernels [in, out]) -> logits
+ * [B * P] (the last Dense's only column, before the sigmoid) and valid [B * P].  Hidden layers on
+ * the exact f32 MFMA (k-ordered accumulation, bias-then-ReLU epilogue: the f32 Dense engine's
+ * arithmetic class); the width-1 layer as a fixed-order dot product per row.  No per-point
+ * intermediate reaches memory; no atomics (bitwise repeatable). */
+int snap_occupancy_head_f32(const float* hits, const float* origins, const uint8_t* ray_mask, int64_t num_rays,
+                            int32_t num_samples, float margin, const float* points, int64_t num_points, int32_t B,
+                            const float* volume, const uint8_t* volume_valid, int32_t X, int32_t Y, int32_t Z,
+                            int32_t D, float cell_size, const float* w0, const float* b0, int32_t h1,
+                            const float* w1, const float* b1, int32_t h2, const float* w_out,
+                            const float* b_out, float* out_points, uint8_t* out_labels, uint8_t* out_ray_valid,
+                            float* logits, uint8_t* valid, void* stream);
 
 /* Semantic-raster embedding (snap/models/semantic_raster_encoder.py:63-79).  rasters [M, N]
  * uint8 (bool); idx_road / idx_other: HOST arrays with the raster channels of the mutually

@@ -91,6 +91,13 @@ SIGNATURES = {
     'snap_presplit_f32': (c_int, [ptr, c_i64, c_int, ptr, ptr]),
     'snap_interpolate_nd_f32': (c_int, [ptr, ptr, c_int, c_int, ptr, ptr, c_i64, ptr, ptr, ptr]),
     'snap_expectation_nd_f32': (c_int, [ptr, c_i64, ptr, c_int, ptr, ptr]),
+    'snap_occupancy_ray_features_f32': (
+        c_int, [ptr, ptr, ptr, c_i64, c_int, c_float, ptr, c_i64, c_int, ptr, ptr, c_int, c_int, c_int, c_int,
+                c_float, ptr, ptr, ptr, ptr, ptr, ptr]),
+    'snap_occupancy_head_supported': (c_int, [c_int, c_int, c_int]),
+    'snap_occupancy_head_f32': (
+        c_int, [ptr, ptr, ptr, c_i64, c_int, c_float, ptr, c_i64, c_int, ptr, ptr, c_int, c_int, c_int, c_int,
+                c_float, ptr, ptr, c_int, ptr, ptr, c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
     'snap_semantic_embed_f32': (
         c_int, [ptr, c_i64, c_int, ptr, c_int, ptr, c_int, ptr, ptr, c_int, ptr, ptr]),
     'snap_semantic_onehot_f32': (c_int, [ptr, c_i64, c_int, ptr, c_int, ptr, c_int, ptr, c_int, ptr]),
@@ -340,7 +347,7 @@ SIGNATURES = {
     ),
 }
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _lib = None
 

@@ -153,6 +153,16 @@ def bev_mapper(
   return cfg.lock()
 
 
+def occupancy_net() -> ConfigDict:
+  """defaults.py:273-283."""
+  predictor = mlp()
+  predictor.layers = (128, 1)
+  return ConfigDict(
+      num_samples_per_ray=100, ray_margin=0.2, streetview_encoder=streetview_encoder(),
+      occupancy_mlp=predictor,
+  ).lock()
+
+
 def semantic_net() -> ConfigDict:
   """defaults.py:286-342."""
   return ConfigDict(

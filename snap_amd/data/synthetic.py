@@ -41,9 +41,13 @@ SURFEL_ROAD_CLASSES = ('crosswalk', 'sidewalk', 'pavedroad', 'stopline', 'line',
 def make_batch(
     batch_size, grid: grids.Grid3D, num_views, image_size, query_image_size=None,
     seed=0, device='cpu', with_aerial=True, with_gt=True, k_radial=0.0,
-    semantic_classes=None,
+    semantic_classes=None, lidar_rays=None,
 ):
-  """Returns a batch dict: map / query scenes + planted T_query2map."""
+  """Returns a batch dict: map / query scenes + planted T_query2map.
+
+  ``lidar_rays=N`` adds ``map['lidar_rays'] = {points, origins, mask}`` ([B, N, 3] x 2, [B, N]: the
+  padded ray schema of loader.py:63-79,101-103), drawn from a generator of its own: every other
+  field is bit-identical with and without it (see ``_lidar_rays``)."""
   rng = np.random.default_rng(seed)
   B, V = batch_size, num_views
   H, W = image_size
@@ -81,6 +85,10 @@ def make_batch(
         sem[..., i] = pick == k
     map_scene.setdefault('rasters', {})['semantics'] = torch.as_tensor(sem).to(device)
 
+  if lidar_rays:
+    map_scene['lidar_rays'] = {k: (t(v) if v.dtype != bool else torch.as_tensor(v).to(device))
+                               for k, v in _lidar_rays(seed, t_map, ext, int(lidar_rays)).items()}
+
   # query: one view at the origin of its gravity-aligned frame, looking along +y.
   R_q = _yaw_camera_rotation(np.full((B, 1), np.pi / 2))
   t_q = np.stack(
@@ -107,6 +115,47 @@ def make_batch(
     tg = np.stack([tx, ty, np.zeros(B)], -1)
     batch['T_query2map'] = geometry.Transform3D(t(Rg), t(tg))
   return batch
+
+
+def _ray_box_t(o, d, lo, hi):
+  """Entry distance of rays o + t d into the axis-aligned box [lo, hi] (inf: missed)."""
+  with np.errstate(divide='ignore', invalid='ignore'):
+    inv = 1.0 / d
+    t0 = (lo - o) * inv
+    t1 = (hi - o) * inv
+  tmin = np.nanmax(np.minimum(t0, t1), -1)
+  tmax = np.nanmin(np.maximum(t0, t1), -1)
+  hit = (tmax >= np.maximum(tmin, 0)) & (tmin > 0)
+  return np.where(hit, tmin, np.inf)
+
+
+def _lidar_rays(seed, t_map, ext, N, ground_z=0.4, max_range=40.0, pad_fraction=0.1):
+  """Lidar rays of a scene with planted geometry: a ground plane at ``ground_z`` and three boxes
+  standing on it.  Origins are jittered map-camera centres; a ray hits the nearest surface, or
+  ends at ``max_range`` (upward rays, long shots: hits outside the grid).  About ``pad_fraction``
+  of the rays are padding (mask False, zeros), as the loader pads to a fixed count."""
+  lrng = np.random.default_rng(seed + 1931)     # own stream: the other fields stay unchanged
+  B, V = t_map.shape[:2]
+  cam = lrng.integers(0, V, (B, N))
+  origins = t_map[np.arange(B)[:, None], cam] + lrng.normal(0.0, 0.1, (B, N, 3))
+  az = lrng.uniform(0, 2 * np.pi, (B, N))
+  el = lrng.uniform(-0.6, 0.15, (B, N))
+  d = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], -1)
+  with np.errstate(divide='ignore'):
+    t_hit = np.where(d[..., 2] < 0, (ground_z - origins[..., 2]) / d[..., 2], np.inf)
+  for b in range(B):
+    for _ in range(3):
+      c = lrng.uniform(0.15, 0.85, 2) * ext[:2]
+      half = lrng.uniform(0.5, 1.5, 2)
+      lo = np.array([c[0] - half[0], c[1] - half[1], ground_z])
+      hi = np.array([c[0] + half[0], c[1] + half[1], ground_z + lrng.uniform(1.0, 4.0)])
+      t_hit[b] = np.minimum(t_hit[b], _ray_box_t(origins[b], d[b], lo, hi))
+  t_hit = np.minimum(t_hit, max_range)
+  points = origins + t_hit[..., None] * d
+  mask = lrng.random((B, N)) >= pad_fraction
+  points = np.where(mask[..., None], points, 0.0).astype(np.float32)
+  origins = np.where(mask[..., None], origins, 0.0).astype(np.float32)
+  return {'points': points, 'origins': origins, 'mask': mask}
 
 
 def meta_data(cell_size=0.2, grid_size=(24, 32, 12), hfov_deg=72.0):

@@ -1,7 +1,9 @@
 """Top-level register of models (``snap/models/__init__.py:25-40``).
 
 The localisation model is the hot path; ``semantic_net`` reuses its
-BEV mapper; ``occupancy_net`` of the reference is out of scope.
+BEV mapper; ``occupancy_net`` is built (``snap_amd.models.occupancy_net.OccupancyNetModel``: the
+StreetView encoder + the fused lidar-ray query kernel of occupancy.hip) but not yet listed here --
+import it from its module.
 """
 import importlib
 

@@ -95,3 +95,28 @@ class FeatureImagePyramid:
 
   def replace(self, **kw):
     return dataclasses.replace(self, **kw)
+
+
+@dataclasses.dataclass
+class LidarRaySamples:
+  """Query points sampled along lidar rays [..., P, 3] with their labels (True = the hit) and the
+  validity of the ray they come from (``snap/models/types.py``, occupancy_net.py:34-60)."""
+
+  points: Any
+  labels: Any
+  valid: Any
+
+  def replace(self, **kw):
+    return dataclasses.replace(self, **kw)
+
+
+@dataclasses.dataclass
+class OccupancySamples:
+  """Per-point occupancy: ``values`` = sigmoid(``logits``), ``valid`` = interpolation validity."""
+
+  values: Any
+  valid: Any
+  logits: Any
+
+  def replace(self, **kw):
+    return dataclasses.replace(self, **kw)

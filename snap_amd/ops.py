@@ -1902,6 +1902,117 @@ def interpolate_nd(array, points, valid_array=None):
   return values, valid
 
 
+def _occupancy_source(volume, volume_valid, rays, points, num_samples, margin):
+  """Shared checks of the two occupancy entry points -> (C arguments of the source + volume, B, P)."""
+  _f32(volume, 'volume')
+  if volume.dim() != 5:
+    raise ValueError(f'occupancy: volume must be [B, X, Y, Z, D], got {tuple(volume.shape)}')
+  B, X, Y, Z, D = (int(v) for v in volume.shape)
+  if volume_valid is not None:
+    _mask(volume_valid, 'volume_valid')
+    if tuple(volume_valid.shape) != (B, X, Y, Z):
+      raise ValueError(f'occupancy: volume_valid {tuple(volume_valid.shape)} vs volume {tuple(volume.shape)}')
+  if (rays is None) == (points is None):
+    raise ValueError('occupancy: give exactly one of rays=(hits, origins, mask) and points')
+  if rays is not None:
+    hits, origins, mask = rays
+    _f32(hits, 'hits'); _f32(origins, 'origins'); _mask(mask, 'ray mask')
+    if hits.dim() != 3 or hits.shape[0] != B or hits.shape[2] != 3 or origins.shape != hits.shape:
+      raise ValueError(f'occupancy: hits / origins must be [B={B}, N, 3], got {tuple(hits.shape)} / '
+                       f'{tuple(origins.shape)}')
+    N = int(hits.shape[1])
+    if tuple(mask.shape) != (B, N):
+      raise ValueError(f'occupancy: ray mask must be [B, N] = {(B, N)}, got {tuple(mask.shape)}')
+    S = int(num_samples)
+    if S < 1 or N < 1:
+      raise ValueError('occupancy: num_samples and the ray count must be positive')
+    src = [_p(hits), _p(origins), _p(mask), N, S, float(margin), None, 0]
+    P = S * N
+  else:
+    _f32(points, 'points')
+    if points.dim() != 3 or points.shape[0] != B or points.shape[2] != 3 or points.shape[1] < 1:
+      raise ValueError(f'occupancy: points must be [B={B}, Q, 3], got {tuple(points.shape)}')
+    P = int(points.shape[1])
+    src = [None, None, None, 0, 1, 0.0, _p(points), P]
+  return src + [B, _p(volume), _p(volume_valid), X, Y, Z, D], B, P, D
+
+
+def occupancy_ray_features(volume, volume_valid, cell_size, *, rays=None, points=None, num_samples=1,
+                           margin=0.0, want_samples=True):
+  """occupancy_net.py:34-60,107-111 up to the MLP: the query points of each scene -- rays=(hits
+  [B, N, 3], origins [B, N, 3], mask [B, N]) sampled into P = num_samples * N points (k * N + n order),
+  or explicit points [B, P, 3] -- interpolated in volume [B, X, Y, Z, D] at point / cell_size.
+  Returns (features [B * P, D], valid [B, P], samples) with samples = (points [B, P, 3], labels
+  [B, P], ray_valid [B, P]) for rays and want_samples, else None."""
+  lib = _lib.load()
+  args, B, P, D = _occupancy_source(volume, volume_valid, rays, points, num_samples, margin)
+  dev = volume.device
+  features = torch.empty((B * P, D), dtype=torch.float32, device=dev)
+  valid = torch.empty((B, P), dtype=torch.bool, device=dev)
+  samples = None
+  if rays is not None and want_samples:
+    samples = (torch.empty((B, P, 3), dtype=torch.float32, device=dev),
+               torch.empty((B, P), dtype=torch.bool, device=dev), torch.empty((B, P), dtype=torch.bool, device=dev))
+  sp = (None, None, None) if samples is None else tuple(_p(t) for t in samples)
+  with _region('occupancy_features', 0.0, 4.0 * B * P * D * 9):
+    st = lib.snap_occupancy_ray_features_f32(*args, float(cell_size), *sp, _p(features), _p(valid), _stream())
+  _lib.check(st, 'snap_occupancy_ray_features_f32')
+  return features, valid, samples
+
+
+def occupancy_head_supported(D, hidden):
+  """True when ``occupancy_head`` takes D -> hidden... -> 1 (one or two hidden widths)."""
+  hidden = tuple(int(h) for h in hidden)
+  if len(hidden) not in (1, 2):
+    return False
+  return bool(_lib.load().snap_occupancy_head_supported(int(D), hidden[0], hidden[1] if len(hidden) == 2 else 0))
+
+
+def occupancy_head(volume, volume_valid, cell_size, mlp_params, *, rays=None, points=None, num_samples=1,
+                   margin=0.0, want_samples=True):
+  """The fused query chain of occupancy_net.py:84-116 (samples -> trilinear gather -> MLP) in one launch.
+  mlp_params: [(kernel [in, out], bias [out]), ...] of MLP(occupancy_mlp), one or two hidden layers and a
+  width-1 last layer (``occupancy_head_supported``).  Returns (logits [B, P], valid [B, P], samples) as
+  ``occupancy_ray_features``.  Exact f32 arithmetic (the f32 Dense engine's class; within 2e-6 of its
+  chain, not bitwise)."""
+  lib = _lib.load()
+  args, B, P, D = _occupancy_source(volume, volume_valid, rays, points, num_samples, margin)
+  layers_ = list(mlp_params)
+  if len(layers_) not in (2, 3):
+    raise ValueError('occupancy_head: one or two hidden layers and a width-1 output layer')
+  widths = []
+  d_in = D
+  for i, (k, b) in enumerate(layers_):
+    _f32(k, f'kernel {i}'); _f32(b, f'bias {i}')
+    if k.dim() != 2 or k.shape[0] != d_in or b.shape != (k.shape[1],):
+      raise ValueError(f'occupancy_head: layer {i} kernel {tuple(k.shape)} / bias {tuple(b.shape)} after width {d_in}')
+    d_in = int(k.shape[1])
+    widths.append(d_in)
+  if widths[-1] != 1:
+    raise ValueError('occupancy_head: the last layer must have width 1')
+  if not occupancy_head_supported(D, widths[:-1]):
+    raise ValueError(f'occupancy_head: shape D={D}, hidden={tuple(widths[:-1])} not supported '
+                     '(see occupancy_head_supported)')
+  h1 = widths[0]
+  h2 = widths[1] if len(widths) == 3 else 0
+  (w0, b0), (w1, b1) = layers_[0], (layers_[1] if h2 else (None, None))
+  wo, bo = layers_[-1]
+  dev = volume.device
+  logits = torch.empty((B, P), dtype=torch.float32, device=dev)
+  valid = torch.empty((B, P), dtype=torch.bool, device=dev)
+  samples = None
+  if rays is not None and want_samples:
+    samples = (torch.empty((B, P, 3), dtype=torch.float32, device=dev),
+               torch.empty((B, P), dtype=torch.bool, device=dev), torch.empty((B, P), dtype=torch.bool, device=dev))
+  sp = (None, None, None) if samples is None else tuple(_p(t) for t in samples)
+  flops = 2.0 * B * P * (D * h1 + (h1 * h2 + h2 if h2 else h1))
+  with _region('occupancy_head', flops, 4.0 * B * P * 2):
+    st = lib.snap_occupancy_head_f32(*args, float(cell_size), _p(w0), _p(b0), h1, _p(w1), _p(b1), h2, _p(wo),
+                                     _p(bo), *sp, _p(logits), _p(valid), _stream())
+  _lib.check(st, 'snap_occupancy_head_f32')
+  return logits, valid, samples
+
+
 def expectation_nd(pdf, extent):
   """pdf [..., *extent] -> expected (fractional) index [..., n] (grids.py:148-153)."""
   lib = _lib.load()

@@ -10,6 +10,7 @@ driver calls.  One process per GPU; the exchange goes through ``snap_amd.dist``
 """
 import dataclasses
 import math
+import re
 from typing import Any, Callable, Dict, List, Optional
 
 import torch
@@ -194,7 +195,7 @@ def _global_norm(tensors):
 
 
 def train_step(state: TrainState, batch, *, model, lr_fn: Callable, max_grad_norm=None,
-               group=None, debug=False, overlap_allreduce=True, precision=None):
+               group=None, debug=False, overlap_allreduce=True, precision=None, freeze_params_reg_exp=None):
   """One optimisation step.  Returns (state, metrics, training_logs).
 
   precision: None (the reference's behaviour: the arithmetic is the MODEL's -- ``model.engine``, chosen
@@ -215,9 +216,25 @@ def train_step(state: TrainState, batch, *, model, lr_fn: Callable, max_grad_nor
 
   With more than one rank and ``overlap_allreduce`` the gradient buckets are all-reduced
   while the backward pass is still running (``dist.OverlappedGradReducer``); otherwise one
-  bucketed all-reduce follows the backward pass.  Same averaged gradients either way."""
+  bucketed all-reduce follows the backward pass.  Same averaged gradients either way.
+
+  freeze_params_reg_exp: the reference's ``optimizer_configs.freeze_params_reg_exp`` (train_occupancy.py:29:
+  ``'streetview_encoder/'``).  A leaf whose '/'-joined name (``dist.flatten_tree``) matches it
+  (``re.search``) is frozen: it is not given requires_grad, has no gradient, takes no part in the all-reduce,
+  ``l2_grads`` or the clip norm, and Adam touches neither it nor its m / v (bitwise unchanged).  Departure from
+  the reference: there a frozen leaf still gets a gradient, which enters ``l2_grads`` and the clip norm; only
+  its update is dropped (train_occupancy sets no max_grad_norm).  None: every leaf trains (as before)."""
   named = flatten_params(state.params)
   leaves = [t for _, t in named]
+  m_tr, v_tr = state.m, state.v
+  if freeze_params_reg_exp is not None:
+    pattern = re.compile(freeze_params_reg_exp)
+    keep = [i for i, (n, _) in enumerate(named) if not pattern.search(n)]
+    for i, t in enumerate(leaves):
+      t.requires_grad_(False)
+      t.grad = None
+    leaves = [leaves[i] for i in keep]
+    m_tr, v_tr = [state.m[i] for i in keep], [state.v[i] for i in keep]
   for t in leaves:
     t.requires_grad_(True)
     t.grad = None
@@ -258,26 +275,27 @@ def train_step(state: TrainState, batch, *, model, lr_fn: Callable, max_grad_nor
   logs['learning_rate'] = lr
   fin_t = sdist.all_finite_tensor(grads, group).to(torch.float32).reshape(())
   gnorm_t = _global_norm(grads).reshape(())
-  device_skip = _fusable(leaves, grads, state.m, state.v)
+  device_skip = _fusable(leaves, grads, m_tr, v_tr)
   if device_skip:
     # ONE host transfer per step, at its end: the update kernel itself reads the finite flag on the
     # device and applies nothing when a gradient is non-finite (the reference does the same inside
     # the traced step, trainer.py:269-276) -- the host need not know before it launches it
     with torch.no_grad():
-      _adam_update_(leaves, grads, state.m, state.v, state.opt_count + 1, lr, apply_flag=fin_t)
+      _adam_update_(leaves, grads, m_tr, v_tr, state.opt_count + 1, lr, apply_flag=fin_t)
     is_fin = None
   else:
     head = torch.stack([fin_t.to(torch.float64), gnorm_t]).cpu()
     is_fin = bool(head[0] > 0)
     if is_fin:                                           # otherwise: skip the update
       with torch.no_grad():
-        _adam_update_(leaves, grads, state.m, state.v, state.opt_count + 1, lr)
+        _adam_update_(leaves, grads, m_tr, v_tr, state.opt_count + 1, lr)
+  all_leaves = [t for _, t in named]
   with torch.no_grad():
     per_example = {k: v.detach() for k, v in metrics.items()}      # (stacked per dtype and widened once by the reduce)
     for k, v in losses.items():
       per_example[f'loss/{k}'] = v.detach()
     keys, means = sdist.reduce_batch_metrics_tensor(per_example, batch['batch_mask'], group)
-    tail = torch.cat([torch.stack([_global_norm(leaves).reshape(()), loss.detach().to(torch.float64).reshape(()),
+    tail = torch.cat([torch.stack([_global_norm(all_leaves).reshape(()), loss.detach().to(torch.float64).reshape(()),
                                    fin_t.to(torch.float64), gnorm_t.to(torch.float64)]),
                       means.to(torch.float64)]).cpu().tolist()
   if is_fin is None:
