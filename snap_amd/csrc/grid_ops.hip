@@ -42,7 +42,10 @@ __global__ __launch_bounds__(256) void interpolate_nd_kernel(const InterpArgs a)
     const float whi = c - lo;
     w[t][0] = 1.f - whi;
     w[t][1] = whi;
-    const int il = (int)lo;
+    // lo is clamped to [-1, size] BEFORE the conversion: a float-to-int conversion out of range is
+    // undefined, and with il = INT_MAX (lo = +inf, 1e30) the compiler's rewrite of the clamp below,
+    // min(max(il, -1) + 1, size - 1), wrapped to INT_MIN: an out-of-bounds tap.  NaN -> -1 (fmaxf).
+    const int il = (int)fminf(fmaxf(lo, -1.f), (float)a.size[t]);
     idx[t][0] = min(max(il, 0), a.size[t] - 1);
     idx[t][1] = min(max(il + 1, 0), a.size[t] - 1);
   }

@@ -107,7 +107,10 @@ __device__ __forceinline__ void occ_taps(const OccArgs& a, const float xyz[3], i
     const float whi = c - lo;
     w[t][0] = 1.f - whi;
     w[t][1] = whi;
-    const int il = (int)lo;
+    // lo is clamped to [-1, size] BEFORE the conversion: a float-to-int conversion out of range is
+    // undefined, and with il = INT_MAX (lo = +inf, 1e30) the compiler's rewrite of the clamp below,
+    // min(max(il, -1) + 1, size - 1), wrapped to INT_MIN: an out-of-bounds tap.  NaN -> -1 (fmaxf).
+    const int il = (int)fminf(fmaxf(lo, -1.f), (float)size[t]);
     idx[t][0] = min(max(il, 0), size[t] - 1);
     idx[t][1] = min(max(il + 1, 0), size[t] - 1);
   }

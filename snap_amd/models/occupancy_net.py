@@ -137,7 +137,9 @@ class OccupancyNet(base.Module):
     cell = float(self.grid.cell_size)
     p = params['mlp_out']
     mlp = [(p[f'Dense_{i}']['kernel'], p[f'Dense_{i}']['bias']) for i in range(len(self.hidden) + 1)]
-    if self.use_fused_head(params):
+    # (the fused head reads the volume in 16-byte taps: a contiguous view at an unaligned offset, which
+    # .contiguous() leaves as it is, takes the producer, which has a scalar kernel for it)
+    if self.use_fused_head(params) and features.data_ptr() % 16 == 0:
       logits, valid, samples = ops.occupancy_head(features, vvalid, cell, mlp, **kw)
     else:
       feats, valid, samples = ops.occupancy_ray_features(features, vvalid, cell, **kw)

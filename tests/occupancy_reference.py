@@ -6,6 +6,10 @@ Composed from the numpy oracle -- ``oracle.lift.streetview_encoder``, ``oracle.g
 restatement of occupancy.hip's point arithmetic (same f32 expressions, no contraction): the kernel's
 sample points must equal it bitwise.  ``occupancy_ray_features`` / ``occupancy_head`` /
 ``occupancy_head_supported`` are numpy twins of the ``snap_amd.ops`` entry points for CPU tests.
+
+``fmaf32`` / ``gather_f32`` / ``head_f32`` restate the rest of occupancy.hip EXACTLY: the build has no
+contraction (every f32 expression is one IEEE operation) and the f32 MFMA is a k-ordered ``fmaf`` chain
+from its C input, so the fused head's logits are reproduced bit for bit on the host.
 """
 import numpy as np
 import torch
@@ -41,6 +45,112 @@ def sample_rays_f32(hits, origins, mask, num_samples, margin):
   labels = np.broadcast_to(labels.reshape(S * N), (*lead, S * N)).copy()
   valid = np.broadcast_to(np.asarray(mask, bool)[..., None, :], (*lead, S, N)).reshape(*lead, S * N).copy()
   return points, labels, valid
+
+
+def fmaf32(a, b, c):
+  """Vectorised f32 fused multiply-add, ONE rounding (C's fmaf; Python 3.10 has no math.fma).  The f32
+  product is exact in float64; TwoSum gives s + e = a*b + c exactly; rounding s to odd (step one float64
+  ulp toward e when e != 0 and s is even) keeps the sticky bit, and 53 >= 24 + 2 makes the final cast to
+  f32 correctly rounded (ties to even, signed zeros, subnormals and overflow to +-inf included)."""
+  a, b, c = (np.asarray(v, f32) for v in (a, b, c))
+  with np.errstate(invalid='ignore', over='ignore'):
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c64 = c.astype(np.float64)
+    s = np.asarray(p + c64)
+    bb = s - p
+    e = (p - (s - bb)) + (c64 - bb)
+    even = (s.view(np.int64) & 1) == 0
+    fix = np.isfinite(s) & (e != 0) & even
+    s = np.where(fix, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+    return s.astype(f32)
+
+
+def _tap_base(lo, size):
+  """occ_taps' il = (int)fminf(fmaxf(lo, -1), size): floor(c) clamped to [-1, size] (NaN -> -1) before
+  the conversion (as int64)."""
+  return np.fmin(np.fmax(lo, f32(-1)), f32(size)).astype(np.int64)
+
+
+def gather_f32(volume, volume_valid, points, cell):
+  """occupancy.hip's occ_taps / occ_taps_ok / occ_blend4 in numpy f32, the same expressions in the same
+  order: volume [B, X, Y, Z, D], volume_valid [B, X, Y, Z] or None, points [B, P, 3] -> (features
+  [B, P, D] f32, valid [B, P]).  Only the 8 taps of each point are read (a lazily zeroed volume stays
+  untouched)."""
+  points = np.asarray(points, f32)
+  B, X, Y, Z, D = volume.shape
+  size = (X, Y, Z)
+  cell = f32(cell)
+  idx, w = [], []
+  inb = np.ones(points.shape[:-1], bool)
+  with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+    for t in range(3):
+      p = points[..., t] / cell
+      inb &= (p >= f32(0)) & (p < f32(size[t]))
+      c = p - f32(0.5)
+      lo = np.floor(c)
+      whi = c - lo
+      w.append((f32(1) - whi, whi))
+      il = _tap_base(lo, size[t])
+      idx.append((np.clip(il, 0, size[t] - 1), np.clip(il + 1, 0, size[t] - 1)))
+    bidx = np.arange(B).reshape(B, *([1] * (points.ndim - 2)))
+    bidx = np.broadcast_to(bidx, points.shape[:-1])
+    acc = None
+    ok = np.ones(points.shape[:-1], bool)
+    for corner in range(8):
+      bits = [(corner >> (2 - t)) & 1 for t in range(3)]
+      wc = (w[0][bits[0]] * w[1][bits[1]]) * w[2][bits[2]]
+      ix, iy, iz = (idx[t][bits[t]] for t in range(3))
+      contrib = wc[..., None] * np.asarray(volume[bidx, ix, iy, iz], f32)
+      acc = contrib if acc is None else acc + contrib
+      if volume_valid is not None:
+        ok &= np.asarray(volume_valid[bidx, ix, iy, iz], bool)
+  return acc.astype(f32), inb & ok
+
+
+def _snap_relu(v):
+  return np.where(v < 0, f32(0), v).astype(f32)                # keeps -0.0 and NaN
+
+
+def _fmaf_chain(x, w, acc=None):
+  """acc = fmaf(x[:, k], w[k, :], acc) for k ascending, from +0.0: x [R, K], w [K, N] -> [R, N]."""
+  x, w = np.asarray(x, f32), np.asarray(w, f32)
+  if acc is None:
+    acc = np.zeros((x.shape[0], w.shape[1]), f32)
+  for k in range(x.shape[1]):
+    acc = fmaf32(x[:, k, None], w[None, k, :], acc)
+  return acc
+
+
+def head_f32(feats, mlp):
+  """The fused head's arithmetic on feature rows feats [R, D]: mlp = [(kernel [in, out], bias [out]),
+  ...] with one or two hidden layers and a width-1 last layer -> logits [R] f32.  Hidden layer:
+  relu(fmaf chain over k from +0.0, + bias).  Output, one hidden layer: fmaf chain over k from +0.0,
+  then + bo.  Two hidden layers: per 32-column tile ct of the second, partial[ct] = fmaf chain over
+  the tile's columns (ascending) from +0.0; acc = partial[0] + partial[1] + ... (ct order), + bo."""
+  mlp = [(np.asarray(k, f32), np.asarray(b, f32)) for k, b in mlp]
+  if len(mlp) not in (2, 3) or mlp[-1][0].shape[1] != 1:
+    raise ValueError('head_f32: one or two hidden layers and a width-1 output layer')
+  x = np.asarray(feats, f32)
+  for k, b in mlp[:-1]:
+    x = _snap_relu(_fmaf_chain(x, k) + b)
+  wo, bo = mlp[-1]
+  if len(mlp) == 2:
+    acc = _fmaf_chain(x, wo)[:, 0]
+  else:
+    n = x.shape[1]
+    partial = [_fmaf_chain(x[:, ct:ct + 32], wo[ct:ct + 32])[:, 0] for ct in range(0, n, 32)]
+    acc = partial[0]
+    for part in partial[1:]:
+      acc = acc + part
+  return (acc + bo[0]).astype(f32)
+
+
+def head_layout(D, h1):
+  """The LDS layout snap_occupancy_head_f32 instantiates for (D, first hidden width): 'small'
+  (D, h1 <= 128), 'wide_a' (D > 128, h1 <= 128) or 'wide_ah' (h1 > 128)."""
+  if D <= 128 and h1 <= 128:
+    return 'small'
+  return 'wide_a' if h1 <= 128 else 'wide_ah'
 
 
 def interpolate_volume(volume, volume_valid, points, cell_size):
