@@ -184,7 +184,8 @@ typedef struct SnapConvExtras {
   int32_t gnb_mode;
 } SnapConvExtras;
 #define SNAP_TUNE_NO_HALO 1   /* split engine: the im2col body for every 3x3 convolution */
-#define SNAP_TUNE_RAW_RING 2   /* split engine: the raw-row LDS-DMA ring body (conv_raw.hip) for the K >= 256 1x1 layers with a GroupNorm prologue -- same bits as the tiled body; opt-in (measured level to 20 % slower: DESIGN.md 5a) */
+/* tune bit 2 is retired (it selected a raw-row ring body, measured slower: DESIGN.md 5a): a launch
+ * that sets it returns SNAP_ERR_UNSUPPORTED */
 #define SNAP_TUNE_NO_PLAIN 8   /* split engine: the general A loader also for 1x1 / stride-1 / unpadded layers */
 #define SNAP_TUNE_RS_NSPLIT_SHIFT 4   /* bits 4..7: row-stationary kernel, forced column split (0 = automatic) */
 /* Pre-split launches (extras->x_presplit): row tile, GroupNorm partial-sum bytes and split-K
@@ -439,10 +440,8 @@ int snap_compact_rows_range_u8(const uint8_t* mask, int64_t M, int32_t lo, int32
  *   relu_in: MLP.apply_input_activation;  plane [ncols, D], pvalid [ncols].
  *   x_split = 1: x holds the rows pre-split (SnapLiftDesc.out_split: [slab][hi | lo][16] bf16,
  *   x_stride still in floats); the A operand then travels global -> LDS by LDS-DMA.  Same
- *   results bit for bit; relu_in must be 0.  x_split = 5 (tuning / tests): the same with the GEMM0
- *   slabs one ahead (two LDS stages) instead of two ahead (three).  x_split = 3 (tuning / tests; H = 256 only, else as 1):
- *   the rows are taken 256 per workgroup (64 per wave, accumulators in AccVGPRs; the weights cross
- *   L2 -> LDS once per 256 rows) -- same bits, measured slower than the 128-row kernel. */
+ *   results bit for bit; relu_in must be 0.  x_split = 0 takes f32 rows; any other value returns
+ *   SNAP_ERR_UNSUPPORTED. */
 int snap_mlp2_pool_max_f32(const float* x, int64_t M, int32_t Cin, int32_t x_stride,
                            const int32_t* rows, const int32_t* row_count,
                            const void* w0_split, size_t w0_bytes, const float* b0, int32_t H,

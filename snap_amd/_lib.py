@@ -347,7 +347,7 @@ SIGNATURES = {
     ),
 }
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _lib = None
 

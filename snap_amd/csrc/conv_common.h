@@ -40,13 +40,10 @@ struct ConvArgs {
   int K;       // KH*KW*Cin
   int ctiles;  // ceil(Cin/16)   (VEC path)
   int nk;      // number of K slabs
-  int prio;    // experiment knob: s_setprio(1) around the MFMA block
   int ncol;    // number of column tiles (set in launch<>)
-  int ablate;  // alt builds only (-DSNAP_CONV_SPLIT_ABLATE=1, env SNAP_ALT_ABLATE): bit0 skip global loads, bit1 skip LDS stores+barrier, bit2 skip LDS reads, bit3 skip the barrier; 0 in the product build
   int bk;      // f32 engine: K-slab depth of the large tiles (16 | 32)
   int no_halo; // split engine: 1 = im2col body for every 3x3
   int no_plain;  // split engine: 1 = the general loader also for 1 x 1 / stride 1 / unpadded layers
-  int use_raw;   // split engine: 1 = the raw-row LDS-DMA ring body (conv_raw.hip) for the K >= 256 1 x 1 layers (opt-in: measured level / slower)
   int rs_nsplit;  // split engine: forced column split of conv_rs.hip (0 = automatic)
   const void* w_bf16;  // bf16 engine: weights packed by snap_conv2d_pack_weights_bf16 ([Cout][taps][cin8])
   int cin8;            // ... channel count rounded up to 8
@@ -88,10 +85,6 @@ int stationary_kind(const SnapConvDesc& d, int parts, bool row_lists);
 int launch_rs(ConvArgs a, hipStream_t s);
 int launch_bs(ConvArgs a, hipStream_t s);
 int launch_root_ws(const ConvArgs& a, hipStream_t s);   // the RGB root convolution, 64 output channels
-// raw-row LDS-DMA body for 1 x 1 / stride 1 layers with a GroupNorm prologue and K >= 256 (conv_raw.hip):
-// bit-identical to the tiled body; `a` as launch<128, bn, pro, 2> of conv_split.hip has set it up
-bool raw_ok(const ConvArgs& a, int bm, int bn, int pro);
-int launch_raw(const ConvArgs& a, int bn, int pro, dim3 grid, hipStream_t s);
 struct PsTile { int bm, bn, nt; };
 PsTile ps_choose_tile(int64_t M, int64_t N, int force);
 int ps_ksplit(int64_t M, int Cout, int64_t nk, int bm, int bn, size_t kpartial_bytes);
@@ -100,21 +93,6 @@ int ps_ksplit(int64_t M, int Cout, int64_t nk, int bm, int bn, size_t kpartial_b
 
 namespace {
 using snapconv::ConvArgs;
-
-// Timing ablations of the K loops (WRONG results; tools/conv_ablate*.py) exist only in an alt build
-// (-DSNAP_CONV_SPLIT_ABLATE=1; the bits come from the environment variable SNAP_ALT_ABLATE): the
-// product build has neither a switch in the ABI nor a run-time branch.
-#if defined(SNAP_CONV_SPLIT_ABLATE) && SNAP_CONV_SPLIT_ABLATE
-inline int snap_alt_ablate_bits() {
-  const char* e = getenv("SNAP_ALT_ABLATE");
-  return e ? atoi(e) : 0;
-}
-#define SNAP_IGEMM_ABL(bit) (a.ablate & (bit))
-#else
-inline int snap_alt_ablate_bits() { return 0; }
-#define SNAP_IGEMM_ABL(bit) false
-#endif
-
 
 // The prologue is a COMPILE-TIME parameter: a run-time switch here is lowered to a
 // branch tree per staged element and wrecks the schedule of the whole main loop.
@@ -553,14 +531,8 @@ inline int launch_splitk_reduce(const ConvArgs& a, hipStream_t s) {
 // C3 train step): off 59.75 / 162.5 ms; tiles<=128 59.96 / 159.9; tiles<=384, target 768
 // 59.34 / 157.8; tiles<=256, target 1024 59.55 / 158.4.  (A caller that wants no split-K
 // passes no workspace.)
-#ifndef SNAP_SPLITK_MAX_TILES
-#define SNAP_SPLITK_MAX_TILES 384
-#endif
-#ifndef SNAP_SPLITK_TARGET
-#define SNAP_SPLITK_TARGET 768
-#endif
-constexpr int64_t splitk_max_tiles() { return SNAP_SPLITK_MAX_TILES; }
-constexpr int splitk_target() { return SNAP_SPLITK_TARGET; }
+constexpr int64_t splitk_max_tiles() { return 384; }
+constexpr int splitk_target() { return 768; }
 
 // Tile choice: the largest tile that still yields >= 2 workgroups per CU; small-M
 // layers (deep stages, few images) fall back to 64x64 tiles to fill the 256 CUs.

@@ -371,13 +371,12 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     const int cur = (kt - kt_begin) & 1;
     const bool more = kt + 1 < kt_end;
-    if (more && !SNAP_IGEMM_ABL(1)) {
+    if (more) {
       load_slab(kt + 1);
       advance();
     }
     const float* as = As0 + cur * (BK * AS);
     const float* bs = Bs0 + cur * (BK * BN);
-    if (a.prio) __builtin_amdgcn_s_setprio(1);
     // LDS -> register operand fetch runs one k-pair ahead of the MFMAs.
     float av[2][TM], bv[2][TN];
 #pragma unroll
@@ -410,11 +409,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
       if (kk + 1 < BK / 2) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, TM * TN, 0);
     }
-    if (a.prio) __builtin_amdgcn_s_setprio(0);
-    if (!SNAP_IGEMM_ABL(2)) {
-      if (more) store_slab(cur ^ 1);
-      if (!SNAP_IGEMM_ABL(8)) __syncthreads();   // bit3: keep the stores, drop only the barrier
-    }
+    if (more) store_slab(cur ^ 1);
+    __syncthreads();
   }
 
   }
@@ -659,6 +655,7 @@ extern "C" int snap_conv2d_nhwc_ex_f32(const SnapConvDesc* desc, const float* x,
   if ((rows_in || rows_out) &&
       (desc->epilogue & (SNAP_EPI_RESIDUAL | SNAP_EPI_UPSAMPLE2X_ADD | SNAP_EPI_ROWMASK)))
     return SNAP_ERR_UNSUPPORTED;  // row-indexed launches carry bias / ReLU only
+  if (ex && (ex->tune_flags & 2)) return SNAP_ERR_UNSUPPORTED;   // tune bit 2: retired
   const bool presplit = ex && ex->x_presplit;
   const bool split_vec = ex && ex->w_bf16 && !ex->w_split_root && !rows_in && !rows_out && !row_count;
   // gn_partial_rows = 32: a split-K launch of the split engine or of the bf16 / fp16 engine (workspace
@@ -729,13 +726,10 @@ extern "C" int snap_conv2d_nhwc_ex_f32(const SnapConvDesc* desc, const float* x,
                    (!gn || (d.Cin % 4 == 0));
   a.ctiles = 0;
   a.nk = 0;  // set per K-slab depth in launch<>
-  a.prio = 0;
-  a.ablate = snap_alt_ablate_bits();   // alt builds only (timing experiments, wrong results); 0 in the product build
   a.bk = (ex && ex->bk_hint == 32) ? 32 : 16;
   a.no_halo = (ex && (ex->tune_flags & SNAP_TUNE_NO_HALO)) ? 1 : 0;
   a.rs_nsplit = ex ? (ex->tune_flags >> SNAP_TUNE_RS_NSPLIT_SHIFT) & 15 : 0;
   a.no_plain = (ex && (ex->tune_flags & SNAP_TUNE_NO_PLAIN)) ? 1 : 0;
-  a.use_raw = (ex && (ex->tune_flags & SNAP_TUNE_RAW_RING)) ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   // bf16-operand engine (training precision): needs the packed bf16 weights and the float4
   // loader's alignment; anything else runs on the (more precise) f32 engine below.

@@ -34,15 +34,6 @@ namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-// Timing-only ablations (alt builds: scripts/build_alt.sh; WRONG results): bit0 no DMA inside the
-// loop, bit1 no fragment fetches, bit3 no MFMAs
-#ifndef SNAP_PS_ABLATE
-#define SNAP_PS_ABLATE 0
-#endif
-#ifndef SNAP_PS_STAGGER
-#define SNAP_PS_STAGGER 1     // 512-thread tiles: the two waves of a SIMD issue their DMA pieces at different points of the stage
-#endif
-
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -249,7 +240,7 @@ __device__ __forceinline__ void conv_ps_body(const ConvArgs& a) {
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
   }
 
-  const int grp = (NT == 512 && SNAP_PS_STAGGER) ? __builtin_amdgcn_readfirstlane(wid >> 2) : 0;
+  const int grp = NT == 512 ? __builtin_amdgcn_readfirstlane(wid >> 2) : 0;
   int slot = 0;                 // ring slot of the stage being multiplied
   int islot = NST - 1;          // ring slot the next issue goes to
   for (int st = 0; st < nst_loc; ++st) {
@@ -263,66 +254,44 @@ __device__ __forceinline__ void conv_ps_body(const ConvArgs& a) {
     // blocks while the vector-memory queue takes them, and right after the barrier every wave of
     // the workgroup would do so at once with the matrix pipes idle: the upper four waves issue
     // theirs after the first block of MFMAs instead, under which the lower four issue.
-    if (!(SNAP_PS_ABLATE & 1) && grp == 0) issue(islot);
+    if (grp == 0) issue(islot);
     const char* const stage = ring + slot * ST;
     slot = slot + 1 == NST ? 0 : slot + 1;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       if (ks == KS / 2 && KS > 1) {
-        if (!(SNAP_PS_ABLATE & 1) && grp == 1) issue(islot);
+        if (grp == 1) issue(islot);
       }
       const char* as = stage + ks * ST1;
       const char* bs = as + A_ST;
       bf16x8 av[TM][NS], bv[TN][NS];
-      if (SNAP_PS_ABLATE & 2) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+      for (int i = 0; i < TM; ++i) {
+        const int R = wr * (BM / WR) + i * 32 + l31;
+        const char* p0 = as + R * 32 + ((lhi ^ ((R >> 3) & 1)) * 16);
 #pragma unroll
-          for (int p = 0; p < NS; ++p) asm volatile("" : "=v"(av[i][p]));
+        for (int p = 0; p < NS; ++p) av[i][p] = *reinterpret_cast<const bf16x8*>(p0 + p * A_PART);
+      }
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
+      for (int j = 0; j < TN; ++j) {
+        const int C = wc * (BN / 2) + j * 32 + l31;
+        const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
 #pragma unroll
-          for (int p = 0; p < NS; ++p) asm volatile("" : "=v"(bv[j][p]));
-      } else {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          const int R = wr * (BM / WR) + i * 32 + l31;
-          const char* p0 = as + R * 32 + ((lhi ^ ((R >> 3) & 1)) * 16);
-#pragma unroll
-          for (int p = 0; p < NS; ++p) av[i][p] = *reinterpret_cast<const bf16x8*>(p0 + p * A_PART);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int C = wc * (BN / 2) + j * 32 + l31;
-          const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
-#pragma unroll
-          for (int p = 0; p < NS; ++p) bv[j][p] = *reinterpret_cast<const bf16x8*>(p0 + p * B_PART);
-        }
+        for (int p = 0; p < NS; ++p) bv[j][p] = *reinterpret_cast<const bf16x8*>(p0 + p * B_PART);
       }
 #define SNAP_PS_PRODUCT(PA, PB)                                                              \
   _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) \
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[i][PA], bv[j][PB], acc[i][j], 0, 0, 0);
-      if (!(SNAP_PS_ABLATE & 8)) {
-        if constexpr (NS == 2) {
-          SNAP_PS_PRODUCT(1, 0)
-          if (KS == 1) {
-            if (!(SNAP_PS_ABLATE & 1) && grp == 1) issue(islot);
-          }
-          SNAP_PS_PRODUCT(0, 1)
-          SNAP_PS_PRODUCT(0, 0)
-        } else {
-          static_assert(NS == 2 || NT == 256 || KS > 1, "one-part 512-thread tiles: two k-steps per stage");
-          SNAP_PS_PRODUCT(0, 0)
+      if constexpr (NS == 2) {
+        SNAP_PS_PRODUCT(1, 0)
+        if (KS == 1) {
+          if (grp == 1) issue(islot);
         }
+        SNAP_PS_PRODUCT(0, 1)
+        SNAP_PS_PRODUCT(0, 0)
       } else {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int p = 0; p < NS; ++p) asm volatile("" ::"v"(av[i][p]));
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int p = 0; p < NS; ++p) asm volatile("" ::"v"(bv[j][p]));
+        static_assert(NS == 2 || NT == 256 || KS > 1, "one-part 512-thread tiles: two k-steps per stage");
+        SNAP_PS_PRODUCT(0, 0)
       }
 #undef SNAP_PS_PRODUCT
     }

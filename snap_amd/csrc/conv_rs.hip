@@ -30,16 +30,9 @@
 // 0.183 -> 0.161 (M = 46240, 256 -> 1024), i.e. 12-15 % over the tiled body; level at M = 147968,
 // 15-25 % SLOWER on the aerial encoder's M <= 36992 layers (too few row tiles: stationary_kind
 // leaves those to the tiled body).  Inside the C2 step the same layers gain 2-8 %.
-// What the ablations (SNAP_RS_ABLATE alt builds, scripts/gpu_rs_ablate.sh) say about these layers:
-// the time of all three shapes is (bytes through the CU boundary) / 5.0-5.5 TB/s, L2-resident
-// tile traffic counted like HBM traffic -- x + weight panel per row tile + residual + output:
-// 2.07 GB -> 0.377 ms, 1.22 GB -> 0.222, 0.83 GB -> 0.164, and the tiled body's larger byte
-// counts (activation tile per column tile) predict ITS times the same way.  MFMAs, fragment
-// fetches and the DMA issue together are 10-25 % of the kernel (removing all three: 0.340 /
-// 0.178 / 0.119 ms); the epilogue alone is 0.30 of the 0.377 ms at Cin = 64.  Skewing the two
-// workgroups of a CU against each other, 512-thread workgroups of 256 rows (half the weight
-// stream, but one barrier chain per CU: 0.44 / 0.246 / 0.178 ms) and other column splits were
-// all measured and are not faster.
+// Timing ablations (round 3) found these layers bound by the bytes through the CU boundary, not by
+// MFMAs, fragment fetches or DMA issue; 512-thread workgroups, skewed workgroups and other column
+// splits were measured and are not faster.
 #include "conv_common.h"
 
 namespace {
@@ -47,12 +40,6 @@ namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// Timing-only ablations (alt builds: scripts/build_alt.sh; WRONG results): bit0 no DMA inside the
-// loop, bit1 no fragment fetches, bit2 no MFMAs, bit3 no epilogue, bit4 no column loop at all
-#ifndef SNAP_RS_ABLATE
-#define SNAP_RS_ABLATE 0
-#endif
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -117,12 +104,10 @@ constexpr int rs_behind(int c, bool first_tile, int SPT, int P, int SR, int XE) 
 }
 
 // KS = Cin / 16 slabs, TN = 32-column MFMA tiles per column tile (BN = 32 TN); a wave = 32 rows
-#ifndef SNAP_RS_NT
-#define SNAP_RS_NT 256        // threads per workgroup: 256 (128 rows, two workgroups per CU) | 512 (256 rows, one)
-#endif
+// 256 threads per workgroup: 128 rows, two workgroups per CU
 template <int KS, int TN, int PRO, bool RES, bool DUAL>
-__global__ __launch_bounds__(SNAP_RS_NT, 2) void conv1x1_rs_kernel(const ConvArgs a) {
-  constexpr int NT = SNAP_RS_NT, NW = NT / 64;
+__global__ __launch_bounds__(256, 2) void conv1x1_rs_kernel(const ConvArgs a) {
+  constexpr int NT = 256, NW = NT / 64;
   constexpr int BM = 32 * NW, BN = 32 * TN;
   constexpr int kStage = 16384;                 // bytes per ring stage
   constexpr int NST = 3;
@@ -348,7 +333,7 @@ __global__ __launch_bounds__(SNAP_RS_NT, 2) void conv1x1_rs_kernel(const ConvArg
   const bool w_straddle = mw0 < m_split && mw0 + 32 > m_split;
   const int w_slot = mw0 >= m_split ? 1 : 0;
   int slot = 0;
-  for (int t = 0; t < ((SNAP_RS_ABLATE & 16) ? 0 : tiles_wg); ++t) {
+  for (int t = 0; t < tiles_wg; ++t) {
     const int n0 = nbase + t * BN;
     f32x16 acc[TN];
 #pragma unroll
@@ -361,7 +346,7 @@ __global__ __launch_bounds__(SNAP_RS_NT, 2) void conv1x1_rs_kernel(const ConvArg
       if (t == 0) wait_vm_n(rs_behind(c, true, SPT, P, SR, XE));
       else wait_vm_n(rs_behind(c, false, SPT, P, SR, XE));
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      if (!(SNAP_RS_ABLATE & 1)) issue();
+      issue();
       if (c == 0) reduce_stats(t - 1);
       const char* const stage = ring + slot * kStage;
       slot = slot + 1 == NST ? 0 : slot + 1;
@@ -374,22 +359,8 @@ __global__ __launch_bounds__(SNAP_RS_NT, 2) void conv1x1_rs_kernel(const ConvArg
         for (int j = 0; j < TN; ++j) {
           const int C = j * 32 + l31;
           const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
-          if (SNAP_RS_ABLATE & 2) {
-            asm volatile("" : "=v"(bv[j][0]));
-            asm volatile("" : "=v"(bv[j][1]));
-          } else {
-            bv[j][0] = *reinterpret_cast<const bf16x8*>(p0);
-            bv[j][1] = *reinterpret_cast<const bf16x8*>(p0 + B_PART);
-          }
-        }
-        if (SNAP_RS_ABLATE & 4) {
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            asm volatile("" ::"v"(bv[j][0]));
-            asm volatile("" ::"v"(bv[j][1]));
-          }
-          asm volatile("" ::"v"(a_lo[s]), "v"(a_hi[s]));
-          continue;
+          bv[j][0] = *reinterpret_cast<const bf16x8*>(p0);
+          bv[j][1] = *reinterpret_cast<const bf16x8*>(p0 + B_PART);
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j)
@@ -403,11 +374,6 @@ __global__ __launch_bounds__(SNAP_RS_NT, 2) void conv1x1_rs_kernel(const ConvArg
       }
     }
     // ---- epilogue of column tile t -----------------------------------------------------------
-    if (SNAP_RS_ABLATE & 8) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(acc[j][0]));   // (a 64-byte "v" operand silently drops the host stub)
-      continue;
-    }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
 #pragma unroll
@@ -1097,9 +1063,9 @@ __global__ __launch_bounds__(512, 2) void conv_root_ws64_kernel(const ConvArgs a
 template <int KS, int TN, bool RES>
 int launch_rs_dual(const ConvArgs& a, dim3 grid, bool dual, hipStream_t s) {
   if (dual)
-    hipLaunchKernelGGL((conv1x1_rs_kernel<KS, TN, SNAP_PRO_GN_RELU, RES, true>), grid, dim3(SNAP_RS_NT), 0, s, a);
+    hipLaunchKernelGGL((conv1x1_rs_kernel<KS, TN, SNAP_PRO_GN_RELU, RES, true>), grid, dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((conv1x1_rs_kernel<KS, TN, SNAP_PRO_GN_RELU, RES, false>), grid, dim3(SNAP_RS_NT), 0, s, a);
+    hipLaunchKernelGGL((conv1x1_rs_kernel<KS, TN, SNAP_PRO_GN_RELU, RES, false>), grid, dim3(256), 0, s, a);
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }
@@ -1159,7 +1125,7 @@ int snapconv::stationary_kind(const SnapConvDesc& d, int parts, bool row_lists) 
   if (mode != 3 && mode != 4 && d.Cin <= 128 && d.Cout % 256 == 0 && HoWo >= 32 &&
       d.N * (HoWo / 32 + 2) * (int64_t)d.Cout * 8 < 0x7ff00000LL)
     return 2;
-  if (HoWo < SNAP_RS_NT / 2) return 0;                           // at most two images per row tile
+  if (HoWo < 128) return 0;                                  // at most two images per row tile
   if (d.N * (HoWo / 128 + 2) * (int64_t)d.Cout * 8 >= 0x7ff00000LL) return 0;
   // the row tile (and with it the statistics layout) must be the tiled engine's
   if (choose_tile(M, d.Cout, d.tile_hint, desc_k(d)).bm != 128) return 0;
@@ -1209,7 +1175,7 @@ int snapconv::launch_rs(ConvArgs a, hipStream_t s) {
   const SnapConvDesc& d = a.d;
   const int bn = d.Cin == 256 ? 64 : 128;
   const int tiles = d.Cout / bn;
-  const int64_t nrow = snap_cdiv(a.M, SNAP_RS_NT / 2);
+  const int64_t nrow = snap_cdiv(a.M, 128);
   if (nrow > 0x7fffffffLL) return SNAP_ERR_BAD_SHAPE;
   // Column split: the fewest workgroup "rounds" over the 256 CUs, counting the activation prologue
   // as half a column tile of work
@@ -1217,7 +1183,7 @@ int snapconv::launch_rs(ConvArgs a, hipStream_t s) {
   double best_cost = 1e30;
   for (int ns = 1; ns <= tiles; ns *= 2) {
     if (tiles % ns) break;
-    const double rounds = (double)snap_cdiv(nrow * ns, (int64_t)(SNAP_RS_NT == 512 ? 256 : 512));
+    const double rounds = (double)snap_cdiv(nrow * ns, (int64_t)512);
     const double cost = rounds * (tiles / ns + 0.5);
     if (cost < best_cost * 0.97) { best_cost = cost; best = ns; }
   }

@@ -79,9 +79,6 @@ __device__ __forceinline__ void split_bf16(const f32x4& v, u32x2 (&out)[NS]) {
 // loader drop out -- rows beyond M are CLAMPED to the last row (their accumulators are garbage the
 // epilogue never stores) and the A rows are fetched with buffer loads: a constant 32-bit byte
 // offset per thread plus the slab's offset in the scalar operand.  Same values, same bits.
-#if defined(SNAP_CONV_TIMELINE) && SNAP_CONV_TIMELINE
-__device__ unsigned long long g_conv_timeline[1024 * 4 * 8];
-#endif
 
 template <int BM, int BN, int PRO, int NS, bool GNT, bool TAIL, bool ROOT = false, bool DUAL = false, bool PLAIN = false>
 __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
@@ -195,17 +192,7 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
   };
   set_tap();
 
-  // Timing ablations of this loop (WRONG results; tools/conv_ablate_split.py) exist ONLY in an alt
-  // build (scripts/build_alt.sh ... -DSNAP_CONV_SPLIT_ABLATE=1 pulls conv_split_ablate.inc in): the
-  // product source carries no hook.  SNAP_ABL(bit) is a compile-time false here.
-#if defined(SNAP_CONV_SPLIT_ABLATE) && SNAP_CONV_SPLIT_ABLATE
-  const int ablate = a.ablate;       // bit0 no A loads, bit1 no B DMA, bit2 no MFMAs, bit3 no prologue /
-#define SNAP_ABL(bit) (ablate & (bit))   // split math, bit4 no A LDS stores, bit5 no fragment fetches
-#else
-#define SNAP_ABL(bit) false
-#endif
   auto load_a = [&]() {
-    if (SNAP_ABL(1)) return;
     if constexpr (PLAIN) {
       static_assert(!PLAIN || (GNT || !need_gn), "PLAIN takes the table variant of the GroupNorm prologue");
 #pragma unroll
@@ -252,7 +239,6 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
               (part < NS ? part : 0) * 4096 + (gcol & 127) * 32 + (rem & 1) * 16;
   }
   auto issue_b = [&](int buf) {
-    if (SNAP_ABL(2)) return;
 #pragma unroll
     for (int p = 0; p < BPIECES; ++p) {
       const int slot = tid + 256 * p;
@@ -288,10 +274,6 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
     }
   };
   auto store_a = [&](int buf, int ring) {
-    if (SNAP_ABL(16)) return;
-#if defined(SNAP_CONV_SPLIT_ABLATE) && SNAP_CONV_SPLIT_ABLATE
-#include "conv_split_ablate.inc"       // (bit 3: raw stores instead of prologue + split)
-#endif
     const float* const tb = reinterpret_cast<const float*>(Gt + ring * kGnRing);
     if constexpr (gn_tab) xbeta = *reinterpret_cast<const f32x4*>(tb + 64 + 4 * akq);
 #pragma unroll
@@ -345,22 +327,10 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
-#if defined(SNAP_CONV_TIMELINE) && SNAP_CONV_TIMELINE
-  // ALT BUILD ONLY (tools/conv_timeline.py): where a wave's cycles go, phase by phase (s_memtime around
-  // fenced phases: the fences themselves cost overlap, so read the SHARES, not the total)
-  unsigned long long tl_acc[7] = {0, 0, 0, 0, 0, 0, 0};
-#define TL_MARK(i) do { asm volatile("" ::: "memory"); const unsigned long long tn_ = __builtin_amdgcn_s_memtime(); \
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tl_acc[i] += tn_ - tl_t; tl_t = tn_; } while (0)
-  unsigned long long tl_t = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-#define TL_MARK(i) do {} while (0)
-#endif
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     const int cur = (kt - kt_begin) & 1;
     const bool more = kt + 1 < kt_end;
     const int ring_next = ring_cur == 2 ? 0 : ring_cur + 1;
-    TL_MARK(6);                       // loop control / back edge
     if (more) {
       load_a();
       issue_b(cur ^ 1);
@@ -369,45 +339,28 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
         if (kt + 2 < kt_end) { issue_gn(ring_next == 2 ? 0 : ring_next + 1, g_ct); next_gct(); }
       }
     }
-    TL_MARK(0);                       // issue of the loads / DMA of the next k-step
     const char* as = Ab + cur * A_ST;
     const char* bs = Bb + cur * B_ST;
     bf16x8 av[TM][NS], bv[TN][NS];
-    if (!SNAP_ABL(32)) {
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int R = wr * (BM / 2) + i * 32 + l31;
-        const char* p0 = as + R * 32 + ((lhi ^ ((R >> 3) & 1)) * 16);
+    for (int i = 0; i < TM; ++i) {
+      const int R = wr * (BM / 2) + i * 32 + l31;
+      const char* p0 = as + R * 32 + ((lhi ^ ((R >> 3) & 1)) * 16);
 #pragma unroll
-        for (int p = 0; p < NS; ++p) av[i][p] = *reinterpret_cast<const bf16x8*>(p0 + p * A_PART);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int C = wc * (BN / 2) + j * 32 + l31;
-        const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
-#pragma unroll
-        for (int p = 0; p < NS; ++p) bv[j][p] = *reinterpret_cast<const bf16x8*>(p0 + p * B_PART);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int p = 0; p < NS; ++p) asm volatile("" : "=v"(av[i][p]));
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int p = 0; p < NS; ++p) asm volatile("" : "=v"(bv[j][p]));
+      for (int p = 0; p < NS; ++p) av[i][p] = *reinterpret_cast<const bf16x8*>(p0 + p * A_PART);
     }
-#if defined(SNAP_CONV_TIMELINE) && SNAP_CONV_TIMELINE
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-    TL_MARK(1);                       // fragment fetches landed
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int C = wc * (BN / 2) + j * 32 + l31;
+      const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
+#pragma unroll
+      for (int p = 0; p < NS; ++p) bv[j][p] = *reinterpret_cast<const bf16x8*>(p0 + p * B_PART);
+    }
     // smallest terms first; the four (i, j) accumulators interleave so that two MFMAs on the
     // same accumulator are TM*TN issues apart
 #define SNAP_SPLIT_PRODUCT(PA, PB)                                                          \
   _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) \
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[i][PA], bv[j][PB], acc[i][j], 0, 0, 0);
-    if (!SNAP_ABL(4)) {
     if constexpr (NS == 3) {
       SNAP_SPLIT_PRODUCT(2, 0)
       SNAP_SPLIT_PRODUCT(0, 2)
@@ -420,40 +373,12 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
       SNAP_SPLIT_PRODUCT(0, 1)
       SNAP_SPLIT_PRODUCT(0, 0)
     }
-    } else {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int p = 0; p < NS; ++p) asm volatile("" ::"v"(av[i][p]));
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int p = 0; p < NS; ++p) asm volatile("" ::"v"(bv[j][p]));
-    }
 #undef SNAP_SPLIT_PRODUCT
-    TL_MARK(2);                       // MFMA issue (12 x 32 cycles if the pipe is free)
-#if defined(SNAP_CONV_TIMELINE) && SNAP_CONV_TIMELINE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    TL_MARK(3);                       // wait for the next k-step's A rows (+ B, table)
     if (more) store_a(cur ^ 1, ring_next);
     ring_cur = ring_next;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // B octets of slab kt+1 (+ table kt+2) landed
-#if defined(SNAP_CONV_TIMELINE) && SNAP_CONV_TIMELINE
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-    TL_MARK(4);                       // prologue + split + LDS stores
     __syncthreads();
-    TL_MARK(5);                       // barrier
   }
-#if defined(SNAP_CONV_TIMELINE) && SNAP_CONV_TIMELINE
-  if (PLAIN && lane == 0 && blockIdx.x < 1024) {
-#pragma unroll
-    for (int i = 0; i < 7; ++i) g_conv_timeline[(blockIdx.x * 4 + wid) * 8 + i] = tl_acc[i];
-    g_conv_timeline[(blockIdx.x * 4 + wid) * 8 + 7] = (unsigned long long)(kt_end - kt_begin);
-  }
-#endif
-#undef TL_MARK
 
   conv_epilogue<BM, BN, DUAL>(a, acc, smem, m0, n0, Meff, row_t, split);
 }
@@ -464,8 +389,8 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
 // ---------------------------------------------------------------------------------------------
 // 3x3 / stride 1 / pad 1 with the input staged ONCE per channel tile ("halo" body).
 // The im2col body above fetches, normalises and splits every input pixel nine times (once per
-// tap); its loop spends 41 % of its time on those loads and 16 % on the conversion
-// (tools/conv_ablate_split.py).  Here the K loop runs channel tile OUTER, tap INNER: per channel
+// tap); its loop spent 41 % of its time on those loads and 16 % on the conversion (timing
+// ablations, docs/DESIGN_HISTORY.md 5e).  Here the K loop runs channel tile OUTER, tap INNER: per channel
 // tile the BM + 2W + 2 consecutive pixels (flattened (n, y, x) order) that the tile's nine taps
 // touch are fetched, normalised (GroupNorm table of at most two images) and split ONCE into an
 // LDS stage; tap (kh, kw) of output row r reads stage row r + kh W + kw.  A tap that falls
@@ -842,15 +767,6 @@ int launch(ConvArgs a, hipStream_t s) {
                      a.d.pad_l == 0 && a.d.H == a.d.Ho && a.d.W == a.d.Wo && a.d.Cin % 16 == 0 &&
                      (a.d.Cin_stride & 3) == 0 && !a.rows_in && !a.row_count && a.M > 0 &&
                      (int64_t)BM * a.d.Cin_stride * 4 < 0x7ff00000LL;
-  // K >= 256 with a GroupNorm prologue: the raw rows through an LDS ring, converted at fragment fetch
-  // (conv_raw.hip: two k-steps in flight instead of one memory round trip per k-step; same bits)
-  if constexpr (BM == 128 && NS == 2 && (PRO == SNAP_PRO_GN_RELU || PRO == SNAP_PRO_RELU_GN)) {
-    if (plain && table_ok && snapconv::raw_ok(a, BM, BN, PRO)) {
-      const int rc = snapconv::launch_raw(a, BN, PRO, grid, s);
-      if (rc != SNAP_OK) return rc;
-      return a.ksplit > 1 ? launch_splitk_reduce(a, s) : SNAP_OK;
-    }
-  }
   if constexpr (NS == 2 && (PRO == SNAP_PRO_GN_RELU || PRO == SNAP_PRO_NONE || PRO == SNAP_PRO_RELU_GN)) {
     if (plain && (!need_gn || table_ok)) {
       hipLaunchKernelGGL((conv_split_kernel<BM, BN, PRO, NS, need_gn, false, false, true>), grid, dim3(256), 0, s, a);
@@ -1103,10 +1019,3 @@ extern "C" int snap_conv2d_pack_weights_split_root_bf16(const float* w, int32_t 
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }
-
-#if defined(SNAP_CONV_TIMELINE) && SNAP_CONV_TIMELINE
-// alt build only: copy the phase counters of the last plain-body launch to the host (tools/conv_timeline.py)
-extern "C" int snap_debug_conv_timeline(unsigned long long* out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_conv_timeline), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -1;
-}
-#endif

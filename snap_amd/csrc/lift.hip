@@ -458,11 +458,6 @@ __device__ __forceinline__ void split_row_quad(const f32x4& v, unsigned (&hi)[2]
   }
 }
 
-#ifndef SNAP_LIFT_ABLATE
-#define SNAP_LIFT_ABLATE 0     // timing experiments only (wrong results): 1 = no row stores (and what
-#endif                         // feeds them: dead code), 2 = no feature loads, 4 = rows stored into a 4 MB
-                               // window (every instruction stays, no HBM write traffic), 8 = phase A alone,
-                               // 16 = no depth-score loads in phase A (tap records)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 pair_lo(const f32x4& v) { return __builtin_shufflevector(v, v, 0, 1); }
 __device__ __forceinline__ f32x2 pair_hi(const f32x4& v) { return __builtin_shufflevector(v, v, 2, 3); }
@@ -622,10 +617,6 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
         const uint32_t o11 = o10 + (o01 - o00);
         const uint32_t c0 = fdb_ + ((pk >> 10) & 0xff) * 4u, c1 = fdb_ + ((pk >> 18) & 0xff) * 4u;
         const char* fb_ = reinterpret_cast<const char*>(a.f);
-#if SNAP_LIFT_ABLATE & 16
-        const float t00 = w00, t01 = w01, t10 = w10, t11 = w11, u00 = w00, u01 = w01, u10 = w10, u11 = w11;
-        (void)fb_; (void)o11; (void)c0; (void)c1;
-#else
         const float t00 = *reinterpret_cast<const float*>(fb_ + (o00 + c0));
         const float t01 = *reinterpret_cast<const float*>(fb_ + (o01 + c0));
         const float t10 = *reinterpret_cast<const float*>(fb_ + (o10 + c0));
@@ -634,7 +625,6 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
         const float u01 = *reinterpret_cast<const float*>(fb_ + (o01 + c1));
         const float u10 = *reinterpret_cast<const float*>(fb_ + (o10 + c1));
         const float u11 = *reinterpret_cast<const float*>(fb_ + (o11 + c1));
-#endif
         const float wb1 = wbs[hw][hl][0], wb0 = 1.f - wb1;
         const float s0 = ((w00 * t00 + w01 * t01) + w10 * t10) + w11 * t11;
         const float s1 = ((w00 * u00 + w01 * u01) + w10 * u10) + w11 * u11;
@@ -672,10 +662,6 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
     order[pos] = (uint8_t)threadIdx.x;
   }
   __syncthreads();
-#if SNAP_LIFT_ABLATE & 8
-  return;                      // (timing: phase A alone)
-#endif
-
   // ---------------- phase B: lane = channel quad ----------------
   // The kernel is VALU-bound (PMC r02: VALU 72 % busy), so phase B spends as few instructions
   // per voxel as the arithmetic allows: tap addresses are 32-bit byte offsets from the (scalar)
@@ -723,14 +709,10 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
       const float u10 = *reinterpret_cast<const float*>(fb + (o10 + c1));
       const float u11 = *reinterpret_cast<const float*>(fb + (o11 + c1));
       if (FD128 || hl < nq) {
-#if SNAP_LIFT_ABLATE & 2
-        const f32x4 a00 = {w00, w01, w10, w11}, a01 = a00, a10 = a00, a11 = a00;
-#else
         const f32x4 a00 = *reinterpret_cast<const f32x4*>(fb + (o00 + lane_off));
         const f32x4 a01 = *reinterpret_cast<const f32x4*>(fb + (o01 + lane_off));
         const f32x4 a10 = *reinterpret_cast<const f32x4*>(fb + (o10 + lane_off));
         const f32x4 a11 = *reinterpret_cast<const f32x4*>(fb + (o11 + lane_off));
-#endif
         const f32x2 p00 = {w00, w00}, p01 = {w01, w01}, p10 = {w10, w10}, p11 = {w11, w11};
         feat[r][0] = ((p00 * pair_lo(a00) + p01 * pair_lo(a01)) + p10 * pair_lo(a10)) + p11 * pair_lo(a11);
         feat[r][1] = ((p00 * pair_hi(a00) + p01 * pair_hi(a01)) + p10 * pair_hi(a10)) + p11 * pair_hi(a11);
@@ -740,11 +722,7 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
       const float s1 = ((w00 * u00 + w01 * u01) + w10 * u10) + w11 * u11;
       score[r] = wb0 * s0 + wb1 * s1;
     }
-#if SNAP_LIFT_ABLATE & 4
-    float* out = a.pooled + (gv & 4095) * d.out_stride;     // (all rows into 4 MB: no HBM writes)
-#else
     float* out = a.pooled + gv * d.out_stride;
-#endif
     f32x2 mean2[2] = {{0.f, 0.f}, {0.f, 0.f}}, var2[2] = {{0.f, 0.f}, {0.f, 0.f}};
     float smax = 0.f;
     if (nvis == 1) {          // half-wave uniform
@@ -789,11 +767,7 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
     const f32x4 var = {var2[0][0], var2[0][1], var2[1][0], var2[1][1]};
     // (valid_rows_only: a voxel no view sees gets its validity byte, not its 1 KB row of zeros --
     // for consumers that read the rows of valid voxels only, 40 % of the map's voxels at C2)
-#if SNAP_LIFT_ABLATE & 1
-    const bool write_row = false;
-#else
     const bool write_row = nvis > 0 || !d.valid_rows_only;
-#endif
     if (d.out_split) {
       // the row as the split-bf16 engines stage it: [16-channel slab][hi | lo][16] bf16, 64 B per
       // slab (hi = bf16(v), lo = bf16(v - hi): the consumer's own split, done here once) -- the

@@ -94,41 +94,31 @@ __device__ __forceinline__ void atomic_max_f32(float* p, float v) {
     atomicMax(reinterpret_cast<int*>(p), (int)u);
 }
 
-#ifndef SNAP_MLP_POOL_PAIRS
-#define SNAP_MLP_POOL_PAIRS 1      // 1: GEMM1 takes TWO k-steps per barrier (four 16 KB ring slots); 0: one (eight 8 KB slots)
-#endif
-// NT = 256: 128 rows per workgroup, two workgroups per CU.  NT = 512: 256 rows (eight waves), one
-// workgroup per CU -- the same 8 waves per CU, and W0 / W1 (426 KB per workgroup, 25 GB per C2 step
-// at 128 rows) stream from L2 once per 256 rows.  Measured at C2 (scripts/gpu_mlp_nt.sh, round 3):
-// 3.64 ms per step against 3.30 ms at NT = 256 -- halving the weight stream buys nothing, eight
-// waves behind ONE barrier chain lose more than two independent workgroups of four: the kernel is
-// bound by its phase structure, not by the L2 -> LDS stream.  NT = 256 stays.
-#ifndef SNAP_MLP_POOL_NT
-#define SNAP_MLP_POOL_NT 256
-#endif
-template <int N0, bool RELU_IN, bool XSPLIT, int NT, int NST = 2, bool GATHER = false>
-__global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
+// 256 threads: 128 rows per workgroup, two workgroups per CU.  256-row workgroups (eight waves, or
+// four with two row blocks each) halve the L2 -> LDS weight stream and measured slower: the kernel is
+// bound by its phase structure, which two co-resident workgroups hide for each other.
+template <int N0, bool RELU_IN, bool XSPLIT, int NST = 2, bool GATHER = false>
+__global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
   // NST = 3 (pre-split rows only, the default for them): the GEMM0 slabs (rows + W0, 24 KB) travel TWO
   // ahead through a three-stage ring -- one barrier per slab as before, but a slab's 24 MFMAs per wave
   // (0.3 us) no longer wait for a memory round trip (~1 us) that started one slab earlier.  The ring
   // takes 72 KB, so W1's first pair cannot travel during GEMM0 any more; all four ring slots are
   // issued after GEMM0 and arrive under the ReLU / split conversion.  C2 map, 6.8 M rows:
   // 3.09-3.10 ms against 3.21-3.39 ms (tools/mlp_pool_bench.py), same bits.
-  static_assert(NST == 2 || (NST == 3 && XSPLIT && NT == 256), "the ring is the LDS-DMA path's");
+  static_assert(NST == 2 || (NST == 3 && XSPLIT), "the ring is the LDS-DMA path's");
   static_assert(!GATHER || (!XSPLIT && !RELU_IN && NST == 2), "the gather stages through registers");
-  constexpr int BM = NT / 2, N1 = 128;
+  constexpr int NT = 256, BM = NT / 2, N1 = 128;
   constexpr int RPP = NT / 4;                                 // rows staged per pass (4 threads per row)
   constexpr int T0 = N0 / 32, T1 = N1 / 32;
   constexpr int A_PART = BM * 32, A_ST = 2 * A_PART;          // 8 KB per stage at 128 rows
   constexpr int B0_ST = (N0 / 128) * 8192;                    // 16 KB per stage at N0 = 256
   constexpr int kB0 = NST * A_ST;
   // [GEMM0 stages | W1 ring] share the front of the buffer with the [BM][128] f32 tile of the max
-  // scan; 128 rows: the ring lies over the GEMM0 stages (64 KB in all), 256 rows: behind them
-  constexpr int kRing = NT == 256 ? 0 : 65536;
-  constexpr int kBias = NT == 256 ? (NST == 3 ? 73728 : 65536) : 131072;   // b0 [N0] | b1 [N1] behind
+  // scan; the ring lies over the GEMM0 stages (64 KB in all)
+  constexpr int kBias = NST == 3 ? 73728 : 65536;               // b0 [N0] | b1 [N1] behind
   static_assert(kB0 + NST * B0_ST <= (NST == 3 ? 73728 : 65536), "GEMM0 stages overlap the ring / the bias table");
   static_assert(BM * N1 * 4 <= kBias, "scan tile overlaps the bias table");
-  __shared__ __attribute__((aligned(16))) float smem[kBias / 4 + N0 + N1];   // 65.5 KB (two per CU) / 129.5 KB
+  __shared__ __attribute__((aligned(16))) float smem[kBias / 4 + N0 + N1];   // 65.5 KB (two per CU)
   char* const sm = reinterpret_cast<char*>(smem);
   float* const bias0 = reinterpret_cast<float*>(sm + kBias);
   float* const bias1 = bias0 + N0;
@@ -183,9 +173,6 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
       g_o[i][0] = o00; g_o[i][1] = o01; g_o[i][2] = o10; g_o[i][3] = o10 + (o01 - o00);
     }
   }
-#ifndef SNAP_MLP_POOL_ABLATE
-#define SNAP_MLP_POOL_ABLATE 0     // timing experiments only (wrong results): 1 = no A loads,
-#endif                             // 2 = no A loads / split / LDS stores, 4 = no GEMM1, 8 = no max scan
   auto load_a = [&](int ct) {
     if constexpr (GATHER) {
       cur_c = ct;
@@ -198,7 +185,6 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
       }
       return;
     }
-    if (SNAP_MLP_POOL_ABLATE & 3) { cur_c = 0; xa[0] = xa[1] = f32x4{1.f, 1.f, 1.f, 1.f}; xin[0] = xin[1] = true; return; }
     const int c = ct * 16 + 4 * akq;
     cur_c = c;
     const bool cvalid = c < a.Cin;
@@ -209,7 +195,6 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
     }
   };
   auto store_a = [&](int buf) {
-    if (SNAP_MLP_POOL_ABLATE & 2) return;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int row = (tid >> 2) + RPP * i;
@@ -252,35 +237,18 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
     }
   };
 
-  // W1 k-step ks (8 KB: [part][column][32 B]) -> slot (ks + 6) & 7 of an eight-slot ring over the
-  // first 64 KB.  A stage is consumed in 12 MFMAs (~0.2 us) but takes ~1 us to arrive, so up to
-  // seven k-steps are kept in flight; slots 6, 7 lie behind the GEMM0 stages: k-steps 0 and 1
-  // travel while GEMM0 runs.
-  auto issue_b1 = [&](int ks) {
-    static_assert(SNAP_MLP_POOL_PAIRS || NT == 256, "the one-k-step ring is the 256-thread layout");
-    const char* src = a.w1 + (int64_t)ks * 8192 + tid * 16;
-    char* dst = sm + ((ks + 6) & 7) * 8192 + tid * 16;
-    __builtin_amdgcn_global_load_lds((cglobal_void_t*)src, (lds_void_t*)dst, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((cglobal_void_t*)(src + 4096), (lds_void_t*)(dst + 4096), 16, 0, 0);
-  };
-  // pair p = k-steps 2p, 2p + 1 (16 KB) -> slot (p + 3) & 3 of a four-slot ring over the same 64 KB:
-  // pair 0 lands behind the GEMM0 stages (it travels while GEMM0 runs), as k-steps 0 and 1 did
+  // W1 pair p = k-steps 2p, 2p + 1 (16 KB: [part][column][32 B] each) -> slot (p + 3) & 3 of a
+  // four-slot ring over the first 64 KB.  A k-step is consumed in 12 MFMAs (~0.2 us) but takes ~1 us to
+  // arrive, so up to four pairs are kept in flight; pair 0 lands behind the GEMM0 stages (it travels while GEMM0 runs)
   constexpr int PP = 16384 / 16 / NT;                             // DMA instructions per thread and pair
   auto issue_b1_pair = [&](int p) {
     const char* src = a.w1 + (int64_t)p * 16384 + tid * 16;
-    char* dst = sm + kRing + ((p + 3) & 3) * 16384 + tid * 16;
+    char* dst = sm + ((p + 3) & 3) * 16384 + tid * 16;
 #pragma unroll
     for (int q = 0; q < PP; ++q)
       __builtin_amdgcn_global_load_lds((cglobal_void_t*)(src + NT * 16 * q), (lds_void_t*)(dst + NT * 16 * q), 16, 0, 0);
   };
-  if (!(SNAP_MLP_POOL_ABLATE & 4) && NST == 2) {
-    if (SNAP_MLP_POOL_PAIRS) {
-      issue_b1_pair(0);
-    } else {
-      issue_b1(0);
-      issue_b1(1);                                                // (H >= 32: two k-steps exist)
-    }
-  }
+  if constexpr (NST == 2) issue_b1_pair(0);
 
   f32x16 acc0[T0];
 #pragma unroll
@@ -391,20 +359,10 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
   // ---- hidden = relu(acc0 + b0) -> the GEMM1 operand fragments, IN PLACE (16 accumulator
   // registers of a tile become 2 k-steps x (hi, lo) x 4 registers), while the first W1 stages
   // travel.  Keeping this VALU chain out of the GEMM1 loop leaves that loop LDS reads + MFMAs only.
-  const int nks = a.H >> 4;                                       // 16-k steps of GEMM1
-  const bool run1 = !(SNAP_MLP_POOL_ABLATE & 4);
-  const int npairs = nks >> 1;                                    // (H % 32 == 0)
-  if (run1) {
-    if (SNAP_MLP_POOL_PAIRS) {
+  const int npairs = a.H >> 5;                                    // 32-k pairs of GEMM1 (H % 32 == 0)
 #pragma unroll
-      for (int p = NST == 3 ? 0 : 1; p < 4; ++p)
-        if (p < npairs) issue_b1_pair(p);                         // (NST = 2: pair 0 was issued at the start)
-    } else {
-#pragma unroll
-      for (int k = 2; k < 8; ++k)
-        if (k < nks) issue_b1(k);                                 // (k-steps 0, 1: issued at the start)
-    }
-  }
+  for (int p = NST == 3 ? 0 : 1; p < 4; ++p)
+    if (p < npairs) issue_b1_pair(p);                             // (NST = 2: pair 0 was issued at the start)
   u32x4 f_hi[T0][2], f_lo[T0][2];
 #pragma unroll
   for (int t = 0; t < T0; ++t)
@@ -433,7 +391,7 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
       f_lo[t][s] = u32x4{l0[0], l0[1], l1[0], l1[1]};
     }
 
-  // ---- GEMM1: one k-step per ring slot -----------------------------------------------------------
+  // ---- GEMM1: one k-step pair per ring slot ------------------------------------------------------
   f32x16 acc1[T1];
 #pragma unroll
   for (int t = 0; t < T1; ++t)
@@ -446,8 +404,7 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
   // barrier (the same 32 operand registers, reloaded between the two) halve that.
 #pragma unroll
   for (int pr = 0; pr < T0; ++pr) {
-    if (!SNAP_MLP_POOL_PAIRS) break;
-    if (pr < npairs && run1) {
+    if (pr < npairs) {
       // wait for pair pr; issued so far: 1 .. pr + 2, so pr + 1 .. min(pr + 2, npairs - 1) may stay
       // in flight, four DMA instructions each (pair 0 was drained by GEMM0's waits)
       if (pr >= 1 || NST == 3) {
@@ -464,7 +421,7 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
       if (pr >= 1 && pr + 3 < npairs) issue_b1_pair(pr + 3);
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
-        const char* ws = sm + kRing + ((pr + 3) & 3) * 16384 + sub * 8192 + w_off;
+        const char* ws = sm + ((pr + 3) & 3) * 16384 + sub * 8192 + w_off;
         bf16x8 h_hi, h_lo;
         __builtin_memcpy(&h_hi, &f_hi[pr][sub], 16);
         __builtin_memcpy(&h_lo, &f_lo[pr][sub], 16);
@@ -485,49 +442,6 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
         for (int j = 0; j < T1; ++j)
           acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_hi[j], h_hi, acc1[j], 0, 0, 0);
       }
-    }
-  }
-#pragma unroll
-  for (int ks = 0; ks < 2 * T0; ++ks) {
-    if (SNAP_MLP_POOL_PAIRS) break;
-    if (ks < nks && run1) {
-      // wait for k-step ks; issued so far: 2 .. ks + 6, so ks + 1 .. min(ks + 6, nks - 1) may
-      // stay in flight, two DMA instructions each (k-steps 0, 1 were drained by GEMM0's waits)
-      if (ks >= 2) {
-        const int younger = min(ks + 6, nks - 1) - ks;
-        switch (younger) {
-          case 6: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-          case 5: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-          case 4: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-          case 3: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-          case 2: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-          case 1: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-          default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      // every wave is past k-step ks - 1: its slot takes k-step ks + 7
-      if (ks >= 1 && ks + 7 < nks) issue_b1(ks + 7);
-      const char* ws = sm + ((ks + 6) & 7) * 8192 + w_off;
-      bf16x8 h_hi, h_lo;
-      __builtin_memcpy(&h_hi, &f_hi[ks >> 1][ks & 1], 16);
-      __builtin_memcpy(&h_lo, &f_lo[ks >> 1][ks & 1], 16);
-      bf16x8 w_hi[T1], w_lo[T1];
-#pragma unroll
-      for (int j = 0; j < T1; ++j) {
-        const char* p0 = ws + j * 1024;
-        w_hi[j] = *reinterpret_cast<const bf16x8*>(p0);
-        w_lo[j] = *reinterpret_cast<const bf16x8*>(p0 + 4096);
-      }
-#pragma unroll
-      for (int j = 0; j < T1; ++j)
-        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_hi[j], h_lo, acc1[j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < T1; ++j)
-        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_lo[j], h_hi, acc1[j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < T1; ++j)
-        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_hi[j], h_hi, acc1[j], 0, 0, 0);
     }
   }
 
@@ -558,7 +472,7 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
   const int cid = my < Meff ? a.rows[my] / a.Z : -1;
   int cur = -1;
   float run = -INFINITY;
-  const bool live = c < a.D && !(SNAP_MLP_POOL_ABLATE & 8);
+  const bool live = c < a.D;
   // (snap_max_nan: a NaN of an observed voxel makes the column's maximum NaN, as jnp.max does
   //  (bev_mapper.py:63-78) -- the same in vertical_pool_kernel; the canonical positive NaN wins the
   //  integer atomic max below.  The MLP's ReLUs propagate it too (snap_relu).)
@@ -580,298 +494,6 @@ __global__ __launch_bounds__(NT, 2) void mlp2_pool_kernel(const MlpPoolArgs a) {
       run = -INFINITY;
     }
     run = snap_max_nan(run, vals[r]);
-  }
-  if (cur >= 0 && live) atomic_max_f32(a.plane + (int64_t)cur * a.D + c, run);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same computation on 256-ROW tiles, for pre-split rows and H = 256: one workgroup of four waves
-// per CU (launch bound: one wave per SIMD, so a wave may hold 512 registers -- the accumulators live
-// in the AccVGPR half), each wave owns 64 rows = TWO 32-row blocks.  Why: the 128-row kernel moves
-// W0 + W1 (up to 400 KB) from L2 into LDS once per 128 rows -- 18 GB of its 24 GB per C2 step, at
-// the ~7 TB/s the CUs take from L2 that IS its run time -- and every weight fragment a wave reads
-// from LDS feeds one MFMA.  Here the weight stream is paid once per 256 rows and a fragment feeds
-// two MFMAs; the eight-wave variant of the old kernel (SNAP_MLP_POOL_NT = 512) had the same stream
-// but twice the waves behind every barrier and measured slower.  With one workgroup per CU nothing
-// else hides a memory round trip, so the GEMM0 slabs travel THREE ahead through a four-stage ring
-// (4 x 32 KB), all of W1 (128 KB) is resident before GEMM1 needs it (pair 0 arrives while GEMM0
-// runs, pairs 1-7 while the hidden activations are converted), and the scan tile ([256][128] f32)
-// takes the ring's place at the end.  Slab order and product order per accumulator are the
-// 128-row kernel's: the plane is bit-identical (tests/test_gpu_kernels.py).
-// MEASURED (tools/mlp_pool_bench.py, the C2 map: 6.8 M rows in two classes): 4.11-4.18 ms against
-// 3.30-3.43 ms for the 128-row kernel.  One wave per SIMD cannot hide its own non-matrix phases --
-// row-list fetch and first slab (~4 us), the ReLU / split conversion of 256 accumulator registers
-// (~3 us), the scan (~4 us), the LDS latency after every barrier -- which two co-resident 128-row
-// workgroups hide for each other: 39 us per 256-row tile for 11-16 us of MFMA time.  Halving the
-// weight stream is worth less than that overlap.  Kept as an opt-in (x_split = 3) with its test.
-template <int N0>
-__global__ __launch_bounds__(256, 1) void mlp2_pool_wide_kernel(const MlpPoolArgs a) {
-  constexpr int NT = 256, BM = 256, N1 = 128, RB = 2;
-  constexpr int T0 = N0 / 32, T1 = N1 / 32;
-  constexpr int A_ST = BM * 64;                               // 16 KB: [row][4 x 16 B] (hi k0-7 | hi k8-15 | lo | lo)
-  constexpr int B0_ST = (N0 / 128) * 8192;                    // 16 KB
-  constexpr int kStage = A_ST + B0_ST;
-  constexpr int NSTG = 4;
-  constexpr int kPair0 = NSTG * kStage;                       // W1 pair 0 behind the ring
-  constexpr int kBias = kPair0 + 16384;
-  static_assert(BM * N1 * 4 <= kPair0, "scan tile overlaps pair 0 / the bias table");
-  static_assert(7 * 16384 <= kPair0, "W1 pairs 1..7 take the ring's place");
-  __shared__ __attribute__((aligned(16))) float smem[kBias / 4 + N0 + N1];   // 145.5 KB
-  char* const sm = reinterpret_cast<char*>(smem);
-  float* const bias0 = reinterpret_cast<float*>(sm + kBias);
-  float* const bias1 = bias0 + N0;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int l31 = lane & 31, lhi = lane >> 5;
-  const int Meff = min(*a.row_count, a.M);
-  const int m0 = blockIdx.x * BM;
-  if (m0 >= Meff) return;
-
-  for (int i = tid; i < N0 + N1; i += NT)
-    bias0[i] = i < N0 ? (i < a.H ? a.b0[i] : 0.f) : (i - N0 < a.D ? a.b1[i - N0] : 0.f);
-
-  // W1 pair p = k-steps 2p, 2p + 1 (16 KB)
-  auto issue_b1_pair = [&](int p, int dst_off) {
-    const char* src = a.w1 + (int64_t)p * 16384 + tid * 16;
-    char* dst = sm + dst_off + tid * 16;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)(src + NT * 16 * q), (lds_void_t*)(dst + NT * 16 * q), 16, 0, 0);
-  };
-  issue_b1_pair(0, kPair0);
-
-  // rows: thread = (row tid >> 2 (+ 64 i), 16-byte chunk tid & 3); the DMA writes LDS lane-contiguously,
-  // so each lane FETCHES the global chunk its (XOR-swizzled) slot holds
-  const char* xs_px[4];
-  bool r_ok[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = (tid >> 2) + 64 * i;
-    const int m = m0 + row;
-    r_ok[i] = m < Meff;
-    const int c = (tid & 3) ^ ((row >> 1) & 3);
-    xs_px[i] = r_ok[i] ? reinterpret_cast<const char*>(a.x + (int64_t)a.rows[m] * a.x_stride) + c * 16
-                       : reinterpret_cast<const char*>(kZeroChunk);
-  }
-  auto issue_slab = [&](int stg, int s_) {
-    char* const base = sm + stg * kStage;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)(xs_px[i] + (r_ok[i] ? s_ * 64 : 0)),
-                                       (lds_void_t*)(base + (tid + NT * i) * 16), 16, 0, 0);
-#pragma unroll
-    for (int p = 0; p < B0_ST / 16 / NT; ++p) {
-      const int slot = tid + NT * p;
-      const int j = slot >> 9;
-      const char* src = a.w0 + ((int64_t)j * a.ctiles0 + s_) * 8192 + (slot & 511) * 16;
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)src, (lds_void_t*)(base + A_ST + 16 * slot), 16, 0, 0);
-    }
-  };
-  constexpr int kSlabOps = 4 + B0_ST / 16 / NT;                 // DMA instructions per thread and slab
-  const int nk0 = a.ctiles0 - a.skip_n;
-  auto slab_of = [&](int kt) { return kt < a.skip_lo ? kt : kt + a.skip_n; };   // the kt-th visited slab
-#pragma unroll
-  for (int kt = 0; kt < NSTG - 1; ++kt)
-    if (kt < nk0) issue_slab(kt, slab_of(kt));
-
-  f32x16 acc0[RB][T0];
-#pragma unroll
-  for (int b = 0; b < RB; ++b)
-#pragma unroll
-    for (int t = 0; t < T0; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc0[b][t][r] = 0.f;
-
-  int a_off[RB], a_lo_off[RB];
-#pragma unroll
-  for (int b = 0; b < RB; ++b) {
-    const int R = 64 * wid + 32 * b + l31;                      // this lane's row of the tile
-    a_off[b] = R * 64 + ((lhi ^ ((R >> 1) & 3)) * 16);
-    a_lo_off[b] = R * 64 + (((2 + lhi) ^ ((R >> 1) & 3)) * 16);
-  }
-  const int w_off = l31 * 32 + ((lhi ^ ((l31 >> 3) & 1)) * 16);   // column 32 t' + l31 of a 128-tile
-
-  for (int kt = 0; kt < nk0; ++kt) {
-    // slabs <= kt + 2 are issued; slab kt must have landed, the younger ones may travel on
-    const int younger = min(kt + 2, nk0 - 1) - kt;
-    if (younger == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kSlabOps) : "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kSlabOps) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    // every wave is past slab kt - 1: its stage takes slab kt + 3
-    if (kt + NSTG - 1 < nk0) issue_slab((kt + NSTG - 1) & (NSTG - 1), slab_of(kt + NSTG - 1));
-    const char* const st = sm + (kt & (NSTG - 1)) * kStage;
-    bf16x8 x_hi[RB], x_lo[RB];
-#pragma unroll
-    for (int b = 0; b < RB; ++b) {
-      x_hi[b] = *reinterpret_cast<const bf16x8*>(st + a_off[b]);
-      x_lo[b] = *reinterpret_cast<const bf16x8*>(st + a_lo_off[b]);
-    }
-    const char* const bs = st + A_ST + w_off;
-#pragma unroll
-    for (int g = 0; g < T0 / 4; ++g) {
-      bf16x8 w_hi[4], w_lo[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int t = 4 * g + j;
-        const char* p0 = bs + (t >> 2) * 8192 + (t & 3) * 1024;
-        w_hi[j] = *reinterpret_cast<const bf16x8*>(p0);
-        w_lo[j] = *reinterpret_cast<const bf16x8*>(p0 + 4096);
-      }
-      // per accumulator: x_lo w_hi, x_hi w_lo, x_hi w_hi (conv_split's order at NS = 2)
-#pragma unroll
-      for (int b = 0; b < RB; ++b) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc0[b][4 * g + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_hi[j], x_lo[b], acc0[b][4 * g + j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc0[b][4 * g + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_lo[j], x_hi[b], acc0[b][4 * g + j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc0[b][4 * g + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_hi[j], x_hi[b], acc0[b][4 * g + j], 0, 0, 0);
-      }
-    }
-  }
-  // every wave is done with the ring: W1 pairs 1..7 take its place while the hidden activations
-  // are converted (pair 0 has landed: the last slab's wait drained the queue)
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma unroll
-  for (int p = 1; p < 8; ++p) issue_b1_pair(p, (p - 1) * 16384);
-
-  // ---- hidden = relu(acc0 + b0) -> the GEMM1 operand fragments, in place of the accumulators ----
-  u32x4 f_hi[RB][T0][2], f_lo[RB][T0][2];
-#pragma unroll
-  for (int b = 0; b < RB; ++b)
-#pragma unroll
-    for (int t = 0; t < T0; ++t)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        f32x4 v[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const f32x4 bb = *reinterpret_cast<const f32x4*>(bias0 + 32 * t + 16 * s + 8 * q + 4 * lhi);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[q][e] = snap_relu(acc0[b][t][8 * s + 4 * q + e] + bb[e]);
-        }
-        // half 0: columns 0-3 | 8-11, half 1: 4-7 | 12-15  ->  half 0: 0-7, half 1: 8-15
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[0][e]),
-                                                           __float_as_uint(v[1][e]), false, false);
-          v[0][e] = __uint_as_float(sw[0]);
-          v[1][e] = __uint_as_float(sw[1]);
-        }
-        u32x2 h0, l0, h1, l1;
-        split2(v[0], h0, l0);
-        split2(v[1], h1, l1);
-        f_hi[b][t][s] = u32x4{h0[0], h0[1], h1[0], h1[1]};
-        f_lo[b][t][s] = u32x4{l0[0], l0[1], l1[0], l1[1]};
-      }
-
-  // ---- GEMM1: W1 resident, one barrier per pair of k-steps (the pair's arrival) ------------------
-  f32x16 acc1[RB][T1];
-#pragma unroll
-  for (int b = 0; b < RB; ++b)
-#pragma unroll
-    for (int t = 0; t < T1; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc1[b][t][r] = 0.f;
-#pragma unroll
-  for (int pr = 0; pr < 8; ++pr) {
-    if (pr >= 1) {                                              // pairs pr + 1 .. 7 may travel on (4 DMAs each)
-      switch (7 - pr) {
-        case 6: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    }
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-      const char* ws = sm + (pr == 0 ? kPair0 : (pr - 1) * 16384) + sub * 8192 + w_off;
-      bf16x8 w_hi[T1], w_lo[T1];
-#pragma unroll
-      for (int j = 0; j < T1; ++j) {
-        const char* p0 = ws + j * 1024;
-        w_hi[j] = *reinterpret_cast<const bf16x8*>(p0);
-        w_lo[j] = *reinterpret_cast<const bf16x8*>(p0 + 4096);
-      }
-#pragma unroll
-      for (int b = 0; b < RB; ++b) {
-        bf16x8 h_hi, h_lo;
-        __builtin_memcpy(&h_hi, &f_hi[b][pr][sub], 16);
-        __builtin_memcpy(&h_lo, &f_lo[b][pr][sub], 16);
-#pragma unroll
-        for (int j = 0; j < T1; ++j)
-          acc1[b][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_hi[j], h_lo, acc1[b][j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < T1; ++j)
-          acc1[b][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_lo[j], h_hi, acc1[b][j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < T1; ++j)
-          acc1[b][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_hi[j], h_hi, acc1[b][j], 0, 0, 0);
-      }
-    }
-  }
-
-  // ---- + b1, stage [256 rows][128 channels] (float4 quads XOR-swizzled by the row) -------------
-#pragma unroll
-  for (int b = 0; b < RB; ++b)
-#pragma unroll
-    for (int j = 0; j < T1; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(bias1 + 32 * j + 8 * q + 4 * lhi);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc1[b][j][4 * q + e] += bb[e];
-      }
-  __syncthreads();                                                // W1 drained
-#pragma unroll
-  for (int b = 0; b < RB; ++b) {
-    const int R = 64 * wid + 32 * b + l31;
-#pragma unroll
-    for (int j = 0; j < T1; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int quad = (8 * j + 2 * q + lhi) ^ (R & 31);
-        *reinterpret_cast<f32x4*>(smem + R * N1 + 4 * quad) =
-            f32x4{acc1[b][j][4 * q], acc1[b][j][4 * q + 1], acc1[b][j][4 * q + 2], acc1[b][j][4 * q + 3]};
-      }
-  }
-  __syncthreads();
-
-  // ---- segmented max down the rows: thread = (channel, half of the tile), 2 x 64 rows ------------
-  const int c = tid & 127;
-  const int h = tid >> 7;                                         // wave-uniform (two waves per half)
-  int cur = -1;
-  float run = -INFINITY;
-  const bool live = c < a.D;
-  for (int q = 0; q < 2; ++q) {
-    const int my = m0 + 128 * h + 64 * q + lane;
-    const int cid = my < Meff ? a.rows[my] / a.Z : -1;
-    float vals[64];                          // (read ahead of the branches, as in the 128-row kernel)
-#pragma unroll
-    for (int r = 0; r < 64; ++r) {
-      const int row = 128 * h + 64 * q + r;
-      vals[r] = smem[row * N1 + ((((c >> 2) ^ (row & 31)) << 2) | (c & 3))];
-    }
-#pragma unroll
-    for (int r = 0; r < 64; ++r) {
-      const int cr = __builtin_amdgcn_readlane(cid, r);
-      if (cr != cur) {
-        if (cur >= 0 && live) atomic_max_f32(a.plane + (int64_t)cur * a.D + c, run);
-        cur = cr;
-        run = -INFINITY;
-      }
-      run = snap_max_nan(run, vals[r]);
-    }
   }
   if (cur >= 0 && live) atomic_max_f32(a.plane + (int64_t)cur * a.D + c, run);
 }
@@ -907,9 +529,9 @@ static int mlp2_pool_check(const float* x, int64_t M, int32_t Cin, int32_t x_str
       ncols <= 0 || ncols * Z > 0x7fffffffLL)
     return SNAP_ERR_BAD_SHAPE;
   if (H <= 0 || H % 32 != 0 || H > 256 || D <= 0 || D % 4 != 0 || D > 128) return SNAP_ERR_UNSUPPORTED;
-  // x_split: 0 f32 rows | 1 pre-split rows (three-stage ring) | 3 / 5 its measured alternatives; 7 (tap records) is
-  // internal to snap_mlp2_pool_max_gather_f32, which brings the records and the image with it
-  if (x_split != 0 && x_split != 1 && x_split != 3 && x_split != 5) return SNAP_ERR_UNSUPPORTED;
+  // x_split: 0 f32 rows | 1 pre-split rows; 7 (tap records) is internal to snap_mlp2_pool_max_gather_f32,
+  // which brings the records and the image with it
+  if (x_split != 0 && x_split != 1) return SNAP_ERR_UNSUPPORTED;
   if (x_split && (relu_in || x_stride < ((Cin + 15) / 16) * 16)) return SNAP_ERR_UNSUPPORTED;
   if (w0_bytes < snap_conv2d_packed_weights_split_bytes(1, Cin, H, 2) ||
       w1_bytes < snap_conv2d_packed_weights_split_bytes(1, H, D, 2))
@@ -921,31 +543,23 @@ static int mlp2_pool_check(const float* x, int64_t M, int32_t Cin, int32_t x_str
 }
 
 static void mlp2_pool_launch(const MlpPoolArgs& a, int relu_in, int x_split, hipStream_t s) {
-  constexpr int NT = SNAP_MLP_POOL_NT;
   if (x_split == 7) {                                // tap records: the gather inside the kernel
     int64_t nb = snap_cdiv(a.M, 128);
     if (a.xcd_group > 0) nb = snap_cdiv(nb, 8LL * a.xcd_group) * 8LL * a.xcd_group;
-    if (a.H <= 128) hipLaunchKernelGGL((mlp2_pool_kernel<128, false, false, 256, 2, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((mlp2_pool_kernel<256, false, false, 256, 2, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+    if (a.H <= 128) hipLaunchKernelGGL((mlp2_pool_kernel<128, false, false, 2, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((mlp2_pool_kernel<256, false, false, 2, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
     return;
   }
-  if (x_split == 3 && !relu_in && a.H == 256) {      // 256-row tiles: measured slower (see the kernel), opt-in
-    hipLaunchKernelGGL((mlp2_pool_wide_kernel<256>), dim3((unsigned)snap_cdiv(a.M, 256)), dim3(256), 0, s, a);
-    return;
-  }
-  const dim3 grid((unsigned)snap_cdiv(a.M, NT / 2));
-  // pre-split rows: the three-stage ring (x_split = 5: the two-stage loop, tuning / tests)
-  constexpr bool kRingOk = NT == 256;
+  const dim3 grid((unsigned)snap_cdiv(a.M, 128));
+  // pre-split rows: the three-stage ring
   if (a.H <= 128) {
-    if (x_split && x_split != 5 && kRingOk) hipLaunchKernelGGL((mlp2_pool_kernel<128, false, true, 256, 3>), grid, dim3(NT), 0, s, a);
-    else if (x_split) hipLaunchKernelGGL((mlp2_pool_kernel<128, false, true, NT>), grid, dim3(NT), 0, s, a);
-    else if (relu_in) hipLaunchKernelGGL((mlp2_pool_kernel<128, true, false, NT>), grid, dim3(NT), 0, s, a);
-    else hipLaunchKernelGGL((mlp2_pool_kernel<128, false, false, NT>), grid, dim3(NT), 0, s, a);
+    if (x_split) hipLaunchKernelGGL((mlp2_pool_kernel<128, false, true, 3>), grid, dim3(256), 0, s, a);
+    else if (relu_in) hipLaunchKernelGGL((mlp2_pool_kernel<128, true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((mlp2_pool_kernel<128, false, false>), grid, dim3(256), 0, s, a);
   } else {
-    if (x_split && x_split != 5 && kRingOk) hipLaunchKernelGGL((mlp2_pool_kernel<256, false, true, 256, 3>), grid, dim3(NT), 0, s, a);
-    else if (x_split) hipLaunchKernelGGL((mlp2_pool_kernel<256, false, true, NT>), grid, dim3(NT), 0, s, a);
-    else if (relu_in) hipLaunchKernelGGL((mlp2_pool_kernel<256, true, false, NT>), grid, dim3(NT), 0, s, a);
-    else hipLaunchKernelGGL((mlp2_pool_kernel<256, false, false, NT>), grid, dim3(NT), 0, s, a);
+    if (x_split) hipLaunchKernelGGL((mlp2_pool_kernel<256, false, true, 3>), grid, dim3(256), 0, s, a);
+    else if (relu_in) hipLaunchKernelGGL((mlp2_pool_kernel<256, true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((mlp2_pool_kernel<256, false, false>), grid, dim3(256), 0, s, a);
   }
 }
 

@@ -169,9 +169,6 @@ __global__ __launch_bounds__(256, DM <= 32 ? 4 : 2) void sim_mfma_kernel(
     const int row = n0 + 32 * t + l31;
     sim_load_operand<DM>(fq + ((int64_t)b * Nq + (row < Nq ? row : 0)) * DM, row < Nq, lhi, aq[t]);
   }
-#ifndef SNAP_SIM_ABLATE
-#define SNAP_SIM_ABLATE 0          // timing experiments only: 1 no sim stores, 2 no MFMAs, 4 no exp
-#endif
   // Epilogue through a per-wave LDS tile (32 rows x 64 cells, one ti at a time): the MFMA C
   // layout gives a lane ONE cell of 16 rows -- 64 dword stores per tile, and narrow stores are
   // issue-bound.  Staged, 16 lanes own one query row's 64 cells as float4: a wave store covers
@@ -195,7 +192,7 @@ __global__ __launch_bounds__(256, DM <= 32 ? 4 : 2) void sim_mfma_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
 #pragma unroll
-    for (int j = 0; j < ((SNAP_SIM_ABLATE & 2) ? 1 : DM / 2); ++j)
+    for (int j = 0; j < DM / 2; ++j)
 #pragma unroll
       for (int tj = 0; tj < 2; ++tj)
         acc[tj] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[ti][j], bq[tj][j], acc[tj], 0, 0, 0);
@@ -227,15 +224,14 @@ __global__ __launch_bounds__(256, DM <= 32 ? 4 : 2) void sim_mfma_kernel(
       float sum = 0.f;
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if (c4 + e < ncell) sum += (SNAP_SIM_ABLATE & 4) ? (x[e] - m) : __expf(x[e] - m);   // v_exp_f32: ~1e-6 relative on the chunk mass
+        if (c4 + e < ncell) sum += __expf(x[e] - m);   // v_exp_f32: ~1e-6 relative on the chunk mass
       sum += snap_dpp<0x128>(sum);
       sum += snap_dpp<0x124>(sum);
       sum += snap_dpp<0x122>(sum);
       sum += snap_dpp<0x121>(sum);
       if (live) {
         float* o = sim + row * XY + cell0 + c4;
-        if (SNAP_SIM_ABLATE & 1) {
-        } else if (c4 + 3 < ncell && ((XY & 3) == 0)) {
+        if (c4 + 3 < ncell && ((XY & 3) == 0)) {
           *reinterpret_cast<f32x4*>(o) = f32x4{x[0] * wrow, x[1] * wrow, x[2] * wrow, x[3] * wrow};
         } else {
 #pragma unroll
@@ -1900,10 +1896,7 @@ extern "C" int snap_ransac_sample_sim_f32(const float* fq, const float* fm,
     const int NC = (X * Y + SIM_CH - 1) / SIM_CH;
     // (without a workspace: the table-free kernel, one correspondence per wave, same samples)
     if (lane_incl && sim && row_unscale && (NC + 63) / 64 <= 64) {
-#ifndef SNAP_RANSAC_NQ
-#define SNAP_RANSAC_NQ 4
-#endif
-      constexpr int NQ = SNAP_RANSAC_NQ;
+      constexpr int NQ = 4;
       const dim3 fgrid((unsigned)snap_cdiv(S, 4 * NQ), (unsigned)B);
       hipLaunchKernelGGL(ransac_sample_fast_kernel<NQ>, fgrid, dim3(256), 0, s, chunk_stats, Nq, X, Y, S,
                          seed, uniforms, corr, (const float*)lane_incl, (const float*)rowmax, row_cdf,

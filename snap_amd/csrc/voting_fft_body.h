@@ -340,12 +340,6 @@ VF_DEV void fft_lds(float2* buf, const float2* tw, const Plan& pl, int tid, int 
   }
 }
 
-// Timing ablations exist only in alt builds (-DVF_ABLATE=<bits>, WRONG results).  Dot launch: 1 = no X1 row
-// load, 2 = no forward transform, 4 = no map-spectrum loads, 8 = no inverse, 16 = no column sums; slow-axis launch
-// of a rotated call: 32 = no tap loads, 64 = no transform, 128 = no store of the half-transformed rows
-#ifndef VF_ABLATE
-#define VF_ABLATE 0
-#endif
 // The first forward stage where its partners are zero padding.  N = 3 * 2^a and n_in <= N / 3 (templates
 // of the map's own size: 256 rows in 768 transform points): the radix-3 butterfly {x[k], x[k + N/3],
 // x[k + 2N/3]} has x1 = x2 = 0, so the thread that STAGES x[k] runs the butterfly on the value it holds
@@ -411,7 +405,7 @@ VF_DEV void slow_body(const SlowArgs& a, int bx, int by, int tid, int nt, float2
     const int r = batch / a.G, g = batch - r * a.G, RQ = a.R >> 2;
     const int k = r / RQ, r0 = r - k * RQ;
     const int c = kGroupCh * g + 2 * p;
-    const bool cok = c < a.D && !(VF_ABLATE & 32);
+    const bool cok = c < a.D;
     const float2 zero2 = {0.f, 0.f};
     for (; row_first + (kRotB - 1) * nslot < M0; row_first += kRotB * nslot) {
       SnapRotSample rs[kRotB];
@@ -478,7 +472,7 @@ VF_DEV void slow_body(const SlowArgs& a, int bx, int by, int tid, int nt, float2
         snap_rot90_source(k, row, col, a.sH, a.sW, &si, &sj);
         const SnapRotSample rs = snap_rot_sample(a.tfm + r0 * 4, si, sj, a.sH, a.sW, a.cell, a.srcb);
         const int c = kGroupCh * g + 2 * p;
-        if (rs.ok && c < a.D && !(VF_ABLATE & 32)) {
+        if (rs.ok && c < a.D) {
           const float* f00 = a.srcf + ((int64_t)rs.i0 * a.sW + rs.j0) * a.D + c;
           const float* f01 = a.srcf + ((int64_t)rs.i0 * a.sW + rs.j1) * a.D + c;
           const float* f10 = a.srcf + ((int64_t)rs.i1 * a.sW + rs.j0) * a.D + c;
@@ -522,9 +516,9 @@ VF_DEV void slow_body(const SlowArgs& a, int bx, int by, int tid, int nt, float2
     }
   }
   VF_SYNC();
-  if (!(VF_ABLATE & 64)) fft_lds<kCols, false>(buf, twl, a.pl, tid, nt, fuse0);
+  fft_lds<kCols, false>(buf, twl, a.pl, tid, nt, fuse0);
   float2* d = a.dst + ((int64_t)batch * N * a.ncols + col) * kCols + p;
-  for (int row = slot; row < N && !(VF_ABLATE & 128); row += nslot) d[(int64_t)row * a.ncols * kCols] = buf[vf_phys<kCols>(row) * kCols + p];
+  for (int row = slot; row < N; row += nslot) d[(int64_t)row * a.ncols * kCols] = buf[vf_phys<kCols>(row) * kCols + p];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -571,7 +565,7 @@ VF_DEV void fast_body(const FastArgs& a, int bx, int by, int tid, int nt, float2
     for (int u = 0; u < kXPre; ++u) {
       const int i = tid + u * nt;
       pre[u].x = pre[u].y = pre[u].z = pre[u].w = 0.f;
-      if (i < n4_in && i < n4_st && !(VF_ABLATE & 1)) pre[u] = src0[i];
+      if (i < n4_in && i < n4_st) pre[u] = src0[i];
     }
   }
   if (fuse0) VF_SYNC();                                      // (the staging reads the twiddles)
@@ -583,7 +577,7 @@ VF_DEV void fast_body(const FastArgs& a, int bx, int by, int tid, int nt, float2
       float4 v; v.x = v.y = v.z = v.w = 0.f;
       if (u < kXPre) {
         v = u == 0 ? pre[0] : pre[kXPre - 1];                // (kXPre == 2)
-      } else if (i < n4_in && !(VF_ABLATE & 1)) {
+      } else if (i < n4_in) {
         v = src[i];
       }
       if (fuse0) {
@@ -607,7 +601,7 @@ VF_DEV void fast_body(const FastArgs& a, int bx, int by, int tid, int nt, float2
       for (int u = 0; u < kXPre; ++u) {
         const int i = tid + u * nt;
         pre[u].x = pre[u].y = pre[u].z = pre[u].w = 0.f;
-        if (i < n4_in && i < n4_st && !(VF_ABLATE & 1)) pre[u] = nsrc[i];
+        if (i < n4_in && i < n4_st) pre[u] = nsrc[i];
       }
     }
     // DOT: this row of the map spectrum (98 KB, shared by every rotation: L2 / Infinity-Cache resident
@@ -625,7 +619,7 @@ VF_DEV void fast_body(const FastArgs& a, int bx, int by, int tid, int nt, float2
       for (int line = tid + nt; line < nlines; line += nt) touch += zt[line * 32];   // ... (smaller workgroups: the rest)
     }
     VF_SYNC();
-    if (!(VF_ABLATE & 2) || a.mode != kFastDot) fft_lds<kCols, false>(buf, twl, a.pl, tid, nt, fuse0);
+    fft_lds<kCols, false>(buf, twl, a.pl, tid, nt, fuse0);
     if (a.mode == kFastStore16) {
       float4* d = reinterpret_cast<float4*>(a.out + (batch * a.N1 + k1) * N * kCols);
       for (int i = tid; i < n4; i += nt) d[i] = b4[vf_phys4(i)];
@@ -641,7 +635,7 @@ VF_DEV void fast_body(const FastArgs& a, int bx, int by, int tid, int nt, float2
         for (int u = 0; u < kZPre; ++u) {
           const int i = i0 + u * nt;
           zreg[u].x = zreg[u].y = zreg[u].z = zreg[u].w = 0.f;
-          if (i < n4 && !(VF_ABLATE & 4)) zreg[u] = z4[i];
+          if (i < n4) zreg[u] = z4[i];
         }
 #pragma unroll
         for (int u = 0; u < kZPre; ++u) {
@@ -651,7 +645,7 @@ VF_DEV void fast_body(const FastArgs& a, int bx, int by, int tid, int nt, float2
       }
       VF_KEEP(touch);                                  // the touch loads' only use: after the transform
       VF_SYNC();
-      for (int k2 = tid; k2 < N && !(VF_ABLATE & 16); k2 += nt) {
+      for (int k2 = tid; k2 < N; k2 += nt) {
         const int ks = vf_phys<1>(k2), kb = vf_phys<kCols>(k2) * kCols;
         float2 acc = sbuf[ks];
 #pragma unroll
@@ -667,7 +661,7 @@ VF_DEV void fast_body(const FastArgs& a, int bx, int by, int tid, int nt, float2
     VF_SYNC();
   }
   if (a.mode == kFastDot) {
-    if (!(VF_ABLATE & 8)) fft_lds<1, true>(sbuf, twl, a.pl, tid, nt);
+    fft_lds<1, true>(sbuf, twl, a.pl, tid, nt);
     float2* d = a.out + ((int64_t)outer * a.N1 + k1) * a.ld_out;
     for (int t = tid; t < a.nb_out; t += nt) d[t] = sbuf[vf_phys<1>(t)];
   } else if (a.mode == kFastMul) {

@@ -41,11 +41,10 @@ SIM_CHUNK = 64
 #   USE_PRESPLIT       bottleneck 3x3 / closing 1x1 convs read their input through gn_norm_split (off:
 #                      the pre-split convs are 10-25 percent faster, the extra pass costs what they gain)
 #   CONV_TILE / CONV_BK / CONV_NO_HALO / CONV_NO_RS / CONV_RS_NSPLIT / CONV_RS_FORCE / CONV_NO_WS /
-#   CONV_NO_PLAIN / CONV_RAW_RING   forced tile ('128x128' | '128x64' | '64x128' | '64x64'), f32 K-slab
+#   CONV_NO_PLAIN      forced tile ('128x128' | '128x64' | '64x128' | '64x64'), f32 K-slab
 #                      depth, and which body a conv launch takes (tests pin every body against the others)
 #   SPLITK_STATS / USE_SPLITK / USE_FUSED_GN_STATS / GN_STATS_BOTH   GroupNorm statistics from the conv
 #                      epilogues / split-K reduce passes vs the stand-alone kernels
-#   MLP_POOL_NO_RING / MLP_POOL_WIDE   fused MLP / pool kernel variants (x_split = 5 / 3)
 #   USE_PRESPLIT_VOTING / FUSED_TEMPLATE_PACK / PS_RES_INIT / PS_TILE   pre-split GEMM engine (direct-form voting)
 #   SIM_GENERAL_KERNEL  tests: pin the general similarity kernel (the full-chunk kernel is bit-identical)
 #   LATTICE_WINDOW     the refinement lattice scored from one window per point (pose_score_window; same bits)
@@ -68,10 +67,7 @@ _TUNING_DEFAULTS = {
     'CONV_RS_FORCE': False,
     'CONV_NO_WS': False,
     'SPLITK_STATS': True,
-    'MLP_POOL_NO_RING': False,
-    'MLP_POOL_WIDE': False,
     'CONV_NO_PLAIN': False,
-    'CONV_RAW_RING': False,
     'USE_PRESPLIT_VOTING': True,
     'PS_RES_INIT': True,
     'PS_TILE': 0,
@@ -751,11 +747,11 @@ def conv2d(
       ex.x_presplit = 1
       ex.ps_tile = pst
       ex.ps_res_init = int(tuning().PS_RES_INIT if res_init is None else bool(res_init))
-  if tuning().CONV_BK or tuning().CONV_NO_HALO or tuning().CONV_RS_NSPLIT or tuning().CONV_NO_PLAIN or tuning().CONV_RAW_RING:
+  if tuning().CONV_BK or tuning().CONV_NO_HALO or tuning().CONV_RS_NSPLIT or tuning().CONV_NO_PLAIN:
     if ex is None:
       ex = _lib.SnapConvExtras(None, None, None, None, 0, 0, None, 0, None, 0)
     ex.bk_hint = int(tuning().CONV_BK or 0)
-    ex.tune_flags = (int(bool(tuning().CONV_NO_HALO)) | 2 * int(bool(tuning().CONV_RAW_RING)) | 8 * int(bool(tuning().CONV_NO_PLAIN))
+    ex.tune_flags = (int(bool(tuning().CONV_NO_HALO)) | 8 * int(bool(tuning().CONV_NO_PLAIN))
                      | ((int(tuning().CONV_RS_NSPLIT) & 15) << 4))
   kflops = 2.0 * KH * KW * Cin * Cout
   if row_count is None:
@@ -1210,7 +1206,7 @@ def mlp2_pool_max(x, row_mask, w0, b0, w1, b1, *, cin, Z, relu_in=False, x_split
     st = lib.snap_mlp2_pool_max_classes_f32(
         _p(x), M, cin, Cs, _p(index), _p(count), _p(index_z) if index_z is not None else None,
         _p(count_z) if count_z is not None else None, zlo, zn, _p(w0p), w0p.numel() * 2, _p(b0), H,
-        _p(w1p), w1p.numel() * 2, _p(b1), D, int(relu_in), (3 if tuning().MLP_POOL_WIDE else 5 if tuning().MLP_POOL_NO_RING else 1) if x_split else 0, Z, ncols, _p(plane),
+        _p(w1p), w1p.numel() * 2, _p(b1), D, int(relu_in), 1 if x_split else 0, Z, ncols, _p(plane),
         _p(pvalid), _stream())
   _lib.check(st, 'snap_mlp2_pool_max_classes_f32')
   return plane, pvalid

@@ -677,14 +677,14 @@ def test_train_step_rejects_a_precision_that_contradicts_the_models_engine():
   assert any('dynamic_scale' in str(w.message) for w in rec)
 
 
-def test_tuning_object_scopes_and_module_aliases():
+def test_tuning_scopes_and_module_aliases():
   """Every tuning / test switch of the kernel wrappers lives in ONE ``ops.Tuning`` object: per-thread scopes
   (``ops.tuning_scope`` / ``ops.engine_scope(engine, tuning=...)``), the module attributes are aliases (read:
   the tuning in force; write: the process default), unknown switches raise."""
   import threading
   assert ops.tuning() is ops._DEFAULT_TUNING and ops.CONV_TILE is None and ops.LIFT_IN_CONSUMER is True
-  with ops.tuning_scope(CONV_TILE='64x64', MLP_POOL_WIDE=True) as t:
-    assert ops.CONV_TILE == '64x64' and ops.MLP_POOL_WIDE is True and ops.tuning() is t
+  with ops.tuning_scope(CONV_TILE='64x64', CONV_NO_PLAIN=True) as t:
+    assert ops.CONV_TILE == '64x64' and ops.CONV_NO_PLAIN is True and ops.tuning() is t
     seen = {}
     th = threading.Thread(target=lambda: seen.update(tile=ops.CONV_TILE))     # another thread: the default
     th.start(); th.join()
@@ -692,7 +692,7 @@ def test_tuning_object_scopes_and_module_aliases():
     with ops.engine_scope('bf16x3', tuning=ops.Tuning(CONV_NO_HALO=True)):
       assert ops.precision() == 'bf16x3' and ops.CONV_NO_HALO is True and ops.CONV_TILE is None
     assert ops.CONV_TILE == '64x64' and ops.CONV_NO_HALO is False
-  assert ops.CONV_TILE is None and ops.MLP_POOL_WIDE is False
+  assert ops.CONV_TILE is None and ops.CONV_NO_PLAIN is False
   ops.CONV_RS_FORCE = True                       # (module attribute = the process default)
   try:
     assert ops.tuning().CONV_RS_FORCE is True and repr(ops.tuning()) == 'Tuning(CONV_RS_FORCE=True)'
@@ -705,3 +705,18 @@ def test_tuning_object_scopes_and_module_aliases():
       pass
   # no switch is left as a plain module global (they would shadow nothing, and nothing would read them)
   assert not [k for k in ops._TUNING_DEFAULTS if k in vars(ops)]
+
+
+def test_every_tuning_switch_is_read():
+  """Each key of ``ops._TUNING_DEFAULTS`` is read by name somewhere in the package (the table holds the keys
+  as strings, so any identifier of that name is a use): a switch whose body was removed goes with it."""
+  import io
+  import pathlib
+  import tokenize
+  pkg = pathlib.Path(ops.__file__).parent
+  names = set()
+  for f in pkg.rglob('*.py'):
+    for tok in tokenize.generate_tokens(io.StringIO(f.read_text()).readline):
+      if tok.type == tokenize.NAME:
+        names.add(tok.string)
+  assert not [k for k in ops._TUNING_DEFAULTS if k not in names]

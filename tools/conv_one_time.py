@@ -1,6 +1,5 @@
 """Average launch time of one layer of tools/conv_bench.LAYERS on one engine (helper of
-conv_ablate_split.py)."""
-import os
+scripts/gpu_r6_pmc_probe.sh)."""
 import sys
 
 import torch
@@ -12,7 +11,6 @@ import conv_bench  # noqa: E402
 
 name, xs, ws, stride, pad, pro = conv_bench.LAYERS[int(sys.argv[1])]
 math = sys.argv[2]
-os.environ['SNAP_ALT_ABLATE'] = sys.argv[3] if len(sys.argv) > 3 else '0'   # timing-only ablation bits (alt build only)
 dev = 'cuda'
 g = torch.Generator(device=dev).manual_seed(0)
 x = torch.randn(xs, device=dev, generator=g)

@@ -1,7 +1,5 @@
 """Isolated timing of the fused fusion-MLP / vertical max-pool kernel at the C2 map size (8 scenes x
-128 x 128 columns x 60 levels, 87 % of the voxels observed, 72 % of those by one view): the 128-row
-kernel with the two-stage GEMM0 loop (ops.MLP_POOL_NO_RING), with the three-stage ring (the default) and the opt-in
-256-row kernel (ops.MLP_POOL_WIDE), on the same pre-split rows."""
+128 x 128 columns x 60 levels, 87 % of the voxels observed, 72 % of those by one view), on pre-split rows."""
 import argparse
 import json
 
@@ -28,29 +26,17 @@ def main():
   b0 = torch.zeros(H, device=dev)
   w1 = torch.randn((H, D), generator=g, device=dev) / H ** 0.5
   b1 = torch.zeros(D, device=dev)
-  out = {}
-  planes = {}
-  for name, narrow, ring3 in (('rows128', True, False), ('rows128_ring3', True, True), ('rows256', False, False),
-                              ('rows128_b', True, False), ('rows128_ring3_b', True, True)):
-    ops.MLP_POOL_WIDE = not narrow
-    ops.MLP_POOL_NO_RING = not ring3
-    kw = dict(cin=cin, Z=Z, x_split=True, zero_slabs=(8, 8))
-    for _ in range(2):
-      p, v = ops.mlp2_pool_max(xs, cls, w0, b0, w1, b1, **kw)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.reps):
-      p, v = ops.mlp2_pool_max(xs, cls, w0, b0, w1, b1, **kw)
-    e1.record()
-    torch.cuda.synchronize()
-    out[name] = round(e0.elapsed_time(e1) / args.reps, 4)
-    planes[name] = p
-  ops.MLP_POOL_WIDE = False
-  ops.MLP_POOL_NO_RING = False
-  out['equal_ring3'] = bool(torch.equal(planes['rows128'], planes['rows128_ring3']))
-  out['equal'] = bool(torch.equal(planes['rows128'], planes['rows256']))
-  print(json.dumps(out))
+  kw = dict(cin=cin, Z=Z, x_split=True, zero_slabs=(8, 8))
+  for _ in range(2):
+    ops.mlp2_pool_max(xs, cls, w0, b0, w1, b1, **kw)
+  torch.cuda.synchronize()
+  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  e0.record()
+  for _ in range(args.reps):
+    ops.mlp2_pool_max(xs, cls, w0, b0, w1, b1, **kw)
+  e1.record()
+  torch.cuda.synchronize()
+  print(json.dumps({'ms': round(e0.elapsed_time(e1) / args.reps, 4)}))
 
 
 if __name__ == '__main__':
