@@ -326,6 +326,26 @@ int snap_occupancy_head_f32(const float* hits, const float* origins, const uint8
                             const float* w1, const float* b1, int32_t h2, const float* w_out,
                             const float* b_out, float* out_points, uint8_t* out_labels, uint8_t* out_ray_valid,
                             float* logits, uint8_t* valid, void* stream);
+/* VJP of snap_occupancy_ray_features_f32 into the volume: the transpose of the trilinear gather of
+ * interpolate_nd (grids.py:116-137) at the query points of occupancy_net.py:106-111.  Same point source
+ * as the forward (rays or explicit points: they are data and get no gradient); volume validity does
+ * not enter.  d_features [B * P, D] -> d_volume [B, X, Y, Z, D], every element written (untouched voxels
+ * +0).  Each point's 8 taps are re-derived with the forward's f32 expressions and clamps; a tap's
+ * contribution is w_tap * d_features[row, ch] (one f32 multiply).  Summation order per voxel (bitwise,
+ * no float atomics): its contributions in ascending (point, tap) order, cut into consecutive chunks of
+ * snap_occupancy_features_vjp_chunk() records; each chunk sum starts from its first contribution and
+ * adds the rest in order, and the voxel's value starts from the first chunk sum and adds the others in
+ * chunk order.  Refuses (SNAP_ERR_BAD_SHAPE) B * P * 8 >= 2^32 and B * X * Y * Z >= 2^32 - 1.
+ * workspace: snap_occupancy_features_vjp_workspace_bytes(P, ...) bytes (0: shape refused), 256-byte
+ * aligned. */
+int32_t snap_occupancy_features_vjp_chunk(void);
+size_t snap_occupancy_features_vjp_workspace_bytes(int64_t num_points, int32_t B, int32_t X, int32_t Y, int32_t Z,
+                                                   int32_t D);
+int snap_occupancy_ray_features_vjp_f32(const float* hits, const float* origins, const uint8_t* ray_mask,
+                                        int64_t num_rays, int32_t num_samples, float margin, const float* points,
+                                        int64_t num_points, int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t D,
+                                        float cell_size, const float* d_features, float* d_volume, void* workspace,
+                                        size_t workspace_bytes, void* stream);
 
 /* Semantic-raster embedding (snap/models/semantic_raster_encoder.py:63-79).  rasters [M, N]
  * uint8 (bool); idx_road / idx_other: HOST arrays with the raster channels of the mutually

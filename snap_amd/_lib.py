@@ -98,6 +98,11 @@ SIGNATURES = {
     'snap_occupancy_head_f32': (
         c_int, [ptr, ptr, ptr, c_i64, c_int, c_float, ptr, c_i64, c_int, ptr, ptr, c_int, c_int, c_int, c_int,
                 c_float, ptr, ptr, c_int, ptr, ptr, c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+    'snap_occupancy_features_vjp_chunk': (c_int, []),
+    'snap_occupancy_features_vjp_workspace_bytes': (c_size, [c_i64, c_int, c_int, c_int, c_int, c_int]),
+    'snap_occupancy_ray_features_vjp_f32': (
+        c_int, [ptr, ptr, ptr, c_i64, c_int, c_float, ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_float,
+                ptr, ptr, ptr, c_size, ptr]),
     'snap_semantic_embed_f32': (
         c_int, [ptr, c_i64, c_int, ptr, c_int, ptr, c_int, ptr, ptr, c_int, ptr, ptr]),
     'snap_semantic_onehot_f32': (c_int, [ptr, c_i64, c_int, ptr, c_int, ptr, c_int, ptr, c_int, ptr]),
@@ -347,7 +352,7 @@ SIGNATURES = {
     ),
 }
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _lib = None
 

@@ -779,6 +779,41 @@ def lift_pool_observations(obs_feat, f_shape, cam, Rt, points, *, K, fisheye, fe
 
 
 @_engine_scoped
+class _OccupancyRayFeatures(torch.autograd.Function):
+  """occupancy_net.py:106-111: the trilinear gather of the feature volume at the query points.  Only the
+  volume gets a gradient (the points are data; validity and samples are not differentiable)."""
+
+  @staticmethod
+  def forward(ctx, volume, volume_valid, cell_size, rays, points, num_samples, margin, want_samples):
+    feats, valid, samples = ops.occupancy_ray_features(volume, volume_valid, cell_size, rays=rays, points=points,
+                                                       num_samples=num_samples, margin=margin,
+                                                       want_samples=want_samples)
+    ctx.cfg = (tuple(volume.shape), cell_size, num_samples, margin, rays is not None)
+    ctx.save_for_backward(*(rays if rays is not None else (points,)))
+    ctx.mark_non_differentiable(valid, *(samples or ()))
+    return (feats, valid) + tuple(samples or ())
+
+  @staticmethod
+  def backward(ctx, dfeats, *_):
+    shape, cell_size, num_samples, margin, has_rays = ctx.cfg
+    src = ctx.saved_tensors
+    kw = dict(rays=tuple(src)) if has_rays else dict(points=src[0])
+    dvol = ops_bwd.occupancy_ray_features_vjp(dfeats.contiguous(), shape, cell_size, num_samples=num_samples,
+                                              margin=margin, **kw)
+    return dvol, None, None, None, None, None, None, None
+
+
+def occupancy_ray_features(volume, volume_valid, cell_size, *, rays=None, points=None, num_samples=1, margin=0.0,
+                           want_samples=True):
+  """Differentiable ``ops.occupancy_ray_features`` (same arguments and returns): the backward is the
+  deterministic gather VJP into the volume (``ops_bwd.occupancy_ray_features_vjp``)."""
+  want = bool(want_samples) and rays is not None
+  out = _OccupancyRayFeatures.apply(volume, volume_valid, float(cell_size), None if rays is None else tuple(rays),
+                                    points, int(num_samples), float(margin), want)
+  return out[0], out[1], (tuple(out[2:]) if want else None)
+
+
+@_engine_scoped
 class _VerticalPool(torch.autograd.Function):
 
   @staticmethod

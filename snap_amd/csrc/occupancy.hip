@@ -39,6 +39,10 @@
 //            train config.  No atomics: the logits are bitwise repeatable.
 // Supported: D, hidden widths multiples of 32 up to 256; one or two hidden layers; last width 1
 // (snap_occupancy_head_supported).  Everything else is the producer + ops.dense.
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+
 #include "common.h"
 
 namespace {
@@ -407,11 +411,10 @@ __global__ __launch_bounds__(kHeadThreads) void occ_head_kernel(const HeadArgs h
   }
 }
 
-int occ_setup(OccArgs& a, const float* hits, const float* origins, const uint8_t* ray_mask, int64_t num_rays,
-              int32_t num_samples, float margin, const float* points, int64_t num_points, int32_t B,
-              const float* volume, const uint8_t* volume_valid, int32_t X, int32_t Y, int32_t Z, int32_t D,
-              float cell_size, float* out_points, uint8_t* out_labels, uint8_t* out_ray_valid) {
-  if (!volume) return SNAP_ERR_NULL;
+// the point source and the grid (everything but the volume and the optional outputs)
+int occ_setup_source(OccArgs& a, const float* hits, const float* origins, const uint8_t* ray_mask, int64_t num_rays,
+                     int32_t num_samples, float margin, const float* points, int64_t num_points, int32_t B, int32_t X,
+                     int32_t Y, int32_t Z, int32_t D, float cell_size) {
   if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || D <= 0 || !(cell_size > 0.f)) return SNAP_ERR_BAD_SHAPE;
   if ((int64_t)X * Y * Z >= ((int64_t)1 << 31)) return SNAP_ERR_BAD_SHAPE;     // (tap offsets are int)
   a = OccArgs{};
@@ -430,8 +433,19 @@ int occ_setup(OccArgs& a, const float* hits, const float* origins, const uint8_t
   }
   a.B = B;
   a.cell = cell_size;
-  a.vol = volume; a.vvalid = volume_valid;
   a.X = X; a.Y = Y; a.Z = Z; a.D = D;
+  return SNAP_OK;
+}
+
+int occ_setup(OccArgs& a, const float* hits, const float* origins, const uint8_t* ray_mask, int64_t num_rays,
+              int32_t num_samples, float margin, const float* points, int64_t num_points, int32_t B,
+              const float* volume, const uint8_t* volume_valid, int32_t X, int32_t Y, int32_t Z, int32_t D,
+              float cell_size, float* out_points, uint8_t* out_labels, uint8_t* out_ray_valid) {
+  if (!volume) return SNAP_ERR_NULL;
+  const int st = occ_setup_source(a, hits, origins, ray_mask, num_rays, num_samples, margin, points, num_points, B,
+                                  X, Y, Z, D, cell_size);
+  if (st != SNAP_OK) return st;
+  a.vol = volume; a.vvalid = volume_valid;
   a.out_points = out_points; a.out_labels = out_labels; a.out_ray_valid = out_ray_valid;
   return SNAP_OK;
 }
@@ -497,6 +511,344 @@ extern "C" int snap_occupancy_head_f32(
     hipLaunchKernelGGL((occ_head_kernel<kHeadRows * 258, kHeadRows * 130>), grid, dim3(kHeadThreads), 0, s, h);
   else
     hipLaunchKernelGGL((occ_head_kernel<kHeadRows * 258, kHeadRows * 258>), grid, dim3(kHeadThreads), 0, s, h);
+  SNAP_CHECK_LAUNCH();
+  return SNAP_OK;
+}
+
+// ---- VJP of the producer into the volume (grids.py:116-137 differentiated, occupancy_net.py:106-111) ----
+// d_volume = (d features / d volume)^T d_features.  Every point is re-derived with occ_point / occ_taps (the
+// forward's f32 expressions, tap order and clamps) into 8 records (voxel, p, c) of weight ww[c]; the
+// contribution of a record to channel ch is ww[c] * d_features[b * P + p, ch] (one f32 multiply).
+// Summation order, per voxel of each scene (bitwise contract):
+//   its records in ascending (p, c), cut into consecutive chunks of kVjpChunk records; each chunk sum starts
+//   from its first contribution and adds the rest in order; the voxel starts from its first chunk sum and
+//   adds the others in chunk order; a voxel with no record is +0.
+// Passes (no float atomics, every d_volume element written once):
+//   1. records: key = b * XYZ + voxel (u32), weight by record id (b * P + p) * 8 + c
+//   2. stable radix sort of the record ids by key (only the key bits in use): ties keep (p, c) order
+//   3. segment bounds of every touched key (start / end in the sorted order)
+//   4. per key: chunk count and, for keys of more than one chunk, partial-sum slots (one packed u64 scan)
+//   5. chunk heads: sorted position of the first record of every chunk
+//   6. chunk pass: one group of D/4 lanes (x float4) per chunk; a key of one chunk writes d_volume directly,
+//      a longer key writes its chunk's partial row
+//   7. combine: per key, zero rows and the in-order sum of the partial rows of multi-chunk keys
+// kVjpChunk follows the split rule of a skewed gather (lists longer than a quarter of one wave's share of
+// the records are cut): ~8 M records over ~8 K resident waves -> ~1000 per wave -> 256.
+namespace {
+
+constexpr int kVjpChunk = 256;
+
+struct VjpLayout {
+  size_t R, nkeys, max_chunks, max_partials;
+  int bits;
+  size_t off_keys, off_keys_out, off_vals_out, off_w, off_seg, off_cval, off_cbase, off_pos, off_part, off_tmp;
+  size_t tmp_bytes, total;
+};
+
+inline size_t vjp_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+int vjp_layout(int64_t P, int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t D, VjpLayout* L) {
+  if (P <= 0 || B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || D <= 0) return SNAP_ERR_BAD_SHAPE;
+  const int64_t XYZ = (int64_t)X * Y * Z;
+  if (XYZ >= ((int64_t)1 << 31)) return SNAP_ERR_BAD_SHAPE;
+  if (P >= ((int64_t)1 << 32) || (int64_t)B * P >= ((int64_t)1 << 29)) return SNAP_ERR_BAD_SHAPE;  // B P 8 < 2^32
+  if ((int64_t)B * XYZ >= ((int64_t)1 << 32) - 1) return SNAP_ERR_BAD_SHAPE;                       // keys in u32
+  L->R = (size_t)B * P * 8;
+  L->nkeys = (size_t)B * XYZ;
+  L->bits = 1;
+  while (((size_t)1 << L->bits) < L->nkeys) ++L->bits;
+  // every chunk holds >= 1 record and all but the last of a key hold kVjpChunk: <= touched keys + R / L;
+  // a key of more than one chunk has > L records and ceil(n / L) < 2 n / L partial slots
+  L->max_chunks = (L->nkeys < L->R ? L->nkeys : L->R) + L->R / kVjpChunk + 1;
+  L->max_partials = 2 * L->R / kVjpChunk + 1;
+  size_t sort_tmp = 0, scan_tmp = 0;
+  unsigned* nul = nullptr;
+  unsigned long long* nul64 = nullptr;
+  if (rocprim::radix_sort_pairs(nullptr, sort_tmp, nul, nul, rocprim::counting_iterator<unsigned>(0), nul, L->R, 0,
+                                L->bits, (hipStream_t)0) != hipSuccess)
+    return SNAP_ERR_LAUNCH;
+  if (rocprim::exclusive_scan(nullptr, scan_tmp, nul64, nul64, 0ull, L->nkeys + 1,
+                              rocprim::plus<unsigned long long>(), (hipStream_t)0) != hipSuccess)
+    return SNAP_ERR_LAUNCH;
+  L->tmp_bytes = sort_tmp > scan_tmp ? sort_tmp : scan_tmp;
+  size_t o = 0;
+  L->off_keys = o;     o += vjp_align(L->R * sizeof(unsigned));
+  L->off_keys_out = o; o += vjp_align(L->R * sizeof(unsigned));
+  L->off_vals_out = o; o += vjp_align(L->R * sizeof(unsigned));
+  L->off_w = o;        o += vjp_align(L->R * sizeof(float));
+  L->off_seg = o;      o += vjp_align(2 * L->nkeys * sizeof(unsigned));             // start [nkeys] | end [nkeys]
+  L->off_cval = o;     o += vjp_align((L->nkeys + 1) * sizeof(unsigned long long));
+  L->off_cbase = o;    o += vjp_align((L->nkeys + 1) * sizeof(unsigned long long));
+  L->off_pos = o;      o += vjp_align(L->max_chunks * sizeof(unsigned));
+  L->off_part = o;     o += vjp_align(L->max_partials * (size_t)D * sizeof(float));
+  L->off_tmp = o;      o += vjp_align(L->tmp_bytes);
+  L->total = o;
+  return SNAP_OK;
+}
+
+struct VjpArgs {
+  OccArgs a;
+  const float* dfeat;        // [B * P, D]
+  float* dvol;               // [B, X, Y, Z, D]
+  unsigned* keys;            // [R] by record id
+  float* w;                  // [R] by record id
+  const unsigned* skeys;     // [R] sorted keys
+  const unsigned* svals;     // [R] record ids in sorted order
+  unsigned* seg_start;       // [nkeys]
+  unsigned* seg_end;         // [nkeys]  (both 0 for an untouched key)
+  unsigned long long* cval;  // [nkeys + 1] chunks << 32 | partial slots
+  const unsigned long long* cbase;   // exclusive scan of cval
+  unsigned* chunk_pos;       // [chunks] sorted position of every chunk's first record
+  float* part;               // [partial slots, D]
+  int64_t R, nkeys;
+};
+
+__global__ __launch_bounds__(256) void occ_vjp_records_kernel(const VjpArgs v) {
+  const OccArgs& a = v.a;
+  const int64_t XYZ = (int64_t)a.X * a.Y * a.Z;
+  const int64_t rows = a.B * a.P;
+  for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < rows; row += (int64_t)gridDim.x * 256) {
+    const int64_t b = row / a.P;
+    const int64_t p = row - b * a.P;
+    float xyz[3];
+    bool label, rvalid, inb;
+    occ_point(a, b, p, xyz, label, rvalid);
+    int off[8];
+    float ww[8];
+    occ_taps(a, xyz, off, ww, inb);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      v.keys[row * 8 + c] = (unsigned)(b * XYZ + off[c]);
+      v.w[row * 8 + c] = ww[c];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void occ_vjp_bounds_kernel(const VjpArgs v) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < v.R; i += (int64_t)gridDim.x * 256) {
+    const unsigned k = v.skeys[i];
+    if (i == 0 || v.skeys[i - 1] != k) v.seg_start[k] = (unsigned)i;
+    if (i == v.R - 1 || v.skeys[i + 1] != k) v.seg_end[k] = (unsigned)(i + 1);
+  }
+}
+
+__global__ __launch_bounds__(256) void occ_vjp_count_kernel(const VjpArgs v) {
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k <= v.nkeys; k += (int64_t)gridDim.x * 256) {
+    unsigned long long c = 0;
+    if (k < v.nkeys) {
+      const unsigned n = v.seg_end[k] - v.seg_start[k];
+      const unsigned long long nch = (n + kVjpChunk - 1) / kVjpChunk;
+      c = (nch << 32) | (nch > 1 ? nch : 0ull);
+    }
+    v.cval[k] = c;
+  }
+}
+
+__global__ __launch_bounds__(256) void occ_vjp_heads_kernel(const VjpArgs v) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < v.R; i += (int64_t)gridDim.x * 256) {
+    const unsigned k = v.skeys[i];
+    const unsigned rank = (unsigned)i - v.seg_start[k];
+    if (rank % kVjpChunk == 0) v.chunk_pos[(v.cbase[k] >> 32) + rank / kVjpChunk] = (unsigned)i;
+  }
+}
+
+template <int VW>
+__device__ __forceinline__ void vjp_load(const float* p, float (&x)[VW]) {
+  if constexpr (VW == 4) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+    x[0] = t[0]; x[1] = t[1]; x[2] = t[2]; x[3] = t[3];
+  } else {
+    x[0] = *p;
+  }
+}
+
+template <int VW>
+__device__ __forceinline__ void vjp_store(float* p, const float (&x)[VW]) {
+  if constexpr (VW == 4) *reinterpret_cast<f32x4*>(p) = f32x4{x[0], x[1], x[2], x[3]};
+  else *p = x[0];
+}
+
+// one group of G lanes per chunk (grid-stride over the chunks); lane l owns the VW-channel slices
+// q = l, l + G, ... < D / VW.  Record ids and weights of up to G entries by one load (lane = entry),
+// handed round by shuffles; 8 feature rows in flight, added in list order.
+template <int VW, int G>
+__global__ __launch_bounds__(256) void occ_vjp_chunks_kernel(const VjpArgs v) {
+  constexpr int U = 8;
+  const int D = v.a.D;
+  const int Q = D / VW;
+  const int lane = threadIdx.x & (G - 1);
+  const int64_t group = ((int64_t)blockIdx.x * 256 + threadIdx.x) / G;
+  const int64_t ngroups = (int64_t)gridDim.x * (256 / G);
+  const int64_t nchunks = (int64_t)(v.cbase[v.nkeys] >> 32);
+  for (int64_t ch = group; ch < nchunks; ch += ngroups) {
+    const unsigned i0 = v.chunk_pos[ch];
+    const unsigned k = v.skeys[i0];
+    const unsigned st = v.seg_start[k], en = v.seg_end[k];
+    const unsigned i1 = min(i0 + (unsigned)kVjpChunk, en);
+    const bool multi = en - st > (unsigned)kVjpChunk;
+    float* out = multi ? v.part + ((int64_t)(v.cbase[k] & 0xffffffffull) + (i0 - st) / kVjpChunk) * D
+                       : v.dvol + (int64_t)k * D;
+    for (int q0 = 0; q0 < Q; q0 += G) {
+      const int q = q0 + lane;
+      const bool on = q < Q;
+      float acc[VW];
+#pragma unroll
+      for (int e = 0; e < VW; ++e) acc[e] = 0.f;
+      bool first = true;
+      for (unsigned base = i0; base < i1; base += G) {
+        const unsigned nb = min((unsigned)G, i1 - base);
+        const unsigned my_rec = v.svals[min(base + (unsigned)lane, i1 - 1u)];
+        const float my_w = v.w[my_rec];
+        for (unsigned u0 = 0; u0 < nb; u0 += U) {
+          float x[U][VW], w[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            const int src = (int)min(u0 + u, nb - 1u);
+            const unsigned rec = (unsigned)__shfl((int)my_rec, src, G);
+            w[u] = __shfl(my_w, src, G);
+            if (on) vjp_load<VW>(v.dfeat + (int64_t)(rec >> 3) * D + VW * q, x[u]);
+          }
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            if (u0 + u >= nb) break;
+#pragma unroll
+            for (int e = 0; e < VW; ++e) {
+              const float contrib = w[u] * x[u][e];
+              acc[e] = first ? contrib : acc[e] + contrib;
+            }
+            first = false;
+          }
+        }
+      }
+      if (on) vjp_store<VW>(out + VW * q, acc);
+    }
+  }
+}
+
+// one thread per (key, VW-channel slice): +0 rows for untouched keys, the in-order sum of the partial rows
+// for multi-chunk keys (16 rows in flight); single-chunk keys were written by the chunk pass
+template <int VW>
+__global__ __launch_bounds__(256) void occ_vjp_combine_kernel(const VjpArgs v) {
+  constexpr int U = 16;
+  const int D = v.a.D;
+  const int Q = D / VW;
+  const int64_t total = v.nkeys * Q;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+    const int64_t k = t / Q;
+    const int q = (int)(t - k * Q);
+    const unsigned n = v.seg_end[k] - v.seg_start[k];
+    float acc[VW];
+    if (n == 0) {
+#pragma unroll
+      for (int e = 0; e < VW; ++e) acc[e] = 0.f;
+    } else if (n <= (unsigned)kVjpChunk) {
+      continue;
+    } else {
+      const int64_t nch = (n + kVjpChunk - 1) / kVjpChunk;
+      const float* p = v.part + (int64_t)(v.cbase[k] & 0xffffffffull) * D + VW * q;
+      vjp_load<VW>(p, acc);
+      int64_t j = 1;
+      for (; j + U <= nch; j += U) {
+        float x[U][VW];
+#pragma unroll
+        for (int u = 0; u < U; ++u) vjp_load<VW>(p + (j + u) * D, x[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+          for (int e = 0; e < VW; ++e) acc[e] = acc[e] + x[u][e];
+        }
+      }
+      for (; j < nch; ++j) {
+        float x[VW];
+        vjp_load<VW>(p + j * D, x);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) acc[e] = acc[e] + x[e];
+      }
+    }
+    vjp_store<VW>(v.dvol + k * D + VW * q, acc);
+  }
+}
+
+inline dim3 vjp_grid(int64_t items) {
+  const int64_t blocks = snap_cdiv(items, 256);
+  return dim3((unsigned)(blocks < (1 << 20) ? (blocks > 0 ? blocks : 1) : (1 << 20)));
+}
+
+}  // namespace
+
+extern "C" int32_t snap_occupancy_features_vjp_chunk(void) { return kVjpChunk; }
+
+extern "C" size_t snap_occupancy_features_vjp_workspace_bytes(int64_t num_points, int32_t B, int32_t X, int32_t Y,
+                                                              int32_t Z, int32_t D) {
+  VjpLayout L;
+  if (vjp_layout(num_points, B, X, Y, Z, D, &L) != SNAP_OK) return 0;
+  return L.total;
+}
+
+extern "C" int snap_occupancy_ray_features_vjp_f32(
+    const float* hits, const float* origins, const uint8_t* ray_mask, int64_t num_rays, int32_t num_samples,
+    float margin, const float* points, int64_t num_points, int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t D,
+    float cell_size, const float* d_features, float* d_volume, void* workspace, size_t workspace_bytes,
+    void* stream) {
+  if (!d_features || !d_volume || !workspace) return SNAP_ERR_NULL;
+  VjpArgs v{};
+  const int st = occ_setup_source(v.a, hits, origins, ray_mask, num_rays, num_samples, margin, points, num_points, B,
+                                  X, Y, Z, D, cell_size);
+  if (st != SNAP_OK) return st;
+  VjpLayout L;
+  const int lst = vjp_layout(v.a.P, B, X, Y, Z, D, &L);
+  if (lst != SNAP_OK) return lst;
+  if (workspace_bytes < L.total || (reinterpret_cast<uintptr_t>(workspace) & 255)) return SNAP_ERR_WORKSPACE;
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  v.dfeat = d_features;
+  v.dvol = d_volume;
+  v.keys = reinterpret_cast<unsigned*>(ws + L.off_keys);
+  v.w = reinterpret_cast<float*>(ws + L.off_w);
+  unsigned* skeys = reinterpret_cast<unsigned*>(ws + L.off_keys_out);
+  unsigned* svals = reinterpret_cast<unsigned*>(ws + L.off_vals_out);
+  v.skeys = skeys;
+  v.svals = svals;
+  v.seg_start = reinterpret_cast<unsigned*>(ws + L.off_seg);
+  v.seg_end = v.seg_start + L.nkeys;
+  v.cval = reinterpret_cast<unsigned long long*>(ws + L.off_cval);
+  unsigned long long* cbase = reinterpret_cast<unsigned long long*>(ws + L.off_cbase);
+  v.cbase = cbase;
+  v.chunk_pos = reinterpret_cast<unsigned*>(ws + L.off_pos);
+  v.part = reinterpret_cast<float*>(ws + L.off_part);
+  v.R = (int64_t)L.R;
+  v.nkeys = (int64_t)L.nkeys;
+  if (hipMemsetAsync(v.seg_start, 0, 2 * L.nkeys * sizeof(unsigned), s) != hipSuccess) return SNAP_ERR_LAUNCH;
+  // 1. records
+  hipLaunchKernelGGL(occ_vjp_records_kernel, vjp_grid(v.a.B * v.a.P), dim3(256), 0, s, v);
+  SNAP_CHECK_LAUNCH();
+  // 2. stable sort of the record ids by key
+  size_t tmp = L.tmp_bytes;
+  if (rocprim::radix_sort_pairs(ws + L.off_tmp, tmp, v.keys, skeys, rocprim::counting_iterator<unsigned>(0), svals,
+                                L.R, 0, L.bits, s) != hipSuccess)
+    return SNAP_ERR_LAUNCH;
+  // 3. segment bounds, 4. chunk counts + their scan, 5. chunk heads
+  hipLaunchKernelGGL(occ_vjp_bounds_kernel, vjp_grid(v.R), dim3(256), 0, s, v);
+  SNAP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(occ_vjp_count_kernel, vjp_grid(v.nkeys + 1), dim3(256), 0, s, v);
+  SNAP_CHECK_LAUNCH();
+  tmp = L.tmp_bytes;
+  if (rocprim::exclusive_scan(ws + L.off_tmp, tmp, v.cval, cbase, 0ull, L.nkeys + 1,
+                              rocprim::plus<unsigned long long>(), s) != hipSuccess)
+    return SNAP_ERR_LAUNCH;
+  hipLaunchKernelGGL(occ_vjp_heads_kernel, vjp_grid(v.R), dim3(256), 0, s, v);
+  SNAP_CHECK_LAUNCH();
+  // 6. chunk pass (grid-stride over the chunks: their count is known on the device only), 7. combine
+  const bool vec = (D % 4) == 0 && (reinterpret_cast<uintptr_t>(d_features) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(d_volume) & 15) == 0;
+  const int64_t chunk_blocks = snap_cdiv((int64_t)L.max_chunks, 4);
+  const dim3 cgrid((unsigned)(chunk_blocks < 8192 ? chunk_blocks : 8192));
+  if (vec && D / 4 <= 32) hipLaunchKernelGGL((occ_vjp_chunks_kernel<4, 32>), cgrid, dim3(256), 0, s, v);
+  else if (vec) hipLaunchKernelGGL((occ_vjp_chunks_kernel<4, 64>), cgrid, dim3(256), 0, s, v);
+  else hipLaunchKernelGGL((occ_vjp_chunks_kernel<1, 64>), cgrid, dim3(256), 0, s, v);
+  SNAP_CHECK_LAUNCH();
+  if (vec) hipLaunchKernelGGL(occ_vjp_combine_kernel<4>, vjp_grid(v.nkeys * (D / 4)), dim3(256), 0, s, v);
+  else hipLaunchKernelGGL(occ_vjp_combine_kernel<1>, vjp_grid(v.nkeys * D), dim3(256), 0, s, v);
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }

@@ -7,9 +7,12 @@ occupancy.hip: ONE fused launch (``ops.occupancy_head``) when nothing needs grad
 producer (``ops.occupancy_ray_features``: samples + interpolated rows) followed by the MLP on the
 Dense engine.  ``OccupancyNetModel`` carries the balanced BCE loss and the metrics (:131-166).
 
-The encoder is frozen in the reference's training config (train_occupancy.py:29); the VJP of the
-gather into the volume is not built, so a forward in which an encoder parameter requires grad
-raises (``trainer.train_step(..., freeze_params_reg_exp='streetview_encoder/')``).
+The encoder is frozen in the reference's training config (train_occupancy.py:29).  A model built with
+``train_encoder=True`` also trains it through the head: when an encoder parameter requires grad, the
+encoder runs under autograd (its own VJPs) and the query chain is ``ag.occupancy_ray_features`` (the
+deterministic gather VJP into the volume, occupancy.hip) followed by the Dense chain.  Without
+``train_encoder`` such a forward raises, as before (freeze it:
+``trainer.train_step(..., freeze_params_reg_exp='streetview_encoder/')``).
 """
 import torch
 
@@ -72,12 +75,14 @@ def dense_chain(mlp, x):
 
 
 class OccupancyNet(base.Module):
-  """occupancy_net.py:66-125."""
+  """occupancy_net.py:66-125.  ``train_encoder``: an encoder parameter that requires grad is trained
+  through the occupancy head (the gather's VJP) instead of raising."""
 
-  def __init__(self, config, grid, dtype=torch.float32):
+  def __init__(self, config, grid, dtype=torch.float32, train_encoder=False):
     self.config = config
     self.grid = grid
     self.dtype = dtype
+    self.train_encoder = bool(train_encoder)
     self.streetview_encoder = streetview_encoder.StreetViewEncoder(config.streetview_encoder, dtype)
     self.feature_dim = int(config.streetview_encoder.feature_dim)
     self.mlp_out = layers.MLP(config.occupancy_mlp, in_dim=self.feature_dim)
@@ -99,13 +104,16 @@ class OccupancyNet(base.Module):
                             owner=self)
     return xyz.unsqueeze(0).expand(B, *xyz.shape)
 
-  def use_fused_head(self, params):
-    """The fused query kernel serves the call when nothing needs gradients, the engine in force is
-    f32-class and the MLP shape is one the kernel takes.  Its hidden products are exact f32 (the f32
-    Dense engine's k-ordered MFMA chain), so on 'bf16x3' / 'bf16x6' it is at least as accurate as
-    the split engines it stands in for; 'bf16' / 'fp16' keep their own arithmetic (producer + Dense)."""
+  def use_fused_head(self, params, volume=None):
+    """The fused query kernel serves the call when nothing needs gradients (neither the MLP nor the
+    ``volume``, when given), the engine in force is f32-class and the MLP shape is one the kernel
+    takes.  Its hidden products are exact f32 (the f32 Dense engine's k-ordered MFMA chain), so on
+    'bf16x3' / 'bf16x6' it is at least as accurate as the split engines it stands in for; 'bf16' /
+    'fp16' keep their own arithmetic (producer + Dense)."""
     p = params['mlp_out']
     leaves = [p[f'Dense_{i}'][k] for i in range(len(self.hidden) + 1) for k in ('kernel', 'bias')]
+    if volume is not None:
+      leaves.append(volume)
     return (not base.needs_grad(*leaves) and ops.precision() in F32_CLASS
             and not self.config.occupancy_mlp.apply_input_activation
             and ops.occupancy_head_supported(self.feature_dim, self.hidden))
@@ -119,15 +127,20 @@ class OccupancyNet(base.Module):
     if queries is None and rays is None:
       raise ValueError('No points or rays given in the data dict.')
     enc_params = params['streetview_encoder']
-    if torch.is_grad_enabled() and any(t.requires_grad for _, t in _leaves(enc_params)):
+    enc_grad = torch.is_grad_enabled() and any(t.requires_grad for _, t in _leaves(enc_params))
+    if enc_grad and not self.train_encoder:
       raise NotImplementedError(
-          'OccupancyNet: training the StreetView encoder through the occupancy head is not built (the '
-          "gather's volume VJP); freeze it: trainer.train_step(..., freeze_params_reg_exp='streetview_encoder/')")
+          'OccupancyNet: this model does not train the StreetView encoder through the occupancy head; '
+          "freeze it: trainer.train_step(..., freeze_params_reg_exp='streetview_encoder/'), or build the "
+          'model with train_encoder=True')
     images = data['images']
     B = len(images)
-    with torch.no_grad():
-      pred = self.streetview_encoder(enc_params, {**data, 'xyz_query': self._voxel_centres(B, images.device)},
-                                     train, ctx=ctx)
+    enc_data = {**data, 'xyz_query': self._voxel_centres(B, images.device)}
+    if enc_grad:
+      pred = self.streetview_encoder(enc_params, enc_data, train, ctx=ctx)
+    else:
+      with torch.no_grad():
+        pred = self.streetview_encoder(enc_params, enc_data, train, ctx=ctx)
     volume = pred['feature_volume']
     features, vvalid = volume.features.contiguous(), volume.valid.contiguous()
     kw = dict(points=queries.to(torch.float32).contiguous()) if queries is not None else dict(
@@ -139,10 +152,11 @@ class OccupancyNet(base.Module):
     mlp = [(p[f'Dense_{i}']['kernel'], p[f'Dense_{i}']['bias']) for i in range(len(self.hidden) + 1)]
     # (the fused head reads the volume in 16-byte taps: a contiguous view at an unaligned offset, which
     # .contiguous() leaves as it is, takes the producer, which has a scalar kernel for it)
-    if self.use_fused_head(params) and features.data_ptr() % 16 == 0:
+    if self.use_fused_head(params, features) and features.data_ptr() % 16 == 0:
       logits, valid, samples = ops.occupancy_head(features, vvalid, cell, mlp, **kw)
     else:
-      feats, valid, samples = ops.occupancy_ray_features(features, vvalid, cell, **kw)
+      producer = ag.occupancy_ray_features if base.needs_grad(features) else ops.occupancy_ray_features
+      feats, valid, samples = producer(features, vvalid, cell, **kw)
       logits = dense_chain(mlp, feats)[..., 0].reshape(valid.shape)
     logits = logits.to(torch.float32)
     if samples is not None:
@@ -161,8 +175,12 @@ def _leaves(tree, prefix=''):
 class OccupancyNetModel(base.BaseModel):
   """Trainer-facing wrapper (occupancy_net.py:128-166)."""
 
+  def __init__(self, config, dataset_meta_data, dtype=torch.float32, engine=None, train_encoder=False):
+    self.train_encoder = bool(train_encoder)
+    super().__init__(config, dataset_meta_data, dtype=dtype, engine=engine)
+
   def build_flax_model(self):
-    return OccupancyNet(self.config, self.dataset_meta_data['grid'], self.dtype)
+    return OccupancyNet(self.config, self.dataset_meta_data['grid'], self.dtype, train_encoder=self.train_encoder)
 
   @classmethod
   def default_flax_model_config(cls):

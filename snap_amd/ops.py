@@ -1908,6 +1908,12 @@ def _occupancy_source(volume, volume_valid, rays, points, num_samples, margin):
     _mask(volume_valid, 'volume_valid')
     if tuple(volume_valid.shape) != (B, X, Y, Z):
       raise ValueError(f'occupancy: volume_valid {tuple(volume_valid.shape)} vs volume {tuple(volume.shape)}')
+  src, P = _occupancy_points(B, rays, points, num_samples, margin)
+  return src + [B, _p(volume), _p(volume_valid), X, Y, Z, D], B, P, D
+
+
+def _occupancy_points(B, rays, points, num_samples, margin):
+  """The point-source checks of the occupancy entry points -> (C arguments of the source, P)."""
   if (rays is None) == (points is None):
     raise ValueError('occupancy: give exactly one of rays=(hits, origins, mask) and points')
   if rays is not None:
@@ -1930,7 +1936,7 @@ def _occupancy_source(volume, volume_valid, rays, points, num_samples, margin):
       raise ValueError(f'occupancy: points must be [B={B}, Q, 3], got {tuple(points.shape)}')
     P = int(points.shape[1])
     src = [None, None, None, 0, 1, 0.0, _p(points), P]
-  return src + [B, _p(volume), _p(volume_valid), X, Y, Z, D], B, P, D
+  return src, P
 
 
 def occupancy_ray_features(volume, volume_valid, cell_size, *, rays=None, points=None, num_samples=1,

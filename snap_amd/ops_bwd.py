@@ -411,6 +411,37 @@ def lift_observations_bwd(dobs, f_shape, cam, Rt, points, *, K, fisheye, feature
   return df
 
 
+def occupancy_features_vjp_chunk():
+  """Records per chunk of the occupancy gather VJP's summation order (the library's constant)."""
+  return int(_lib.load().snap_occupancy_features_vjp_chunk())
+
+
+def occupancy_ray_features_vjp(d_features, volume_shape, cell_size, *, rays=None, points=None, num_samples=1,
+                               margin=0.0):
+  """VJP of ``ops.occupancy_ray_features`` w.r.t. the volume: d_features [B * P, D] -> d_volume [B, X, Y, Z, D]
+  (the points are data; the volume's validity does not enter).  records -> stable sort by voxel -> chunked
+  in-order sums: no atomics, bitwise reproducible (the order contract of include/snap_hip.h)."""
+  lib = _lib.load()
+  _f32(d_features, 'd_features')
+  if len(volume_shape) != 5:
+    raise ValueError(f'occupancy VJP: volume_shape must be [B, X, Y, Z, D], got {tuple(volume_shape)}')
+  B, X, Y, Z, D = (int(v) for v in volume_shape)
+  src, P = ops._occupancy_points(B, rays, points, num_samples, margin)
+  if tuple(d_features.shape) != (B * P, D):
+    raise ValueError(f'occupancy VJP: d_features must be [B * P, D] = {(B * P, D)}, got {tuple(d_features.shape)}')
+  wsb = lib.snap_occupancy_features_vjp_workspace_bytes(P, B, X, Y, Z, D)
+  if not wsb:
+    raise ValueError(f'occupancy VJP: shape B={B}, P={P}, grid={(X, Y, Z)}, D={D} refused '
+                     '(B * P * 8 and B * X * Y * Z must stay below 2^32)')
+  ws, wsp = _aligned_ws(wsb, d_features.device)
+  d_volume = torch.empty((B, X, Y, Z, D), dtype=torch.float32, device=d_features.device)
+  with _region('occupancy_features_vjp', 0.0, 4.0 * (d_features.numel() * 8 + d_volume.numel())):
+    st = lib.snap_occupancy_ray_features_vjp_f32(*src, B, X, Y, Z, D, float(cell_size), _p(d_features),
+                                                 _p(d_volume), wsp, wsb, _stream())
+  _lib.check(st, 'snap_occupancy_ray_features_vjp_f32')
+  return d_volume
+
+
 def vertical_pool_bwd(vol, valid, dplane, pooling='max', arg=None):
   """arg = (argz, ties) of ``ops.vertical_pool(want_arg=True)``: max pooling without a pass over vol."""
   lib = _lib.load()

@@ -4,15 +4,24 @@ against the unfused chain (ops.occupancy_ray_features + one ops.dense per layer 
 engine), alternating A / B in one process with device events.  Prints one JSON line per MLP shape.
 
   python tools/occupancy_bench.py [--reps 15] [--warmup 3] [--out FILE]
+  python tools/occupancy_bench.py --vjp [--out FILE]     the gather VJP leg (below)
 
 Floor = max(algorithmic FLOP / 157 TFLOP/s (f32 MFMA), compulsory bytes / 8 TB/s); compulsory bytes =
 the distinct 512-byte voxel rows the 8 taps of all samples touch (counted on the host) + the volume
 validity bytes of those voxels + the outputs.  Intermediate bytes avoided = what the unfused chain
 writes and re-reads: the [P, 128] feature rows and every hidden activation.
+
+--vjp: the producer's VJP into the volume (ops_bwd.occupancy_ray_features_vjp) on the same volume and rays,
+alternating with the producer forward; the record histogram (records per touched voxel, host sampler);
+essential bytes = the record keys + weights written and read back (8 B each way), the gathered d_features
+row of every record, and the d_volume write; and one train_step of a small OccupancyNet with the encoder
+frozen vs trained through the head (train_encoder=True).  The per-kernel split comes from running this
+leg under rocprofv3 --kernel-trace --stats.
 """
 import argparse
 import json
 import sys
+import time
 
 import numpy as np
 import torch
@@ -53,6 +62,100 @@ def compulsory_rows(points):
   return int(np.unique(np.concatenate(ids)).size)
 
 
+def voxel_keys(points):
+  """The voxel of each of the 8 taps of every sample, in record order (occ_taps' clamped indices)."""
+  p = points.reshape(-1, 3) / np.float32(CELL)
+  c = p - np.float32(0.5)
+  lo = np.fmin(np.fmax(np.floor(c), np.float32(-1)), np.float32(max(X, Y, Z))).astype(np.int64)
+  ids = []
+  for bits in range(8):
+    idx = [np.clip(lo[:, t] + ((bits >> (2 - t)) & 1), 0, s - 1) for t, s in enumerate((X, Y, Z))]
+    ids.append((idx[0] * Y + idx[1]) * Z + idx[2])
+  return np.stack(ids, -1).reshape(-1)
+
+
+def train_step_ms(train_encoder, reps):
+  sys.path.insert(0, 'tests')
+  import copy
+  import helpers
+  from snap_amd import trainer
+  from snap_amd.configs import defaults
+  from snap_amd.data import synthetic
+  sv = helpers.tiny_localizer_config(aerial=False, feature_dim=32).bev_mapper.streetview_encoder
+  cfg = defaults.occupancy_net()
+  cfg.streetview_encoder = copy.deepcopy(sv)
+  cfg.occupancy_mlp.layers = (32, 64, 1)
+  cfg.num_samples_per_ray = 8
+  meta = synthetic.meta_data(0.2, (6.4, 6.4, 3.2))
+  model = occupancy_net.OccupancyNetModel(cfg, meta, engine='f32', train_encoder=train_encoder)
+  params = helpers.params_to_device(model.flax_model.init(0, device='cpu')['params'], torch.device('cuda'))
+  batch = helpers.batch_to_device(synthetic.make_batch(2, meta['grid'], 2, (128, 128), seed=1, with_aerial=False,
+                                                       lidar_rays=5000), torch.device('cuda'))
+  state = trainer.TrainState.create(params)
+  freeze = None if train_encoder else 'streetview_encoder/'
+  ts = []
+  for i in range(reps + 2):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    state, _, _ = trainer.train_step(state, batch, model=model, lr_fn=lambda s: 1e-3, freeze_params_reg_exp=freeze)
+    torch.cuda.synchronize()
+    if i >= 2:
+      ts.append((time.perf_counter() - t0) * 1e3)
+  return float(np.median(ts)), meta['grid'].extent
+
+
+def vjp_leg(args, vol, vvalid, r, pts):
+  from snap_amd import ops_bwd
+  dev = vol.device
+  P = S * N
+  g = torch.Generator(device='cpu').manual_seed(3)
+  dfeat = (torch.rand((P, D), generator=g) * 2 - 1).to(dev)
+  kw = dict(rays=r, num_samples=S, margin=0.2)
+
+  def fwd():
+    return ops.occupancy_ray_features(vol, vvalid, CELL, want_samples=False, **kw)[0]
+
+  def vjp():
+    return ops_bwd.occupancy_ray_features_vjp(dfeat, vol.shape, CELL, **kw)
+
+  for _ in range(args.warmup):
+    fwd(); vjp()
+  torch.cuda.synchronize()
+  tf, tv = [], []
+  for _ in range(args.reps):
+    tf.append(timeit(fwd, args.inner))
+    tv.append(timeit(vjp, args.inner))
+  a, b = vjp(), vjp()
+  same = bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
+  del a, b
+  keys = voxel_keys(pts)
+  counts = np.bincount(keys, minlength=X * Y * Z)
+  touched = counts[counts > 0]
+  R = keys.size
+  L = ops_bwd.occupancy_features_vjp_chunk()
+  nbytes = R * 8 * 2 + R * D * 4 + X * Y * Z * D * 4
+  f_ms, v_ms = float(np.median(tf)), float(np.median(tv))
+  tr_frozen, ext = train_step_ms(False, args.reps)
+  tr_enc, _ = train_step_ms(True, args.reps)
+  res = dict(
+      workload=f'occupancy VJP {X}x{Y}x{Z}x{D} volume, {N} rays x {S} samples', records=int(R), chunk=L,
+      vjp_ms=round(v_ms, 4), producer_fwd_ms=round(f_ms, 4), vjp_ms_all=[round(t, 4) for t in tv],
+      producer_fwd_ms_all=[round(t, 4) for t in tf], vjp_bitwise_repeatable=same,
+      touched_voxels=int(touched.size), records_per_voxel_median=float(np.median(touched)),
+      records_per_voxel_p99=float(np.percentile(touched, 99)), records_per_voxel_max=int(touched.max()),
+      voxels_over_512=int((touched > 512).sum()),
+      share_of_records_in_voxels_over_512=round(float(touched[touched > 512].sum()) / R, 4),
+      chunks=int(((touched + L - 1) // L).sum()), essential_mb=round(nbytes / 1e6, 1),
+      essential_tb_per_s=round(nbytes / v_ms / 1e9, 3),
+      train_step=dict(shape=f'1 x 2 views 128 x 128, grid {tuple(ext)}, 5000 rays x 8 samples, f32 engine',
+                      frozen_encoder_ms=round(tr_frozen, 2), train_encoder_ms=round(tr_enc, 2)),
+      reps=args.reps, inner=args.inner)
+  print(json.dumps(res), flush=True)
+  if args.out:
+    with open(args.out, 'w') as f:
+      json.dump(res, f, indent=1)
+
+
 def timeit(fn, n):
   e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
   e0.record()
@@ -69,6 +172,7 @@ def main():
   ap.add_argument('--warmup', type=int, default=3)
   ap.add_argument('--inner', type=int, default=3)
   ap.add_argument('--out', default=None)
+  ap.add_argument('--vjp', action='store_true', help='the gather VJP leg instead of fused vs unfused')
   args = ap.parse_args()
   dev = torch.device('cuda')
   g = torch.Generator(device='cpu').manual_seed(0)
@@ -78,6 +182,8 @@ def main():
   r = tuple(torch.from_numpy(a).to(dev) for a in (h, o, m))
   kw = dict(rays=r, num_samples=S, margin=0.2, want_samples=False)
   _, _, (pts, _, _) = ops.occupancy_ray_features(vol, vvalid, CELL, rays=r, num_samples=S, margin=0.2)
+  if args.vjp:
+    return vjp_leg(args, vol, vvalid, r, pts.cpu().numpy())
   P = S * N
   rows = compulsory_rows(pts.cpu().numpy())
   results = []
