@@ -437,9 +437,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel_dma(const ConvArgs a) {
   conv_igemm_body<BM, BN, true, PRO, 16, true>(a);
 }
 
-inline bool conv_dma_enabled() { return true; }   // (the LDS-DMA loader of the NONE / RELU prologues: settled)
-
-
 template <int BM, int BN, bool VEC, int PRO, int BK>
 int launch(ConvArgs a, hipStream_t s) {
   if (VEC) {
@@ -476,12 +473,10 @@ int launch(ConvArgs a, hipStream_t s) {
   constexpr bool kGn = PRO == SNAP_PRO_GN_RELU || PRO == SNAP_PRO_RELU_GN;
   constexpr bool kDmaOk = VEC && BK == 16 && (PRO == SNAP_PRO_NONE || PRO == SNAP_PRO_RELU);
   bool launched = false;
-  if constexpr (kDmaOk) {
-    if (conv_dma_enabled()) {
-      hipLaunchKernelGGL((conv_igemm_kernel_dma<BM, BN, PRO>), dim3((unsigned)nblocks), dim3(256), 0,
-                         s, a);
-      launched = true;
-    }
+  if constexpr (kDmaOk) {   // (the LDS-DMA loader of the NONE / RELU prologues)
+    hipLaunchKernelGGL((conv_igemm_kernel_dma<BM, BN, PRO>), dim3((unsigned)nblocks), dim3(256), 0,
+                       s, a);
+    launched = true;
   }
   if (launched) {
   } else if constexpr (!kGn && BK == 16 && (VEC || BM * BN < 128 * 128)) {  // (scalar 128x128 would spill)

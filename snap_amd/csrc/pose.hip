@@ -1742,10 +1742,9 @@ extern "C" int snap_sim_softmax_weighted_f32(const float* fq, const float* fm, i
   const dim3 grid((unsigned)snap_cdiv(XY, 256), (unsigned)snap_cdiv(Nq, SIM_TQ), (unsigned)B);
   // (the VALU kernel takes unaligned inputs and other Dm; tests reach it through a 4-byte
   //  offset view and compare the two bit for bit)
-  const bool use_mfma = true;
   const bool aligned = ((reinterpret_cast<uintptr_t>(fq) | reinterpret_cast<uintptr_t>(fm)) & 15) == 0;
   int rc = SNAP_OK;
-  if (use_mfma && aligned && (Dm == 8 || Dm == 16 || Dm == 32 || Dm == 64)) {
+  if (aligned && (Dm == 8 || Dm == 16 || Dm == 32 || Dm == 64)) {
 #define SNAP_SIM_MFMA_CASE(D)                                                                     \
   case D:                                                                                         \
     hipLaunchKernelGGL(sim_mfma_kernel<D>, grid, dim3(256), 0, s, fq, fm, Nq, XY, scale,          \

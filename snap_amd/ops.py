@@ -9,6 +9,7 @@ import contextlib
 import sys
 import ctypes
 import threading
+import typing
 import weakref
 import os
 
@@ -38,11 +39,14 @@ SIM_CHUNK = 64
 #                      blended inside the fused MLP / pool kernel (the lift inside the consumer)
 #   MLP_GATHER_XCD_GROUP  runs of 128-row tiles of the gathered class per XCD (its L2 keeps their taps)
 #   NATIVE_GLUE        image padding / voxel-centre grid as native passes instead of torch fill + copies
-#   USE_PRESPLIT       bottleneck 3x3 / closing 1x1 convs read their input through gn_norm_split (off:
-#                      the pre-split convs are 10-25 percent faster, the extra pass costs what they gain)
+#   USE_PRESPLIT       bottleneck 3x3 / closing 1x1 convs read their input through gn_norm_split on the 'bf16x3'
+#                      engine (off: measured at C2 -- tools/unit_bench.py, profiles/r03_unit_bench.json -- the pre-split
+#                      convs are 10-25 percent faster, the extra pass costs what they gain; the engine's own user is
+#                      the exhaustive voting)
 #   CONV_TILE / CONV_BK / CONV_NO_HALO / CONV_NO_RS / CONV_RS_NSPLIT / CONV_RS_FORCE / CONV_NO_WS /
-#   CONV_NO_PLAIN      forced tile ('128x128' | '128x64' | '64x128' | '64x64'), f32 K-slab
-#                      depth, and which body a conv launch takes (tests pin every body against the others)
+#   CONV_NO_PLAIN      forced tile ('128x128' | '128x64' | '64x128' | '64x64'; travels as SnapConvDesc.tile_hint),
+#                      f32 K-slab depth (16 | 32), and which body a conv launch takes (tests pin every body against
+#                      the others).  None / False / 0 = the engines' choice
 #   SPLITK_STATS / USE_SPLITK / USE_FUSED_GN_STATS / GN_STATS_BOTH   GroupNorm statistics from the conv
 #                      epilogues / split-K reduce passes vs the stand-alone kernels
 #   USE_PRESPLIT_VOTING / FUSED_TEMPLATE_PACK / PS_RES_INIT / PS_TILE   pre-split GEMM engine (direct-form voting)
@@ -142,12 +146,7 @@ def _stream():
 
 # A second HIP stream for work that does not depend on the main chain (the aerial encoder runs
 # next to the StreetView encoder: its deep stages are launches of 19-73 workgroups on a 256-CU
-# part).  SNAP_OVERLAP_AERIAL=0 keeps everything on one stream.
-# the lift hands `pooled` to the fused MLP / pool kernel pre-split (LDS-DMA A operand); 0: as f32 rows
-# ... and classed by their number of observations (single-observation rows carry no variance slabs); 0: off
-# ... and the class-1 rows (one observation) are never written: the lift leaves a 32-byte tap record and the
-# fused MLP / pool kernel blends the four image taps itself (the lift inside the consumer); 0: rows through HBM
-# image padding and the voxel-centre grid as one native pass each instead of torch fill + strided copies; 0: torch
+# part).  ``Tuning.OVERLAP_AERIAL = False`` keeps everything on one stream.
 _SIDE_STREAMS = {}
 
 
@@ -373,16 +372,6 @@ class PreSplit:
     return int(np.prod(self.shape))
 
 
-# USE_PRESPLIT: the 3x3 and the closing 1x1 convolution of a bottleneck unit read their input
-# through ``gn_norm_split`` (one pass that also replaces the statistics finalize launch) on the
-# 'bf16x3' engine.  Measured at C2 (tools/unit_bench.py, profiles/r03_unit_bench.json): the
-# pre-split convolutions are 10-25 % faster than the fused-prologue ones, the extra pass over the
-# activation costs what they gain -- off by default; the engine's own user is the exhaustive voting.
-# Tests / tuning tools: force the conv engines' output tile ('128x128' | '128x64' | '64x128' |
-# '64x64'; travels as SnapConvDesc.tile_hint), the f32 engine's K-slab depth (16 | 32) and the
-# im2col body for every 3x3 convolution of the split engine.  None / False = the engines' choice.
-
-
 def gn_norm_split(y, gamma, beta, *, groups=32, eps=1e-5, want_stats=False):
   """relu(GroupNorm(y)) of a conv output that carries its fused partial sums, written once in the
   pre-split format -> ``PreSplit`` (or None where the pre-split engine does not apply: another
@@ -424,13 +413,14 @@ def presplit(x):
   return PreSplit(out, shape)
 
 
-def _stationary_mode():
+def _stationary_mode(T=None):
   """SnapConvDesc.tile_hint // 1 000 000: which 1x1 bodies of the split engine may run."""
-  if tuning().CONV_NO_RS:
+  T = tuning() if T is None else T
+  if T.CONV_NO_RS:
     return 1
-  if tuning().CONV_RS_FORCE:
-    return 4 if tuning().CONV_NO_WS else 2
-  return 3 if tuning().CONV_NO_WS else 0
+  if T.CONV_RS_FORCE:
+    return 4 if T.CONV_NO_WS else 2
+  return 3 if T.CONV_NO_WS else 0
 
 
 class PackedWeights:
@@ -464,6 +454,26 @@ def pack_stacked_templates_split(templates, S):
   return PackedWeights(out, (KH, KW, D, RS))
 
 
+# the training-precision engines: operands rounded to bf16 / IEEE half, f32 accumulate
+HALF_MATH = ('bf16', 'fp16')
+# the split-bf16 engines: bf16 parts per operand
+SPLIT_PARTS = {'bf16x3': 2, 'bf16x6': 3}
+
+
+def kernel_image(w_shape, math):
+  """Which engine a [KH,KW,Cin,Cout] kernel's launches take under ``math`` and whether they read a
+  packed weight image -> ``(math, parts, packed)``: a split image beyond the engine's 32-bit offsets
+  (template banks) drops the kernel to 'f32'; 'f32' and Cin < 4 read the f32 kernel itself (the
+  f32 engine).  ``parts`` is the split engines' number of bf16 parts (0: a bf16 / fp16 image).  The
+  ONE statement of this rule: ``plan_conv`` and the functions that prepare the images ahead of the
+  launches (``pack_weights_*_multi``, ``conv2d_presplit_supported``) all ask here."""
+  KH, KW, Cin, Cout = w_shape
+  parts = SPLIT_PARTS.get(math, 0)
+  if parts and _lib.load().snap_conv2d_packed_weights_split_bytes(KH * KW, Cin, Cout, parts) == 0:
+    math, parts = 'f32', 0
+  return math, parts, math != 'f32' and Cin >= 4
+
+
 def conv2d_presplit_supported(x_shape, w_shape, stride=1, padding=((0, 0), (0, 0))):
   """True when ``conv2d(presplit(x), w, ...)`` has an engine for the shape: the pre-split engine's
   own limits (``snap_conv2d_presplit_supported``) and a two-part weight image within the split
@@ -478,10 +488,213 @@ def conv2d_presplit_supported(x_shape, w_shape, stride=1, padding=((0, 0), (0, 0
   Wo = (W + pl + pr - KW) // stride + 1
   if Ho <= 0 or Wo <= 0:
     return False
-  if lib.snap_conv2d_packed_weights_split_bytes(KH * KW, Cin, Cout, 2) == 0:
+  if kernel_image(w_shape, 'bf16x3')[1] != 2:
     return False
   d = _lib.SnapConvDesc(N, H, W, Cin, Cs, KH, KW, stride, pt, pl, Ho, Wo, Cout, Cout, PRO_NONE, 0, 1.0, 0.0)
   return bool(lib.snap_conv2d_presplit_supported(ctypes.byref(d)))
+
+
+class ConvPlan(typing.NamedTuple):
+  """Everything one ``conv2d`` launch decides before it touches a tensor (``plan_conv``)."""
+  desc: _lib.SnapConvDesc   # the launch descriptor, tile_hint included (read-only: it is passed by reference)
+  out_shape: tuple          # (N, Ho, Wo, Cout)
+  out_dtype: torch.dtype    # float32; bfloat16 / float16 with out_half
+  engine: str               # the arithmetic the launch runs on ('f32' where no weight image applies: ``kernel_image``)
+  family: str               # profiler family: conv_igemm | conv_split_<math> | conv_bf16 | conv_fp16
+  tag: str                  # profiler tag prefix: '' | 'PS_' | 'PS1_' | 'RS_' | 'WS_'
+  image: str                # ``_packed_weights`` key of the weight image the kernel reads; None: the f32 kernel
+  parts: int                # ... and its bf16 parts (0: a bf16 / fp16 image)
+  extras: bool              # the launch passes a SnapConvExtras at all (else NULL)
+  workspace_bytes: int      # split-K workspace (0: K is not split)
+  stats_bytes: int          # ONE buffer of GroupNorm partial sums (0: none emitted)
+  stats_count: int          # 0 | 1 | 2 (2: those of y and, as a request, of relu(y))
+  stats_relu: bool          # the first buffer holds the sums of relu(y)
+  gn_partial_rows: int      # 32: the split-K reduce pass emits them per 32-row slab; 0: the engine's own layout
+  tile_rows: int            # rows per slab as the statistics' consumers read them (``_snap_gn_partial[1]``)
+  gnb: bool                 # the buffer holds the statistics of the GroupNorm VJP (``gn_bwd_stats`` accepted)
+  w_split_parts: int        # the scalar SnapConvExtras fields of the same names
+  w_split_root: int
+  w_half: int
+  x_half: int
+  x_presplit: int
+  ps_tile: int
+  ps_res_init: int
+  bk_hint: int
+  tune_flags: int
+
+
+def plan_conv(
+    x, w, stride=1, padding=((0, 0), (0, 0)), cin=None, prologue=PRO_NONE,
+    gn=None, in_affine=(1.0, 0.0), bias=None, relu=False, residual=None,
+    up_prev=None, row_mask=None, rows_in=None, rows_out=None, row_count=None, out=None,
+    emit_gn_stats=None, math=None, gelu=False, res_init=None, ps_tile=None, out_half=False, out_stride=None,
+    gn_bwd_stats=None, bf16_ring=False,
+):
+  """The ``ConvPlan`` of ``conv2d(x, w, ...)`` (same arguments) under the engine and ``Tuning`` in
+  force.  Pure: of every tensor argument only ``shape`` / ``dtype`` / ``numel()`` are read (meta
+  tensors, ``PreSplit`` / ``PackedWeights`` of meta tensors do), nothing is allocated or launched and
+  no device is needed -- the library is asked only its host queries.  Raises every ``ValueError`` of
+  ``conv2d`` that follows from shapes, dtypes and flags."""
+  lib = _lib.load()
+  T = tuning()
+  ps = isinstance(x, PreSplit)
+  pw = isinstance(w, PackedWeights)
+  xh = (not ps) and x.dtype in (torch.bfloat16, torch.float16)
+  no_rows = rows_in is None and rows_out is None and row_count is None
+  if xh:
+    # the input already in the training-precision engine's element type (the half twin a GroupNorm
+    # VJP wrote next to its f32 gradient): both operands by LDS-DMA (conv_bf16.hip)
+    want = 'fp16' if x.dtype == torch.float16 else 'bf16'
+    math = want if math is None else math
+    if (math != want or prologue != PRO_NONE or rows_in is not None or x.shape[-1] % 8 or w.shape[2] % 8
+        or emit_gn_stats is not None):
+      raise ValueError('conv2d: a half-precision input takes the matching engine, prologue NONE, whole '
+                       'channel octets, no input row list / statistics')
+  if ps:
+    if prologue != PRO_NONE or not no_rows or math not in (None, 'bf16x3'):
+      raise ValueError('conv2d: a PreSplit input takes prologue NONE, no row lists, math bf16x3')
+    math = 'bf16x3'
+  if pw and not ps:
+    raise ValueError('conv2d: PackedWeights (a two-part split image) go with a PreSplit input')
+  N, H, W, Cs = x.shape
+  KH, KW, Cin, Cout = w.shape
+  if cin is None:
+    cin = Cs
+  if cin != Cin:
+    raise ValueError(f'conv2d: kernel expects Cin={Cin}, input has {cin}')
+  (pt, pb), (pl, pr) = padding
+  Ho = (H + pt + pb - KH) // stride + 1
+  Wo = (W + pl + pr - KW) // stride + 1
+  M = N * Ho * Wo
+  out_dtype = torch.float32
+  if out_half:
+    hm = precision() if math is None else math
+    if (hm not in HALF_MATH or out is not None or emit_gn_stats is not None or up_prev is not None
+        or prologue not in (PRO_NONE, PRO_RELU) or Cs % 4 or Cin < 4 or Cout % 4):
+      raise ValueError('conv2d: out_half needs a training-precision engine launch (prologue NONE / RELU, '
+                       'no statistics / up-sampling epilogue, channel quads)')
+    out_dtype = torch.float16 if hm == 'fp16' else torch.bfloat16
+  elif out is not None:
+    if out_stride is not None:
+      if (out_stride % 4 or out_stride < Cout or out.numel() != M * out_stride or emit_gn_stats is not None
+          or residual is not None or up_prev is not None):
+        raise ValueError('conv2d: out_stride needs out [rows, out_stride], out_stride % 4 == 0, a plain epilogue')
+    elif out.numel() != M * Cout:
+      raise ValueError('conv2d: out has the wrong size')
+  if out_stride is not None and out is None:
+    raise ValueError('conv2d: out_stride goes with out')
+  epi = 0
+  if prologue in (PRO_GN_RELU, PRO_RELU_GN):
+    mu, sc, beta = gn
+    if mu.numel() != N * Cin or sc.numel() != N * Cin or beta.numel() != Cin:
+      raise ValueError('conv2d: GroupNorm statistics have the wrong size')
+  if bias is not None:
+    epi |= EPI_BIAS
+    if bias.numel() != Cout:
+      raise ValueError('conv2d: bias size')
+  if relu:
+    epi |= EPI_RELU
+  if gelu:                                   # tanh-approximated GELU (ViT MLP)
+    epi |= EPI_GELU
+  if residual is not None:
+    epi |= EPI_RESIDUAL
+    y_shape = (N, Ho, Wo, Cout) if out is None else tuple(out.shape)
+    if tuple(residual.shape) != y_shape:
+      raise ValueError(f'conv2d: residual {tuple(residual.shape)} vs {y_shape}')
+  if up_prev is not None:
+    epi |= EPI_UPSAMPLE2X_ADD
+    if tuple(up_prev.shape) != (N, Ho // 2, Wo // 2, Cout):
+      raise ValueError('conv2d: up_prev shape')
+  if row_mask is not None:
+    epi |= EPI_ROWMASK
+    if row_mask.numel() != M:
+      raise ValueError('conv2d: row_mask size')
+  tile_hint = 1000000 * _stationary_mode(T)
+  if T.CONV_TILE:
+    bm, bn = (int(v) for v in T.CONV_TILE.split('x'))
+    tile_hint += bm * 1000 + bn
+  d = _lib.SnapConvDesc(
+      N, H, W, Cin, Cs, KH, KW, stride, pt, pl, Ho, Wo, Cout, Cout if out_stride is None else int(out_stride), prologue,
+      epi, float(in_affine[0]), float(in_affine[1]), tile_hint,
+  )
+  dref = ctypes.byref(d)
+  # the engine the launch will take (the statistics layout depends on it)
+  math = precision() if math is None else math
+  if math not in ENGINES:
+    raise ValueError(f'conv2d: math={math!r}')
+  math, parts, packed = kernel_image((KH, KW, Cin, Cout), math)
+  packed = packed and Cs % 4 == 0
+  qparts = parts if packed and not ps else 0   # (SnapConvExtras.w_split_parts of a plain-input launch)
+  # a bf16 input whose launch needs nothing but the GEMM + a plain epilogue runs on the ONE-PART pre-split engine
+  # (conv_ps.hip, NS = 1: both operands by LDS-DMA through the three-stage ring, 256 x 128 tiles) -- the same
+  # arithmetic as the training-precision engine (operands rounded to bf16, f32 accumulate)
+  ps1 = bool(bf16_ring and xh and x.dtype == torch.bfloat16 and math == 'bf16' and T.BF16_PS and Cs == Cin and Cin % 16 == 0
+             and rows_out is None and row_count is None and up_prev is None and gn_bwd_stats is None
+             and out is None and Cout % 4 == 0 and lib.snap_conv2d_presplit_supported(dref))
+  if xh and out_half and not ps1:
+    raise ValueError('conv2d: a half-precision input AND output need the one-part pre-split engine (bf16, Cin % 16 == 0, '
+                     'no row lists)')
+  # a stationary-operand 1 x 1 / 3 x 3 kernel of the two-part engine (1: RS, 2 / 3: WS) takes the launch
+  kind = lib.snap_conv2d_stationary_kind(dref, qparts) if (qparts == 2 and no_rows) else 0
+  pst = (T.PS_TILE if ps_tile is None else int(ps_tile)) if (ps or ps1) else 0
+  wbytes = sbytes = scount = rows32 = tile_rows = 0
+  gnb = False
+  if no_rows:
+    if ps:
+      wbytes = lib.snap_conv2d_presplit_workspace_bytes(dref, pst) if T.USE_SPLITK else 0
+    elif not (ps1 or kind or out_half):          # (the stationary kernels and the one-part engine never split K)
+      wbytes = lib.snap_conv2d_workspace_bytes(dref) if T.USE_SPLITK else 0
+    if wbytes:   # small-M / deep-K layer: split K
+      half_engine = math in HALF_MATH and packed and Cin % 4 == 0 and not ps
+      if emit_gn_stats is not None and (qparts >= 2 or half_engine) and T.SPLITK_STATS:
+        # the reduce pass of the split / bf16 / fp16 engine emits the partial sums (per 32-row slab)
+        sbytes = lib.snap_conv2d_splitk_gn_partial_bytes(dref)
+        if sbytes:
+          scount, rows32, tile_rows = 1, 32, 32
+    elif (gn_bwd_stats is not None and xh and emit_gn_stats is None and out is None and up_prev is None
+          and not relu and not gelu and row_mask is None):
+      gx, gmu, grs, gga, gbe, gmode = gn_bwd_stats
+      pbytes = lib.snap_conv2d_gn_partial_bytes_ex(dref, 0)
+      if (pbytes and tuple(gx.shape) == (N, Ho, Wo, Cout) and gmu.numel() == N * Cout and grs.numel() == N * Cout
+          and gga.numel() == Cout and gbe.numel() == Cout and gmode in (PRO_GN_RELU, PRO_RELU_GN)):
+        sbytes, scount, gnb = pbytes, 1, True
+        tile_rows = lib.snap_conv2d_tile_rows_ex(dref, 0)
+    elif emit_gn_stats is not None:
+      sbytes = (lib.snap_conv2d_presplit_gn_partial_bytes(dref, pst) if ps
+                else lib.snap_conv2d_gn_partial_bytes_ex(dref, qparts))
+      if sbytes:
+        # 'both' on a split engine: the statistics of y AND of relu(y), a request (SnapConvExtras.gn_partial2_done)
+        scount = 2 if (emit_gn_stats == 'both' and math in SPLIT_PARTS) else 1
+        tile_rows = lib.snap_conv2d_presplit_tile_rows(dref, pst) if ps else lib.snap_conv2d_tile_rows_ex(dref, qparts)
+  if ps and (parts != 2 or Cin % 16):
+    raise ValueError('conv2d: the pre-split engine needs Cin % 16 == 0 and a two-part weight image')
+  family, image, iparts = 'conv_igemm', None, 0
+  root = xpre = res0 = 0
+  if (parts and (KH, KW, stride, Cin, Cs) == (7, 7, 2, 3, 4) and (pt, pl) == (3, 3)
+      and prologue in (PRO_NONE, PRO_AFFINE) and no_rows and not sbytes and not ps):
+    # the RGB root convolution (7 x 7 / stride 2 / pad 3) of an image stored with 4 floats per pixel
+    # runs on the split engine with its own weight image (a K slab = 4 pixels of a kernel row)
+    family, image, iparts, root = f'conv_split_{math}', math + '/root', parts, 1
+  elif ps1:
+    family, image, iparts, xpre = 'conv_bf16', 'bf16/ps1', 1, 1
+  elif packed:
+    family = f'conv_split_{math}' if parts else ('conv_fp16' if math == 'fp16' else 'conv_bf16')
+    image, iparts = math, parts
+    if ps:
+      xpre, res0 = 1, int(T.PS_RES_INIT if res_init is None else bool(res_init))
+  bk_hint = tune_flags = 0
+  tuned = bool(T.CONV_BK or T.CONV_NO_HALO or T.CONV_RS_NSPLIT or T.CONV_NO_PLAIN)
+  if tuned:
+    bk_hint = int(T.CONV_BK or 0)
+    tune_flags = int(bool(T.CONV_NO_HALO)) | 8 * int(bool(T.CONV_NO_PLAIN)) | ((int(T.CONV_RS_NSPLIT) & 15) << 4)
+  return ConvPlan(
+      desc=d, out_shape=(N, Ho, Wo, Cout), out_dtype=out_dtype, engine=math if image else 'f32', family=family,
+      tag='PS_' if ps else 'PS1_' if ps1 else ('', 'RS_', 'WS_', 'WS_')[kind], image=image, parts=iparts,
+      extras=bool(not no_rows or wbytes or sbytes or image or tuned), workspace_bytes=wbytes,
+      stats_bytes=sbytes, stats_count=scount, stats_relu=bool(sbytes) and emit_gn_stats == 'relu',
+      gn_partial_rows=rows32, tile_rows=tile_rows, gnb=gnb,
+      w_split_parts=iparts, w_split_root=root, w_half=int(image == 'fp16'), x_half=int(xh and not ps1),
+      x_presplit=xpre, ps_tile=pst if xpre else 0, ps_res_init=res0, bk_hint=bk_hint, tune_flags=tune_flags)
 
 
 def conv2d(
@@ -530,260 +743,95 @@ def conv2d(
   """
   lib = _lib.load()
   ps = isinstance(x, PreSplit)
-  xh = (not ps) and x.dtype in (torch.bfloat16, torch.float16)
-  if xh:
-    # the input already in the training-precision engine's element type (the half twin a GroupNorm
-    # VJP wrote next to its f32 gradient): both operands by LDS-DMA (conv_bf16.hip)
-    want = 'fp16' if x.dtype == torch.float16 else 'bf16'
-    math = want if math is None else math
-    if (math != want or prologue != PRO_NONE or rows_in is not None or x.shape[-1] % 8 or w.shape[2] % 8
-        or emit_gn_stats is not None):
-      raise ValueError('conv2d: a half-precision input takes the matching engine, prologue NONE, whole '
-                       'channel octets, no input row list / statistics')
-    _chk(x, x.dtype, 'x')
-    N, H, W, Cs = x.shape
-  if ps:
-    if (prologue != PRO_NONE or rows_in is not None or rows_out is not None or row_count is not None
-        or math not in (None, 'bf16x3')):
-      raise ValueError('conv2d: a PreSplit input takes prologue NONE, no row lists, math bf16x3')
-    math = 'bf16x3'
-    xs, x = x, x.data
-    _chk(x, torch.bfloat16, 'x')
-    N, H, W, Cs = xs.shape
-  elif not xh:
-    _f32(x, 'x')
-    N, H, W, Cs = x.shape
   pw = isinstance(w, PackedWeights)
-  if pw:
-    if not ps:
-      raise ValueError('conv2d: PackedWeights (a two-part split image) go with a PreSplit input')
-    w_img, w = w, w.data          # (the engine reads only the image; `w` passes a non-NULL pointer)
-    KH, KW, Cin, Cout = w_img.shape
+  # the tensors: device, dtype, contiguity (what the plan cannot see); the plan checks shapes and flags
+  if ps:
+    xd = _chk(x.data, torch.bfloat16, 'x')
   else:
-    _f32(w, 'w')
-    KH, KW, Cin, Cout = w.shape
-  if cin is None:
-    cin = Cs
-  if cin != Cin:
-    raise ValueError(f'conv2d: kernel expects Cin={Cin}, input has {cin}')
-  (pt, pb), (pl, pr) = padding
-  Ho = (H + pt + pb - KH) // stride + 1
-  Wo = (W + pl + pr - KW) // stride + 1
-  yh = None
-  if out_half:
-    hm = precision() if math is None else math
-    if (hm not in HALF_MATH or out is not None or emit_gn_stats is not None or up_prev is not None
-        or prologue not in (PRO_NONE, PRO_RELU) or Cs % 4 or Cin < 4 or Cout % 4):
-      raise ValueError('conv2d: out_half needs a training-precision engine launch (prologue NONE / RELU, '
-                       'no statistics / up-sampling epilogue, channel quads)')
-    yh = torch.empty((N, Ho, Wo, Cout), dtype=torch.float16 if hm == 'fp16' else torch.bfloat16, device=x.device)
-    y = yh                      # (shape carrier for the checks below; the f32 pointer passed is NULL)
-  elif out is None:
-    y = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-  else:
-    y = _f32(out, 'out')
-    if out_stride is not None:
-      if (out_stride % 4 or out_stride < Cout or y.numel() != N * Ho * Wo * out_stride or emit_gn_stats is not None
-          or residual is not None or up_prev is not None or isinstance(x, PreSplit)):
-        raise ValueError('conv2d: out_stride needs out [rows, out_stride], out_stride % 4 == 0, a plain epilogue')
-    elif y.numel() != N * Ho * Wo * Cout:
-      raise ValueError('conv2d: out has the wrong size')
-  if out_stride is not None and out is None:
-    raise ValueError('conv2d: out_stride goes with out')
+    xd = _chk(x, x.dtype if x.dtype in (torch.bfloat16, torch.float16) else torch.float32, 'x')
+  wd = w.data if pw else _f32(w, 'w')   # (the pre-split engine reads only the image; this passes a non-NULL pointer)
+  if out is not None:
+    _f32(out, 'out')
   for t, nm in ((rows_in, 'rows_in'), (rows_out, 'rows_out'), (row_count, 'row_count')):
     if t is not None:
       _chk(t, torch.int32, nm)
-  epi = 0
   mu = sc = beta = None
   if prologue in (PRO_GN_RELU, PRO_RELU_GN):
     mu, sc, beta = gn
     _f32(mu, 'gn_mu'); _f32(sc, 'gn_sc'); _f32(beta, 'gn_beta')
-    if mu.numel() != N * Cin or sc.numel() != N * Cin or beta.numel() != Cin:
-      raise ValueError('conv2d: GroupNorm statistics have the wrong size')
   if bias is not None:
-    _f32(bias, 'bias'); epi |= EPI_BIAS
-    if bias.numel() != Cout:
-      raise ValueError('conv2d: bias size')
-  if relu:
-    epi |= EPI_RELU
-  if gelu:                                   # tanh-approximated GELU (ViT MLP)
-    epi |= EPI_GELU
+    _f32(bias, 'bias')
   if residual is not None:
-    _f32(residual, 'residual'); epi |= EPI_RESIDUAL
-    if residual.shape != y.shape:
-      raise ValueError(f'conv2d: residual {tuple(residual.shape)} vs {tuple(y.shape)}')
+    _f32(residual, 'residual')
   if up_prev is not None:
-    _f32(up_prev, 'up_prev'); epi |= EPI_UPSAMPLE2X_ADD
-    if tuple(up_prev.shape) != (N, Ho // 2, Wo // 2, Cout):
-      raise ValueError('conv2d: up_prev shape')
+    _f32(up_prev, 'up_prev')
   if row_mask is not None:
-    _mask(row_mask, 'row_mask'); epi |= EPI_ROWMASK
-    if row_mask.numel() != N * Ho * Wo:
-      raise ValueError('conv2d: row_mask size')
-  d = _lib.SnapConvDesc(
-      N, H, W, Cin, Cs, KH, KW, stride, pt, pl, Ho, Wo, Cout, Cout if out_stride is None else int(out_stride), prologue,
-      epi, float(in_affine[0]), float(in_affine[1]),
-  )
-  if tuning().CONV_TILE:
-    bm, bn = (int(v) for v in tuning().CONV_TILE.split('x'))
-    d.tile_hint = bm * 1000 + bn
-  d.tile_hint += 1000000 * _stationary_mode()
-  M = N * Ho * Wo
-  # the engine the launch will take (the statistics layout depends on it)
-  math = precision() if math is None else math
-  if math not in ('f32', 'bf16', 'fp16', 'bf16x3', 'bf16x6'):
-    raise ValueError(f'conv2d: math={math!r}')
-  parts = SPLIT_PARTS.get(math, 0)
-  if parts and lib.snap_conv2d_packed_weights_split_bytes(KH * KW, Cin, Cout, parts) == 0:
-    math, parts = 'f32', 0     # weight image beyond the split engine's 32-bit offsets (template banks)
-  qparts = parts if (Cs % 4 == 0 and Cin >= 4 and not ps) else 0   # (what SnapConvExtras.w_split_parts will say)
-  # a bf16 input whose launch needs nothing but the GEMM + a plain epilogue runs on the ONE-PART pre-split engine
-  # (conv_ps.hip, NS = 1: both operands by LDS-DMA through the three-stage ring, 256 x 128 tiles) -- the same
-  # arithmetic as the training-precision engine (operands rounded to bf16, f32 accumulate)
-  ps1 = bool(bf16_ring and xh and x.dtype == torch.bfloat16 and math == 'bf16' and tuning().BF16_PS and Cs == Cin and Cin % 16 == 0
-             and rows_out is None and row_count is None and up_prev is None and gn_bwd_stats is None
-             and out is None and Cout % 4 == 0 and lib.snap_conv2d_presplit_supported(ctypes.byref(d)))
-  if xh and out_half and not ps1:
-    raise ValueError('conv2d: a half-precision input AND output need the one-part pre-split engine (bf16, Cin % 16 == 0, '
-                     'no row lists)')
-  ex = None
-  partial = partial2 = None
-  kws = None
-  rows32 = False
-  gnb_done = False
-  if rows_in is not None or rows_out is not None or row_count is not None:
-    ex = _lib.SnapConvExtras(_pv(rows_in), _pv(rows_out), _pv(row_count), None, 0, 0, None, 0,
-                             None, 0)
-  else:
-    pst = (tuning().PS_TILE if ps_tile is None else int(ps_tile)) if ps else 0
-    if ps:
-      wbytes = lib.snap_conv2d_presplit_workspace_bytes(ctypes.byref(d), pst) if tuning().USE_SPLITK else 0
-    elif ps1 or (qparts == 2 and lib.snap_conv2d_stationary_kind(ctypes.byref(d), qparts)):
-      wbytes = 0        # a stationary-operand kernel / the one-part pre-split engine takes the launch: it never splits K
-    else:
-      wbytes = lib.snap_conv2d_workspace_bytes(ctypes.byref(d)) if (tuning().USE_SPLITK and yh is None) else 0
-    if wbytes:   # small-M / deep-K layer: split K
-      kws = torch.empty(wbytes // 4, dtype=torch.float32, device=x.device)
-      ex = _lib.SnapConvExtras(None, None, None, None, 0, 0, kws.data_ptr(), wbytes, None, 0)
-      half_engine = math in ('bf16', 'fp16') and Cs % 4 == 0 and Cin % 4 == 0 and Cin >= 4 and not ps
-      if emit_gn_stats is not None and (qparts >= 2 or half_engine) and tuning().SPLITK_STATS:
-        # the reduce pass of the split / bf16 / fp16 engine emits the partial sums (per 32-row slab)
-        pbytes = lib.snap_conv2d_splitk_gn_partial_bytes(ctypes.byref(d))
-        if pbytes:
-          partial = torch.empty(pbytes // 4, dtype=torch.float32, device=x.device)
-          ex.gn_partial = partial.data_ptr()
-          ex.gn_partial_bytes = pbytes
-          ex.gn_partial_relu = int(emit_gn_stats == 'relu')
-          ex.gn_partial_rows = 32
-          rows32 = True
-    elif (gn_bwd_stats is not None and xh and emit_gn_stats is None and out is None and up_prev is None
-          and not relu and not gelu and row_mask is None):
-      pbytes = lib.snap_conv2d_gn_partial_bytes_ex(ctypes.byref(d), 0)
-      gx, gmu, grs, gga, gbe, gmode = gn_bwd_stats
-      if (pbytes and tuple(gx.shape) == (N, Ho, Wo, Cout) and gmu.numel() == N * Cout and grs.numel() == N * Cout
-          and gga.numel() == Cout and gbe.numel() == Cout and gmode in (PRO_GN_RELU, PRO_RELU_GN)):
-        for t, nm in ((gx, 'gn_bwd x'), (gmu, 'gn_bwd mu'), (grs, 'gn_bwd rstd'), (gga, 'gn_bwd gamma'), (gbe, 'gn_bwd beta')):
-          _f32(t, nm)
-        partial = torch.empty(pbytes // 4, dtype=torch.float32, device=x.device)
-        ex = _lib.SnapConvExtras(None, None, None, partial.data_ptr(), pbytes, 0, None, 0, None, 0)
-        ex.gnb_x, ex.gnb_mu, ex.gnb_rstd = gx.data_ptr(), gmu.data_ptr(), grs.data_ptr()
-        ex.gnb_gamma, ex.gnb_beta, ex.gnb_mode = gga.data_ptr(), gbe.data_ptr(), int(gmode)
-        gnb_done = True
-    elif emit_gn_stats is not None:
-      pbytes = (lib.snap_conv2d_presplit_gn_partial_bytes(ctypes.byref(d), pst) if ps
-                else lib.snap_conv2d_gn_partial_bytes_ex(ctypes.byref(d), qparts))
-      if pbytes:
-        partial = torch.empty(pbytes // 4, dtype=torch.float32, device=x.device)
-        ex = _lib.SnapConvExtras(None, None, None, partial.data_ptr(), pbytes,
-                                 int(emit_gn_stats == 'relu'), None, 0, None, 0)
-        if emit_gn_stats == 'both' and math in SPLIT_PARTS:
-          # the statistics of y AND of relu(y): a request (SnapConvExtras.gn_partial2_done)
-          partial2 = torch.empty(pbytes // 4, dtype=torch.float32, device=x.device)
-          ex.gn_partial2 = partial2.data_ptr()
-          ex.gn_partial2_bytes = pbytes
-  family = 'conv_igemm'
+    _mask(row_mask, 'row_mask')
+  # (positional, in the order of the two signatures: this call is on every launch's host path)
+  p = plan_conv(x, w, stride, padding, cin, prologue, gn, in_affine, bias, relu, residual, up_prev, row_mask, rows_in,
+                rows_out, row_count, out, emit_gn_stats, math, gelu, res_init, ps_tile, out_half, out_stride,
+                gn_bwd_stats, bf16_ring)
+  # what the plan says: the result, split-K workspace, statistics buffers, weight image
+  dev = xd.device
+  y = out if out is not None else torch.empty(p.out_shape, dtype=p.out_dtype, device=dev)
+  kws = torch.empty(p.workspace_bytes // 4, dtype=torch.float32, device=dev) if p.workspace_bytes else None
+  partial = torch.empty(p.stats_bytes // 4, dtype=torch.float32, device=dev) if p.stats_count else None
+  partial2 = torch.empty(p.stats_bytes // 4, dtype=torch.float32, device=dev) if p.stats_count == 2 else None
   wpk = None
-  # the RGB root convolution (7 x 7 / stride 2 / pad 3) of an image stored with 4 floats per pixel
-  # runs on the split engine with its own weight image (a K slab = 4 pixels of a kernel row)
-  if ps and (parts != 2 or Cin % 16):
-    raise ValueError('conv2d: the pre-split engine needs Cin % 16 == 0 and a two-part weight image')
-  root = (parts and (KH, KW, stride, Cin, Cs) == (7, 7, 2, 3, 4) and (pt, pl) == (3, 3)
-          and prologue in (PRO_NONE, PRO_AFFINE) and rows_in is None and rows_out is None
-          and row_count is None and partial is None and not ps)
-  if root:
-    wpk = _packed_weights(w, math + '/root', parts)
-    if ex is None:
-      ex = _lib.SnapConvExtras(None, None, None, None, 0, 0, None, 0, None, 0)
-    ex.w_bf16 = wpk.data_ptr()
-    ex.w_bf16_bytes = wpk.numel() * 2
-    ex.w_split_parts = parts
-    ex.w_split_root = 1
-    family = f'conv_split_{math}'
-  elif ps1:
-    wpk = _packed_weights(w, 'bf16/ps1', 1)
-    if ex is None:
-      ex = _lib.SnapConvExtras(None, None, None, None, 0, 0, None, 0, None, 0)
-    ex.w_bf16 = wpk.data_ptr()
-    ex.w_bf16_bytes = wpk.numel() * 2
-    ex.w_split_parts = 1
-    ex.x_presplit = 1
-    ex.ps_tile = int(tuning().PS_TILE if ps_tile is None else ps_tile)
-    if yh is not None:
-      ex.y_half = yh.data_ptr()
-    family = 'conv_bf16'
-  elif math != 'f32' and Cs % 4 == 0 and Cin >= 4:
-    wpk = w_img.data if pw else _packed_weights(w, math, parts)
-    if ex is None:
-      ex = _lib.SnapConvExtras(None, None, None, None, 0, 0, None, 0, None, 0)
-    ex.w_bf16 = wpk.data_ptr()
-    ex.w_bf16_bytes = wpk.numel() * 2
-    ex.w_split_parts = parts
-    ex.w_half = int(math == 'fp16')
-    ex.x_half = int(xh)
-    if yh is not None:
-      ex.y_half = yh.data_ptr()
-    family = f'conv_split_{math}' if parts else ('conv_fp16' if math == 'fp16' else 'conv_bf16')
-    if ps:
-      ex.x_presplit = 1
-      ex.ps_tile = pst
-      ex.ps_res_init = int(tuning().PS_RES_INIT if res_init is None else bool(res_init))
-  if tuning().CONV_BK or tuning().CONV_NO_HALO or tuning().CONV_RS_NSPLIT or tuning().CONV_NO_PLAIN:
-    if ex is None:
-      ex = _lib.SnapConvExtras(None, None, None, None, 0, 0, None, 0, None, 0)
-    ex.bk_hint = int(tuning().CONV_BK or 0)
-    ex.tune_flags = (int(bool(tuning().CONV_NO_HALO)) | 8 * int(bool(tuning().CONV_NO_PLAIN))
-                     | ((int(tuning().CONV_RS_NSPLIT) & 15) << 4))
+  if p.image is not None:
+    wpk = wd if pw else _packed_weights(w, p.image, p.parts)
+  ex = None
+  if p.extras:
+    ex = _lib.SnapConvExtras()
+    if rows_in is not None or rows_out is not None or row_count is not None:
+      ex.rows_in, ex.rows_out, ex.row_count = _pv(rows_in), _pv(rows_out), _pv(row_count)
+    if kws is not None:
+      ex.workspace, ex.workspace_bytes = kws.data_ptr(), p.workspace_bytes
+    if partial is not None:
+      ex.gn_partial, ex.gn_partial_bytes = partial.data_ptr(), p.stats_bytes
+      ex.gn_partial_relu, ex.gn_partial_rows = int(p.stats_relu), p.gn_partial_rows
+    if partial2 is not None:
+      ex.gn_partial2, ex.gn_partial2_bytes = partial2.data_ptr(), p.stats_bytes
+    if p.gnb:
+      for t, nm in zip(gn_bwd_stats[:5], ('gn_bwd x', 'gn_bwd mu', 'gn_bwd rstd', 'gn_bwd gamma', 'gn_bwd beta')):
+        _f32(t, nm)
+      ex.gnb_x, ex.gnb_mu, ex.gnb_rstd, ex.gnb_gamma, ex.gnb_beta = (t.data_ptr() for t in gn_bwd_stats[:5])
+      ex.gnb_mode = int(gn_bwd_stats[5])
+    if wpk is not None:
+      ex.w_bf16, ex.w_bf16_bytes = wpk.data_ptr(), wpk.numel() * 2
+      ex.w_split_parts, ex.w_split_root, ex.w_half, ex.x_half = p.w_split_parts, p.w_split_root, p.w_half, p.x_half
+      ex.x_presplit, ex.ps_tile, ex.ps_res_init = p.x_presplit, p.ps_tile, p.ps_res_init
+      if out_half:
+        ex.y_half = y.data_ptr()
+    ex.bk_hint, ex.tune_flags = p.bk_hint, p.tune_flags
+  N, Ho, Wo, Cout = p.out_shape
+  KH, KW, Cin = w.shape[:3]
+  M = N * Ho * Wo
   kflops = 2.0 * KH * KW * Cin * Cout
   if row_count is None:
     flops = kflops * M
-    nbytes = 4.0 * ((xs.numel() if ps else x.numel() * (0.5 if xh else 1.0)) + (w_img.numel() if pw else w.numel()) + y.numel()
+    nbytes = 4.0 * ((x.numel() if ps else x.numel() * (0.5 if p.x_half or p.image == 'bf16/ps1' else 1.0)) + w.numel() + y.numel()
                     + (residual.numel() if residual is not None else 0))
   else:  # resolved after the sync: only the listed rows are multiplied / moved
     flops = lambda: kflops * int(row_count.item())
-    nbytes = lambda: 4.0 * (int(row_count.item()) * (Cin + Cout) + w.numel())
-  kind = (lib.snap_conv2d_stationary_kind(ctypes.byref(d), qparts)
-          if (qparts == 2 and rows_in is None and rows_out is None and row_count is None) else 0)
+    nbytes = lambda: 4.0 * (int(row_count.item()) * (Cin + Cout) + wd.numel())
   with _region(
-      family, flops, nbytes,
-      lambda: f'{"PS_" if ps else "PS1_" if ps1 else ("", "RS_", "WS_", "WS_")[kind]}M{M}{"r" if row_count is not None else ""}_K{KH}x{KW}x{Cin}_N{Cout}'
-              f'_s{stride}_p{prologue}_e{epi}',
+      p.family, flops, nbytes,
+      lambda: f'{p.tag}M{M}{"r" if row_count is not None else ""}_K{KH}x{KW}x{Cin}_N{Cout}_s{stride}_p{prologue}_e{p.desc.epilogue}',
   ):
     st = lib.snap_conv2d_nhwc_ex_f32(
-        ctypes.byref(d), _p(x), _p(w), None if yh is not None else _p(y), _p(mu), _p(sc), _p(beta), _p(bias),
+        ctypes.byref(p.desc), _p(xd), _p(wd), None if out_half else _p(y), _p(mu), _p(sc), _p(beta), _p(bias),
         _p(residual), _p(up_prev), _p(row_mask), None if ex is None else ctypes.byref(ex),
         _stream(),
     )
   _lib.check(st, 'snap_conv2d_nhwc_ex_f32')
-  if gnb_done:
+  if p.gnb:
     # (the GroupNorm VJP checks that it is handed the same x before it trusts these sums)
-    y._snap_gnb_partial = (partial, lib.snap_conv2d_tile_rows_ex(ctypes.byref(d), 0), gn_bwd_stats[0].data_ptr(),
-                           gn_bwd_stats[0]._version, int(gn_bwd_stats[5]))
+    y._snap_gnb_partial = (partial, p.tile_rows, gn_bwd_stats[0].data_ptr(), gn_bwd_stats[0]._version, int(gn_bwd_stats[5]))
   elif partial is not None:
-    tile_rows = (32 if rows32 else lib.snap_conv2d_presplit_tile_rows(ctypes.byref(d), pst) if ps
-                 else lib.snap_conv2d_tile_rows_ex(ctypes.byref(d), qparts))
-    y._snap_gn_partial = (partial, tile_rows, emit_gn_stats == 'relu')
+    y._snap_gn_partial = (partial, p.tile_rows, p.stats_relu)
     if partial2 is not None and ex.gn_partial2_done:
-      y._snap_gn_partial_relu = (partial2, y._snap_gn_partial[1], True)
+      y._snap_gn_partial_relu = (partial2, p.tile_rows, True)
   return y
 
 
@@ -801,40 +849,43 @@ def pack_weights_bf16(w, half=False):
   return out
 
 
-# the training-precision engines: operands rounded to bf16 / IEEE half, f32 accumulate
-HALF_MATH = ('bf16', 'fp16')
-
-
-SPLIT_PARTS = {'bf16x3': 2, 'bf16x6': 3}
 # Bumped by every ``ForwardContext`` (= every ``apply``): the bf16 weight images are prepared
 # once per apply and tensor (the map and query passes of one apply share them), never carried
 # from one apply / timed step to the next -- like the StdConv standardisation.
 PACK_EPOCH = 0
 
 
+def _image_get(w, key, explicit=False):
+  """The image remembered on ``w`` under ``key`` (``w._snap_packed``: key -> image) if it still
+  holds -- packed in the current ``PACK_EPOCH``, tensor not modified in place since --, else None.
+  ``explicit``: a bare image stored under the key by hand (tools) is returned as it is."""
+  slot = getattr(w, '_snap_packed', None)
+  hit = None if slot is None else slot.get(key)
+  if isinstance(hit, tuple):
+    return hit[2] if hit[0] == PACK_EPOCH and hit[1] == w._version else None
+  return hit if explicit else None
+
+
+def _image_put(w, key, image):
+  slot = getattr(w, '_snap_packed', None)
+  if slot is None:
+    slot = w._snap_packed = {}
+  slot[key] = (PACK_EPOCH, w._version, image)
+
+
 def _packed_weights(w, math, parts):
   """The engine's weight image of ``w`` for this apply: an explicit ``w._snap_packed[math]``
-  (tools) wins; otherwise packed at first use and remembered on the tensor for the current
-  ``PACK_EPOCH`` while the tensor is not modified in place."""
-  slot = getattr(w, '_snap_packed', None)
-  if slot is not None:
-    hit = slot.get(math)
-    if hit is not None:
-      if not isinstance(hit, tuple):
-        return hit
-      if hit[0] == PACK_EPOCH and hit[1] == w._version:
-        return hit[2]
-  if math.endswith('/root'):
-    wpk = pack_weights_split_root_bf16(w, parts)
-  else:
-    wpk = pack_weights_split_bf16(w, parts) if parts else pack_weights_bf16(w, half=(math == 'fp16'))
-  if slot is None:
-    slot = {}
+  (tools) wins; otherwise packed at first use and remembered on the tensor (``_image_get``)."""
+  wpk = _image_get(w, math, explicit=True)
+  if wpk is None:
+    if math.endswith('/root'):
+      wpk = pack_weights_split_root_bf16(w, parts)
+    else:
+      wpk = pack_weights_split_bf16(w, parts) if parts else pack_weights_bf16(w, half=(math == 'fp16'))
     try:
-      w._snap_packed = slot
+      _image_put(w, math, wpk)
     except AttributeError:
-      return wpk
-  slot[math] = (PACK_EPOCH, w._version, wpk)
+      pass
   return wpk
 
 
@@ -876,16 +927,8 @@ def pack_weights_split_multi(ws, math):
   launch and remember it on the tensors for the current apply (see ``_packed_weights``)."""
   parts = SPLIT_PARTS[math]
   lib = _lib.load()
-  todo = []
-  for w in ws:
-    slot = getattr(w, '_snap_packed', None)
-    hit = None if slot is None else slot.get(math)
-    if isinstance(hit, tuple) and hit[0] == PACK_EPOCH and hit[1] == w._version:
-      continue
-    KH, KW, Cin, Cout = w.shape
-    if Cin < 4 or lib.snap_conv2d_packed_weights_split_bytes(KH * KW, Cin, Cout, parts) == 0:
-      continue                       # runs on the f32 engine (conv2d decides the same way)
-    todo.append(w)
+  # (kernels that run on the f32 engine get no image: ``kernel_image``)
+  todo = [w for w in ws if _image_get(w, math) is None and kernel_image(w.shape, math)[2]]
   if not todo:
     return
   items = np.zeros(len(todo), dtype=_PACK_ITEM)
@@ -903,11 +946,7 @@ def pack_weights_split_multi(ws, math):
   st = lib.snap_conv2d_pack_weights_split_multi_bf16(_p(table), len(todo), blk, parts, _stream())
   _lib.check(st, 'snap_conv2d_pack_weights_split_multi_bf16')
   for w, out in zip(todo, outs):
-    slot = getattr(w, '_snap_packed', None)
-    if slot is None:
-      slot = {}
-      w._snap_packed = slot
-    slot[math] = (PACK_EPOCH, w._version, out)
+    _image_put(w, math, out)
 
 
 def pack_weights_bf16_multi(ws, with_rotated=True, math='bf16'):
@@ -918,15 +957,7 @@ def pack_weights_bf16_multi(ws, with_rotated=True, math='bf16'):
   if math not in HALF_MATH:
     raise ValueError(f'pack_weights_bf16_multi: math={math!r}')
   half = math == 'fp16'
-  todo = []
-  for w in ws:
-    slot = getattr(w, '_snap_packed', None)
-    hit = None if slot is None else slot.get(math)
-    if isinstance(hit, tuple) and hit[0] == PACK_EPOCH and hit[1] == w._version:
-      continue
-    if w.shape[2] < 4:
-      continue                       # (runs on the f32 engine)
-    todo.append(w)
+  todo = [w for w in ws if _image_get(w, math) is None and kernel_image(w.shape, math)[2]]
   if not todo:
     return
   n = len(todo) * (2 if with_rotated else 1)
@@ -952,22 +983,14 @@ def pack_weights_bf16_multi(ws, with_rotated=True, math='bf16'):
   _lib.check(st, 'snap_conv2d_pack_weights_multi_f16' if half else 'snap_conv2d_pack_weights_multi_bf16')
   k = 0
   for w in todo:
-    slot = getattr(w, '_snap_packed', None)
-    if slot is None:
-      slot = {}
-      w._snap_packed = slot
-    slot[math] = (PACK_EPOCH, w._version, outs[k]); k += 1
+    _image_put(w, math, outs[k]); k += 1
     if with_rotated:
-      slot[math + '/rot'] = (PACK_EPOCH, w._version, outs[k]); k += 1
+      _image_put(w, math + '/rot', outs[k]); k += 1
 
 
 def packed_rot_image(w, math='bf16'):
   """The rotated image ``pack_weights_bf16_multi`` prepared for ``w`` in this apply, or None."""
-  slot = getattr(w, '_snap_packed', None)
-  hit = None if slot is None else slot.get(math + '/rot')
-  if isinstance(hit, tuple) and hit[0] == PACK_EPOCH and hit[1] == w._version:
-    return hit[2]
-  return None
+  return _image_get(w, math + '/rot')
 
 
 def dense(x, kernel, bias=None, *, cin=None, prologue=PRO_NONE, relu=False,
@@ -976,22 +999,17 @@ def dense(x, kernel, bias=None, *, cin=None, prologue=PRO_NONE, relu=False,
   """x [..., Cs] @ kernel [Cin, Cout] (+bias) through the conv engine (1x1).  out_stride: ``conv2d``."""
   lead = x.shape[:-1]
   M = int(np.prod(lead)) if len(lead) else 1
-  if out_stride is not None:
-    conv2d(x.reshape(1, 1, M, x.shape[-1]), kernel.reshape(1, 1, *kernel.shape),
-           cin=cin if cin is not None else kernel.shape[0], prologue=prologue, bias=bias, relu=relu, row_mask=row_mask,
-           rows_in=rows_in, rows_out=rows_out, row_count=row_count, out=out, math=math, gelu=gelu,
-           out_stride=out_stride)
-    return out
+  strided = out_stride is not None     # (``out`` [rows, out_stride] goes through as it is and is the result)
   y = conv2d(
       x.reshape(1, 1, M, x.shape[-1]), kernel.reshape(1, 1, *kernel.shape),
       cin=cin if cin is not None else kernel.shape[0], prologue=prologue,
       bias=bias, relu=relu, row_mask=row_mask, rows_in=rows_in, rows_out=rows_out,
-      row_count=row_count, out=None if out is None else out.reshape(1, 1, M, kernel.shape[1]),
-      math=math, gelu=gelu,
-      residual=None if residual is None else residual.reshape(1, 1, M, kernel.shape[1]), out_half=out_half,
-      bf16_ring=bf16_ring,
+      row_count=row_count, out=out if (strided or out is None) else out.reshape(1, 1, M, kernel.shape[1]),
+      math=math, gelu=gelu, out_stride=out_stride,
+      residual=None if residual is None else residual.reshape(1, 1, M, kernel.shape[1]),
+      out_half=out_half, bf16_ring=bf16_ring,
   )
-  return y.reshape(*lead, kernel.shape[1])
+  return out if strided else y.reshape(*lead, kernel.shape[1])
 
 
 def semantic_embed(rasters, idx_road, idx_other, table_road, table_other):
