@@ -17,10 +17,6 @@
 
 static inline int64_t snap_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // Wave-level reductions over all 64 lanes; the (bitwise identical) result lands in every
 // lane.  Within each 16-lane row: four DPP rotate steps (row_ror 8/4/2/1 -- no LDS traffic,
 // unlike __shfl_xor, which lowers to ds_bpermute_b32 and a full LDS round trip per step);
@@ -59,5 +55,7 @@ __device__ __forceinline__ float snap_max_nan(float a, float b) {
   return (a != a || b != b) ? __int_as_float(0x7fc00000) : m;
 }
 __device__ __forceinline__ float snap_relu(float v) { return v < 0.f ? 0.f : v; }   // relu(NaN) = NaN
+
+#include "mma_common.h"
 
 #endif  // SNAP_CSRC_COMMON_H_

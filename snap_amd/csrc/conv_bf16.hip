@@ -20,29 +20,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-// Element type of the rounded operands: bf16 (default) or IEEE half (F16: the reference's
-// dtype=float16 train config, train_localization.py:93 -- 11 significand bits instead of 8, the
-// exponent range of half: values beyond 65504 round to inf and reach the trainer's non-finite
-// check, gradients below 6e-8 flush -- which is what DynamicScale is for, trainer.py:391-392).
-template <bool F16> struct Elem;
-template <> struct Elem<false> {
-  typedef __bf16 T; typedef bf16x8 x8; typedef bf16x4 x4;
-  static __device__ __forceinline__ f32x16 mfma(x8 a, x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Elem<true> {
-  typedef _Float16 T; typedef f16x8 x8; typedef f16x4 x4;
-  static __device__ __forceinline__ f32x16 mfma(x8 a, x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
 // GNT (as conv_split.hip): the GroupNorm operands of the slab's 32 channels -- mean and rstd * gamma of the (at
 // most two) images a row tile of BM <= Ho Wo pixels touches, and beta -- come from a 640-byte LDS table that 40
 // lanes fetch by LDS-DMA two slabs ahead (three-slot ring; the slab's closing barrier publishes it), instead of
@@ -183,8 +160,7 @@ __device__ __forceinline__ void conv_bf16_body(const ConvArgs& a) {
       const bool ok = kc < a.cin8 && (n0 + col) < d.Cout;
       const void* src = ok ? static_cast<const void*>(wt + ((int64_t)(n0 + col) * taps + kpos) * a.cin8 + kc)
                            : static_cast<const void*>(kZeroChunk);
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)src,
-                                       (lds_void_t*)(Bb + buf * (B_ST * 4) + 16 * slot), 16, 0, 0);
+      lds_dma16(src, Bb + buf * (B_ST * 4) + 16 * slot);
     }
   };
   // GroupNorm table of channel tile `ctile` -> ring slot `ring` (lanes 0..39 of wave 0)
@@ -198,8 +174,7 @@ __device__ __forceinline__ void conv_bf16_body(const ConvArgs& a) {
                                            (int64_t)(seg >= 2 ? n_second : n_first) * d.Cin;
         const void* src = c < d.Cin ? static_cast<const void*>(base + c)
                                     : static_cast<const void*>(kZeroChunk);
-        __builtin_amdgcn_global_load_lds((cglobal_void_t*)src,
-                                         (lds_void_t*)(Gt + ring * kGnRing + 16 * tid), 16, 0, 0);
+        lds_dma16(src, Gt + ring * kGnRing + 16 * tid);
       }
     }
   };
@@ -250,11 +225,11 @@ __device__ __forceinline__ void conv_bf16_body(const ConvArgs& a) {
     issue_b(0);
     advance();
     if constexpr (gn_tab) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
       __syncthreads();           // tables of slabs 0 and 1 visible to every wave
     }
     store_a(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
   }
   for (int kt = kt_begin; kt < kt_end; ++kt) {
@@ -292,7 +267,7 @@ __device__ __forceinline__ void conv_bf16_body(const ConvArgs& a) {
     }
     if (more) store_a(cur ^ 1, ring_next);
     ring_cur = ring_next;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the B octets of slab kt+1 landed
+    wait_vm<0>();   // the B octets of slab kt+1 landed
     __syncthreads();
   }
 
@@ -396,8 +371,7 @@ __device__ __forceinline__ void conv_bf16_xh_body(const ConvArgs& a) {
       const bool ok = r_ok[p] && hi >= 0 && hi < d.H && wi >= 0 && wi < d.W &&
                       (ct * BK + 8 * r_oct[p]) < d.Cin;          // (Cin % 8 == 0: whole octets)
       const void* src = ok ? static_cast<const void*>(r_px[p] + delta) : static_cast<const void*>(kZeroChunk);
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)src,
-                                       (lds_void_t*)(Ab + buf * (A_ST * 4) + 16 * slot), 16, 0, 0);
+      lds_dma16(src, Ab + buf * (A_ST * 4) + 16 * slot);
     }
 #pragma unroll
     for (int p = 0; p < BPIECES; ++p) {
@@ -408,8 +382,7 @@ __device__ __forceinline__ void conv_bf16_xh_body(const ConvArgs& a) {
       const bool ok = kc < a.cin8 && (n0 + col) < d.Cout;
       const void* src = ok ? static_cast<const void*>(wt + ((int64_t)(n0 + col) * taps + kpos) * a.cin8 + kc)
                            : static_cast<const void*>(kZeroChunk);
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)src,
-                                       (lds_void_t*)(Bb + buf * (B_ST * 4) + 16 * slot), 16, 0, 0);
+      lds_dma16(src, Bb + buf * (B_ST * 4) + 16 * slot);
     }
     if (++ct == a.ctiles) {
       ct = 0;
@@ -426,8 +399,8 @@ __device__ __forceinline__ void conv_bf16_xh_body(const ConvArgs& a) {
   if (nslab > 1) issue(1);
   for (int i = 0; i < nslab; ++i) {
     const int cur = i % NST;
-    if (i + 1 < nslab) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(APIECES + BPIECES) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (i + 1 < nslab) wait_vm<APIECES + BPIECES>();
+    else wait_vm<0>();
     __syncthreads();                      // slab i landed everywhere; stage (i + 2) % 3 was consumed in iteration i - 1
     if (i + 2 < nslab) issue((i + 2) % NST);
     const char* as = Ab + cur * (A_ST * 4);

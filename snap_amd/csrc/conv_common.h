@@ -94,21 +94,6 @@ int ps_ksplit(int64_t M, int Cout, int64_t nk, int bm, int bn, size_t kpartial_b
 namespace {
 using snapconv::ConvArgs;
 
-// The prologue is a COMPILE-TIME parameter: a run-time switch here is lowered to a
-// branch tree per staged element and wrecks the schedule of the whole main loop.
-template <int PRO>
-__device__ __forceinline__ float apply_pro(float v, float mu, float sc, float beta, float s,
-                                           float t) {
-  if constexpr (PRO == SNAP_PRO_AFFINE) return v * s + t;
-  if constexpr (PRO == SNAP_PRO_GN_RELU) return snap_relu((v - mu) * sc + beta);
-  if constexpr (PRO == SNAP_PRO_RELU_GN) return (snap_relu(v) - mu) * sc + beta;
-  if constexpr (PRO == SNAP_PRO_RELU) return snap_relu(v);
-  return v;
-}
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void cglobal_void_t;
-
 // zero source for LDS-DMA lanes whose tap / channel / row is out of range
 __device__ __attribute__((aligned(64))) const float kZeroChunk[16] = {0.f};
 
@@ -259,13 +244,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a,
         *reinterpret_cast<f32x4*>(a.y + o) = v;
       } else {
         if (a.y) *reinterpret_cast<f32x4*>(a.y + o) = v;
-        if constexpr (OUTH == 1) {
-          typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-          *reinterpret_cast<bf16x4_t*>(static_cast<__bf16*>(a.y_half) + o) = __builtin_convertvector(v, bf16x4_t);
-        } else {
-          typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-          *reinterpret_cast<f16x4_t*>(static_cast<_Float16*>(a.y_half) + o) = __builtin_convertvector(v, f16x4_t);
-        }
+        store_half4<OUTH>(a.y_half, o, v);
       }
       if (GNB && gnb) {
         const int sl = m >= m_split ? 1 : 0;

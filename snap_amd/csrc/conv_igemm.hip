@@ -301,8 +301,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
         const int c = ct * BK + 4 * q;
         const bool ok = tap_in[i] && c < d.Cin;          // (Cin % 4 == 0 on the VEC path)
         const float* src = ok ? tap_px[i] + c : kZeroChunk;
-        __builtin_amdgcn_global_load_lds((cglobal_void_t*)src,
-                                         (lds_void_t*)(Ad + stage * A_ST + 4 * (tid + 256 * i)), 16, 0, 0);
+        lds_dma16(src, Ad + stage * A_ST + 4 * (tid + 256 * i));
       }
 #pragma unroll
       for (int p = 0; p < BPASS; ++p) {
@@ -310,15 +309,14 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
         const int col = n0 + 4 * bcq;
         const bool ok = (ct * BK + kr) < d.Cin && col < d.Cout;
         const float* src = ok ? a.w + ((int64_t)(kpos * d.Cin + ct * BK + kr) * d.Cout + col) : kZeroChunk;
-        __builtin_amdgcn_global_load_lds((cglobal_void_t*)src,
-                                         (lds_void_t*)(Bd + stage * B_ST + 4 * (tid + 256 * p)), 16, 0, 0);
+        lds_dma16(src, Bd + stage * B_ST + 4 * (tid + 256 * p));
       }
     };
     if (nslab > 0) { issue(0); advance(); }
     if (nslab > 1) { issue(1); advance(); }
     for (int t = 0; t < nslab; ++t) {
-      if (t + 1 < nslab) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AROWS + BPASS) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (t + 1 < nslab) wait_vm<AROWS + BPASS>();
+      else wait_vm<0>();
       __syncthreads();   // slab t landed for every wave; stage (t+2)%3 (slab t-1) is free
       if (t + 2 < nslab) { issue((t + 2) % kDmaStages); advance(); }
       const float* as = Ad + (t % kDmaStages) * A_ST;
@@ -418,7 +416,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
   conv_epilogue<BM, BN>(a, acc, smem, m0, n0, Meff, row_t, split);
 }
 
-
 // Two entry points over one body.  Variants WITHOUT a GroupNorm prologue fit 128 VGPRs
 // and are held to 4 waves per SIMD (measured +3-4 % on the big Dense layers: more waves to
 // cover the global-load latency); the GroupNorm variants carry the statistics operands
@@ -516,7 +513,6 @@ int launch_pro(const ConvArgs& a, hipStream_t s) {
 
 // K-slab depth of the big tiles (SnapConvExtras.bk_hint = 16 | 32; default 16, set by
 // measurement on MI355X)
-
 
 template <bool VEC>
 int launch_tile(const ConvArgs& a, hipStream_t s) {

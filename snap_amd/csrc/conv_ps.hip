@@ -32,13 +32,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // KS = 16-k steps per ring stage (one barrier per stage), NST = ring depth in stages
 // NS = 2: the two-part pre-split image (f32-grade, three products per MAC).  NS = 1: ONE part -- x is a plain bf16
 // matrix [pixel][Cin] (16 channels = the 32-byte run of a k-step), the weights the one-part image of the same
@@ -266,34 +259,18 @@ __device__ __forceinline__ void conv_ps_body(const ConvArgs& a) {
       const char* bs = as + A_ST;
       bf16x8 av[TM][NS], bv[TN][NS];
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int R = wr * (BM / WR) + i * 32 + l31;
-        const char* p0 = as + R * 32 + ((lhi ^ ((R >> 3) & 1)) * 16);
+      for (int i = 0; i < TM; ++i)
+        load_frag<NS>(as + frag_offset(wr * (BM / WR) + i * 32 + l31, lhi), A_PART, av[i]);
 #pragma unroll
-        for (int p = 0; p < NS; ++p) av[i][p] = *reinterpret_cast<const bf16x8*>(p0 + p * A_PART);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int C = wc * (BN / 2) + j * 32 + l31;
-        const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
-#pragma unroll
-        for (int p = 0; p < NS; ++p) bv[j][p] = *reinterpret_cast<const bf16x8*>(p0 + p * B_PART);
-      }
-#define SNAP_PS_PRODUCT(PA, PB)                                                              \
-  _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[i][PA], bv[j][PB], acc[i][j], 0, 0, 0);
-      if constexpr (NS == 2) {
-        SNAP_PS_PRODUCT(1, 0)
+      for (int j = 0; j < TN; ++j)
+        load_frag<NS>(bs + frag_offset(wc * (BN / 2) + j * 32 + l31, lhi), B_PART, bv[j]);
+      // (a one-part product has no first group to issue behind)
+      static_assert(NS == 2 || NT == 256 || KS > 1, "one-part 512-thread tiles: two k-steps per stage");
+      split_product<NS>(acc, av, bv, [&]() {
         if (KS == 1) {
           if (grp == 1) issue(islot);
         }
-        SNAP_PS_PRODUCT(0, 1)
-        SNAP_PS_PRODUCT(0, 0)
-      } else {
-        static_assert(NS == 2 || NT == 256 || KS > 1, "one-part 512-thread tiles: two k-steps per stage");
-        SNAP_PS_PRODUCT(0, 0)
-      }
-#undef SNAP_PS_PRODUCT
+      });
     }
     islot = islot + 1 == NST ? 0 : islot + 1;
   }

@@ -37,51 +37,11 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// four f32 -> hi / lo bf16 pairs (conv_split.hip's split_bf16<2>: RNE, exact residual)
-__device__ __forceinline__ void split2(const f32x4& v, u32x2& hi, u32x2& lo) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const f32x2 pr = {v[2 * h], v[2 * h + 1]};
-    const bf16x2 b = __builtin_convertvector(pr, bf16x2);
-    unsigned u;
-    __builtin_memcpy(&u, &b, 4);
-    hi[h] = u;
-    const f32x2 rr = {pr[0] - __uint_as_float(u << 16), pr[1] - __uint_as_float(u & 0xffff0000u)};
-    const bf16x2 c = __builtin_convertvector(rr, bf16x2);
-    unsigned w;
-    __builtin_memcpy(&w, &c, 4);
-    lo[h] = w;
-  }
-}
-
 __device__ __forceinline__ float xor_sum3(float v) {     // over lane bits 3, 4, 5
   v += __shfl_xor(v, 8);
   v += __shfl_xor(v, 16);
   v += __shfl_xor(v, 32);
   return v;
-}
-
-// s_waitcnt vmcnt(n) for an n the optimiser knows (the unrolled stage loop): one case survives
-__device__ __forceinline__ void wait_vm_n(int n) {
-  switch (n) {
-#define SNAP_W(N) case N: wait_vm<N>(); break;
-#define SNAP_W8(B) SNAP_W(B) SNAP_W(B + 1) SNAP_W(B + 2) SNAP_W(B + 3) SNAP_W(B + 4) SNAP_W(B + 5) SNAP_W(B + 6) SNAP_W(B + 7)
-    SNAP_W8(0) SNAP_W8(8) SNAP_W8(16) SNAP_W8(24) SNAP_W8(32) SNAP_W8(40) SNAP_W8(48) SNAP_W8(56)
-#undef SNAP_W8
-#undef SNAP_W
-    default: wait_vm<0>(); break;
-  }
 }
 
 // Vector-memory instructions a wave issues BEHIND the DMA of the stage it is about to read (ring of
@@ -166,8 +126,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rs_kernel(const ConvArgs a) {
     char* dst = ring + i_slot * kStage;
 #pragma unroll
     for (int p = 0; p < P; ++p)
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)(src + b_off[p]),
-                                       (lds_void_t*)(dst + 16 * (tid + NT * p)), 16, 0, 0);
+      lds_dma16(src + b_off[p], dst + 16 * (tid + NT * p));
     if (++i_c == SPT) { i_c = 0; ++i_t; }
     i_slot = i_slot + 1 == NST ? 0 : i_slot + 1;
   };
@@ -243,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rs_kernel(const ConvArgs a) {
           const float pv = apply_pro<PRO>(v[e], mu[e], sc[e], be[e], d.in_scale, d.in_shift);
           v[e] = ok ? pv : 0.f;
         }
-        split2(v, h[hq], l[hq]);
+        split_bf16(v, h[hq], l[hq]);
       }
       const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
       const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
@@ -356,12 +315,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rs_kernel(const ConvArgs a) {
         const char* bs = stage + sl * B_SLAB;
         bf16x8 bv[TN][2];
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int C = j * 32 + l31;
-          const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
-          bv[j][0] = *reinterpret_cast<const bf16x8*>(p0);
-          bv[j][1] = *reinterpret_cast<const bf16x8*>(p0 + B_PART);
-        }
+        for (int j = 0; j < TN; ++j) load_frag<2>(bs + frag_offset(j * 32 + l31, lhi), B_PART, bv[j]);
 #pragma unroll
         for (int j = 0; j < TN; ++j)
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo[s], bv[j][0], acc[j], 0, 0, 0);
@@ -524,9 +478,9 @@ __global__ __launch_bounds__(512, 2) void conv1x1_bs_kernel(const ConvArgs a) {
       const int q = tid + NT * p;                                  // 16-byte piece
       const int ct = q / (KS * 512);
       const char* src = wt + (int64_t)((nbase >> 7) + ct) * col_tile_bytes + (q - ct * (KS * 512)) * 16;
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)src, (lds_void_t*)(panel + 16 * q), 16, 0, 0);
+      lds_dma16(src, panel + 16 * q);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
   }
 
@@ -601,7 +555,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_bs_kernel(const ConvArgs a) {
             const float pv = apply_pro<SNAP_PRO_GN_RELU>(v[e], mu[e], sc[e], be[e], d.in_scale, d.in_shift);
             v[e] = ok ? pv : 0.f;
           }
-          split2(v, h[hq], l[hq]);
+          split_bf16(v, h[hq], l[hq]);
         }
         const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
         const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
@@ -626,12 +580,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_bs_kernel(const ConvArgs a) {
         const char* bs = panel + (ct * KS + s) * B_SLAB;
         bf16x8 bv[TN][2];
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int C = j * 32 + l31;
-          const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
-          bv[j][0] = *reinterpret_cast<const bf16x8*>(p0);
-          bv[j][1] = *reinterpret_cast<const bf16x8*>(p0 + B_PART);
-        }
+        for (int j = 0; j < TN; ++j) load_frag<2>(bs + frag_offset(j * 32 + l31, lhi), B_PART, bv[j]);
 #pragma unroll
         for (int j = 0; j < TN; ++j)
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo[s], bv[j][0], acc[j], 0, 0, 0);
@@ -793,9 +742,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64_kernel(const ConvArgs a) 
       const int sl = q >> 8, within = q & 255;
       const int part = within >> 7, rem = within & 127;
       const char* src = wt + (int64_t)sl * 8192 + part * 4096 + (rem >> 1) * 32 + (rem & 1) * 16;
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)src, (lds_void_t*)(panel + 16 * q), 16, 0, 0);
+      lds_dma16(src, panel + 16 * q);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
   }
 
@@ -856,7 +805,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64_kernel(const ConvArgs a) 
             const float pv = apply_pro<SNAP_PRO_GN_RELU>(v[e], mu[e], sc[e], be[e], d.in_scale, d.in_shift);
             v[e] = px_ok ? pv : 0.f;
           }
-          split2(v, h[hq], l[hq]);
+          split_bf16(v, h[hq], l[hq]);
         }
         const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
         const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
@@ -873,12 +822,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64_kernel(const ConvArgs a) 
           const char* bs = panel + ((kh * 3 + kw) * KS + s) * B_SLAB;
           bf16x8 bv[TN][2];
 #pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const int C = j * 32 + l31;
-            const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
-            bv[j][0] = *reinterpret_cast<const bf16x8*>(p0);
-            bv[j][1] = *reinterpret_cast<const bf16x8*>(p0 + B_PART);
-          }
+          for (int j = 0; j < TN; ++j) load_frag<2>(bs + frag_offset(j * 32 + l31, lhi), B_PART, bv[j]);
 #pragma unroll
           for (int j = 0; j < TN; ++j)
             acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, bv[j][0], acc[j], 0, 0, 0);
@@ -961,9 +905,9 @@ __global__ __launch_bounds__(512, 2) void conv_root_ws64_kernel(const ConvArgs a
       const int sl = q >> 8, within = q & 255;
       const int part = within >> 7, rem = within & 127;
       const char* src = wt + (int64_t)sl * 8192 + part * 4096 + (rem >> 1) * 32 + (rem & 1) * 16;
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)src, (lds_void_t*)(panel + 16 * q), 16, 0, 0);
+      lds_dma16(src, panel + 16 * q);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
   }
   const int relu_out = d.epilogue & SNAP_EPI_RELU;
@@ -1008,7 +952,7 @@ __global__ __launch_bounds__(512, 2) void conv_root_ws64_kernel(const ConvArgs a
             const float pv = apply_pro<PRO>(v[e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
             v[e] = in ? pv : 0.f;
           }
-          split2(v, h[q], l[q]);
+          split_bf16(v, h[q], l[q]);
         }
         const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
         const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
@@ -1018,12 +962,7 @@ __global__ __launch_bounds__(512, 2) void conv_root_ws64_kernel(const ConvArgs a
         const char* bs = panel + (kh * 2 + g) * B_SLAB;
         bf16x8 bv[TN][2];
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int C = j * 32 + l31;
-          const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
-          bv[j][0] = *reinterpret_cast<const bf16x8*>(p0);
-          bv[j][1] = *reinterpret_cast<const bf16x8*>(p0 + B_PART);
-        }
+        for (int j = 0; j < TN; ++j) load_frag<2>(bs + frag_offset(j * 32 + l31, lhi), B_PART, bv[j]);
 #pragma unroll
         for (int j = 0; j < TN; ++j)
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, bv[j][0], acc[j], 0, 0, 0);

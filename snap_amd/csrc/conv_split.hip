@@ -27,38 +27,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// Four f32 -> NS x four bf16 (packed two per dword).  Each part is one v_cvt_pk_bf16_f32 (RNE)
-// per element PAIR; the value it represents is recovered by a shift / mask of the packed dword
-// and subtracted exactly in f32 (3 VALU per element and part instead of the 4 the generic
-// vector conversion costs).
-template <int NS>
-__device__ __forceinline__ void split_bf16(const f32x4& v, u32x2 (&out)[NS]) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  f32x4 r = v;
-#pragma unroll
-  for (int p = 0; p < NS; ++p) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const f32x2 pr = {r[2 * h], r[2 * h + 1]};
-      const bf16x2 b = __builtin_convertvector(pr, bf16x2);
-      unsigned u;
-      __builtin_memcpy(&u, &b, 4);
-      out[p][h] = u;
-      if (p + 1 < NS) {
-        r[2 * h] = r[2 * h] - __uint_as_float(u << 16);               // exact
-        r[2 * h + 1] = r[2 * h + 1] - __uint_as_float(u & 0xffff0000u);
-      }
-    }
-  }
-}
-
 // GNT: the GroupNorm operands (mean, rstd*gamma per (image, channel); beta per channel) of the
 // slab's 16 channels come from a small LDS table instead of two float4 global loads per staged
 // ROW: a row tile of BM <= Ho*Wo pixels touches at most two images, so 20 lanes fetch
@@ -243,8 +211,7 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
     for (int p = 0; p < BPIECES; ++p) {
       const int slot = tid + 256 * p;
       if (BSLOTS % 256 != 0 && slot >= BSLOTS) break;       // wave-uniform (BSLOTS % 64 == 0)
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)bsrc[p],
-                                       (lds_void_t*)(Bb + buf * B_ST + 16 * slot), 16, 0, 0);
+      lds_dma16(bsrc[p], Bb + buf * B_ST + 16 * slot);
       bsrc[p] += NS * 4096;
     }
   };
@@ -260,8 +227,7 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
                                            (int64_t)(seg >= 2 ? n_second : n_first) * d.Cin;
         const void* src = c < d.Cin ? static_cast<const void*>(base + c)
                                     : static_cast<const void*>(kZeroChunk);
-        __builtin_amdgcn_global_load_lds((cglobal_void_t*)src,
-                                         (lds_void_t*)(Gt + ring * kGnRing + 16 * tid), 16, 0, 0);
+        lds_dma16(src, Gt + ring * kGnRing + 16 * tid);
       }
     }
   };
@@ -320,11 +286,11 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
     issue_b(0);
     advance();
     if constexpr (gn_tab) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
       __syncthreads();           // tables of slabs 0 and 1 visible to every wave
     }
     store_a(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
   }
   for (int kt = kt_begin; kt < kt_end; ++kt) {
@@ -343,40 +309,15 @@ __device__ __forceinline__ void conv_split_body(const ConvArgs& a) {
     const char* bs = Bb + cur * B_ST;
     bf16x8 av[TM][NS], bv[TN][NS];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int R = wr * (BM / 2) + i * 32 + l31;
-      const char* p0 = as + R * 32 + ((lhi ^ ((R >> 3) & 1)) * 16);
+    for (int i = 0; i < TM; ++i)
+      load_frag<NS>(as + frag_offset(wr * (BM / 2) + i * 32 + l31, lhi), A_PART, av[i]);
 #pragma unroll
-      for (int p = 0; p < NS; ++p) av[i][p] = *reinterpret_cast<const bf16x8*>(p0 + p * A_PART);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int C = wc * (BN / 2) + j * 32 + l31;
-      const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
-#pragma unroll
-      for (int p = 0; p < NS; ++p) bv[j][p] = *reinterpret_cast<const bf16x8*>(p0 + p * B_PART);
-    }
-    // smallest terms first; the four (i, j) accumulators interleave so that two MFMAs on the
-    // same accumulator are TM*TN issues apart
-#define SNAP_SPLIT_PRODUCT(PA, PB)                                                          \
-  _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[i][PA], bv[j][PB], acc[i][j], 0, 0, 0);
-    if constexpr (NS == 3) {
-      SNAP_SPLIT_PRODUCT(2, 0)
-      SNAP_SPLIT_PRODUCT(0, 2)
-      SNAP_SPLIT_PRODUCT(1, 1)
-      SNAP_SPLIT_PRODUCT(1, 0)
-      SNAP_SPLIT_PRODUCT(0, 1)
-      SNAP_SPLIT_PRODUCT(0, 0)
-    } else {
-      SNAP_SPLIT_PRODUCT(1, 0)
-      SNAP_SPLIT_PRODUCT(0, 1)
-      SNAP_SPLIT_PRODUCT(0, 0)
-    }
-#undef SNAP_SPLIT_PRODUCT
+    for (int j = 0; j < TN; ++j)
+      load_frag<NS>(bs + frag_offset(wc * (BN / 2) + j * 32 + l31, lhi), B_PART, bv[j]);
+    split_product<NS>(acc, av, bv);
     if (more) store_a(cur ^ 1, ring_next);
     ring_cur = ring_next;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // B octets of slab kt+1 (+ table kt+2) landed
+    wait_vm<0>();   // B octets of slab kt+1 (+ table kt+2) landed
     __syncthreads();
   }
 
@@ -497,8 +438,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& a) {
         const float* base = seg == 4 ? a.gn_beta
                                      : ((seg & 1) ? a.gn_sc : a.gn_mu) +
                                            (int64_t)(seg >= 2 ? n_second : n_first) * d.Cin;
-        __builtin_amdgcn_global_load_lds((cglobal_void_t*)(base + c),
-                                         (lds_void_t*)(Gt + ring * kGnRing + 16 * tid), 16, 0, 0);
+        lds_dma16(base + c, Gt + ring * kGnRing + 16 * tid);
       }
     }
   };
@@ -552,8 +492,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& a) {
     for (int p = 0; p < BPIECES; ++p) {
       const int slot = tid + 256 * p;
       if (BSLOTS % 256 != 0 && slot >= BSLOTS) break;
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)(bbase[p] + off),
-                                       (lds_void_t*)(Bb + buf * B_ST + 16 * slot), 16, 0, 0);
+      lds_dma16(bbase[p] + off, Bb + buf * B_ST + 16 * slot);
     }
   };
 
@@ -572,11 +511,11 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& a) {
   load_halo(ct_begin);
   issue_b(0, ct_begin, 0);
   if constexpr (need_gn) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
   }
   store_halo(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   __syncthreads();
 
   int bcur = 0;
@@ -604,7 +543,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& a) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int h = wr * 64 + i * 32 + l31 + toff;
-        const char* p0 = hs + h * 32 + ((lhi ^ ((h >> 3) & 1)) * 16);
+        const char* p0 = hs + frag_offset(h, lhi);
         const bool in = (tapmask[i] >> t) & 1;
 #pragma unroll
         for (int p = 0; p < NS; ++p) {
@@ -614,35 +553,16 @@ __device__ __forceinline__ void conv3x3_halo_body(const ConvArgs& a) {
         }
       }
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int C = wc * (BN / 2) + j * 32 + l31;
-        const char* p0 = bs + C * 32 + ((lhi ^ ((C >> 3) & 1)) * 16);
-#pragma unroll
-        for (int p = 0; p < NS; ++p) bv[j][p] = *reinterpret_cast<const bf16x8*>(p0 + p * B_PART);
-      }
-#define SNAP_SPLIT_PRODUCT(PA, PB)                                                          \
-  _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[i][PA], bv[j][PB], acc[i][j], 0, 0, 0);
-      if constexpr (NS == 3) {
-        SNAP_SPLIT_PRODUCT(2, 0)
-        SNAP_SPLIT_PRODUCT(0, 2)
-        SNAP_SPLIT_PRODUCT(1, 1)
-        SNAP_SPLIT_PRODUCT(1, 0)
-        SNAP_SPLIT_PRODUCT(0, 1)
-        SNAP_SPLIT_PRODUCT(0, 0)
-      } else {
-        SNAP_SPLIT_PRODUCT(1, 0)
-        SNAP_SPLIT_PRODUCT(0, 1)
-        SNAP_SPLIT_PRODUCT(0, 0)
-      }
-#undef SNAP_SPLIT_PRODUCT
+      for (int j = 0; j < TN; ++j)
+        load_frag<NS>(bs + frag_offset(wc * (BN / 2) + j * 32 + l31, lhi), B_PART, bv[j]);
+      split_product<NS>(acc, av, bv);
       // the next channel tile's pixels (fetched during tap 0) -> the other halo stage: nobody
       // reads it before the barrier that closes tap 8
       if (t == 2 && more_ct) store_halo(hb ^ 1, hb ^ 1);
       if (fetch)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPER) : "memory");
+        wait_vm<NPER>();
       else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       bcur ^= 1;
     }
@@ -834,15 +754,14 @@ __device__ __forceinline__ void pack_weights_split_body(const float* __restrict_
     const int col = n & 127;
     const int oct = ko ^ ((col >> 3) & 1);
     const int64_t blk = ((int64_t)(n >> 7) * taps + t) * ctiles + (cb >> 4);
-    typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-    bf16x8v v;
+    bf16x8 v;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float r = tile[16 * slab + 8 * ko + e][j];
       for (int pp = 0; pp < p; ++pp) r -= (float)(__bf16)r;
       v[e] = (__bf16)r;
     }
-    *reinterpret_cast<bf16x8v*>(out + blk * ((int64_t)parts * 2048) + p * 2048 + col * 16 + oct * 8) = v;
+    *reinterpret_cast<bf16x8*>(out + blk * ((int64_t)parts * 2048) + p * 2048 + col * 16 + oct * 8) = v;
   }
 }
 

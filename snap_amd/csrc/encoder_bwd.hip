@@ -232,13 +232,7 @@ __global__ void gn_bwd_apply_kernel(const float* __restrict__ x, const float* __
     for (int e = 0; e < 4; ++e) o[e] += av[e];
   }
   reinterpret_cast<f32x4*>(dx)[i] = o;
-  if constexpr (HALF == 1) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-    reinterpret_cast<bf16x4*>(dx_half)[i] = __builtin_convertvector(o, bf16x4);
-  } else if constexpr (HALF == 2) {
-    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-    reinterpret_cast<f16x4*>(dx_half)[i] = __builtin_convertvector(o, f16x4);
-  }
+  if constexpr (HALF != 0) store_half4<HALF>(dx_half, 4 * i, o);
 }
 
 // ---------------------------------------------------------------------------

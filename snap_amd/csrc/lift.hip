@@ -440,25 +440,6 @@ __global__ __launch_bounds__(256) void lift_pool_kernel(const LiftArgs a) {
 // ---------------------------------------------------------------------------
 constexpr int LB_REC = 4;    // dwords per (voxel, slot) record: tap byte offset | packed | wi1 | wj1  (+ wb1 apart)
 
-// hi / lo bf16 parts of four f32, two per dword (the split of conv_split.hip / mlp_pool.hip)
-__device__ __forceinline__ void split_row_quad(const f32x4& v, unsigned (&hi)[2], unsigned (&lo)[2]) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const f32x2 pr = {v[2 * h], v[2 * h + 1]};
-    const bf16x2 b = __builtin_convertvector(pr, bf16x2);
-    unsigned u;
-    __builtin_memcpy(&u, &b, 4);
-    hi[h] = u;
-    const f32x2 rs = {pr[0] - __uint_as_float(u << 16), pr[1] - __uint_as_float(u & 0xffff0000u)};
-    const bf16x2 bl = __builtin_convertvector(rs, bf16x2);
-    __builtin_memcpy(&u, &bl, 4);
-    lo[h] = u;
-  }
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 pair_lo(const f32x4& v) { return __builtin_shufflevector(v, v, 0, 1); }
 __device__ __forceinline__ f32x2 pair_hi(const f32x4& v) { return __builtin_shufflevector(v, v, 2, 3); }
 
@@ -784,7 +765,7 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
           uint4 chunk = {0u, 0u, 0u, 0u};
           if (t == 0 || nvis > 1) {          // (one observation: the variance is exactly 0)
             unsigned hi[2], lo[2];
-            split_row_quad(stat[t], hi, lo);
+            split_bf16(stat[t], hi, lo);
             // (lane ^ 1 by DPP quad_perm [1, 0, 3, 2]: one VALU move each, no LDS permute)
             const unsigned g0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(odd ? hi[0] : lo[0]), 0xB1, 0xf, 0xf, true);
             const unsigned g1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(odd ? hi[1] : lo[1]), 0xB1, 0xf, 0xf, true);
@@ -799,7 +780,7 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
       }
       if (hl == 0 && write_row) {           // (2 fd % 16 == 0: score_max opens a slab of its own)
         unsigned hi[2], lo[2];
-        split_row_quad(f32x4{smax, 0.f, 0.f, 0.f}, hi, lo);
+        split_bf16(f32x4{smax, 0.f, 0.f, 0.f}, hi, lo);
         uint4* ps = reinterpret_cast<uint4*>(orow + ((2 * fd) >> 4) * 64);
         ps[0] = uint4{hi[0], 0u, 0u, 0u};
         ps[1] = uint4{0u, 0u, 0u, 0u};

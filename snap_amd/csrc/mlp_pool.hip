@@ -33,10 +33,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 struct MlpPoolArgs {
   const float* x;          // [*, x_stride] f32 rows (the lift's pooled statistics)
   int64_t x_stride;
@@ -67,24 +63,6 @@ struct MlpPoolArgs {
   // consecutive tiles owned by one XCD (0: dispatch order): a tile's taps then stay in ITS L2
   int xcd_group;
 };
-
-// hi / lo bf16 parts of four f32 (as conv_split.hip: one v_cvt_pk per pair, exact residual)
-__device__ __forceinline__ void split2(const f32x4& v, u32x2& hi, u32x2& lo) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const f32x2 pr = {v[2 * h], v[2 * h + 1]};
-    const bf16x2 b = __builtin_convertvector(pr, bf16x2);
-    unsigned u;
-    __builtin_memcpy(&u, &b, 4);
-    hi[h] = u;
-    const f32x2 rs = {pr[0] - __uint_as_float(u << 16), pr[1] - __uint_as_float(u & 0xffff0000u)};
-    const bf16x2 bl = __builtin_convertvector(rs, bf16x2);
-    __builtin_memcpy(&u, &bl, 4);
-    lo[h] = u;
-  }
-}
 
 __device__ __forceinline__ void atomic_max_f32(float* p, float v) {
   const unsigned u = __float_as_uint(v);
@@ -217,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) 
         }
       }
       u32x2 hi, lo;
-      split2(v, hi, lo);
+      split_bf16(v, hi, lo);
       const int oct = (akq >> 1) ^ ((row >> 3) & 1);
       char* dst = sm + buf * A_ST + row * 32 + oct * 16 + (akq & 1) * 8;
       *reinterpret_cast<u32x2*>(dst) = hi;
@@ -232,8 +210,7 @@ __global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) 
       const int slot = tid + NT * p;
       const int j = slot >> 9;
       const char* src = a.w0 + ((int64_t)j * a.ctiles0 + s) * 8192 + (slot & 511) * 16;
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)src,
-                                       (lds_void_t*)(sm + kB0 + buf * B0_ST + 16 * slot), 16, 0, 0);
+      lds_dma16(src, sm + kB0 + buf * B0_ST + 16 * slot);
     }
   };
 
@@ -246,7 +223,7 @@ __global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) 
     char* dst = sm + ((p + 3) & 3) * 16384 + tid * 16;
 #pragma unroll
     for (int q = 0; q < PP; ++q)
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)(src + NT * 16 * q), (lds_void_t*)(dst + NT * 16 * q), 16, 0, 0);
+      lds_dma16(src + NT * 16 * q, dst + NT * 16 * q);
   };
   if constexpr (NST == 2) issue_b1_pair(0);
 
@@ -272,8 +249,7 @@ __global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) 
   auto issue_a = [&](int buf, int s_) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_global_load_lds((cglobal_void_t*)(xs_px[i] + (r_ok[i] ? s_ * 64 : 0)),
-                                       (lds_void_t*)(sm + buf * A_ST + (tid + NT * i) * 16), 16, 0, 0);
+      lds_dma16(xs_px[i] + (r_ok[i] ? s_ * 64 : 0), sm + buf * A_ST + (tid + NT * i) * 16);
   };
   const int s_first = a.skip_lo > 0 ? 0 : a.skip_n;
   const int nk0 = a.ctiles0 - a.skip_n;
@@ -294,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) 
       issue_b0(0, s_first);
       store_a(0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
   }
 
@@ -309,8 +285,8 @@ __global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) 
     const bool more = kt + 1 < nk0;
     if constexpr (NST == 3) {
       // slabs <= kt + 1 are issued: slab kt must have landed, the next one may travel on
-      if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kSlabOps) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (more) wait_vm<kSlabOps>();
+      else wait_vm<0>();
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       // every wave is past slab kt - 1: its stage takes slab kt + 2
       if (kt + 2 < nk0) {
@@ -350,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) 
       if (more) store_a(cur ^ 1);
     }
     if constexpr (NST == 2) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
       __syncthreads();
     }
   }
@@ -385,8 +361,8 @@ __global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) 
         v[1][e] = __uint_as_float(sw[1]);
       }
       u32x2 h0, l0, h1, l1;
-      split2(v[0], h0, l0);
-      split2(v[1], h1, l1);
+      split_bf16(v[0], h0, l0);
+      split_bf16(v[1], h1, l1);
       f_hi[t][s] = u32x4{h0[0], h0[1], h1[0], h1[1]};
       f_lo[t][s] = u32x4{l0[0], l0[1], l1[0], l1[1]};
     }
@@ -410,10 +386,10 @@ __global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) 
       if (pr >= 1 || NST == 3) {
         const int younger = min(pr == 0 ? 3 : pr + 2, npairs - 1) - pr;
         switch (younger) {
-          case 3: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PP) : "memory"); break;
-          case 2: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PP) : "memory"); break;
-          case 1: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PP) : "memory"); break;
-          default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+          case 3: wait_vm<3 * PP>(); break;
+          case 2: wait_vm<2 * PP>(); break;
+          case 1: wait_vm<PP>(); break;
+          default: wait_vm<0>(); break;
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

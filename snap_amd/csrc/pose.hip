@@ -19,8 +19,6 @@
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int SIM_CH = 64;  // cells per softmax chunk == one wave
 constexpr int SIM_TQ = 64;  // query rows per workgroup tile
 
@@ -254,7 +252,6 @@ __global__ __launch_bounds__(256, DM <= 32 ? 4 : 2) void sim_mfma_kernel(
 // six part products per MAC, error ~2^-24 per product -- inside the f32 chain's own rounding) by
 // sim_presplit_kernel, and the tile is NS (NS + 1) / 2 x DM / 16 v_mfma_f32_32x32x16_bf16 per
 // 32 x 32 block instead of DM / 2 f32 MFMAs: 2.7 x fewer matrix cycles at NS = 3.  Same epilogue.
-typedef __bf16 sim_bf16x8 __attribute__((ext_vector_type(8)));
 
 // x [R, DM] f32 -> [R][NS][DM] bf16
 template <int NS>
@@ -289,7 +286,7 @@ __global__ __launch_bounds__(256, 3) void sim_split_kernel(
   const int NC = (XY + SIM_CH - 1) / SIM_CH;
   if (cell0 >= XY) return;
   // B operand (map cells), both 32-cell tiles, kept for both row halves
-  sim_bf16x8 bq[2][KS][NS];
+  bf16x8 bq[2][KS][NS];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int cell = cell0 + 32 * t + l31;
@@ -299,8 +296,8 @@ __global__ __launch_bounds__(256, 3) void sim_split_kernel(
     for (int s = 0; s < KS; ++s)
 #pragma unroll
       for (int p = 0; p < NS; ++p) {
-        bq[t][s][p] = *reinterpret_cast<const sim_bf16x8*>(src + p * DM + 16 * s);
-        if (!cv) bq[t][s][p] = sim_bf16x8{};
+        bq[t][s][p] = *reinterpret_cast<const bf16x8*>(src + p * DM + 16 * s);
+        if (!cv) bq[t][s][p] = bf16x8{};
       }
   }
   __shared__ __attribute__((aligned(16))) float stage[4][32][64 + 4];
@@ -311,7 +308,7 @@ __global__ __launch_bounds__(256, 3) void sim_split_kernel(
   const int ncell = XY - cell0;
 #pragma unroll
   for (int ti = 0; ti < 2; ++ti) {
-    sim_bf16x8 aq[KS][NS];
+    bf16x8 aq[KS][NS];
     {
       const int row = n0 + 32 * ti + l31;
       const bool rv = row < Nq;
@@ -320,8 +317,8 @@ __global__ __launch_bounds__(256, 3) void sim_split_kernel(
       for (int s = 0; s < KS; ++s)
 #pragma unroll
         for (int p = 0; p < NS; ++p) {
-          aq[s][p] = *reinterpret_cast<const sim_bf16x8*>(src + p * DM + 16 * s);
-          if (!rv) aq[s][p] = sim_bf16x8{};
+          aq[s][p] = *reinterpret_cast<const bf16x8*>(src + p * DM + 16 * s);
+          if (!rv) aq[s][p] = bf16x8{};
         }
     }
     f32x16 acc[2];
@@ -334,7 +331,7 @@ __global__ __launch_bounds__(256, 3) void sim_split_kernel(
       acc[tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[s][PA], bq[tj][s][PB], acc[tj], 0, 0, 0);
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      if constexpr (NS == 3) {               // smallest terms first, as conv_split.hip
+      if constexpr (NS == 3) {               // smallest terms first: the order of split_product
         SNAP_SIM_PRODUCT(2, 0)
         SNAP_SIM_PRODUCT(0, 2)
         SNAP_SIM_PRODUCT(1, 1)
@@ -427,14 +424,14 @@ __global__ __launch_bounds__(256, 3) void sim_split_fast_kernel(
   const int chunk = blockIdx.x * 4 + wave;
   const int cell0 = chunk * SIM_CH;
   const int NC = XY / SIM_CH;
-  sim_bf16x8 bq[2][KS][NS];
+  bf16x8 bq[2][KS][NS];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const __bf16* src = fms + ((int64_t)b * XY + cell0 + 32 * t + l31) * (NS * DM) + 8 * lhi;
 #pragma unroll
     for (int s = 0; s < KS; ++s)
 #pragma unroll
-      for (int p = 0; p < NS; ++p) bq[t][s][p] = *reinterpret_cast<const sim_bf16x8*>(src + p * DM + 16 * s);
+      for (int p = 0; p < NS; ++p) bq[t][s][p] = *reinterpret_cast<const bf16x8*>(src + p * DM + 16 * s);
   }
   __shared__ __attribute__((aligned(16))) float stage[4][32][LD];
   __shared__ __attribute__((aligned(16))) float sstat[SIM_TQ][8];
@@ -444,7 +441,7 @@ __global__ __launch_bounds__(256, 3) void sim_split_fast_kernel(
   const int c4 = (lane & 15) * 4;
 #pragma unroll
   for (int ti = 0; ti < 2; ++ti) {
-    sim_bf16x8 aq[KS][NS];
+    bf16x8 aq[KS][NS];
     {
       const int row = n0 + 32 * ti + l31;
       const bool rv = row < Nq;
@@ -453,8 +450,8 @@ __global__ __launch_bounds__(256, 3) void sim_split_fast_kernel(
       for (int s = 0; s < KS; ++s)
 #pragma unroll
         for (int p = 0; p < NS; ++p) {
-          aq[s][p] = *reinterpret_cast<const sim_bf16x8*>(src + p * DM + 16 * s);
-          if (!rv) aq[s][p] = sim_bf16x8{};
+          aq[s][p] = *reinterpret_cast<const bf16x8*>(src + p * DM + 16 * s);
+          if (!rv) aq[s][p] = bf16x8{};
         }
     }
     f32x16 acc[2];
@@ -1149,8 +1146,6 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_kernel(const ScoreArgs 
 // base + lane*16, i.e. a linear copy) while every thread gathers from the current
 // one; one barrier per point.  This keeps the HBM stream busy during the gather
 // phase -- the kernel's roofline is the single read of sim.
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void global_void_t;
 
 __device__ __forceinline__ float uniform_f(float v) {
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
@@ -1214,8 +1209,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_db_kernel(const ScoreAr
     for (int k = 0; k < PS_DB_ROUNDS; ++k) {
       const int c = k * PS_THREADS + tid;
       if (c < nchunks)
-        __builtin_amdgcn_global_load_lds((global_void_t*)(src + goff[k]),
-                                         (lds_void_t*)(dst + 4 * c), 16, 0, 0);
+        lds_dma16(src + goff[k], dst + 4 * c);
     }
   };
   // The chunk's valid points, compacted (ascending) into LDS up front: the plane loop
@@ -1301,7 +1295,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_db_kernel(const ScoreAr
     const int inext = min(i + 1, count - 1);
     const float qx = uniform_f(pt_x[i]), qy = uniform_f(pt_y[i]);  // wave-uniform: keep in SGPRs
     const float nqx = uniform_f(pt_x[inext]), nqy = uniform_f(pt_y[inext]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();  // plane i landed for every wave; the other buffer is free
     if (i + 1 < count) issue(pt_n[i + 1], buf ^ 1);
     const float* pl = plane + buf * PLANE;
@@ -1391,8 +1385,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_band_db_kernel(const Sc
     for (int k = 0; k < PS_DB_ROUNDS; ++k) {
       const int c = k * PS_THREADS + tid;
       if (c < nchunks)
-        __builtin_amdgcn_global_load_lds((global_void_t*)(src + goff[k]),
-                                         (lds_void_t*)(dst + 4 * c), 16, 0, 0);
+        lds_dma16(src + goff[k], dst + 4 * c);
     }
   };
   __shared__ int pt_n[PS_DB_MAX_POINTS];
@@ -1437,7 +1430,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_band_db_kernel(const Sc
         off[k] = (int)fmaf(f.x, Sf, f.y);
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();  // band t landed for every wave; the other buffer is free
     {
       int ni = i, nb = band + 1;
@@ -1543,8 +1536,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_window_kernel(const Sco
     for (int k = 0; k < PS_WIN_ROUNDS; ++k) {
       const int c = k * PS_THREADS + tid;
       if (c < nchunks)
-        __builtin_amdgcn_global_load_lds((global_void_t*)(src + goff[k]),
-                                         (lds_void_t*)(dst + 4 * c), 16, 0, 0);
+        lds_dma16(src + goff[k], dst + 4 * c);
     }
   };
   __shared__ int pt_n[PS_DB_MAX_POINTS];
@@ -1579,7 +1571,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_window_kernel(const Sco
     const float qx = uniform_f(pt_x[i]), qy = uniform_f(pt_y[i]);
     const f32x2 qx2 = {qx, qx}, qyn = {-qy, qy};
     const int obase = o_cur.x * S + o_cur.y;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();  // window i landed for every wave; the other buffer is free
     if (i + 1 < count) {
       o_cur = origin(uniform_f(pt_x[i + 1]), uniform_f(pt_y[i + 1]));

@@ -92,7 +92,6 @@ __global__ __launch_bounds__(PB_THREADS) void pose_score_bwd_kernel(const ScoreB
 // skipped) and keeps the four CORNER cells -- where every sample that leaves the map in both
 // directions lands, thousands per plane -- in registers instead of serialising LDS atomics on
 // one address; they are reduced per wave (DPP) and added once per plane.
-typedef float bf32x2 __attribute__((ext_vector_type(2)));
 
 __global__ __launch_bounds__(PB_THREADS) void pose_score_bwd_fast_kernel(const ScoreBwdArgs a) {
   extern __shared__ float plane[];

@@ -17,27 +17,6 @@
 
 namespace {
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// hi / lo bf16 parts of four f32 (one v_cvt_pk per pair, exact residual: as conv_split.hip)
-__device__ __forceinline__ void split2x4(const f32x4& v, u32x2& hi, u32x2& lo) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const f32x2 pr = {v[2 * h], v[2 * h + 1]};
-    const bf16x2 b = __builtin_convertvector(pr, bf16x2);
-    unsigned u;
-    __builtin_memcpy(&u, &b, 4);
-    hi[h] = u;
-    const f32x2 rs = {pr[0] - __uint_as_float(u << 16), pr[1] - __uint_as_float(u & 0xffff0000u)};
-    const bf16x2 bl = __builtin_convertvector(rs, bf16x2);
-    __builtin_memcpy(&u, &bl, 4);
-    lo[h] = u;
-  }
-}
-
 // lanes 2j (channel quad q even) and 2j + 1 hold the two halves of one k-octet: after one quad-
 // permuted exchange the even lane owns the octet's 16 hi bytes, the odd lane its 16 lo bytes
 __device__ __forceinline__ u32x4 pair_chunks(const u32x2& hi, const u32x2& lo, bool odd) {
@@ -141,7 +120,7 @@ __global__ __launch_bounds__(256) void gn_norm_split_kernel(const NormSplitArgs 
 #pragma unroll
       for (int e = 0; e < 4; ++e) p[e] = apply_pro<SNAP_PRO_GN_RELU>(v[u][e], mu[e], sc[e], be[e], 1.f, 0.f);
       u32x2 hi, lo;
-      split2x4(p, hi, lo);
+      split_bf16(p, hi, lo);
       const bool odd = q4 & 1;
       const u32x4 ch = pair_chunks(hi, lo, odd);     // (C4 is even: a pair never straddles rows)
       if (i < total) {
@@ -160,7 +139,7 @@ __global__ __launch_bounds__(256) void presplit_kernel(const float* __restrict__
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const f32x4 v = i < total4 ? reinterpret_cast<const f32x4*>(x)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
   u32x2 hi, lo;
-  split2x4(v, hi, lo);
+  split_bf16(v, hi, lo);
   const bool odd = i & 1;
   const u32x4 ch = pair_chunks(hi, lo, odd);
   if (i < total4) {

@@ -15,9 +15,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 // ---- LayerNorm backward -------------------------------------------------------------------
 constexpr int LN_MAXQ = 4;
 constexpr int LNB_ROWS = 8;    // rows per workgroup: 2 per wave, both in flight together

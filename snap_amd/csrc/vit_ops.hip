@@ -15,9 +15,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 // ---- LayerNorm ------------------------------------------------------------------------------
 // y[m, :] = (x[m, :] - mean) * rsqrt(var + eps) * gamma + beta   (biased variance, as
 // flax.linen.LayerNorm).  C % 4 == 0, C <= 64 * 4 * LN_MAXQ.
@@ -65,8 +62,7 @@ __global__ __launch_bounds__(256) void layer_norm_kernel(
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mean) * rstd * g[e] + b[e];
       if constexpr (HALF) {
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-        *reinterpret_cast<bf16x4*>(y_half + m * C + 4 * q) = __builtin_convertvector(o, bf16x4);
+        store_half4<1>(y_half, m * C + 4 * q, o);
       } else {
         *reinterpret_cast<f32x4*>(y + m * C + 4 * q) = o;
       }
@@ -282,9 +278,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
     if (q < a.N) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(stage + row * 68 + 4 * qd);
       if (a.out_half) {
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-        *reinterpret_cast<bf16x4*>(a.out_half + ((int64_t)b * a.N + q) * (a.H * AT_D) + h * AT_D + 4 * qd) =
-            __builtin_convertvector(v, bf16x4);
+        store_half4<1>(a.out_half, ((int64_t)b * a.N + q) * (a.H * AT_D) + h * AT_D + 4 * qd, v);
       } else {
         *reinterpret_cast<f32x4*>(a.out + ((int64_t)b * a.N + q) * (a.H * AT_D) + h * AT_D + 4 * qd) = v;
       }

@@ -230,7 +230,6 @@ __global__ __launch_bounds__(256) void pack_stacked_templates_split_kernel(
       }
     }
   }
-  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
   bf16x8 hi, lo;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {

@@ -182,9 +182,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
         for (int e = 0; e < 4; ++e) {
           float pv;
           if constexpr (need_gn)
-            pv = wg_pro<PRO>(v[e], zmu[p][e], zsc[p][e], zbeta[e], d.in_scale, d.in_shift);
+            pv = apply_pro<PRO>(v[e], zmu[p][e], zsc[p][e], zbeta[e], d.in_scale, d.in_shift);
           else
-            pv = wg_pro<PRO>(v[e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
+            pv = apply_pro<PRO>(v[e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
           v[e] = (zin[p] && (zc + e < d.Cin)) ? pv : 0.f;
         }
         *reinterpret_cast<f32x4*>(zs + (zrow0 + p * ZRPP) * BKT + 4 * zq) = v;
@@ -195,9 +195,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
         const int idx = tid + 256 * e;
         float pv;
         if constexpr (need_gn)
-          pv = wg_pro<PRO>(se[e], smu[e], ssc[e], sbeta[e], d.in_scale, d.in_shift);
+          pv = apply_pro<PRO>(se[e], smu[e], ssc[e], sbeta[e], d.in_scale, d.in_shift);
         else
-          pv = wg_pro<PRO>(se[e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
+          pv = apply_pro<PRO>(se[e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
         zs[idx] = sin_[e] ? pv : 0.f;
       }
     }

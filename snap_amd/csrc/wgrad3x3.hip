@@ -18,26 +18,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-template <bool F16> struct Elem;
-template <> struct Elem<false> {
-  typedef bf16x8 x8; typedef bf16x4 x4;
-  static __device__ __forceinline__ f32x16 mfma(x8 a, x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Elem<true> {
-  typedef f16x8 x8; typedef f16x4 x4;
-  static __device__ __forceinline__ f32x16 mfma(x8 a, x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
 constexpr int W3_NT = 512;
 constexpr int W3_ZC = 64;            // input channels per workgroup
 constexpr int W3_ZROW = 112;         // bytes per (kw, channel): 6 rows x 16 B + 16 B pad (conflict-free b128 reads)
@@ -162,8 +142,8 @@ __global__ __launch_bounds__(W3_NT) void wgrad3x3_kernel(const WgradArgs a) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           float v;
-          if constexpr (need_gn) v = wg_pro<PRO>(zv[j][e][c], zmu[j][c], zsc[j][c], zbeta[j][c], d.in_scale, d.in_shift);
-          else v = wg_pro<PRO>(zv[j][e][c], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
+          if constexpr (need_gn) v = apply_pro<PRO>(zv[j][e][c], zmu[j][c], zsc[j][c], zbeta[j][c], d.in_scale, d.in_shift);
+          else v = apply_pro<PRO>(zv[j][e][c], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
           pv[e][c] = zin[j][e] ? v : 0.f;              // (the reference pads the normalised tensor)
         }
 #pragma unroll

@@ -15,30 +15,9 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-// element type of the rounded operands (as conv_bf16.hip): bf16, or IEEE half for SNAP_MATH_F16
-template <bool F16> struct Elem;
-template <> struct Elem<false> {
-  typedef bf16x8 x8; typedef bf16x4 x4;
-  static __device__ __forceinline__ f32x16 mfma(x8 a, x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Elem<true> {
-  typedef f16x8 x8; typedef f16x4 x4;
-  static __device__ __forceinline__ f32x16 mfma(x8 a, x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
 // ZH / DH: the Z / dY operand is read in the engine's element type (2 bytes) instead of f32: 8-byte
 // row quads, transposed with byte permutes (two v_perm_b32 per output dword) instead of converted --
 // half the bytes of that operand, no rounding work (the values ARE the rounded ones)
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 //
 // NT = 512 (eight waves, 4 x 2): the WIDE tile of the flat (Dense) kernel gradients -- a whole 256 x 256 (or
@@ -203,10 +182,10 @@ __global__ __launch_bounds__(NT) void wgrad_bf16_kernel(const WgradArgs a) {
         for (int e = 0; e < 4; ++e) {
           float pv;
           if constexpr (need_gn)
-            pv = wg_pro<PRO>(zr[p][e], zfirst[p] ? zmu[0][e] : zmu[1][e], zfirst[p] ? zsc[0][e] : zsc[1][e], zbeta[e],
-                             d.in_scale, d.in_shift);
+            pv = apply_pro<PRO>(zr[p][e], zfirst[p] ? zmu[0][e] : zmu[1][e], zfirst[p] ? zsc[0][e] : zsc[1][e], zbeta[e],
+                                d.in_scale, d.in_shift);
           else
-            pv = wg_pro<PRO>(zr[p][e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
+            pv = apply_pro<PRO>(zr[p][e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
           zv[p][e] = (zin[p] && (zc + e < d.Cin)) ? pv : 0.f;
         }
       }
@@ -328,8 +307,6 @@ int wg_launch_pro(const WgradArgs& a, const WgPlan& p, bool half, hipStream_t s)
     default: return SNAP_ERR_UNSUPPORTED;
   }
 }
-
-
 
 // the wide tiles (wg_plan_wide): prologues NONE / RELU / AFFINE
 template <int BN, int PRO, bool ZH, bool DH>
