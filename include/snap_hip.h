@@ -397,6 +397,7 @@ int snap_attention_lse_bf16_f32(const float* qkv, float* out, float* lse, int32_
 int snap_attention_bwd_bf16_f32(const float* qkv, const float* out, const float* dout,
                                 const float* lse, float* delta, float* dqkv, int32_t B, int32_t N,
                                 int32_t H, int32_t D, float scale, void* stream);
+/* Exact: no launch touches a byte beyond this size. */
 size_t snap_layer_norm_bwd_workspace_bytes(int64_t M, int32_t C);
 int snap_layer_norm_bwd_f32(const float* x, const float* dy, const float* gamma, float* dx,
                             float* dgamma, float* dbeta, int64_t M, int32_t C, float eps,
@@ -435,6 +436,7 @@ int snap_group_norm_stats_from_partial_f32(const float* partial, int32_t N, int3
 
 /* Ascending list of the rows with mask != 0: index[0..count) (stable order,
  * deterministic), count written to *count (device).  index must hold M entries. */
+/* Exact: no launch touches a byte beyond this size. */
 size_t snap_compact_rows_workspace_bytes(int64_t M);
 int snap_compact_rows_u8(const uint8_t* mask, int64_t M, int32_t* index, int32_t* count,
                          void* workspace, size_t workspace_bytes, void* stream);
@@ -543,6 +545,7 @@ int snap_weight_standardize_bwd_multi_f32(const SnapWstdItem* items, int32_t n_i
  * (H,W,C/G) per (image, group).  relu_first != 0 computes them on relu(x)
  * (FPN order, image_encoder.py:80-83).  Outputs mu[N,C], sc[N,C] = rstd*gamma[c].
  * workspace: snap_group_norm_stats_workspace_bytes(N, HW, C, groups) bytes. */
+/* Exact: no launch touches a byte beyond this size. */
 size_t snap_group_norm_stats_workspace_bytes(int32_t N, int32_t HW, int32_t C,
                                              int32_t groups);
 int snap_group_norm_stats_f32(const float* x, int32_t N, int32_t HW, int32_t C,
@@ -802,6 +805,8 @@ int snap_ransac_sample_ws_f32(const float* fq, const float* fm, const float* chu
  * snap_pose_score_window_supported: 1 when the window of that radius fits the kernel's LDS buffers
  * (else call snap_pose_score_f32).  A pose outside the promised radius reads a clamped cell of the
  * window (a wrong score, never out of bounds). */
+/* snap_pose_score_workspace_bytes + the per-scene centre table (B x 4 floats) + 16 bytes that let the table start
+ * 16-byte aligned behind the partial sums; no launch touches a byte beyond this size. */
 size_t snap_pose_score_window_workspace_bytes(int32_t B, int32_t Nq, int32_t P, int32_t X, int32_t Y);
 int32_t snap_pose_score_window_supported(int32_t X, int32_t Y, int32_t radius_cells);
 int snap_pose_score_window_f32(const float* sim, const float* poses, const float* centers,
@@ -818,6 +823,7 @@ int snap_poses_from_corr_f32(const int32_t* corr, const float* q_xy, int32_t B,
 /* scores[B,P] = sum_n valid_q[b,n] * bilinear(sim[b,n], (R(theta) q_xy[n] + t)/cell)
  * (pose_estimation.py:63-82).  poses[B,P,3]; map_valid [B,X,Y] only read when
  * mask_oob != 0.  workspace: snap_pose_score_workspace_bytes(B,Nq,P,X,Y). */
+/* Exact: no launch touches a byte beyond this size. */
 size_t snap_pose_score_workspace_bytes(int32_t B, int32_t Nq, int32_t P,
                                        int32_t X, int32_t Y);
 int snap_pose_score_f32(const float* sim, const float* poses, const float* q_xy,
@@ -944,6 +950,8 @@ int snap_vertical_pool_conf_bwd_f32(const float* vol, const uint8_t* vvalid, con
  * with the rotated / transposed kernel (host side, snap_amd/autograd.py).
  * ------------------------------------------------------------------------- */
 /* dw[KH*KW*Cin, Cout] (+)= im2col(prologue(x))^T dy   on f32 MFMA; dy [N,Ho,Wo,Cout]. */
+/* The maximum over the loader plans the launch may take (the plan depends on the pointer alignment seen at launch):
+ * an upper bound, and no launch touches a byte beyond it. */
 size_t snap_conv2d_wgrad_workspace_bytes(const SnapConvDesc* desc);
 /* Per-call A/B switches (tools, tests) of the half-precision engines' plans, OR-ed into
  * desc->tile_hint of a snap_conv2d_wgrad_* call (no process-wide state):
@@ -1016,6 +1024,7 @@ int snap_adam_multi_f32(const SnapAdamItem* items, int32_t n_items, int64_t tota
 /* GroupNorm(+ReLU) backward.  dz: grad w.r.t. the prologue output; add: optional extra
  * gradient summed into dx (identity-residual branch).  mode: SNAP_PRO_GN_RELU /
  * SNAP_PRO_RELU_GN.  dgamma/dbeta [C] (+)=. */
+/* Exact: no launch touches a byte beyond this size. */
 size_t snap_group_norm_bwd_workspace_bytes(int32_t N, int32_t HW, int32_t C, int32_t groups);
 /* ... _ex: dx_half (optional, [N, HW, C] 2-byte elements) also receives dx rounded to bf16
  * (half_kind = 1) or IEEE half (half_kind = 2), RNE -- the operand image the producing layer's
@@ -1055,6 +1064,7 @@ int snap_upsample2x_bwd_f32(const float* dy, float* dprev, int32_t N, int32_t Hp
 int snap_epilogue_bwd_f32(const float* dy, const float* y, const uint8_t* row_mask, float* out,
                           int64_t M, int32_t C, int32_t relu, void* stream);
 /* out[C] (+)= column sums of a[M,C]  (bias gradients). */
+/* Exact: no launch touches a byte beyond this size. */
 size_t snap_colsum_workspace_bytes(int64_t M, int32_t C);
 /* snap_epilogue_bwd_f32 and the column sums of ITS OUTPUT over the first *row_count rows (all M if
  * NULL) in one pass: the gradient of a bias that sits in front of a ReLU / row mask (layers.py:55-78
@@ -1145,6 +1155,7 @@ int snap_plane_fuse_match_bwd_f32(const float* const* planes, const uint8_t* con
                                   void* stream);
 
 /* VJP of snap_pose_score_f32 w.r.t. sim: dsim[B,Nq,X,Y] (planes <= 96 KiB). */
+/* Exact: no launch touches a byte beyond this size. */
 size_t snap_pose_score_bwd_workspace_bytes(int32_t B, int32_t P);
 int snap_pose_score_bwd_f32(const float* dscores, const float* poses, const float* q_xy,
                             const uint8_t* valid_q, const uint8_t* map_valid, int32_t B,

@@ -299,7 +299,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
         const int row = (tid / QPR) + RPP * i;
         const int q = akq ^ ((row >> 2) & 3);            // logical k-quad held by this slot
         const int c = ct * BK + 4 * q;
-        const bool ok = tap_in[i] && c < d.Cin;          // (Cin % 4 == 0 on the VEC path)
+        const bool ok = tap_in[i] && c < d.Cin;          // (Cin % 4 == 0: launch() keeps other shapes off this path)
         const float* src = ok ? tap_px[i] + c : kZeroChunk;
         lds_dma16(src, Ad + stage * A_ST + 4 * (tid + 256 * i));
       }
@@ -471,9 +471,14 @@ int launch(ConvArgs a, hipStream_t s) {
   constexpr bool kDmaOk = VEC && BK == 16 && (PRO == SNAP_PRO_NONE || PRO == SNAP_PRO_RELU);
   bool launched = false;
   if constexpr (kDmaOk) {   // (the LDS-DMA loader of the NONE / RELU prologues)
-    hipLaunchKernelGGL((conv_igemm_kernel_dma<BM, BN, PRO>), dim3((unsigned)nblocks), dim3(256), 0,
-                       s, a);
-    launched = true;
+    // The DMA copies whole 16-byte quads: with Cin % 4 != 0 (257 live channels in a 260-float row) the last quad
+    // would bring the row's pad floats into LDS, where only the zero kernel rows stand against them -- a NaN or
+    // Inf in the pad would reach the result.  Such shapes take the register loader, which zeroes k >= Cin.
+    if (a.d.Cin % 4 == 0) {
+      hipLaunchKernelGGL((conv_igemm_kernel_dma<BM, BN, PRO>), dim3((unsigned)nblocks), dim3(256), 0,
+                         s, a);
+      launched = true;
+    }
   }
   if (launched) {
   } else if constexpr (!kGn && BK == 16 && (VEC || BM * BN < 128 * 128)) {  // (scalar 128x128 would spill)

@@ -1142,7 +1142,7 @@ def compact_rows(mask, lo=1, hi=255):
   _mask(mask, 'mask')
   M = mask.numel()
   wsb = lib.snap_compact_rows_workspace_bytes(M)
-  ws = torch.empty(wsb // 4 + 4, dtype=torch.int32, device=mask.device)
+  ws = torch.empty(wsb // 4, dtype=torch.int32, device=mask.device)
   index = torch.empty(M, dtype=torch.int32, device=mask.device)
   count = torch.empty(1, dtype=torch.int32, device=mask.device)
   st = lib.snap_compact_rows_range_u8(_p(mask), M, int(lo), int(hi), _p(index), _p(count), _p(ws),
@@ -1357,7 +1357,7 @@ def group_norm_stats(x, gamma, *, groups=32, eps=1e-5, relu_first=False, want_rs
   N, H, W, C = x.shape
   HW = H * W
   wsb = lib.snap_group_norm_stats_workspace_bytes(N, HW, C, groups)
-  ws = torch.empty(wsb // 4 + 4, dtype=torch.float32, device=x.device)
+  ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device)
   mu = torch.empty((N, C), dtype=torch.float32, device=x.device)
   sc = torch.empty((N, C), dtype=torch.float32, device=x.device)
   rstd = torch.empty((N, C), dtype=torch.float32, device=x.device) if want_rstd else None
@@ -1824,7 +1824,7 @@ def pose_score(sim, poses, q_xy, valid_q, map_valid, cell_size, mask_oob=False):
   B, Nq, X, Y = sim.shape
   P = poses.shape[1]
   wsb = lib.snap_pose_score_workspace_bytes(B, Nq, P, X, Y)
-  ws = torch.empty(wsb // 4 + 4, dtype=torch.float32, device=sim.device)
+  ws = torch.empty(wsb // 4, dtype=torch.float32, device=sim.device)
   scores = torch.empty((B, P), dtype=torch.float32, device=sim.device)
   # algorithmic bytes: every VALID query point's score plane read once + poses + scores.
   with _region(
@@ -1855,7 +1855,7 @@ def pose_score_window(sim, poses, centers, radius_cells, q_xy, valid_q, cell_siz
   if tuple(centers.shape) != (B, 3):
     raise ValueError('pose_score_window: centers [B, 3]')
   wsb = lib.snap_pose_score_window_workspace_bytes(B, Nq, P, X, Y)
-  ws = torch.empty(wsb // 4 + 4, dtype=torch.float32, device=sim.device)
+  ws = torch.empty(wsb // 4, dtype=torch.float32, device=sim.device)
   scores = torch.empty((B, P), dtype=torch.float32, device=sim.device)
   WR, WC = min(2 * radius_cells + 3, X), min((2 * radius_cells + 9) & ~3, Y)
   with _region('pose_score', 0.0, 4.0 * (B * Nq * WR * WC + poses.numel() + scores.numel())):

@@ -87,7 +87,7 @@ def conv2d_wgrad(x, dy, w_shape, *, stride=1, padding=((0, 0), (0, 0)), prologue
   if prologue in (ops.PRO_GN_RELU, ops.PRO_RELU_GN):
     mu, sc, beta = gn
   wsb = lib.snap_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
-  ws = torch.empty(wsb // 4 + 4, dtype=torch.float32, device=x.device)
+  ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device)
   dw = torch.empty(w_shape, dtype=torch.float32, device=x.device)
   KH, KW, Cin, Cout = w_shape
   M = yshape[0] * yshape[1] * yshape[2]
@@ -170,7 +170,7 @@ def group_norm_bwd(x, dz, mu, rstd, gamma, beta, mode, *, groups=32, add=None, h
   _f32(x, 'x'); _f32(dz, 'dz'); _f32(mu, 'mu'); _f32(rstd, 'rstd')
   N, H, W, C = x.shape
   wsb = lib.snap_group_norm_bwd_workspace_bytes(N, H * W, C, groups)
-  ws = torch.empty(wsb // 4 + 4, dtype=torch.float32, device=x.device)
+  ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device)
   dx = torch.empty_like(x)
   dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
   dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -270,7 +270,7 @@ def epilogue_bwd_colsum(dy, y=None, row_mask=None, relu=False, row_count=None, w
       ops._chk(y, y.dtype, 'y')
     out = torch.empty_like(dy)
     wsb = lib.snap_colsum_workspace_bytes(M, C) * (2 if wsum is not None else 1)
-    ws = torch.empty(wsb // 4 + 4, dtype=torch.float32, device=dy.device)
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=dy.device)
     sums = torch.empty(C, dtype=torch.float32, device=dy.device)
     kind = 2 if dy.dtype == torch.float16 else 1
     if wsum is None:
@@ -307,7 +307,7 @@ def epilogue_bwd_colsum(dy, y=None, row_mask=None, relu=False, row_count=None, w
     return out, colsum(out, row_count=row_count)
   out = torch.empty_like(dy)
   wsb = lib.snap_colsum_workspace_bytes(M, C)
-  ws = torch.empty(wsb // 4 + 4, dtype=torch.float32, device=dy.device)
+  ws = torch.empty(wsb // 4, dtype=torch.float32, device=dy.device)
   sums = torch.empty(C, dtype=torch.float32, device=dy.device)
   st = lib.snap_epilogue_bwd_colsum_f32(_p(dy), _p(y), _p(row_mask), _p(out), M, C, int(relu),
                                         _p(row_count), _p(sums), _p(ws), ws.numel() * 4, _stream())
@@ -322,7 +322,7 @@ def colsum(a, rows=None, row_count=None):
   C = a.shape[-1]
   M = a.numel() // C
   wsb = lib.snap_colsum_workspace_bytes(M, C)
-  ws = torch.empty(wsb // 4 + 4, dtype=torch.float32, device=a.device)
+  ws = torch.empty(wsb // 4, dtype=torch.float32, device=a.device)
   out = torch.empty(C, dtype=torch.float32, device=a.device)
   st = lib.snap_colsum_rows_f32(_p(a), M, C, _p(rows), _p(row_count), _p(out), 0, _p(ws),
                                 ws.numel() * 4, _stream())
@@ -546,7 +546,7 @@ def pose_score_bwd(dscores, poses, q_xy, valid_q, map_valid, sim_shape, cell_siz
   B, Nq, X, Y = sim_shape
   P = poses.shape[1]
   wsb = lib.snap_pose_score_bwd_workspace_bytes(B, P)
-  ws = torch.empty(wsb // 4 + 4, dtype=torch.float32, device=poses.device)
+  ws = torch.empty(wsb // 4, dtype=torch.float32, device=poses.device)
   dsim = mark_scratch(torch.empty(sim_shape, dtype=torch.float32, device=poses.device))
   with _region('pose_score_bwd', 0.0, 4.0 * dsim.numel()):
     st = lib.snap_pose_score_bwd_ex_f32(
@@ -598,7 +598,7 @@ def layer_norm_bwd(x, dy, gamma, eps=1e-6):
   C = x.shape[-1]
   M = x.numel() // C
   wsb = lib.snap_layer_norm_bwd_workspace_bytes(M, C)
-  ws = torch.empty(wsb // 4 + 4, dtype=torch.float32, device=x.device)
+  ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device)
   dx = torch.empty_like(x)
   dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
   dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
