@@ -427,6 +427,19 @@ size_t snap_conv2d_splitk_gn_partial_bytes(const SnapConvDesc* desc);   /* see S
  * function of the descriptor (desc->tile_hint carries the A/B mode).  For profiling labels and tests. */
 int32_t snap_conv2d_stationary_kind(const SnapConvDesc* desc, int32_t parts);
 
+/* The ResNet stem in one launch: the 7 x 7 / stride 2 / pad 3 root convolution of a 4-floats-per-pixel RGB
+ * image (desc as for snap_conv2d_nhwc_ex_f32: Ho x Wo is the CONV output) and the 3 x 3 / stride 2 / pad 1
+ * max-pool that reads it (snap_max_pool_3x3s2_f32), the conv output never written: y_pool is
+ * [N, (Ho - 1) / 2 + 1, (Wo - 1) / 2 + 1, 64], bit for bit what the two launches give.  w_bf16 = the root
+ * weight image (snap_conv2d_pack_weights_split_root_bf16, parts = 2).  Supported (the query is a pure host
+ * function): two-part split engine, Cout = Cout_stride = 64, prologue NONE / AFFINE, epilogue nothing but
+ * RELU; anything else returns SNAP_ERR_UNSUPPORTED and the caller launches the two kernels.  band_rows =
+ * pooled rows a wave computes in one march (0 = chosen from the shape; every value gives the same bits). */
+int32_t snap_conv2d_root_pool_supported(const SnapConvDesc* desc, int32_t parts);
+int snap_conv2d_root_pool_f32(const SnapConvDesc* desc, const float* x, const void* w_bf16,
+                              size_t w_bf16_bytes, int32_t parts, int32_t band_rows, float* y_pool,
+                              void* stream);
+
 /* mu / sc (/ rstd) [N, C] from a conv launch's gn_partial.  tile_rows =
  * snap_conv2d_tile_rows(desc of that launch); HW = Ho*Wo of its output. */
 int snap_group_norm_stats_from_partial_f32(const float* partial, int32_t N, int32_t HW,

@@ -79,6 +79,8 @@ SIGNATURES = {
     'snap_conv2d_pack_weights_multi_bf16': (c_int, [ptr, c_int, c_int, ptr]),
     'snap_conv2d_pack_weights_multi_f16': (c_int, [ptr, c_int, c_int, ptr]),
     'snap_conv2d_stationary_kind': (c_int, [ctypes.POINTER(SnapConvDesc), c_int]),
+    'snap_conv2d_root_pool_supported': (c_int, [ctypes.POINTER(SnapConvDesc), c_int]),
+    'snap_conv2d_root_pool_f32': (c_int, [ctypes.POINTER(SnapConvDesc), ptr, ptr, c_size, c_int, c_int, ptr, ptr]),
     'snap_conv2d_tile_rows_ex': (c_int, [ctypes.POINTER(SnapConvDesc), c_int]),
     'snap_conv2d_gn_partial_bytes_ex': (c_size, [ctypes.POINTER(SnapConvDesc), c_int]),
     'snap_conv2d_splitk_gn_partial_bytes': (c_size, [ctypes.POINTER(SnapConvDesc)]),
@@ -352,7 +354,7 @@ SIGNATURES = {
     ),
 }
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 _lib = None
 

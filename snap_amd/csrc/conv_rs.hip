@@ -999,6 +999,201 @@ __global__ __launch_bounds__(512, 2) void conv_root_ws64_kernel(const ConvArgs a
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The ResNet stem in one launch: the root convolution above and the 3 x 3 / stride 2 / pad 1 max-pool
+// that is its only reader (max_pool_kernel).  a.y is the POOLED tensor [N, Hp, Wp, 64]; the conv
+// output never reaches memory.  Same panel, slab, product and kh order as conv_root_ws64_kernel, so
+// every conv value is the one that kernel stores.  A wave owns (image, band of `band` pooled rows,
+// column tile k) and marches down conv rows 2 p0 - 1 ... 2 p1 - 1 (those inside the image), each
+// computed once per band; its 32 conv pixels start at 30 k - 1 and give pooled pixels 15 k ... 15 k
+// + 14 (pooled pixel p reads conv pixels 2 p - 1 ... 2 p + 1: the one-pixel overlap of neighbouring
+// tiles is recomputed).  Conv pixels outside [0, Wo) take no part in a maximum (they become -inf, the
+// pool kernel's start value; they are not zero padding of the conv).
+// Horizontal maxima in the MFMA layout (lane = channel, tile pixel ri = (r & 3) + 8 (r >> 2) + 4 lhi): the
+// pixel group g = 2 (r >> 2) + lhi of four holds pooled pixel 2 g (its elements 0 1 2) and 2 g + 1
+// (elements 2 3 and element 0 of group g + 1, which the other lane half holds: one exchange).
+// Vertical: a running maximum per pooled row; an odd conv row closes one pooled row and opens the next.
+// snap_max_nan over a set of taps does not depend on their order (any NaN -> the canonical NaN; else
+// v_max_f32, a total order with -0 < +0), so these are max_pool_kernel's bits.
+template <int PRO>
+__global__ __launch_bounds__(512, 2) void conv_root_pool_ws64_kernel(const ConvArgs a, const int band) {
+  constexpr int NT = 512, NW = NT / 64;
+  constexpr int NSLAB = 14, TN = 2;
+  constexpr int B_PART = 2048, B_SLAB = 4096;
+  constexpr int kPanel = NSLAB * B_SLAB;          // 57344
+  __shared__ __attribute__((aligned(16))) char panel[kPanel];
+
+  const SnapConvDesc& d = a.d;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, lhi = lane >> 5;
+  const int W = d.W, H = d.H, Wo = d.Wo, Ho = d.Ho;
+  const int Hp = (Ho - 1) / 2 + 1, Wp = (Wo - 1) / 2 + 1;
+  const int TX = (Wp + 14) / 15;
+  const int NB = (Hp + band - 1) / band;
+  {
+    const char* const wt = static_cast<const char*>(a.w_bf16);
+#pragma unroll
+    for (int p = 0; p < kPanel / 16 / NT; ++p) {
+      const int q = tid + NT * p;                 // 16-byte piece: [slab][part][64 columns][2 octets]
+      const int sl = q >> 8, within = q & 255;
+      const int part = within >> 7, rem = within & 127;
+      const char* src = wt + (int64_t)sl * 8192 + part * 4096 + (rem >> 1) * 32 + (rem & 1) * 16;
+      lds_dma16(src, panel + 16 * q);
+    }
+    wait_vm<0>();
+    __syncthreads();
+  }
+  const int relu_out = d.epilogue & SNAP_EPI_RELU;
+  const int ntile = d.N * NB * TX;
+  const int nwaves = gridDim.x * NW;
+  for (int t = blockIdx.x * NW + wid; t < ntile; t += nwaves) {
+    const int n = t / (NB * TX);
+    const int rb = t - n * (NB * TX);
+    const int bi = rb / TX, k = rb - bi * TX;
+    const int p0 = bi * band, p1 = min(p0 + band, Hp);
+    const int c0 = 30 * k - 1;                    // first conv pixel of the tile
+    const int xo = c0 + l31;                      // this lane's conv pixel (outside the row: never used)
+    const int xi0 = 2 * xo - 3 + 2 * lhi;         // first input pixel of the lane's octet at g = 0
+    const bool edge = c0 < 0 || c0 + 32 > Wo;     // wave-uniform: some tile pixels lie outside the row
+    const float* const img = a.x + (int64_t)n * H * W * 4;
+    float best[TN][8];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) best[j][i] = -INFINITY;
+    const int y_first = max(2 * p0 - 1, 0), y_last = min(2 * p1 - 1, Ho - 1);
+#pragma unroll 1
+    for (int yo = y_first; yo <= y_last; ++yo) {
+      f32x16 acc[TN];
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+      auto load_row = [&](int kh, f32x4 (&xs)[2][2]) {
+        const int yy = min(max(2 * yo - 3 + kh, 0), H - 1);     // (a row outside the image: loaded, never used)
+        const float* p = img + (int64_t)yy * W * 4;
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const int xi = min(max(xi0 + 4 * g + q, 0), W - 1);
+            xs[g][q] = *reinterpret_cast<const f32x4*>(p + 4 * xi);
+          }
+      };
+      auto do_row = [&](int kh, const f32x4 (&xs)[2][2]) {
+        const int yy = 2 * yo - 3 + kh;
+        if (yy < 0 || yy >= H) return;                          // wave-uniform: zero padding
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          u32x2 h[2], l[2];
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const int xi = xi0 + 4 * g + q;
+            const bool in = xi >= 0 && xi < W;
+            f32x4 v = xs[g][q];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float pv = apply_pro<PRO>(v[e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
+              v[e] = in ? pv : 0.f;
+            }
+            split_bf16(v, h[q], l[q]);
+          }
+          const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
+          const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
+          bf16x8 a_hi, a_lo;
+          __builtin_memcpy(&a_hi, &hh, 16);
+          __builtin_memcpy(&a_lo, &ll, 16);
+          const char* bs = panel + (kh * 2 + g) * B_SLAB;
+          bf16x8 bv[TN][2];
+#pragma unroll
+          for (int j = 0; j < TN; ++j) load_frag<2>(bs + frag_offset(j * 32 + l31, lhi), B_PART, bv[j]);
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, bv[j][0], acc[j], 0, 0, 0);
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bv[j][1], acc[j], 0, 0, 0);
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bv[j][0], acc[j], 0, 0, 0);
+        }
+      };
+      // the next kernel row's pixels travel while this one is converted / multiplied
+      f32x4 xa[2][2], xb[2][2];
+      load_row(0, xa);
+#pragma unroll 1
+      for (int kh = 0; kh < 6; kh += 2) {
+        load_row(kh + 1, xb);
+        do_row(kh, xa);
+        load_row(kh + 2, xa);
+        do_row(kh + 1, xb);
+      }
+      do_row(6, xa);
+
+      // ---- the conv row's epilogue, then its 15 pooled-column maxima per channel
+      if (relu_out) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[j][r] = snap_relu(acc[j][r]);
+      }
+      if (edge) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int cx = c0 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            acc[j][r] = (cx >= 0 && cx < Wo) ? acc[j][r] : -INFINITY;
+          }
+      }
+      float hm[TN][8];
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          // element 0 of the next pixel group: the lower half needs the upper half's of this register block,
+          // the upper half the lower half's of the next block (none after the last: pooled pixel 15 is not ours)
+          const float up = b < 3 ? acc[j][4 * b + 4] : -INFINITY;
+          const float nxt = __shfl_xor(lhi ? acc[j][4 * b] : up, 32);
+          float m0 = snap_max_nan(-INFINITY, acc[j][4 * b]);
+          m0 = snap_max_nan(m0, acc[j][4 * b + 1]);
+          m0 = snap_max_nan(m0, acc[j][4 * b + 2]);
+          float m1 = snap_max_nan(-INFINITY, acc[j][4 * b + 2]);
+          m1 = snap_max_nan(m1, acc[j][4 * b + 3]);
+          m1 = snap_max_nan(m1, nxt);
+          hm[j][2 * b] = m0;
+          hm[j][2 * b + 1] = m1;
+        }
+      // ---- vertical: conv row 2 p + 1 closes pooled row p and opens p + 1; the image's last row closes its own
+      const bool odd = yo & 1;
+      const int p = yo >> 1;
+      const bool close = odd ? p >= p0 : yo == Ho - 1;
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) best[j][i] = snap_max_nan(best[j][i], hm[j][i]);
+      if (close) {
+        float* const yb = a.y + (((int64_t)n * Hp + p) * Wp + 15 * k) * 64 + l31;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const int q = 4 * (i >> 1) + 2 * lhi + (i & 1);     // pooled pixel 15 k + q
+            if (q < 15 && 15 * k + q < Wp) yb[q * 64 + 32 * j] = best[j][i];
+          }
+      }
+      if (odd) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int i = 0; i < 8; ++i) best[j][i] = hm[j][i];
+      }
+    }
+  }
+}
+
 template <int KS, int TN, bool RES>
 int launch_rs_dual(const ConvArgs& a, dim3 grid, bool dual, hipStream_t s) {
   if (dual)
@@ -1080,6 +1275,59 @@ int snapconv::launch_root_ws(const ConvArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((conv_root_ws64_kernel<SNAP_PRO_AFFINE>), grid, dim3(512), 0, s, a);
   else
     hipLaunchKernelGGL((conv_root_ws64_kernel<SNAP_PRO_NONE>), grid, dim3(512), 0, s, a);
+  SNAP_CHECK_LAUNCH();
+  return SNAP_OK;
+}
+
+// ... and the stem in one launch (conv_root_pool_ws64_kernel): what launch_root_ws takes, at any row count
+extern "C" int32_t snap_conv2d_root_pool_supported(const SnapConvDesc* desc, int32_t parts) {
+  if (!desc) return 0;
+  const SnapConvDesc& d = *desc;
+  if (d.N <= 0 || d.H <= 0 || d.W < 8 || d.Ho != (d.H - 1) / 2 + 1 || d.Wo != (d.W - 1) / 2 + 1) return 0;
+  if (d.KH != 7 || d.KW != 7 || d.stride != 2 || d.pad_t != 3 || d.pad_l != 3 || d.Cin != 3 || d.Cin_stride != 4)
+    return 0;
+  if (parts != 2 || d.Cout != 64 || d.Cout_stride != 64 || hint_mode(d.tile_hint) == 1) return 0;
+  if ((d.prologue != SNAP_PRO_AFFINE && d.prologue != SNAP_PRO_NONE) || (d.epilogue & ~SNAP_EPI_RELU)) return 0;
+  const int64_t Hp = (d.Ho - 1) / 2 + 1, Wp = (d.Wo - 1) / 2 + 1;
+  if ((int64_t)d.N * d.Ho * d.Wo > 0x7fffffffLL || (int64_t)d.N * Hp * ((Wp + 14) / 15) > 0x7fffffffLL) return 0;
+  return 1;
+}
+
+extern "C" int snap_conv2d_root_pool_f32(const SnapConvDesc* desc, const float* x, const void* w_bf16,
+                                         size_t w_bf16_bytes, int32_t parts, int32_t band_rows, float* y_pool,
+                                         void* stream) {
+  if (!desc || !x || !w_bf16 || !y_pool) return SNAP_ERR_NULL;
+  if (!snap_conv2d_root_pool_supported(desc, parts)) return SNAP_ERR_UNSUPPORTED;
+  if (band_rows < 0) return SNAP_ERR_BAD_SHAPE;
+  if (w_bf16_bytes < snap_conv2d_packed_weights_split_root_bytes(desc->Cout, parts)) return SNAP_ERR_WORKSPACE;
+  if ((reinterpret_cast<uintptr_t>(w_bf16) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y_pool)) & 15)
+    return SNAP_ERR_BAD_SHAPE;
+  ConvArgs a = {};
+  a.d = *desc;
+  a.x = x;
+  a.w_bf16 = w_bf16;
+  a.y = y_pool;
+  const SnapConvDesc& d = a.d;
+  const int Hp = (d.Ho - 1) / 2 + 1, Wp = (d.Wo - 1) / 2 + 1;
+  const int64_t cols = (int64_t)d.N * ((Wp + 14) / 15);
+  // pooled rows per band: a band of B costs 2 B + 1 conv rows (its first is the one vertical recompute), and the
+  // launch takes as long as the wave with the most bands: the fewest conv rows per wave slot (2 workgroups x 8
+  // waves on each of 256 CUs) wins -- at C2 (40 x 136 pooled rows x 10 column tiles) B = 14, one band per slot
+  const int64_t slots = 256 * 2 * 8;
+  int band = 1;
+  int64_t cost = INT64_MAX;
+  for (int B = 1; B <= Hp && B <= 32; ++B) {
+    const int64_t c = snap_cdiv(cols * snap_cdiv(Hp, B), slots) * (2 * B + 1);
+    if (c < cost) cost = c, band = B;
+  }
+  if (band_rows) band = band_rows < Hp ? band_rows : Hp;   // (tests: every band length gives the same bits)
+  const int64_t nt = cols * snap_cdiv(Hp, band);
+  const dim3 grid((unsigned)(nt / 8 < 512 ? (nt + 7) / 8 : 512));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d.prologue == SNAP_PRO_AFFINE)
+    hipLaunchKernelGGL((conv_root_pool_ws64_kernel<SNAP_PRO_AFFINE>), grid, dim3(512), 0, s, a, band);
+  else
+    hipLaunchKernelGGL((conv_root_pool_ws64_kernel<SNAP_PRO_NONE>), grid, dim3(512), 0, s, a, band);
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }

@@ -194,11 +194,15 @@ class ResNetV2(base.Module):
                emit_gn_stats='raw', **cin_kw)
     else:
       w = _std(ctx, params['root_block']['conv_root']['kernel'])
-      conv = ag.conv2d if base.needs_grad(w) else ops.conv2d
-      x = conv(image, w, stride=2, padding=((3, 3), (3, 3)), prologue=ops.PRO_AFFINE,
-               in_affine=(2.0, -1.0), **cin_kw)
-      pool = ag.max_pool_3x3s2 if base.needs_grad(x) else ops.max_pool_3x3s2
-      x = out['stem'] = pool(x)
+      if not base.needs_grad(w, image) and ops.precision() == 'bf16x3':
+        # inference: the root conv and its max-pool as one launch (the pool is the conv output's only reader)
+        x = out['stem'] = ops.conv2d_root_pool(image, w, prologue=ops.PRO_AFFINE, in_affine=(2.0, -1.0), **cin_kw)
+      else:
+        conv = ag.conv2d if base.needs_grad(w) else ops.conv2d
+        x = conv(image, w, stride=2, padding=((3, 3), (3, 3)), prologue=ops.PRO_AFFINE,
+                 in_affine=(2.0, -1.0), **cin_kw)
+        pool = ag.max_pool_3x3s2 if base.needs_grad(x) else ops.max_pool_3x3s2
+        x = out['stem'] = pool(x)
     for i, size in enumerate(self.blocks):
       stage = {}
       nmid = self.width * 2**i

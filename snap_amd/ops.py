@@ -52,6 +52,8 @@ SIM_CHUNK = 64
 #   USE_PRESPLIT_VOTING / FUSED_TEMPLATE_PACK / PS_RES_INIT / PS_TILE   pre-split GEMM engine (direct-form voting)
 #   SIM_GENERAL_KERNEL  tests: pin the general similarity kernel (the full-chunk kernel is bit-identical)
 #   LATTICE_WINDOW     the refinement lattice scored from one window per point (pose_score_window; same bits)
+#   FUSE_STEM          inference, 'bf16x3' engine: the ResNet stem (7x7/2 root conv + 3x3/2 max-pool) as ONE launch that
+#                      never writes the conv output (conv2d_root_pool; same bits as the two launches)
 #   WGRAD_SIDE_STREAM  backward: a node's kernel-gradient launches run on the second HIP stream next to its
 #                      data-gradient / GroupNorm-VJP chain and are joined before the node returns (same bits)
 # ----------------------------------------------------------------------------------------------------
@@ -83,6 +85,7 @@ _TUNING_DEFAULTS = {
     'SIM_GENERAL_KERNEL': False,
     'LATTICE_WINDOW': True,
     'WGRAD_SIDE_STREAM': True,
+    'FUSE_STEM': True,
 }
 
 
@@ -832,6 +835,45 @@ def conv2d(
     y._snap_gn_partial = (partial, p.tile_rows, p.stats_relu)
     if partial2 is not None and ex.gn_partial2_done:
       y._snap_gn_partial_relu = (partial2, p.tile_rows, True)
+  return y
+
+
+def _root_pool_plan(x, w, cin, prologue, in_affine, relu, math):
+  """The ``ConvPlan`` of the root convolution where the stem runs as one launch, else None."""
+  if not tuning().FUSE_STEM or isinstance(x, PreSplit) or isinstance(w, PackedWeights):
+    return None
+  p = plan_conv(x, w, 2, ((3, 3), (3, 3)), cin, prologue, None, in_affine, None, relu, math=math)
+  ok = p.w_split_root and _lib.load().snap_conv2d_root_pool_supported(ctypes.byref(p.desc), p.parts)
+  return p if ok else None
+
+
+def conv2d_root_pool_supported(x, w, *, cin=None, prologue=PRO_NONE, in_affine=(1.0, 0.0), relu=False, math=None):
+  """Whether ``conv2d_root_pool`` (same arguments) runs as one launch; else it is ``conv2d`` -> ``max_pool_3x3s2``.
+  Pure, like ``plan_conv``."""
+  return _root_pool_plan(x, w, cin, prologue, in_affine, relu, math) is not None
+
+
+def conv2d_root_pool(x, w, *, cin=None, prologue=PRO_NONE, in_affine=(1.0, 0.0), relu=False, math=None, band_rows=0):
+  """The ResNet stem: ``max_pool_3x3s2(conv2d(x, w, stride=2, padding=((3, 3), (3, 3)), ...))`` for a 7 x 7 root
+  kernel over an image stored with 4 floats per pixel -- in ONE launch that never writes the conv output, where the
+  library supports the shape (two-part split engine, 64 output channels, ``Tuning.FUSE_STEM``); as those two
+  launches everywhere else.  Bit-identical either way.  ``band_rows``: tests (pooled rows per wave; 0 = automatic).
+  """
+  p = _root_pool_plan(x, w, cin, prologue, in_affine, relu, math)
+  if p is None:
+    return max_pool_3x3s2(conv2d(x, w, stride=2, padding=((3, 3), (3, 3)), cin=cin, prologue=prologue,
+                                 in_affine=in_affine, relu=relu, math=math))
+  lib = _lib.load()
+  xd = _f32(x, 'x')
+  _f32(w, 'w')
+  wpk = _packed_weights(w, p.image, p.parts)
+  N, Ho, Wo, Cout = p.out_shape
+  y = torch.empty((N, (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1, Cout), dtype=torch.float32, device=xd.device)
+  with _region(p.family, 2.0 * 147 * Cout * N * Ho * Wo, 4.0 * (x.numel() + w.numel() + y.numel()),
+               lambda: f'POOL_M{N * Ho * Wo}_K7x7x3_N{Cout}_s2_p{prologue}_e{p.desc.epilogue}'):
+    st = lib.snap_conv2d_root_pool_f32(ctypes.byref(p.desc), _p(xd), _p(wpk), wpk.numel() * 2, p.parts, int(band_rows),
+                                       _p(y), _stream())
+  _lib.check(st, 'snap_conv2d_root_pool_f32')
   return y
 
 
