@@ -1,9 +1,165 @@
-// 1 x 1 convolution / Dense with the ACTIVATION TILE STATIONARY IN REGISTERS: the f32-grade
-// split-bf16 arithmetic of conv_split.hip at NS = 2 ("bf16x3": a_lo b_hi + a_hi b_lo + a_hi b_hi
-// per MAC on v_mfma_f32_32x32x16_bf16, f32 accumulate, the same slab order and the same product
-// order per accumulator: the output is BIT-IDENTICAL to conv_split's), for the shape of the
-// closing / projection convolution of a bottleneck unit (snap/models/resnet.py:112-132: 1 x 1,
-// Cin = 64 / 128 / 256 -> Cout >= 2 Cin, GroupNorm + ReLU in front, the unit's residual behind).
+// The five STATIONARY convolution kernels of the bf16x3 path: the f32-grade split-bf16 arithmetic of
+// conv_split.hip at NS = 2 (a_lo b_hi + a_hi b_lo + a_hi b_hi per MAC on v_mfma_f32_32x32x16_bf16,
+// f32 accumulate) with one operand resident on the CU instead of re-streamed per output tile:
+//   conv1x1_rs_kernel           1 x 1, the activation row tile stationary in registers, weights ringed
+//   conv1x1_bs_kernel           1 x 1, the weight panel of 256 columns stationary in LDS
+//   conv3x3_ws64_kernel         3 x 3 / 64 -> 64 channels, all nine taps' weights stationary in LDS
+//   conv_root_ws64_kernel       7 x 7 / stride 2 RGB root convolution, weights stationary in LDS
+//   conv_root_pool_ws64_kernel  the same with the stem's 3 x 3 / 2 max-pool behind it, one launch
+// Every one of them walks the tiled engine's slabs in the tiled engine's order with the same product
+// order per accumulator, so its output is BIT-IDENTICAL to conv_split's.  That order is written once:
+// the kernels are built from the pieces below (and mma_common.h's bf16x3_step / pack_frag /
+// mfma_row); what stands at a kernel is what is particular to it.
+#include "conv_common.h"
+
+namespace {
+
+// A resident weight panel of 64 output columns: [slab][part][64 columns][2 octets]
+constexpr int kPart64 = 2048, kSlab64 = 2 * kPart64;
+constexpr int kStgRow = 32;   // floats per row of a wave's staging tile (conflict-free for the b32 stores and the b128 row reads)
+
+__device__ __forceinline__ float xor_sum3(float v) {     // over lane bits 3, 4, 5
+  v += __shfl_xor(v, 8);
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  return v;
+}
+
+// One 16-channel slab of a lane's pixel, held raw as two f32x4 (channels c0 + {0..3, 4..7} behind the
+// lane half's octet) -> the hi / lo A fragments: the prologue (GroupNorm operands mean, rstd * gamma,
+// beta from LDS tables, already offset by the octet), zero where the pixel does not exist, split.
+template <int PRO>
+__device__ __forceinline__ void gn_split_slab(const f32x4 (&xs)[2], const float* tmu, const float* tsc,
+                                              const float* tbe, int c0, bool ok, const SnapConvDesc& d,
+                                              bf16x8& hi, bf16x8& lo) {
+  constexpr bool need_gn = (PRO == SNAP_PRO_GN_RELU || PRO == SNAP_PRO_RELU_GN);
+  u32x2 h[2], l[2];
+#pragma unroll
+  for (int hq = 0; hq < 2; ++hq) {
+    const int c = c0 + 4 * hq;
+    f32x4 v = xs[hq];
+    f32x4 mu = {0.f, 0.f, 0.f, 0.f}, sc = mu, be = mu;
+    if constexpr (need_gn) {
+      mu = *reinterpret_cast<const f32x4*>(tmu + c);
+      sc = *reinterpret_cast<const f32x4*>(tsc + c);
+      be = *reinterpret_cast<const f32x4*>(tbe + c);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float pv = apply_pro<PRO>(v[e], mu[e], sc[e], be[e], d.in_scale, d.in_shift);
+      v[e] = ok ? pv : 0.f;
+    }
+    split_bf16(v, h[hq], l[hq]);
+  }
+  pack_frag(h, l, hi, lo);
+}
+
+// The first 64 columns of SLABS slabs of a split weight image (128-column tiles: 8 KB per slab, 4 KB
+// per part) -> a resident 64-column panel, by LDS-DMA; landed for the whole workgroup on return.
+template <int SLABS, int NT>
+__device__ __forceinline__ void load_panel64(const void* w, char* panel, int tid) {
+  const char* const wt = static_cast<const char*>(w);
+#pragma unroll
+  for (int p = 0; p < SLABS * kSlab64 / 16 / NT; ++p) {
+    const int q = tid + NT * p;                   // 16-byte piece
+    const int sl = q >> 8, within = q & 255;
+    const int part = within >> 7, rem = within & 127;
+    const char* src = wt + (int64_t)sl * 8192 + part * 4096 + (rem >> 1) * 32 + (rem & 1) * 16;
+    lds_dma16(src, panel + 16 * q);
+  }
+  wait_vm<0>();
+  __syncthreads();
+}
+
+// Row yo of the 7 x 7 / stride 2 / pad 3 root convolution of an RGB image stored with four floats per
+// pixel, for one wave's 32 output pixels, against the resident 14-slab panel (conv_split_root_kernel's
+// K slab = 4 consecutive pixels x 4 floats of one kernel row; same slab and product order: its bits).
+// Per kernel row a lane fetches the 2 x 32 bytes its two k-octets cover (pixels xi0 + 4 g + {0, 1}
+// for the lane's output pixel xo, which may lie outside the row), applies the prologue, zeroes what
+// lies outside the image, splits and multiplies.  The sums are built in a local and handed over at
+// the end: accumulating through the reference keeps them out of registers across the kh loop
+// (conv_root_pool_ws64_kernel: 128 -> 198 VGPRs).
+template <int PRO>
+__device__ __forceinline__ void root_conv_row(f32x16 (&acc)[2], const char* panel, const float* img, int yo,
+                                              int xo, int H, int W, const SnapConvDesc& d, int l31, int lhi) {
+  const int xi0 = 2 * xo - 3 + 2 * lhi;         // first input pixel of the lane's octet at g = 0
+  f32x16 lacc[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) lacc[j][r] = 0.f;
+  auto load_row = [&](int kh, f32x4 (&xs)[2][2]) {
+    const int yy = min(max(2 * yo - 3 + kh, 0), H - 1);     // (a row outside the image: loaded, never used)
+    const float* p = img + (int64_t)yy * W * 4;
+#pragma unroll
+    for (int g = 0; g < 2; ++g)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int xi = min(max(xi0 + 4 * g + q, 0), W - 1);
+        xs[g][q] = *reinterpret_cast<const f32x4*>(p + 4 * xi);
+      }
+  };
+  auto do_row = [&](int kh, const f32x4 (&xs)[2][2]) {
+    const int yy = 2 * yo - 3 + kh;
+    if (yy < 0 || yy >= H) return;                          // wave-uniform: zero padding
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      u32x2 h[2], l[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int xi = xi0 + 4 * g + q;
+        const bool in = xi >= 0 && xi < W;
+        f32x4 v = xs[g][q];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float pv = apply_pro<PRO>(v[e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
+          v[e] = in ? pv : 0.f;
+        }
+        split_bf16(v, h[q], l[q]);
+      }
+      bf16x8 a_hi, a_lo;
+      pack_frag(h, l, a_hi, a_lo);
+      bf16x3_step(lacc, a_hi, a_lo, panel + (kh * 2 + g) * kSlab64, kPart64, l31, lhi);
+    }
+  };
+  // the next kernel row's pixels travel while this one is converted / multiplied
+  f32x4 xa[2][2], xb[2][2];
+  load_row(0, xa);
+#pragma unroll 1
+  for (int kh = 0; kh < 6; kh += 2) {
+    load_row(kh + 1, xb);
+    do_row(kh, xa);
+    load_row(kh + 2, xa);
+    do_row(kh + 1, xb);
+  }
+  do_row(6, xa);
+  acc[0] = lacc[0];
+  acc[1] = lacc[1];
+}
+
+// Vector-memory instructions a wave issues BEHIND the DMA of the stage it is about to read (ring of
+// three: that DMA went out two stages ago), by the stage's position c in its column tile.  A stage
+// runs [wait, barrier, DMA of stage + 2 (P), statistics of the previous tile if c == 0 (SR),
+// MFMAs, epilogue if c == SPT - 1 (XE)].
+constexpr int rs_behind(int c, bool first_tile, int SPT, int P, int SR, int XE) {
+  if (first_tile && c == 0) return 0;          // (the prologue is drained as a whole)
+  int x = P;
+  for (int back = 2; back >= 1; --back) {
+    int cc = c - back;
+    if (cc < 0) {
+      if (first_tile) continue;                // no such stage
+      cc += SPT;
+    }
+    if (cc == 0) x += SR;
+    if (cc == SPT - 1) x += XE;
+  }
+  return x;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ACTIVATION TILE STATIONARY IN REGISTERS, for the shape of the closing / projection convolution of a
+// bottleneck unit (snap/models/resnet.py:112-132: 1 x 1, Cin = 64 / 128 / 256 -> Cout >= 2 Cin,
+// GroupNorm + ReLU in front, the unit's residual behind).
 //
 // conv_split.hip tiles the output 128 x 128: every column tile fetches, normalises and splits its
 // 128 x Cin activation tile again (N / 128 = 2 ... 8 times per element) and streams its own copy
@@ -33,36 +189,7 @@
 // Timing ablations (round 3) found these layers bound by the bytes through the CU boundary, not by
 // MFMAs, fragment fetches or DMA issue; 512-thread workgroups, skewed workgroups and other column
 // splits were measured and are not faster.
-#include "conv_common.h"
-
-namespace {
-
-__device__ __forceinline__ float xor_sum3(float v) {     // over lane bits 3, 4, 5
-  v += __shfl_xor(v, 8);
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-
-// Vector-memory instructions a wave issues BEHIND the DMA of the stage it is about to read (ring of
-// three: that DMA went out two stages ago), by the stage's position c in its column tile.  A stage
-// runs [wait, barrier, DMA of stage + 2 (P), statistics of the previous tile if c == 0 (SR),
-// MFMAs, epilogue if c == SPT - 1 (XE)].
-constexpr int rs_behind(int c, bool first_tile, int SPT, int P, int SR, int XE) {
-  if (first_tile && c == 0) return 0;          // (the prologue is drained as a whole)
-  int x = P;
-  for (int back = 2; back >= 1; --back) {
-    int cc = c - back;
-    if (cc < 0) {
-      if (first_tile) continue;                // no such stage
-      cc += SPT;
-    }
-    if (cc == 0) x += SR;
-    if (cc == SPT - 1) x += XE;
-  }
-  return x;
-}
-
+//
 // KS = Cin / 16 slabs, TN = 32-column MFMA tiles per column tile (BN = 32 TN); a wave = 32 rows
 // 256 threads per workgroup: 128 rows, two workgroups per CU
 template <int KS, int TN, int PRO, bool RES, bool DUAL>
@@ -76,7 +203,6 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rs_kernel(const ConvArgs a) {
   static_assert(KS % CH == 0 && SPT >= 2, "whole stages; the statistics hand-over needs two barriers per tile");
   constexpr int P = kStage / 16 / NT;           // DMA pieces per thread and stage
   constexpr int B_PART = BN * 32, B_SLAB = 2 * B_PART;
-  constexpr int kStgRow = 32;                   // floats per staged row (conflict-free for the b32 stores and the b128 row reads)
   constexpr int kStg = 32 * kStgRow;            // floats per wave
   constexpr int NSTAT = DUAL ? 8 : 4;           // [slot][sum, sum of squares] (x 2: of relu(y))
   constexpr int SR = DUAL ? 2 : 1;              // statistics stores per thread and tile
@@ -101,7 +227,9 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rs_kernel(const ConvArgs a) {
   // ---- weight ring ------------------------------------------------------------------------
   const char* const wt = static_cast<const char*>(a.w_bf16);
   const int64_t col_tile_bytes = (int64_t)KS * 8192;
-  // piece q = tid + NT p of a stage: LDS offset 16 q ([slab][part][column][octet])
+  // piece q = tid + NT p of a stage: LDS offset 16 q ([slab][part][column][octet]); a stage's source
+  // is contiguous at BN = 128, load_panel64's address formula at BN = 64 (kept here: the offsets are
+  // computed once per thread, in front of the ring)
   int b_off[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) {
@@ -186,28 +314,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rs_kernel(const ConvArgs a) {
     const float* const tmu = tab + (mm / HoWo - n_first) * 2 * Cin + 8 * lhi;
     const float* const tbe = tab + 4 * Cin + 8 * lhi;
     auto convert = [&](int s, const f32x4 (&xs)[2]) {
-      u32x2 h[2], l[2];
-#pragma unroll
-      for (int hq = 0; hq < 2; ++hq) {
-        const int c = 16 * s + 4 * hq;
-        f32x4 v = xs[hq];
-        f32x4 mu = {0.f, 0.f, 0.f, 0.f}, sc = mu, be = mu;
-        if constexpr (need_gn) {
-          mu = *reinterpret_cast<const f32x4*>(tmu + c);
-          sc = *reinterpret_cast<const f32x4*>(tmu + Cin + c);
-          be = *reinterpret_cast<const f32x4*>(tbe + c);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float pv = apply_pro<PRO>(v[e], mu[e], sc[e], be[e], d.in_scale, d.in_shift);
-          v[e] = ok ? pv : 0.f;
-        }
-        split_bf16(v, h[hq], l[hq]);
-      }
-      const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
-      const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
-      __builtin_memcpy(&a_hi[s], &hh, 16);
-      __builtin_memcpy(&a_lo[s], &ll, 16);
+      gn_split_slab<PRO>(xs, tmu, tmu + Cin, tbe, 16 * s, ok, d, a_hi[s], a_lo[s]);
       // (the conversion must END here: left alone, the table reads of ALL slabs -- 6 x 4
       //  registers each -- are issued in front of the first conversion and spilled)
       asm volatile("" : "+v"(a_hi[s]), "+v"(a_lo[s]) : : "memory");
@@ -310,29 +417,19 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rs_kernel(const ConvArgs a) {
       const char* const stage = ring + slot * kStage;
       slot = slot + 1 == NST ? 0 : slot + 1;
 #pragma unroll
-      for (int sl = 0; sl < CH; ++sl) {
-        const int s = c * CH + sl;
-        const char* bs = stage + sl * B_SLAB;
-        bf16x8 bv[TN][2];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) load_frag<2>(bs + frag_offset(j * 32 + l31, lhi), B_PART, bv[j]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo[s], bv[j][0], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi[s], bv[j][1], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi[s], bv[j][0], acc[j], 0, 0, 0);
-      }
+      for (int sl = 0; sl < CH; ++sl)
+        bf16x3_step(acc, a_hi[c * CH + sl], a_lo[c * CH + sl], stage + sl * B_SLAB, B_PART, l31, lhi);
     }
-    // ---- epilogue of column tile t -----------------------------------------------------------
+    // ---- epilogue of column tile t: accumulators -> the wave-private staging tile -> rows of float4 ->
+    // residual -> ReLU -> buffer store -> GroupNorm sums into the wave's LDS table.  (Its twin in
+    // conv1x1_bs_kernel differs only in where `publish` writes, but the two stay separate: as one
+    // function template the bs kernels lose registers -- conv1x1_bs_kernel<8, true, 1> 36 -> 84 bytes
+    // of scratch, <4, false, 2> 156 -> 161 VGPRs -- and a piece for this kernel alone is none.)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ri = (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const int ri = mfma_row(r, lhi);
         stg[ri * kStgRow + l31] = acc[j][r];
       }
       float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
@@ -454,7 +551,6 @@ __global__ __launch_bounds__(512, 2) void conv1x1_bs_kernel(const ConvArgs a) {
   constexpr int Cin = 16 * KS;
   constexpr int kPanel = KS * NCT * 8192;       // [column tile][slab][part][128 columns][32 B]
   constexpr int B_PART = 4096, B_SLAB = 8192;
-  constexpr int kStgRow = 32;
   constexpr int kStg = 32 * kStgRow;            // floats per wave (also holds the wave's GroupNorm table)
   static_assert(5 * Cin <= kStg, "GroupNorm table in the staging tile");
   __shared__ __attribute__((aligned(16))) char panel[kPanel];
@@ -542,25 +638,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_bs_kernel(const ConvArgs a) {
       const float* const tbe = stg + 4 * Cin + 8 * lhi;
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
-        u32x2 h[2], l[2];
-#pragma unroll
-        for (int hq = 0; hq < 2; ++hq) {
-          const int c = 16 * s + 4 * hq;
-          f32x4 v = xv[s][hq];
-          const f32x4 mu = *reinterpret_cast<const f32x4*>(tmu + c);
-          const f32x4 sc = *reinterpret_cast<const f32x4*>(tmu + Cin + c);
-          const f32x4 be = *reinterpret_cast<const f32x4*>(tbe + c);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float pv = apply_pro<SNAP_PRO_GN_RELU>(v[e], mu[e], sc[e], be[e], d.in_scale, d.in_shift);
-            v[e] = ok ? pv : 0.f;
-          }
-          split_bf16(v, h[hq], l[hq]);
-        }
-        const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
-        const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
-        __builtin_memcpy(&a_hi[s], &hh, 16);
-        __builtin_memcpy(&a_lo[s], &ll, 16);
+        gn_split_slab<SNAP_PRO_GN_RELU>(xv[s], tmu, tmu + Cin, tbe, 16 * s, ok, d, a_hi[s], a_lo[s]);
         asm volatile("" : "+v"(a_hi[s]), "+v"(a_lo[s]) : : "memory");
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -576,27 +654,15 @@ __global__ __launch_bounds__(512, 2) void conv1x1_bs_kernel(const ConvArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
 #pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const char* bs = panel + (ct * KS + s) * B_SLAB;
-        bf16x8 bv[TN][2];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) load_frag<2>(bs + frag_offset(j * 32 + l31, lhi), B_PART, bv[j]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo[s], bv[j][0], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi[s], bv[j][1], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi[s], bv[j][0], acc[j], 0, 0, 0);
-      }
-      // ---- epilogue of (row tile, column tile) ---------------------------------------------------
+      for (int s = 0; s < KS; ++s)
+        bf16x3_step(acc, a_hi[s], a_lo[s], panel + (ct * KS + s) * B_SLAB, B_PART, l31, lhi);
+      // ---- epilogue of (row tile, column tile): conv1x1_rs_kernel's, the sums straight to global memory
+      // (kept apart from it: see there)
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int ri = (r & 3) + 8 * (r >> 2) + 4 * lhi;
+          const int ri = mfma_row(r, lhi);
           stg[ri * kStgRow + l31] = acc[j][r];
         }
         float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
@@ -700,10 +766,10 @@ __global__ __launch_bounds__(512, 2) void conv1x1_bs_kernel(const ConvArgs a) {
 // and the fragments of kw = 0 / kw = 2 are the same registers shifted by one lane (v_mov_b32 with
 // the wave_shr:1 / wave_shl:1 DPP controls: one VALU instruction per register instead of ~30 for
 // a conversion).  Three conversions per pixel instead of nine.  Slab order = tap major, channel
-// tile minor, products lo-hi / hi-lo / hi-hi: the im2col body's, bit for bit.  No staging tile (LDS
-// is full): the epilogue stores straight from the MFMA layout and takes the GroupNorm sums of a
-// column from one lane's 16 rows + its partner half-wave; a tile never straddles images, its sums
-// go to slab (y, tile of the row) of the image (the finalize pass is told to sum all slabs).
+// tile minor: the im2col body's, bit for bit.  No staging tile (LDS is full): the epilogue stores
+// straight from the MFMA layout and takes the GroupNorm sums of a column from one lane's 16 rows +
+// its partner half-wave; a tile never straddles images, its sums go to slab (y, tile of the row) of
+// the image (the finalize pass is told to sum all slabs).
 __device__ __forceinline__ bf16x8 lane_shift(const bf16x8& v, bool left) {
   u32x4 r;
   __builtin_memcpy(&r, &v, 16);
@@ -720,8 +786,7 @@ template <int STATS /* 0 none, 1 one set */>
 __global__ __launch_bounds__(512, 2) void conv3x3_ws64_kernel(const ConvArgs a) {
   constexpr int NT = 512, NW = NT / 64;
   constexpr int KS = 4, TAPS = 9, TN = 2, Cin = 64, TP = 30;
-  constexpr int B_PART = 2048, B_SLAB = 4096;
-  constexpr int kPanel = TAPS * KS * B_SLAB;      // 147456
+  constexpr int kPanel = TAPS * KS * kSlab64;     // 147456
   constexpr int kTab = 3 * Cin;                   // floats per wave: mu | sc | beta of the tile's image
   __shared__ __attribute__((aligned(16))) char panel[kPanel];
   __shared__ __attribute__((aligned(16))) float tables[NW * kTab];
@@ -734,19 +799,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64_kernel(const ConvArgs a) 
   const int W = d.W, H = d.H;
   const int TX = (W + TP - 1) / TP;               // tiles per image row
 
-  {
-    const char* const wt = static_cast<const char*>(a.w_bf16);
-#pragma unroll
-    for (int p = 0; p < kPanel / 16 / NT; ++p) {
-      const int q = tid + NT * p;                 // 16-byte piece: [slab][part][64 columns][2 octets]
-      const int sl = q >> 8, within = q & 255;
-      const int part = within >> 7, rem = within & 127;
-      const char* src = wt + (int64_t)sl * 8192 + part * 4096 + (rem >> 1) * 32 + (rem & 1) * 16;
-      lds_dma16(src, panel + 16 * q);
-    }
-    wait_vm<0>();
-    __syncthreads();
-  }
+  load_panel64<TAPS * KS, NT>(a.w_bf16, panel, tid);
 
   float* const tab = tables + wid * kTab;
   const int relu_out = d.epilogue & SNAP_EPI_RELU;
@@ -791,27 +844,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64_kernel(const ConvArgs a) 
       if (yy < 0 || yy >= H) return;                          // wave-uniform: the row is zero padding
       bf16x8 f_hi[KS], f_lo[KS];
 #pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        u32x2 h[2], l[2];
-#pragma unroll
-        for (int hq = 0; hq < 2; ++hq) {
-          const int c = 16 * s + 4 * hq;
-          f32x4 v = xs[s][hq];
-          const f32x4 mu = *reinterpret_cast<const f32x4*>(tmu + c);
-          const f32x4 sc = *reinterpret_cast<const f32x4*>(tmu + Cin + c);
-          const f32x4 be = *reinterpret_cast<const f32x4*>(tmu + 2 * Cin + c);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float pv = apply_pro<SNAP_PRO_GN_RELU>(v[e], mu[e], sc[e], be[e], d.in_scale, d.in_shift);
-            v[e] = px_ok ? pv : 0.f;
-          }
-          split_bf16(v, h[hq], l[hq]);
-        }
-        const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
-        const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
-        __builtin_memcpy(&f_hi[s], &hh, 16);
-        __builtin_memcpy(&f_lo[s], &ll, 16);
-      }
+      for (int s = 0; s < KS; ++s)
+        gn_split_slab<SNAP_PRO_GN_RELU>(xs[s], tmu, tmu + Cin, tmu + 2 * Cin, 16 * s, px_ok, d, f_hi[s], f_lo[s]);
 #pragma unroll
       for (int kw = 0; kw < 3; ++kw) {
 #pragma unroll
@@ -819,19 +853,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64_kernel(const ConvArgs a) 
           // tap kw of output lane l = the pixel of lane l + kw - 1
           const bf16x8 a_hi = kw == 1 ? f_hi[s] : lane_shift(f_hi[s], kw == 2);
           const bf16x8 a_lo = kw == 1 ? f_lo[s] : lane_shift(f_lo[s], kw == 2);
-          const char* bs = panel + ((kh * 3 + kw) * KS + s) * B_SLAB;
-          bf16x8 bv[TN][2];
-#pragma unroll
-          for (int j = 0; j < TN; ++j) load_frag<2>(bs + frag_offset(j * 32 + l31, lhi), B_PART, bv[j]);
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, bv[j][0], acc[j], 0, 0, 0);
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bv[j][1], acc[j], 0, 0, 0);
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bv[j][0], acc[j], 0, 0, 0);
+          bf16x3_step(acc, a_hi, a_lo, panel + ((kh * 3 + kw) * KS + s) * kSlab64, kPart64, l31, lhi);
         }
       }
     };
@@ -844,14 +866,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64_kernel(const ConvArgs a) 
     do_row(1, xb);
     do_row(2, xa);
 
-    // ---- epilogue straight from the MFMA layout: lane = column 32 j + l31, tile rows 8 (r >> 2) + 4 lhi + (r & 3)
+    // ---- epilogue straight from the MFMA layout: lane = column 32 j + l31
     float* const yb = a.y + (((int64_t)n * H + y) * W + x0 - 1) * d.Cout_stride + l31;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       float s1 = 0.f, s2 = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ri = (r & 3) + 8 * (r >> 2) + 4 * lhi;      // tile row = pixel x0 - 1 + ri
+        const int ri = mfma_row(r, lhi);                      // tile row = pixel x0 - 1 + ri
         float v = acc[j][r];
         if (relu_out) v = snap_relu(v);
         const bool live = ri >= 1 && ri <= TP && x0 - 1 + ri < W;
@@ -875,20 +897,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64_kernel(const ConvArgs a) 
 }
 
 // ------------------------------------------------------------------------------------------------
-// ... and for the 7 x 7 / stride 2 / pad 3 root convolution of an RGB image stored with four floats
-// per pixel (conv_split_root_kernel: K slab = 4 consecutive pixels x 4 floats of one kernel row, 14
-// slabs): the 56 KB panel resident in LDS, eight independent waves, a wave = a row-aligned tile of
-// 32 output pixels; per kernel row a lane fetches the 2 x 32 bytes its two k-octets cover (pixels
-// 2 xo - 3 + 4 g + 2 lhi + {0, 1}), applies the affine prologue, zeroes what lies outside the
-// image, splits, and multiplies against the resident slab.  Same slab and product order as the
-// tiled root kernel: bit-identical.  Output straight from the MFMA layout.
+// ... and for the 7 x 7 / stride 2 / pad 3 root convolution (root_conv_row): the 56 KB panel resident
+// in LDS, eight independent waves, a wave = a row-aligned tile of 32 output pixels.  Output straight
+// from the MFMA layout.
 template <int PRO>
 __global__ __launch_bounds__(512, 2) void conv_root_ws64_kernel(const ConvArgs a) {
   constexpr int NT = 512, NW = NT / 64;
   constexpr int NSLAB = 14, TN = 2;
-  constexpr int B_PART = 2048, B_SLAB = 4096;
-  constexpr int kPanel = NSLAB * B_SLAB;          // 57344
-  __shared__ __attribute__((aligned(16))) char panel[kPanel];
+  __shared__ __attribute__((aligned(16))) char panel[NSLAB * kSlab64];    // 57344
 
   const SnapConvDesc& d = a.d;
   const int tid = threadIdx.x;
@@ -897,19 +913,7 @@ __global__ __launch_bounds__(512, 2) void conv_root_ws64_kernel(const ConvArgs a
   const int l31 = lane & 31, lhi = lane >> 5;
   const int W = d.W, H = d.H, Wo = d.Wo, Ho = d.Ho;
   const int TX = (Wo + 31) / 32;
-  {
-    const char* const wt = static_cast<const char*>(a.w_bf16);
-#pragma unroll
-    for (int p = 0; p < kPanel / 16 / NT; ++p) {
-      const int q = tid + NT * p;                 // 16-byte piece: [slab][part][64 columns][2 octets]
-      const int sl = q >> 8, within = q & 255;
-      const int part = within >> 7, rem = within & 127;
-      const char* src = wt + (int64_t)sl * 8192 + part * 4096 + (rem >> 1) * 32 + (rem & 1) * 16;
-      lds_dma16(src, panel + 16 * q);
-    }
-    wait_vm<0>();
-    __syncthreads();
-  }
+  load_panel64<NSLAB, NT>(a.w_bf16, panel, tid);
   const int relu_out = d.epilogue & SNAP_EPI_RELU;
   const int ntile = d.N * Ho * TX;
   const int nwaves = gridDim.x * NW;
@@ -918,80 +922,15 @@ __global__ __launch_bounds__(512, 2) void conv_root_ws64_kernel(const ConvArgs a
     const int ry = t - n * (Ho * TX);
     const int yo = ry / TX, x0 = (ry - yo * TX) * 32;
     const int xo = x0 + l31;                      // this lane's output pixel (may lie beyond the row: dropped)
-    const int xi0 = 2 * xo - 3 + 2 * lhi;         // first input pixel of the lane's octet at g = 0
     f32x16 acc[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    const float* const img = a.x + (int64_t)n * H * W * 4;
-    auto load_row = [&](int kh, f32x4 (&xs)[2][2]) {
-      const int yy = min(max(2 * yo - 3 + kh, 0), H - 1);     // (a row outside the image: loaded, never used)
-      const float* p = img + (int64_t)yy * W * 4;
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int xi = min(max(xi0 + 4 * g + q, 0), W - 1);
-          xs[g][q] = *reinterpret_cast<const f32x4*>(p + 4 * xi);
-        }
-    };
-    auto do_row = [&](int kh, const f32x4 (&xs)[2][2]) {
-      const int yy = 2 * yo - 3 + kh;
-      if (yy < 0 || yy >= H) return;                          // wave-uniform: zero padding
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        u32x2 h[2], l[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int xi = xi0 + 4 * g + q;
-          const bool in = xi >= 0 && xi < W;
-          f32x4 v = xs[g][q];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float pv = apply_pro<PRO>(v[e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
-            v[e] = in ? pv : 0.f;
-          }
-          split_bf16(v, h[q], l[q]);
-        }
-        const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
-        const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
-        bf16x8 a_hi, a_lo;
-        __builtin_memcpy(&a_hi, &hh, 16);
-        __builtin_memcpy(&a_lo, &ll, 16);
-        const char* bs = panel + (kh * 2 + g) * B_SLAB;
-        bf16x8 bv[TN][2];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) load_frag<2>(bs + frag_offset(j * 32 + l31, lhi), B_PART, bv[j]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, bv[j][0], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bv[j][1], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bv[j][0], acc[j], 0, 0, 0);
-      }
-    };
-    // the next kernel row's pixels travel while this one is converted / multiplied
-    f32x4 xa[2][2], xb[2][2];
-    load_row(0, xa);
-#pragma unroll 1
-    for (int kh = 0; kh < 6; kh += 2) {
-      load_row(kh + 1, xb);
-      do_row(kh, xa);
-      load_row(kh + 2, xa);
-      do_row(kh + 1, xb);
-    }
-    do_row(6, xa);
+    root_conv_row<PRO>(acc, panel, a.x + (int64_t)n * H * W * 4, yo, xo, H, W, d, l31, lhi);
 
     float* const yb = a.y + (((int64_t)n * Ho + yo) * Wo + x0) * d.Cout_stride + l31;
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ri = (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const int ri = mfma_row(r, lhi);
         float v = acc[j][r];
         if (relu_out) v = snap_relu(v);
         if (x0 + ri < Wo) yb[(int64_t)ri * d.Cout_stride + 32 * j] = v;
@@ -1002,14 +941,14 @@ __global__ __launch_bounds__(512, 2) void conv_root_ws64_kernel(const ConvArgs a
 // ------------------------------------------------------------------------------------------------
 // The ResNet stem in one launch: the root convolution above and the 3 x 3 / stride 2 / pad 1 max-pool
 // that is its only reader (max_pool_kernel).  a.y is the POOLED tensor [N, Hp, Wp, 64]; the conv
-// output never reaches memory.  Same panel, slab, product and kh order as conv_root_ws64_kernel, so
-// every conv value is the one that kernel stores.  A wave owns (image, band of `band` pooled rows,
+// output never reaches memory.  The conv rows are root_conv_row's, so every conv value is the one
+// conv_root_ws64_kernel stores.  A wave owns (image, band of `band` pooled rows,
 // column tile k) and marches down conv rows 2 p0 - 1 ... 2 p1 - 1 (those inside the image), each
 // computed once per band; its 32 conv pixels start at 30 k - 1 and give pooled pixels 15 k ... 15 k
 // + 14 (pooled pixel p reads conv pixels 2 p - 1 ... 2 p + 1: the one-pixel overlap of neighbouring
 // tiles is recomputed).  Conv pixels outside [0, Wo) take no part in a maximum (they become -inf, the
 // pool kernel's start value; they are not zero padding of the conv).
-// Horizontal maxima in the MFMA layout (lane = channel, tile pixel ri = (r & 3) + 8 (r >> 2) + 4 lhi): the
+// Horizontal maxima in the MFMA layout (lane = channel, tile pixel ri = mfma_row(r, lhi)): the
 // pixel group g = 2 (r >> 2) + lhi of four holds pooled pixel 2 g (its elements 0 1 2) and 2 g + 1
 // (elements 2 3 and element 0 of group g + 1, which the other lane half holds: one exchange).
 // Vertical: a running maximum per pooled row; an odd conv row closes one pooled row and opens the next.
@@ -1019,9 +958,7 @@ template <int PRO>
 __global__ __launch_bounds__(512, 2) void conv_root_pool_ws64_kernel(const ConvArgs a, const int band) {
   constexpr int NT = 512, NW = NT / 64;
   constexpr int NSLAB = 14, TN = 2;
-  constexpr int B_PART = 2048, B_SLAB = 4096;
-  constexpr int kPanel = NSLAB * B_SLAB;          // 57344
-  __shared__ __attribute__((aligned(16))) char panel[kPanel];
+  __shared__ __attribute__((aligned(16))) char panel[NSLAB * kSlab64];    // 57344
 
   const SnapConvDesc& d = a.d;
   const int tid = threadIdx.x;
@@ -1032,19 +969,7 @@ __global__ __launch_bounds__(512, 2) void conv_root_pool_ws64_kernel(const ConvA
   const int Hp = (Ho - 1) / 2 + 1, Wp = (Wo - 1) / 2 + 1;
   const int TX = (Wp + 14) / 15;
   const int NB = (Hp + band - 1) / band;
-  {
-    const char* const wt = static_cast<const char*>(a.w_bf16);
-#pragma unroll
-    for (int p = 0; p < kPanel / 16 / NT; ++p) {
-      const int q = tid + NT * p;                 // 16-byte piece: [slab][part][64 columns][2 octets]
-      const int sl = q >> 8, within = q & 255;
-      const int part = within >> 7, rem = within & 127;
-      const char* src = wt + (int64_t)sl * 8192 + part * 4096 + (rem >> 1) * 32 + (rem & 1) * 16;
-      lds_dma16(src, panel + 16 * q);
-    }
-    wait_vm<0>();
-    __syncthreads();
-  }
+  load_panel64<NSLAB, NT>(a.w_bf16, panel, tid);
   const int relu_out = d.epilogue & SNAP_EPI_RELU;
   const int ntile = d.N * NB * TX;
   const int nwaves = gridDim.x * NW;
@@ -1055,7 +980,6 @@ __global__ __launch_bounds__(512, 2) void conv_root_pool_ws64_kernel(const ConvA
     const int p0 = bi * band, p1 = min(p0 + band, Hp);
     const int c0 = 30 * k - 1;                    // first conv pixel of the tile
     const int xo = c0 + l31;                      // this lane's conv pixel (outside the row: never used)
-    const int xi0 = 2 * xo - 3 + 2 * lhi;         // first input pixel of the lane's octet at g = 0
     const bool edge = c0 < 0 || c0 + 32 > Wo;     // wave-uniform: some tile pixels lie outside the row
     const float* const img = a.x + (int64_t)n * H * W * 4;
     float best[TN][8];
@@ -1067,70 +991,7 @@ __global__ __launch_bounds__(512, 2) void conv_root_pool_ws64_kernel(const ConvA
 #pragma unroll 1
     for (int yo = y_first; yo <= y_last; ++yo) {
       f32x16 acc[TN];
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-      auto load_row = [&](int kh, f32x4 (&xs)[2][2]) {
-        const int yy = min(max(2 * yo - 3 + kh, 0), H - 1);     // (a row outside the image: loaded, never used)
-        const float* p = img + (int64_t)yy * W * 4;
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const int xi = min(max(xi0 + 4 * g + q, 0), W - 1);
-            xs[g][q] = *reinterpret_cast<const f32x4*>(p + 4 * xi);
-          }
-      };
-      auto do_row = [&](int kh, const f32x4 (&xs)[2][2]) {
-        const int yy = 2 * yo - 3 + kh;
-        if (yy < 0 || yy >= H) return;                          // wave-uniform: zero padding
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-          u32x2 h[2], l[2];
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const int xi = xi0 + 4 * g + q;
-            const bool in = xi >= 0 && xi < W;
-            f32x4 v = xs[g][q];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float pv = apply_pro<PRO>(v[e], 0.f, 0.f, 0.f, d.in_scale, d.in_shift);
-              v[e] = in ? pv : 0.f;
-            }
-            split_bf16(v, h[q], l[q]);
-          }
-          const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
-          const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
-          bf16x8 a_hi, a_lo;
-          __builtin_memcpy(&a_hi, &hh, 16);
-          __builtin_memcpy(&a_lo, &ll, 16);
-          const char* bs = panel + (kh * 2 + g) * B_SLAB;
-          bf16x8 bv[TN][2];
-#pragma unroll
-          for (int j = 0; j < TN; ++j) load_frag<2>(bs + frag_offset(j * 32 + l31, lhi), B_PART, bv[j]);
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, bv[j][0], acc[j], 0, 0, 0);
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bv[j][1], acc[j], 0, 0, 0);
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, bv[j][0], acc[j], 0, 0, 0);
-        }
-      };
-      // the next kernel row's pixels travel while this one is converted / multiplied
-      f32x4 xa[2][2], xb[2][2];
-      load_row(0, xa);
-#pragma unroll 1
-      for (int kh = 0; kh < 6; kh += 2) {
-        load_row(kh + 1, xb);
-        do_row(kh, xa);
-        load_row(kh + 2, xa);
-        do_row(kh + 1, xb);
-      }
-      do_row(6, xa);
+      root_conv_row<PRO>(acc, panel, img, yo, xo, H, W, d, l31, lhi);
 
       // ---- the conv row's epilogue, then its 15 pooled-column maxima per channel
       if (relu_out) {
@@ -1144,7 +1005,7 @@ __global__ __launch_bounds__(512, 2) void conv_root_pool_ws64_kernel(const ConvA
         for (int j = 0; j < TN; ++j)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int cx = c0 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            const int cx = c0 + mfma_row(r, lhi);
             acc[j][r] = (cx >= 0 && cx < Wo) ? acc[j][r] : -INFINITY;
           }
       }

@@ -1,7 +1,8 @@
 // Device primitives shared by the GEMM-shaped kernels (included by common.h; no kernels, nothing
-// host-side): the vector types, the f32 -> bf16 split, the operand element types, the vector-memory
-// waits, the 16-byte LDS-DMA, the half-type stores, the swizzled fragment fetch with the ordered
-// split product, and the fused input prologue.
+// host-side): the vector types, the f32 -> bf16 split and its packing into MFMA fragments, the
+// operand element types, the vector-memory waits, the 16-byte LDS-DMA, the half-type stores, the
+// swizzled fragment fetch with the ordered split product (and its k-step for an operand that is
+// stationary in registers), the accumulator row map, and the fused input prologue.
 #ifndef SNAP_CSRC_MMA_COMMON_H_
 #define SNAP_CSRC_MMA_COMMON_H_
 
@@ -49,6 +50,13 @@ __device__ __forceinline__ void split_bf16(const f32x4& v, U2& hi, U2& lo) {
     hi[h] = split_step(pr);
     lo[h] = split_step(pr);
   }
+}
+// Two split 4-element halves (k = 0..3 | 4..7 of a lane's octet) -> the hi / lo MFMA fragments
+__device__ __forceinline__ void pack_frag(const u32x2 (&h)[2], const u32x2 (&l)[2], bf16x8& hi, bf16x8& lo) {
+  const u32x4 hh = {h[0][0], h[0][1], h[1][0], h[1][1]};
+  const u32x4 ll = {l[0][0], l[0][1], l[1][0], l[1][1]};
+  __builtin_memcpy(&hi, &hh, 16);
+  __builtin_memcpy(&lo, &ll, 16);
 }
 
 // Element type of the rounded operands of the training-precision engines: bf16 (default) or IEEE
@@ -150,6 +158,22 @@ __device__ __forceinline__ void split_product(f32x16 (&acc)[TM][TN], const bf16x
   }
   part_product<0, 0>(acc, av, bv);
 }
+// The two-part ("bf16x3") k-step of a kernel whose A operand is ONE row tile held in registers as
+// separate hi / lo fragments: fetch the slab's TN column-tile fragments (parts `part_stride` bytes
+// apart), then split_product's groups lo hi, hi lo, hi hi on a [1][2] view of the operands.
+template <int TN>
+__device__ __forceinline__ void bf16x3_step(f32x16 (&acc)[TN], const bf16x8& a_hi, const bf16x8& a_lo,
+                                            const char* slab, int part_stride, int l31, int lhi) {
+  bf16x8 bv[TN][2];
+#pragma unroll
+  for (int j = 0; j < TN; ++j) load_frag<2>(slab + frag_offset(j * 32 + l31, lhi), part_stride, bv[j]);
+  const bf16x8 av[1][2] = {{a_hi, a_lo}};
+  split_product<2>(reinterpret_cast<f32x16(&)[1][TN]>(acc), av, bv);
+}
+
+// Row of a 32 x 32 accumulator tile that element r of an f32x16 holds in lane half lhi (the MFMA
+// C layout: lane & 31 is the column)
+__device__ __forceinline__ int mfma_row(int r, int lhi) { return (r & 3) + 8 * (r >> 2) + 4 * lhi; }
 
 // The fused input prologue.  PRO is a COMPILE-TIME parameter: a run-time switch here is lowered to
 // a branch tree per staged element and wrecks the schedule of the whole main loop.

@@ -200,8 +200,6 @@ __device__ __forceinline__ bf16x8 pack8(const f32x4& lo, const f32x4& hi) {
   const bf16x4 bl = __builtin_convertvector(lo, bf16x4), bh = __builtin_convertvector(hi, bf16x4);
   return bf16x8{bl[0], bl[1], bl[2], bl[3], bh[0], bh[1], bh[2], bh[3]};
 }
-// rows of an acc tile held by this lane: rmap(r) = (r & 3) + 8 (r >> 2) + 4 lhi
-__device__ __forceinline__ int rmap(int r, int lhi) { return (r & 3) + 8 * (r >> 2) + 4 * lhi; }
 
 // B-fragment of a row-major global [*, 64] row: 8 consecutive d at 16 s + 8 lhi, times `mul`
 __device__ __forceinline__ bf16x8 row_frag(const float* row, int s, int lhi, float mul) {
@@ -232,7 +230,7 @@ __device__ __forceinline__ void store_transposed(const f32x16 (&acc)[2], float m
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) stage[l31 * 68 + 32 * t + rmap(r, lhi)] = acc[t][r] * mul;
+    for (int r = 0; r < 16; ++r) stage[l31 * 68 + 32 * t + mfma_row(r, lhi)] = acc[t][r] * mul;
   __syncthreads();                       // (every wave of the workgroup stores: uniform call)
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -334,7 +332,7 @@ __global__ __launch_bounds__(256) void attention_bwd_dq_kernel(const AttnBwdArgs
       float ds[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = kb * AT_BLK + 32 * t2 + rmap(r, lhi);
+        const int key = kb * AT_BLK + 32 * t2 + mfma_row(r, lhi);
         const float p = key < a.N ? exp2f(st[r] - lse) : 0.f;
         ds[r] = p * (dp[r] - delta);
       }
@@ -453,7 +451,7 @@ __global__ __launch_bounds__(256) void attention_bwd_dkv_kernel(const AttnBwdArg
       float p[16], ds[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ql = 32 * t2 + rmap(r, lhi);
+        const int ql = 32 * t2 + mfma_row(r, lhi);
         const bool ok = key_ok && (qb * AT_BLK + ql) < a.N;
         p[r] = ok ? exp2f(st[r] - ls[ql]) : 0.f;
         ds[r] = p[r] * (dp[r] - ls[AT_BLK + ql]);

@@ -173,9 +173,11 @@ def _kind3(N, H, W):
   return int(_lib.load().snap_conv2d_stationary_kind(ctypes.byref(d), 2))
 
 
-@pytest.mark.parametrize('N,H,W', CASES_3X3)
+# (... and one shape with the ReLU epilogue)
+@pytest.mark.parametrize('N,H,W,relu', [(*c, False) for c in CASES_3X3] + [(2, 9, 91, True)],
+                         ids=['%d-%d-%d' % c for c in CASES_3X3] + ['2-9-91-relu_out'])
 @pytest.mark.parametrize('emit', [None, 'raw', 'relu'])
-def test_weights_stationary_3x3_equals_the_im2col_body(N, H, W, emit):
+def test_weights_stationary_3x3_equals_the_im2col_body(N, H, W, relu, emit):
   if emit is not None and N == 40:
     pytest.skip('one statistics variant at full size is enough')
   ops.CONV_TILE = None
@@ -186,7 +188,8 @@ def test_weights_stationary_3x3_equals_the_im2col_body(N, H, W, emit):
   b_in = rnd((64,), 3003) * 0.3
   xd = x.to(DEV)
   mu, sc = ops.group_norm_stats(xd, g_in.to(DEV))
-  kw = dict(padding=((1, 1), (1, 1)), prologue=ops.PRO_GN_RELU, gn=(mu, sc, b_in.to(DEV)), emit_gn_stats=emit)
+  kw = dict(padding=((1, 1), (1, 1)), prologue=ops.PRO_GN_RELU, gn=(mu, sc, b_in.to(DEV)), emit_gn_stats=emit,
+            relu=relu)
   y_ws = ops.conv2d(xd, w.to(DEV), **kw)
   ops.CONV_NO_RS = True
   ops.USE_SPLITK = False
@@ -199,7 +202,7 @@ def test_weights_stationary_3x3_equals_the_im2col_body(N, H, W, emit):
   assert torch.equal(y_ws, y_t), float((y_ws - y_t).abs().max())
   if N <= 3:
     want = oracle_ops.conv2d(x, w, padding=((1, 1), (1, 1)), prologue=ops.PRO_GN_RELU,
-                             gn=(*oracle_ops.group_norm_stats(x, g_in), b_in))
+                             gn=(*oracle_ops.group_norm_stats(x, g_in), b_in), relu=relu)
     helpers.report('ws 3x3 vs oracle', y_ws, want, atol=TOL * float(want.abs().max()))
   if emit is None:
     return
@@ -212,16 +215,21 @@ def test_weights_stationary_3x3_equals_the_im2col_body(N, H, W, emit):
 
 
 # ---- the weights-stationary RGB root convolution (7 x 7 / stride 2 / pad 3, 64 output channels)
-@pytest.mark.parametrize('N,H,W', [(2, 64, 96), (1, 50, 70), (3, 33, 130), (40, 544, 680)])
+CASES_ROOT = [(2, 64, 96), (1, 50, 70), (3, 33, 130), (40, 544, 680)]
+
+
+# (... and one shape with the ReLU epilogue)
+@pytest.mark.parametrize('N,H,W,relu', [(*c, False) for c in CASES_ROOT] + [(1, 50, 70, True)],
+                         ids=['%d-%d-%d' % c for c in CASES_ROOT] + ['1-50-70-relu_out'])
 @pytest.mark.parametrize('affine', [True, False])
-def test_weights_stationary_root_conv_equals_the_tiled_root_kernel(N, H, W, affine):
+def test_weights_stationary_root_conv_equals_the_tiled_root_kernel(N, H, W, relu, affine):
   if N == 40 and not affine:
     pytest.skip('one variant at full size is enough')
   ops.CONV_TILE = None
   x = torch.rand((N, H, W, 4), generator=torch.Generator().manual_seed(4000 + W))
   x[..., 3] = 0.37                                  # (must not matter: zero weights)
   w = rnd((7, 7, 3, 64), 4001, 1 / np.sqrt(147))
-  kw = dict(stride=2, padding=((3, 3), (3, 3)), cin=3)
+  kw = dict(stride=2, padding=((3, 3), (3, 3)), cin=3, relu=relu)
   if affine:
     kw.update(prologue=ops.PRO_AFFINE, in_affine=(2.0, -1.0))
   xd, wd = x.to(DEV), w.to(DEV)
