@@ -851,7 +851,8 @@ int snap_refine_lattice_f32(const float* init, const float* offs_r,
                             const float* offs_p, int32_t B, int32_t nr,
                             int32_t np_, float* out, void* stream);
 
-/* Row-wise argmax with first-index tie-break: idx[B] over scores[B, start:P]. */
+/* Row-wise argmax with first-index tie-break: idx[B] over scores[B, start:P].  NaN is the maximum and the
+ * first NaN wins (np.argmax / jnp.argmax). */
 int snap_argmax_rows_f32(const float* scores, int32_t B, int32_t P, int32_t start,
                          int32_t* idx, void* stream);
 

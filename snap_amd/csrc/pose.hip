@@ -533,10 +533,17 @@ __global__ __launch_bounds__(256, 3) void sim_split_fast_kernel(
 
 // layers.masked_softmax over the query points (snap/models/layers.py:38-43) + its inclusive CDF
 // (the sampler's row distribution).  One workgroup per scene; fixed-order sums.
+// The CDF is NON-DECREASING, a row of weight 0 repeats its predecessor's value bit for bit (the sampler's
+// search for the first cdf[n] > target can then never return it) and cdf[N - 1] == 1: the segment boundaries
+// are a SERIAL sum of the segment masses (two prefixes of a tree-ordered scan may differ by an ulp the wrong
+// way, also across a segment of mass 0), the running sum inside a segment is capped by the segment's upper
+// boundary, and everything from the segment's last non-zero entry on IS that boundary.
 __global__ __launch_bounds__(256) void masked_softmax_rows_kernel(
     const float* __restrict__ x, const uint8_t* __restrict__ mask, int N, float* __restrict__ w,
     float* __restrict__ cdf) {
   __shared__ float red[256];
+  __shared__ float seg_s[256];
+  __shared__ float edge[257];
   __shared__ int any_s;
   const int b = blockIdx.x, t = threadIdx.x;
   const float* xr = x + (int64_t)b * N;
@@ -562,8 +569,14 @@ __global__ __launch_bounds__(256) void masked_softmax_rows_kernel(
   m = red[0];
   __syncthreads();
   float loc = 0.f;
-  for (int i = i0; i < i1; ++i) loc += (all || mr[i]) ? expf(xr[i] - m) : 0.f;
+  int lastnz = -1;                             // last entry of the segment with a non-zero weight
+  for (int i = i0; i < i1; ++i) {
+    const float e = (all || mr[i]) ? expf(xr[i] - m) : 0.f;
+    if (e > 0.f) lastnz = i;
+    loc += e;
+  }
   red[t] = loc;
+  seg_s[t] = loc;
   __syncthreads();
   // inclusive scan of the 256 segment sums (Hillis-Steele, fixed order)
   for (int o = 1; o < 256; o <<= 1) {
@@ -573,12 +586,22 @@ __global__ __launch_bounds__(256) void masked_softmax_rows_kernel(
     __syncthreads();
   }
   const float total = red[255];
-  float run = red[t] - loc;
+  if (t == 0) {
+    float acc = 0.f;
+    edge[0] = 0.f;
+    for (int k = 0; k < 256; ++k) {
+      acc += seg_s[k];
+      edge[k + 1] = acc;
+    }
+  }
+  __syncthreads();
+  const float lo = edge[t], hi = edge[t + 1], ctotal = edge[256];
+  float run = lo;
   for (int i = i0; i < i1; ++i) {
     const float e = (all || mr[i]) ? expf(xr[i] - m) : 0.f;
     run += e;
     w[(int64_t)b * N + i] = e / total;
-    cdf[(int64_t)b * N + i] = run / total;
+    cdf[(int64_t)b * N + i] = (i >= lastnz ? hi : fminf(run, hi)) / ctotal;
   }
 }
 
@@ -1658,6 +1681,15 @@ __global__ void refine_lattice_kernel(const float* __restrict__ init,
   out[i * 3 + 2] = ty0 + (s * ox + c * oy);
 }
 
+// The order np.argmax / jnp.argmax put on (value, index) pairs: NaN is the maximum and the FIRST NaN wins;
+// among numbers the larger value wins and the first of equal values.  An empty slot is (-inf, 0x7fffffff):
+// it loses to every real element, including a real -inf.  `>` alone would drop a NaN behind any number.
+__device__ __forceinline__ bool argmax_takes(float ov, int oi, float mv, int mi) {
+  const bool on = ov != ov, mn = mv != mv;
+  if (on != mn) return on;
+  return (on || ov == mv) ? oi < mi : ov > mv;
+}
+
 // NT threads per row: long rows (the 68 921-pose refinement lattice with one scene per GPU) take 1024 -- one
 // workgroup is all the parallelism a row has here, and the scan is bound by its loads in flight
 template <int NT>
@@ -1671,7 +1703,7 @@ __global__ __launch_bounds__(NT) void argmax_rows_kernel(const float* __restrict
   int besti = 0x7fffffff;
   for (int p = start + threadIdx.x; p < P; p += NT) {
     const float v = row[p];
-    if (v > best || besti == 0x7fffffff) { best = v; besti = p; }
+    if (argmax_takes(v, p, best, besti)) { best = v; besti = p; }
   }
   bv[threadIdx.x] = best;
   bi[threadIdx.x] = besti;
@@ -1682,7 +1714,7 @@ __global__ __launch_bounds__(NT) void argmax_rows_kernel(const float* __restrict
       const int oi = bi[threadIdx.x + o];
       const float mv = bv[threadIdx.x];
       const int mi = bi[threadIdx.x];
-      if (oi != 0x7fffffff && (mi == 0x7fffffff || ov > mv || (ov == mv && oi < mi))) {
+      if (argmax_takes(ov, oi, mv, mi)) {
         bv[threadIdx.x] = ov;
         bi[threadIdx.x] = oi;
       }

@@ -1781,7 +1781,8 @@ def sim_softmax(fq, fm, scale, clip_negative, num_valid, want_prob=False,
 
 def masked_softmax_rows(x, mask):
   """layers.masked_softmax over the last axis of x [B, N] (layers.py:38-43) -> (weights, inclusive
-  CDF), both [B, N]."""
+  CDF), both [B, N].  The CDF is non-decreasing, repeats its predecessor bit for bit on an entry of weight 0
+  (``ransac_sample`` never draws such a row) and ends at exactly 1."""
   lib = _lib.load()
   _f32(x, 'x'); _mask(mask, 'mask')
   B, N = x.shape
@@ -1923,7 +1924,9 @@ def refine_lattice(init, offs_r, offs_p):
 
 
 def argmax_rows(scores, start=0):
-  """First-index argmax of scores[:, start:] -> int32 [B] (relative to start)."""
+  """argmax of scores[:, start:] -> int32 [B] (relative to start), with the order of np.argmax / jnp.argmax:
+  NaN is the maximum and the FIRST NaN wins; among numbers the first maximum wins (+inf included; an all -inf row
+  gives 0)."""
   lib = _lib.load()
   _f32(scores, 'scores')
   B, P = scores.shape
