@@ -104,10 +104,8 @@ __global__ __launch_bounds__(256) void sim_kernel(
 // grid as above; a wave owns the 64 cells of one softmax chunk (B operand, held in registers for
 // the whole tile) and the tile's 64 query rows (A operand): 2 x 2 tiles of 32 x 32, DM / 2 MFMAs
 // each.  Neither operand touches LDS: lane (l31, lhi) of an MFMA holds element k = 2 j + lhi of
-// row / column l31, picked out of the lane's own contiguous DM-vector.  Epilogue straight from the
-// accumulators: a register holds, per half-wave, 32 consecutive cells of one query row -> one
-// 128-byte line per half-wave and store; the chunk's (max, sum exp) pair is a half-wave
-// reduction (4 DPP row rotates + one cross-row exchange).
+// row / column l31, picked out of the lane's own contiguous DM-vector.  The epilogue is the staged
+// one below (sim_stage_tile, sim_row_stats, sim_row_store), shared with the split-bf16 kernels.
 // The VALU kernel was bound by its packed-FMA issue (97 % VALU busy, 1.65 ms at C2 for a
 // 2.44 GB write that the HBM can take in 0.4 ms).
 // ---------------------------------------------------------------------------
@@ -128,19 +126,103 @@ __device__ __forceinline__ void sim_load_operand(const float* __restrict__ row, 
   }
 }
 
-__device__ __forceinline__ float half_wave_max(float v) {
+// max / sum over the 16 lanes of a DPP row (row_ror 8/4/2/1: symmetric steps, so every lane of
+// the row ends with the same bits)
+__device__ __forceinline__ float row16_max(float v) {
   v = fmaxf(v, snap_dpp<0x128>(v));
   v = fmaxf(v, snap_dpp<0x124>(v));
   v = fmaxf(v, snap_dpp<0x122>(v));
-  v = fmaxf(v, snap_dpp<0x121>(v));
-  return fmaxf(v, __shfl_xor(v, 16, 64));
+  return fmaxf(v, snap_dpp<0x121>(v));
 }
-__device__ __forceinline__ float half_wave_sum(float v) {
+__device__ __forceinline__ float row16_sum(float v) {
   v += snap_dpp<0x128>(v);
   v += snap_dpp<0x124>(v);
   v += snap_dpp<0x122>(v);
-  v += snap_dpp<0x121>(v);
-  return v + __shfl_xor(v, 16, 64);
+  return v + snap_dpp<0x121>(v);
+}
+
+// ---- the staged epilogue of the matrix-core similarity kernels ---------------------------------
+// The MFMA C layout gives a lane ONE cell of 16 rows -- 64 dword stores per 32-row tile, and narrow
+// stores are issue-bound.  So the tile (32 rows x 64 cells) goes through a per-wave LDS buffer:
+// staged, 16 lanes own one query row's 64 cells as float4, a wave store covers four 256-byte row
+// segments with dwordx4 (8 stores per tile instead of 32), and the chunk's (max, sum exp) is a
+// reduction inside one 16-lane DPP row.  The buffer is private to the wave: LDS ops of one wave
+// complete in order, no barrier.
+constexpr int SIM_LD = 64 + 4;   // +4: rows 4 apart hit distinct banks
+
+// rows as the A operand, cells as B: acc[tj][r] = sim[row (r & 3) + 8 (r >> 2) + 4 lhi][cell 32 tj + l31]
+__device__ __forceinline__ void sim_stage_tile(float (*st)[SIM_LD], const f32x16 (&acc)[2], int l31,
+                                               int lhi) {
+#pragma unroll
+  for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) st[(r & 3) + 8 * (r >> 2) + 4 * lhi][32 * tj + l31] = acc[tj][r];
+}
+
+// One staged query row of a 4-row pass: which row, whether it exists, the factor sim carries
+// (bev_localizer.py:165-172: the confidence weight replaces 1 / num_valid).
+struct SimRow {
+  int rr;        // row of the 32-row tile
+  bool live;
+  int64_t row;   // b * Nq + n (row 0 of the scene for a dead row: never stored)
+  float wrow;
+};
+__device__ __forceinline__ SimRow sim_staged_row(int p, int sub, int b, int Nq, int n_tile,
+                                                 const float* __restrict__ row_weight, float rnv) {
+  SimRow r;
+  r.rr = 4 * p + sub;
+  const int n = n_tile + r.rr;
+  r.live = n < Nq;
+  r.row = (int64_t)b * Nq + (r.live ? n : 0);
+  r.wrow = row_weight ? row_weight[r.row] : rnv;
+  return r;
+}
+
+// The staged row epilogue, in two steps around the caller's `if (live)`.
+//   TAIL: the chunk may end after `ncell` < 64 cells and sim rows may be unaligned (XY % 4 != 0).
+//   Without TAIL every chunk is full and every row segment 16-byte aligned: no masks (4 compare /
+//   select per element), and sim leaves with non-temporal stores (streamed once, read back later
+//   by the scoring kernel: nothing of it is worth an L2 line now).
+//   CLIP: 0 / 1 at compile time, -1 = the run-time flag `clip`.
+// Step 1 (every lane: the DPP rows must be whole): the lane's four cells [c4, c4 + 4) of the row
+// -> x = clip, scale, and the chunk's (max, sum exp) over the row's 16 lanes.
+struct SimRowStats {
+  f32x4 x;
+  float m, sum;
+};
+template <bool TAIL, int CLIP>
+__device__ __forceinline__ SimRowStats sim_row_stats(const float* staged, int clip, float scale,
+                                                     int c4, int ncell) {
+  f32x4 x = *reinterpret_cast<const f32x4*>(staged);
+  float m = -INFINITY;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (CLIP < 0 ? clip != 0 : CLIP != 0) x[e] = fmaxf(x[e], 0.f);
+    x[e] *= scale;
+    if (!TAIL || c4 + e < ncell) m = fmaxf(m, x[e]);
+  }
+  m = row16_max(m);
+  float sum = 0.f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (!TAIL || c4 + e < ncell) sum += __expf(x[e] - m);   // v_exp_f32: ~1e-6 relative on the chunk mass
+  sum = row16_sum(sum);
+  return SimRowStats{x, m, sum};
+}
+// Step 2 (live rows): sim = x * wrow at o = &sim[row][cell0 + c4].
+template <bool TAIL>
+__device__ __forceinline__ void sim_row_store(const f32x4& x, float wrow, float* o, int c4, int ncell,
+                                              int XY) {
+  if constexpr (!TAIL) {
+    __builtin_nontemporal_store(f32x4{x[0] * wrow, x[1] * wrow, x[2] * wrow, x[3] * wrow},
+                                reinterpret_cast<f32x4*>(o));
+  } else if (c4 + 3 < ncell && ((XY & 3) == 0)) {
+    *reinterpret_cast<f32x4*>(o) = f32x4{x[0] * wrow, x[1] * wrow, x[2] * wrow, x[3] * wrow};
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (c4 + e < ncell) o[e] = x[e] * wrow;
+  }
 }
 
 template <int DM>
@@ -167,13 +249,9 @@ __global__ __launch_bounds__(256, DM <= 32 ? 4 : 2) void sim_mfma_kernel(
     const int row = n0 + 32 * t + l31;
     sim_load_operand<DM>(fq + ((int64_t)b * Nq + (row < Nq ? row : 0)) * DM, row < Nq, lhi, aq[t]);
   }
-  // Epilogue through a per-wave LDS tile (32 rows x 64 cells, one ti at a time): the MFMA C
-  // layout gives a lane ONE cell of 16 rows -- 64 dword stores per tile, and narrow stores are
-  // issue-bound.  Staged, 16 lanes own one query row's 64 cells as float4: a wave store covers
-  // four 256-byte row segments with dwordx4 (8 stores per ti instead of 32), and the chunk's
-  // (max, sum exp) is a reduction inside one 16-lane DPP row.
-  __shared__ __attribute__((aligned(16))) float stage[4][32][64 + 4];   // +4: rows 4 apart hit distinct banks
-  float (*st)[64 + 4] = stage[wave];
+  // staged epilogue, one 32-row tile (ti) at a time
+  __shared__ __attribute__((aligned(16))) float stage[4][32][SIM_LD];
+  float (*st)[SIM_LD] = stage[wave];
   const float rnv = 1.0f / num_valid[b];   // as the VALU kernel: the two stay bit-identical
   const int sub = lane >> 4;            // row within a 4-row pass
   const int c4 = (lane & 15) * 4;       // first of the lane's 4 cells
@@ -194,51 +272,16 @@ __global__ __launch_bounds__(256, DM <= 32 ? 4 : 2) void sim_mfma_kernel(
 #pragma unroll
       for (int tj = 0; tj < 2; ++tj)
         acc[tj] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[ti][j], bq[tj][j], acc[tj], 0, 0, 0);
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        st[(r & 3) + 8 * (r >> 2) + 4 * lhi][32 * tj + l31] = acc[tj][r];   // MFMA C layout
-    // (the tile is private to the wave: LDS ops of one wave complete in order, no barrier)
+    sim_stage_tile(st, acc, l31, lhi);
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
-      const int rr = 4 * p + sub;
-      const int n = n0 + 32 * ti + rr;
-      const bool live = n < Nq;
-      const int64_t row = (int64_t)b * Nq + (live ? n : 0);
-      const float wrow = row_weight ? row_weight[row] : rnv;
-      f32x4 x = *reinterpret_cast<const f32x4*>(&st[rr][c4]);
-      float m = -INFINITY;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (clip) x[e] = fmaxf(x[e], 0.f);
-        x[e] *= scale;
-        if (c4 + e < ncell) m = fmaxf(m, x[e]);
-      }
-      m = fmaxf(m, snap_dpp<0x128>(m));
-      m = fmaxf(m, snap_dpp<0x124>(m));
-      m = fmaxf(m, snap_dpp<0x122>(m));
-      m = fmaxf(m, snap_dpp<0x121>(m));
-      float sum = 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (c4 + e < ncell) sum += __expf(x[e] - m);   // v_exp_f32: ~1e-6 relative on the chunk mass
-      sum += snap_dpp<0x128>(sum);
-      sum += snap_dpp<0x124>(sum);
-      sum += snap_dpp<0x122>(sum);
-      sum += snap_dpp<0x121>(sum);
-      if (live) {
-        float* o = sim + row * XY + cell0 + c4;
-        if (c4 + 3 < ncell && ((XY & 3) == 0)) {
-          *reinterpret_cast<f32x4*>(o) = f32x4{x[0] * wrow, x[1] * wrow, x[2] * wrow, x[3] * wrow};
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (c4 + e < ncell) o[e] = x[e] * wrow;
-        }
+      const SimRow r = sim_staged_row(p, sub, b, Nq, n0 + 32 * ti, row_weight, rnv);
+      const SimRowStats e = sim_row_stats<true, -1>(&st[r.rr][c4], clip, scale, c4, ncell);
+      if (r.live) {
+        sim_row_store<true>(e.x, r.wrow, sim + r.row * XY + cell0 + c4, c4, ncell, XY);
         if ((lane & 15) == 0) {
-          stats[(row * NC + chunk) * 2 + 0] = m;
-          stats[(row * NC + chunk) * 2 + 1] = sum;
+          stats[(r.row * NC + chunk) * 2 + 0] = e.m;
+          stats[(r.row * NC + chunk) * 2 + 1] = e.sum;
         }
       }
     }
@@ -251,7 +294,8 @@ __global__ __launch_bounds__(256, DM <= 32 ? 4 : 2) void sim_mfma_kernel(
 // bf16(v - hi - mid): conv_split.hip's arithmetic; NS = 3 keeps 24 significand bits per operand,
 // six part products per MAC, error ~2^-24 per product -- inside the f32 chain's own rounding) by
 // sim_presplit_kernel, and the tile is NS (NS + 1) / 2 x DM / 16 v_mfma_f32_32x32x16_bf16 per
-// 32 x 32 block instead of DM / 2 f32 MFMAs: 2.7 x fewer matrix cycles at NS = 3.  Same epilogue.
+// 32 x 32 block instead of DM / 2 f32 MFMAs: 2.7 x fewer matrix cycles at NS = 3.  The epilogue is
+// sim_stage_tile, sim_row_stats and sim_row_store, as in sim_mfma_kernel.
 
 // x [R, DM] f32 -> [R][NS][DM] bf16
 template <int NS>
@@ -268,6 +312,42 @@ __global__ __launch_bounds__(256) void sim_presplit_kernel(const float* __restri
     out[(r * NS + p) * DM + k] = b;
     v -= (float)b;
   }
+}
+
+// One operand row's split parts for an MFMA lane: out[s][p] = elements [16 s + 8 lhi, + 8) of part p.
+// `src` = the row's [NS][DM] block + 8 lhi (any readable row when !valid: the registers are zeroed).
+template <int DM, int NS>
+__device__ __forceinline__ void sim_split_load(const __bf16* __restrict__ src, bool valid,
+                                               bf16x8 (&out)[DM / 16][NS]) {
+#pragma unroll
+  for (int s = 0; s < DM / 16; ++s)
+#pragma unroll
+    for (int p = 0; p < NS; ++p) {
+      out[s][p] = *reinterpret_cast<const bf16x8*>(src + p * DM + 16 * s);
+      if (!valid) out[s][p] = bf16x8{};
+    }
+}
+
+// acc[tj] = sum over k-steps and part pairs (pa + pb < NS) of aq[.][pa] x bq[tj][.][pb], smallest
+// terms first: the order of split_product (NS = 2 runs the last three pairs of the NS = 3 list).
+// SWAP = false: query rows are the MFMA's A operand (the C layout of sim_stage_tile); SWAP = true:
+// map cells are A -- the same products in the same k positions, the transposed accumulator tile.
+template <int NS, bool SWAP, int KS>
+__device__ __forceinline__ void sim_split_products(const bf16x8 (&aq)[KS][NS],
+                                                   const bf16x8 (&bq)[2][KS][NS], f32x16 (&acc)[2]) {
+  constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+#pragma unroll
+  for (int s = 0; s < KS; ++s)
+#pragma unroll
+    for (int i = (NS == 3 ? 0 : 3); i < 6; ++i)
+#pragma unroll
+      for (int tj = 0; tj < 2; ++tj)
+        acc[tj] = SWAP ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[tj][s][PB[i]], aq[s][PA[i]], acc[tj], 0, 0, 0)
+                       : __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[s][PA[i]], bq[tj][s][PB[i]], acc[tj], 0, 0, 0);
 }
 
 template <int DM, int NS>
@@ -291,17 +371,10 @@ __global__ __launch_bounds__(256, 3) void sim_split_kernel(
   for (int t = 0; t < 2; ++t) {
     const int cell = cell0 + 32 * t + l31;
     const bool cv = cell < XY;
-    const __bf16* src = fms + ((int64_t)b * XY + (cv ? cell : 0)) * (NS * DM) + 8 * lhi;
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int p = 0; p < NS; ++p) {
-        bq[t][s][p] = *reinterpret_cast<const bf16x8*>(src + p * DM + 16 * s);
-        if (!cv) bq[t][s][p] = bf16x8{};
-      }
+    sim_split_load<DM, NS>(fms + ((int64_t)b * XY + (cv ? cell : 0)) * (NS * DM) + 8 * lhi, cv, bq[t]);
   }
-  __shared__ __attribute__((aligned(16))) float stage[4][32][64 + 4];
-  float (*st)[64 + 4] = stage[wave];
+  __shared__ __attribute__((aligned(16))) float stage[4][32][SIM_LD];
+  float (*st)[SIM_LD] = stage[wave];
   const float rnv = 1.0f / num_valid[b];
   const int sub = lane >> 4;
   const int c4 = (lane & 15) * 4;
@@ -309,86 +382,21 @@ __global__ __launch_bounds__(256, 3) void sim_split_kernel(
 #pragma unroll
   for (int ti = 0; ti < 2; ++ti) {
     bf16x8 aq[KS][NS];
-    {
-      const int row = n0 + 32 * ti + l31;
-      const bool rv = row < Nq;
-      const __bf16* src = fqs + ((int64_t)b * Nq + (rv ? row : 0)) * (NS * DM) + 8 * lhi;
-#pragma unroll
-      for (int s = 0; s < KS; ++s)
-#pragma unroll
-        for (int p = 0; p < NS; ++p) {
-          aq[s][p] = *reinterpret_cast<const bf16x8*>(src + p * DM + 16 * s);
-          if (!rv) aq[s][p] = bf16x8{};
-        }
-    }
+    const int arow = n0 + 32 * ti + l31;
+    sim_split_load<DM, NS>(fqs + ((int64_t)b * Nq + (arow < Nq ? arow : 0)) * (NS * DM) + 8 * lhi,
+                           arow < Nq, aq);
     f32x16 acc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-#define SNAP_SIM_PRODUCT(PA, PB)                                                               \
-  _Pragma("unroll") for (int tj = 0; tj < 2; ++tj)                                               \
-      acc[tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aq[s][PA], bq[tj][s][PB], acc[tj], 0, 0, 0);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      if constexpr (NS == 3) {               // smallest terms first: the order of split_product
-        SNAP_SIM_PRODUCT(2, 0)
-        SNAP_SIM_PRODUCT(0, 2)
-        SNAP_SIM_PRODUCT(1, 1)
-        SNAP_SIM_PRODUCT(1, 0)
-        SNAP_SIM_PRODUCT(0, 1)
-        SNAP_SIM_PRODUCT(0, 0)
-      } else {
-        SNAP_SIM_PRODUCT(1, 0)
-        SNAP_SIM_PRODUCT(0, 1)
-        SNAP_SIM_PRODUCT(0, 0)
-      }
-    }
-#undef SNAP_SIM_PRODUCT
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        st[(r & 3) + 8 * (r >> 2) + 4 * lhi][32 * tj + l31] = acc[tj][r];
+    sim_split_products<NS, false>(aq, bq, acc);
+    sim_stage_tile(st, acc, l31, lhi);
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
-      const int rr = 4 * p + sub;
-      const int n = n0 + 32 * ti + rr;
-      const bool live = n < Nq;
-      const int64_t row = (int64_t)b * Nq + (live ? n : 0);
-      const float wrow = row_weight ? row_weight[row] : rnv;
-      f32x4 x = *reinterpret_cast<const f32x4*>(&st[rr][c4]);
-      float m = -INFINITY;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (clip) x[e] = fmaxf(x[e], 0.f);
-        x[e] *= scale;
-        if (c4 + e < ncell) m = fmaxf(m, x[e]);
-      }
-      m = fmaxf(m, snap_dpp<0x128>(m));
-      m = fmaxf(m, snap_dpp<0x124>(m));
-      m = fmaxf(m, snap_dpp<0x122>(m));
-      m = fmaxf(m, snap_dpp<0x121>(m));
-      float sum = 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (c4 + e < ncell) sum += __expf(x[e] - m);
-      sum += snap_dpp<0x128>(sum);
-      sum += snap_dpp<0x124>(sum);
-      sum += snap_dpp<0x122>(sum);
-      sum += snap_dpp<0x121>(sum);
-      if (live) {
-        float* o = sim + row * XY + cell0 + c4;
-        if (c4 + 3 < ncell && ((XY & 3) == 0)) {
-          *reinterpret_cast<f32x4*>(o) = f32x4{x[0] * wrow, x[1] * wrow, x[2] * wrow, x[3] * wrow};
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (c4 + e < ncell) o[e] = x[e] * wrow;
-        }
+      const SimRow r = sim_staged_row(p, sub, b, Nq, n0 + 32 * ti, row_weight, rnv);
+      const SimRowStats e = sim_row_stats<true, -1>(&st[r.rr][c4], clip, scale, c4, ncell);
+      if (r.live) {
+        sim_row_store<true>(e.x, r.wrow, sim + r.row * XY + cell0 + c4, c4, ncell, XY);
         if ((lane & 15) == 0) {
-          stats[(row * NC + chunk) * 2 + 0] = m;
-          stats[(row * NC + chunk) * 2 + 1] = sum;
+          stats[(r.row * NC + chunk) * 2 + 0] = e.m;
+          stats[(r.row * NC + chunk) * 2 + 1] = e.sum;
         }
       }
     }
@@ -396,26 +404,22 @@ __global__ __launch_bounds__(256, 3) void sim_split_kernel(
 }
 
 // The same kernel for XY % 256 == 0 (every chunk of every workgroup full: C2 128 x 128, C4 256 x 256,
-// the reference's 120 x 160 map), leaner around the same arithmetic -- identical bits in sim and in
+// the reference's 120 x 160 map), leaner around the same pieces -- identical bits in sim and in
 // the chunk statistics (tests/test_gpu_kernels.py compares the two kernels bit for bit):
-//   * operand roles swapped in the MFMA (A = map cells, B = query rows: the same products in the same
-//     k positions, the transposed accumulator tile): a lane then holds FOUR CONSECUTIVE cells of one
-//     row per accumulator quad, so the tile goes to the staging buffer in 8 ds_write_b128 instead of
-//     32 ds_write_b32 (stride 68 floats: the 16 rows of a lane group land on distinct banks; the old
-//     b32 pattern had a 25 % conflict rate);
-//   * no tail masks (4 compare / select per element) and the clip flag at compile time;
+//   * operand roles swapped in the MFMA (sim_split_products<NS, true>): a lane then holds FOUR
+//     CONSECUTIVE cells of one row per accumulator quad, so the tile goes to the staging buffer in
+//     8 ds_write_b128 instead of 32 ds_write_b32 (stride 68 floats: the 16 rows of a lane group land
+//     on distinct banks; the b32 pattern of sim_stage_tile has a 25 % conflict rate);
+//   * the row epilogue without TAIL and with the clip flag at compile time;
 //   * the (max, sum) pairs of the workgroup's four chunks leave as ONE 32-byte store per row (they
 //     are adjacent in [row][chunk][2]) instead of four 8-byte partial-line writes: the statistics
-//     were a third of the kernel's write requests;
-//   * sim is written with non-temporal stores (2.5 GB streamed once, read back later by the scoring
-//     kernel: nothing of it is worth an L2 line now).
+//     were a third of the kernel's write requests.
 template <int DM, int NS, bool CLIP>
 __global__ __launch_bounds__(256, 3) void sim_split_fast_kernel(
     const __bf16* __restrict__ fqs, const __bf16* __restrict__ fms, int Nq, int XY, float scale,
     const float* __restrict__ num_valid, float* __restrict__ sim, float* __restrict__ stats,
     const float* __restrict__ row_weight) {
   constexpr int KS = DM / 16;
-  constexpr int LD = 64 + 4;
   const int b = blockIdx.z;
   const int n0 = blockIdx.y * SIM_TQ;
   const int lane = threadIdx.x & 63;
@@ -426,59 +430,23 @@ __global__ __launch_bounds__(256, 3) void sim_split_fast_kernel(
   const int NC = XY / SIM_CH;
   bf16x8 bq[2][KS][NS];
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const __bf16* src = fms + ((int64_t)b * XY + cell0 + 32 * t + l31) * (NS * DM) + 8 * lhi;
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int p = 0; p < NS; ++p) bq[t][s][p] = *reinterpret_cast<const bf16x8*>(src + p * DM + 16 * s);
-  }
-  __shared__ __attribute__((aligned(16))) float stage[4][32][LD];
+  for (int t = 0; t < 2; ++t)
+    sim_split_load<DM, NS>(fms + ((int64_t)b * XY + cell0 + 32 * t + l31) * (NS * DM) + 8 * lhi, true, bq[t]);
+  __shared__ __attribute__((aligned(16))) float stage[4][32][SIM_LD];
   __shared__ __attribute__((aligned(16))) float sstat[SIM_TQ][8];
-  float (*st)[LD] = stage[wave];
+  float (*st)[SIM_LD] = stage[wave];
   const float rnv = 1.0f / num_valid[b];
   const int sub = lane >> 4;
   const int c4 = (lane & 15) * 4;
 #pragma unroll
   for (int ti = 0; ti < 2; ++ti) {
     bf16x8 aq[KS][NS];
-    {
-      const int row = n0 + 32 * ti + l31;
-      const bool rv = row < Nq;
-      const __bf16* src = fqs + ((int64_t)b * Nq + (rv ? row : 0)) * (NS * DM) + 8 * lhi;
-#pragma unroll
-      for (int s = 0; s < KS; ++s)
-#pragma unroll
-        for (int p = 0; p < NS; ++p) {
-          aq[s][p] = *reinterpret_cast<const bf16x8*>(src + p * DM + 16 * s);
-          if (!rv) aq[s][p] = bf16x8{};
-        }
-    }
+    const int arow = n0 + 32 * ti + l31;
+    sim_split_load<DM, NS>(fqs + ((int64_t)b * Nq + (arow < Nq ? arow : 0)) * (NS * DM) + 8 * lhi,
+                           arow < Nq, aq);
     f32x16 acc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
     // (cells as the A operand, rows as B: acc[tj][r] = sim[row l31][cell 32 tj + (r & 3) + 8 (r >> 2) + 4 lhi])
-#define SNAP_SIM_PRODUCT(PA, PB)                                                               \
-  _Pragma("unroll") for (int tj = 0; tj < 2; ++tj)                                               \
-      acc[tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[tj][s][PB], aq[s][PA], acc[tj], 0, 0, 0);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      if constexpr (NS == 3) {
-        SNAP_SIM_PRODUCT(2, 0)
-        SNAP_SIM_PRODUCT(0, 2)
-        SNAP_SIM_PRODUCT(1, 1)
-        SNAP_SIM_PRODUCT(1, 0)
-        SNAP_SIM_PRODUCT(0, 1)
-        SNAP_SIM_PRODUCT(0, 0)
-      } else {
-        SNAP_SIM_PRODUCT(1, 0)
-        SNAP_SIM_PRODUCT(0, 1)
-        SNAP_SIM_PRODUCT(0, 0)
-      }
-    }
-#undef SNAP_SIM_PRODUCT
+    sim_split_products<NS, true>(aq, bq, acc);
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
@@ -487,37 +455,12 @@ __global__ __launch_bounds__(256, 3) void sim_split_fast_kernel(
             f32x4{acc[tj][4 * g], acc[tj][4 * g + 1], acc[tj][4 * g + 2], acc[tj][4 * g + 3]};
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
-      const int rr = 4 * p + sub;
-      const int n = n0 + 32 * ti + rr;
-      const bool live = n < Nq;
-      const int64_t row = (int64_t)b * Nq + (live ? n : 0);
-      const float wrow = row_weight ? row_weight[row] : rnv;
-      f32x4 x = *reinterpret_cast<const f32x4*>(&st[rr][c4]);
-      float m = -INFINITY;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if constexpr (CLIP) x[e] = fmaxf(x[e], 0.f);
-        x[e] *= scale;
-        m = fmaxf(m, x[e]);
-      }
-      m = fmaxf(m, snap_dpp<0x128>(m));
-      m = fmaxf(m, snap_dpp<0x124>(m));
-      m = fmaxf(m, snap_dpp<0x122>(m));
-      m = fmaxf(m, snap_dpp<0x121>(m));
-      float sum = 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sum += __expf(x[e] - m);
-      sum += snap_dpp<0x128>(sum);
-      sum += snap_dpp<0x124>(sum);
-      sum += snap_dpp<0x122>(sum);
-      sum += snap_dpp<0x121>(sum);
-      if (live) {
-        const f32x4 o = f32x4{x[0] * wrow, x[1] * wrow, x[2] * wrow, x[3] * wrow};
-        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(sim + row * XY + cell0 + c4));
-      }
+      const SimRow r = sim_staged_row(p, sub, b, Nq, n0 + 32 * ti, row_weight, rnv);
+      const SimRowStats e = sim_row_stats<false, CLIP ? 1 : 0>(&st[r.rr][c4], 0, scale, c4, SIM_CH);
+      if (r.live) sim_row_store<false>(e.x, r.wrow, sim + r.row * XY + cell0 + c4, c4, SIM_CH, XY);
       if ((lane & 15) == 0) {
-        sstat[32 * ti + rr][2 * wave] = m;
-        sstat[32 * ti + rr][2 * wave + 1] = sum;
+        sstat[32 * ti + r.rr][2 * wave] = e.m;
+        sstat[32 * ti + r.rr][2 * wave + 1] = e.sum;
       }
     }
   }
@@ -656,11 +599,96 @@ __device__ __forceinline__ float wave_scan_incl(float v, int lane) {
   return v;
 }
 
-// one wave per (b, n): the row maximum M and, per lane l, the inclusive prefix over lanes of
-// the mass of lane l's chunk range (w_c = s_c * exp(m_c - M)) -- exactly the quantities the
-// sampler used to rebuild per SAMPLE (2 passes over the row's statistics, 2 x cpl expf, a
-// wave max and a wave scan).  ~34 samples share a row at C2; with this table a sample reads 64
-// floats and only the selected lane re-evaluates its own chunks.  Bit-identical samples.
+// ---- the steps of one draw, shared by both sampler kernels (and the prefix table's builder) ----
+// All wave-uniform except lane_prefix / pick_lane / pick_cell_store, which run across the 64 lanes.
+
+// (u1, u2) of sample s of scene b: read from `uniforms` or drawn from Philox(seed; s, b).  A dead
+// slot (!live: the NQ-per-wave kernel's tail) reads nothing.
+__device__ __forceinline__ void draw_uniforms(const float* __restrict__ uniforms, int b, int S, int s,
+                                              uint64_t seed, bool live, float& u1, float& u2) {
+  if (uniforms) {
+    u1 = live ? uniforms[((int64_t)b * S + s) * 2 + 0] : 0.f;
+    u2 = live ? uniforms[((int64_t)b * S + s) * 2 + 1] : 0.f;
+  } else {
+    uint32_t rnd[4];
+    philox4x32_10((uint32_t)s, (uint32_t)b, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+    u1 = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
+    u2 = (float)(rnd[1] >> 8) * (1.0f / 16777216.0f);
+  }
+}
+
+// the query row of a draw: uniform over the rows, or -- rows carrying the confidence weights as
+// mass (bev_localizer.py:165-168) -- the first n whose inclusive CDF exceeds u1 * total
+// (wave-uniform binary search)
+__device__ __forceinline__ int pick_row(const float* __restrict__ row_cdf, int b, int Nq, float u1) {
+  int n;
+  if (row_cdf) {
+    const float* cdf = row_cdf + (int64_t)b * Nq;
+    const float tgt = u1 * cdf[Nq - 1];
+    int lo = 0, hi = Nq - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (cdf[mid] > tgt) hi = mid; else lo = mid + 1;
+    }
+    n = lo;
+  } else {
+    n = min((int)(u1 * (float)Nq), Nq - 1);
+  }
+  return __builtin_amdgcn_readfirstlane(n);
+}
+
+// level 1 of a row with chunk statistics st[NC][2]: lane l owns the contiguous chunk range
+// [cb, ce).  M = the row maximum, local = the mass of the lane's range (w_c = s_c * exp(m_c - M));
+// returns the inclusive prefix of `local` over the lanes.
+__device__ __forceinline__ float lane_prefix(const float* __restrict__ st, int cb, int ce, int lane,
+                                             float& M, float& local) {
+  M = -INFINITY;
+  for (int c = cb; c < ce; ++c) M = fmaxf(M, st[2 * c]);
+  M = wave_max(M);
+  local = 0.f;
+  for (int c = cb; c < ce; ++c) local += st[2 * c + 1] * __expf(st[2 * c] - M);
+  return wave_scan_incl(local, lane);
+}
+
+// the first lane whose inclusive prefix exceeds the target (rounding: else the last non-empty lane)
+__device__ __forceinline__ int pick_lane(float incl, float target, bool nonempty) {
+  const unsigned long long bal = __ballot(incl > target && nonempty);
+  int L;
+  if (bal) {
+    L = __ffsll((long long)bal) - 1;
+  } else {
+    const unsigned long long ne = __ballot(nonempty);
+    L = 63 - __clzll((long long)ne);
+  }
+  return __builtin_amdgcn_readfirstlane(L);
+}
+
+// level 2: e = the lane's cell mass relative to the chunk maximum (0 for !cvalid); the first valid
+// cell of chunk `cstar` whose inclusive prefix exceeds resid (else the last valid one) is the draw.
+// Lane 0 writes corr[b, s] = (n, i, j) if `write`.
+__device__ __forceinline__ void pick_cell_store(float e, bool cvalid, float resid, int lane, int cstar,
+                                                int n, int Y, bool write, int32_t* __restrict__ o) {
+  const float ci = wave_scan_incl(e, lane);
+  const unsigned long long b2 = __ballot(cvalid && ci > resid);
+  int pick;
+  if (b2) {
+    pick = __ffsll((long long)b2) - 1;
+  } else {
+    const unsigned long long nv = __ballot(cvalid);
+    pick = 63 - __clzll((long long)nv);
+  }
+  if (lane == 0 && write) {
+    const int c = cstar * SIM_CH + pick;
+    o[0] = n;
+    o[1] = c / Y;
+    o[2] = c - (c / Y) * Y;
+  }
+}
+
+// one wave per (b, n): lane_prefix of the row, stored -- exactly the quantities the table-free
+// sampler rebuilds per SAMPLE (2 passes over the row's statistics, 2 x cpl expf, a wave max and a
+// wave scan).  ~34 samples share a row at C2; with this table a sample reads 64 floats and only the
+// selected lane re-evaluates its own chunks.  Bit-identical samples.
 __global__ __launch_bounds__(256) void chunk_prefix_kernel(const float* __restrict__ stats,
                                                            int64_t rows, int NC,
                                                            float* __restrict__ lane_incl,
@@ -668,15 +696,10 @@ __global__ __launch_bounds__(256) void chunk_prefix_kernel(const float* __restri
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const float* st = stats + row * NC * 2;
   const int cpl = (NC + 63) / 64;
   const int cb = lane * cpl, ce = min(cb + cpl, NC);
-  float M = -INFINITY;
-  for (int c = cb; c < ce; ++c) M = fmaxf(M, st[2 * c]);
-  M = wave_max(M);
-  float local = 0.f;
-  for (int c = cb; c < ce; ++c) local += st[2 * c + 1] * __expf(st[2 * c] - M);
-  lane_incl[row * 64 + lane] = wave_scan_incl(local, lane);
+  float M, local;
+  lane_incl[row * 64 + lane] = lane_prefix(stats + row * NC * 2, cb, ce, lane, M, local);
   if (lane == 0) rowmax[row] = M;
 }
 
@@ -698,31 +721,8 @@ __global__ __launch_bounds__(256) void ransac_sample_kernel(
   const int XY = X * Y;
   const int NC = (XY + SIM_CH - 1) / SIM_CH;
   float u1, u2;
-  if (uniforms) {
-    u1 = uniforms[((int64_t)b * S + s) * 2 + 0];
-    u2 = uniforms[((int64_t)b * S + s) * 2 + 1];
-  } else {
-    uint32_t rnd[4];
-    philox4x32_10((uint32_t)s, (uint32_t)b, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
-    u1 = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
-    u2 = (float)(rnd[1] >> 8) * (1.0f / 16777216.0f);
-  }
-  int n;
-  if (row_cdf) {
-    // rows carry the confidence weights as mass (bev_localizer.py:165-168): first n whose
-    // inclusive CDF exceeds u1 * total (wave-uniform binary search)
-    const float* cdf = row_cdf + (int64_t)b * Nq;
-    const float tgt = u1 * cdf[Nq - 1];
-    int lo = 0, hi = Nq - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (cdf[mid] > tgt) hi = mid; else lo = mid + 1;
-    }
-    n = lo;
-  } else {
-    n = min((int)(u1 * (float)Nq), Nq - 1);
-  }
-  n = __builtin_amdgcn_readfirstlane(n);
+  draw_uniforms(uniforms, b, S, s, seed, true, u1, u2);
+  const int n = pick_row(row_cdf, b, Nq, u1);
   const int64_t row = (int64_t)b * Nq + n;
   const float* st = stats + row * NC * 2;
 
@@ -735,26 +735,14 @@ __global__ __launch_bounds__(256) void ransac_sample_kernel(
     M = rowmax[row];
     incl = lane_incl[row * 64 + lane];
   } else {
-    M = -INFINITY;
-    for (int c = cb; c < ce; ++c) M = fmaxf(M, st[2 * c]);
-    M = wave_max(M);
-    for (int c = cb; c < ce; ++c) local += st[2 * c + 1] * __expf(st[2 * c] - M);
-    incl = wave_scan_incl(local, lane);
+    incl = lane_prefix(st, cb, ce, lane, M, local);
   }
   const float total = __shfl(incl, 63, 64);
   const float target = u2 * total;
-  unsigned long long bal = __ballot(incl > target && ce > cb);
-  int L;
-  if (bal) {
-    L = __ffsll((long long)bal) - 1;
-  } else {  // rounding: fall back to the last non-empty lane
-    const unsigned long long ne = __ballot(ce > cb);
-    L = 63 - __clzll((long long)ne);
-  }
+  const int L = pick_lane(incl, target, ce > cb);
   // the chunks of lane L: lane i evaluates the mass of chunk cbL + i (one exp per lane, side by
   // side), then the walk runs over those values in the same order and with the same additions as
   // a serial walk by lane L would
-  L = __builtin_amdgcn_readfirstlane(L);
   const int cbL = L * cpl, ceL = min(cbL + cpl, NC);
   const int nL = ceL - cbL;                                 // 1 .. cpl chunks (uniform)
   const float inclL = __shfl(incl, L, 64);
@@ -815,22 +803,7 @@ __global__ __launch_bounds__(256) void ransac_sample_kernel(
     x *= scale;
     e = __expf(x - mc);
   }
-  const float ci = wave_scan_incl(e, lane);
-  unsigned long long b2 = __ballot(cvalid && ci > resid);
-  int pick;
-  if (b2) {
-    pick = __ffsll((long long)b2) - 1;
-  } else {
-    const unsigned long long nv = __ballot(cvalid);
-    pick = 63 - __clzll((long long)nv);
-  }
-  if (lane == 0) {
-    const int c = cstar * SIM_CH + pick;
-    int32_t* o = corr + ((int64_t)b * S + s) * 3;
-    o[0] = n;
-    o[1] = c / Y;
-    o[2] = c - (c / Y) * Y;
-  }
+  pick_cell_store(e, cvalid, resid, lane, cstar, n, Y, true, corr + ((int64_t)b * S + s) * 3);
 }
 
 // The same draw for the common configuration (per-row prefix table + chunk scores read from sim),
@@ -838,8 +811,8 @@ __global__ __launch_bounds__(256) void ransac_sample_kernel(
 // trips (row table -> chunk statistics -> the chunk's 64 scores) and ~450 instructions: with one
 // per wave the kernel ran at the pace of those round trips (32 waves per CU / ~5 us each = the
 // measured 0.8 ms for 1.28 M correspondences at C2).  Here the NQ chains of a wave are issued
-// phase by phase, so each round trip serves NQ correspondences.  Same arithmetic per
-// correspondence, in the same order: identical samples.
+// phase by phase, so each round trip serves NQ correspondences.  Every step is the piece
+// ransac_sample_kernel calls, and the walk adds in the same order: identical samples.
 template <int NQ>
 __global__ __launch_bounds__(256) void ransac_sample_fast_kernel(
     const float* __restrict__ stats, int Nq, int X, int Y, int S, uint64_t seed,
@@ -860,31 +833,10 @@ __global__ __launch_bounds__(256) void ransac_sample_fast_kernel(
   float u2[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
-    const int s = s0 + q;
-    live[q] = s < S;
+    live[q] = s0 + q < S;
     float u1;
-    if (uniforms) {
-      u1 = live[q] ? uniforms[((int64_t)b * S + s) * 2 + 0] : 0.f;
-      u2[q] = live[q] ? uniforms[((int64_t)b * S + s) * 2 + 1] : 0.f;
-    } else {
-      uint32_t rnd[4];
-      philox4x32_10((uint32_t)s, (uint32_t)b, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
-      u1 = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
-      u2[q] = (float)(rnd[1] >> 8) * (1.0f / 16777216.0f);
-    }
-    if (row_cdf) {
-      const float* cdf = row_cdf + (int64_t)b * Nq;
-      const float tgt = u1 * cdf[Nq - 1];
-      int lo = 0, hi = Nq - 1;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cdf[mid] > tgt) hi = mid; else lo = mid + 1;
-      }
-      n[q] = lo;
-    } else {
-      n[q] = min((int)(u1 * (float)Nq), Nq - 1);
-    }
-    n[q] = __builtin_amdgcn_readfirstlane(n[q]);
+    draw_uniforms(uniforms, b, S, s0 + q, seed, live[q], u1, u2[q]);
+    n[q] = pick_row(row_cdf, b, Nq, u1);
   }
   // round trip 1: the row's maximum, its per-lane inclusive prefix, its un-scale factor
   float M[NQ], incl[NQ], ru[NQ];
@@ -902,15 +854,7 @@ __global__ __launch_bounds__(256) void ransac_sample_fast_kernel(
   for (int q = 0; q < NQ; ++q) {
     const float total = __shfl(incl[q], 63, 64);
     target[q] = u2[q] * total;
-    const unsigned long long bal = __ballot(incl[q] > target[q] && ce > cb);
-    int L;
-    if (bal) {
-      L = __ffsll((long long)bal) - 1;
-    } else {
-      const unsigned long long ne = __ballot(ce > cb);
-      L = 63 - __clzll((long long)ne);
-    }
-    L = __builtin_amdgcn_readfirstlane(L);
+    const int L = pick_lane(incl[q], target[q], ce > cb);
     cbL[q] = L * cpl;
     nL[q] = min(cbL[q] + cpl, NC) - cbL[q];
     inclL[q] = __shfl(incl[q], L, 64);
@@ -952,25 +896,10 @@ __global__ __launch_bounds__(256) void ransac_sample_fast_kernel(
   }
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
-    const int cell = cstar[q] * SIM_CH + lane;
-    const bool cvalid = cell < XY;
+    const bool cvalid = cstar[q] * SIM_CH + lane < XY;
     const float e = cvalid ? __expf(x[q] * ru[q] - mc[q]) : 0.f;
-    const float ci = wave_scan_incl(e, lane);
-    const unsigned long long b2 = __ballot(cvalid && ci > resid[q]);
-    int pick;
-    if (b2) {
-      pick = __ffsll((long long)b2) - 1;
-    } else {
-      const unsigned long long nv = __ballot(cvalid);
-      pick = 63 - __clzll((long long)nv);
-    }
-    if (lane == 0 && live[q]) {
-      const int c = cstar[q] * SIM_CH + pick;
-      int32_t* o = corr + ((int64_t)b * S + s0 + q) * 3;
-      o[0] = n[q];
-      o[1] = c / Y;
-      o[2] = c - (c / Y) * Y;
-    }
+    pick_cell_store(e, cvalid, resid[q], lane, cstar[q], n[q], Y, live[q],
+                    corr + ((int64_t)b * S + s0 + q) * 3);
   }
 }
 
@@ -1036,13 +965,11 @@ constexpr int PS_LDS_FLOATS = 24 * 1024;  // 96 KiB plane / band buffer
 
 struct ScoreArgs {
   const float* sim;
-  const float* poses;
   const float* q_xy;
   const uint8_t* valid_q;
   const uint8_t* map_valid;
-  int B, Nq, X, Y, P;
-  float cell;
-  int mask_oob;
+  int Nq, X, Y, P;
+  float cell;      // (pose_score_kernel only: its table is in metres)
   int points_per_chunk;
   int RB, NB;      // rows per band, number of bands
   float* partial;  // [B, NCH, P]
@@ -1075,6 +1002,33 @@ __global__ void pose_table_cells_kernel(const float* __restrict__ poses, int64_t
   reinterpret_cast<f32x4*>(table)[i] = t;
 }
 
+// ---- pieces shared by the scoring kernels -------------------------------------------------------
+// the thread's PPT poses (slot k = pose p_base + k * PS_THREADS + tid) from the pose table, sums at 0.
+// Out-of-range slots score pose P-1 again; only the final store is guarded.
+template <int PPT>
+__device__ __forceinline__ void score_load_poses(const ScoreArgs& a, int b, int p_base, int tid,
+                                                 f32x2 (&pcs)[PPT], f32x2 (&pt)[PPT],
+                                                 float (&acc)[PPT]) {
+#pragma unroll
+  for (int k = 0; k < PPT; ++k) {
+    const int p = p_base + k * PS_THREADS + tid;
+    acc[k] = 0.f;
+    const f32x4 t = reinterpret_cast<const f32x4*>(a.table)[(int64_t)b * a.P + min(p, a.P - 1)];
+    pcs[k] = f32x2{t[0], t[1]};
+    pt[k] = f32x2{t[2], t[3]};
+  }
+}
+// ... and their sums over the point chunk into partial[b, chunk, p]
+template <int PPT>
+__device__ __forceinline__ void score_store_partial(const ScoreArgs& a, int b, int NCH, int chunk,
+                                                    int p_base, int tid, const float (&acc)[PPT]) {
+#pragma unroll
+  for (int k = 0; k < PPT; ++k) {
+    const int p = p_base + k * PS_THREADS + tid;
+    if (p < a.P) a.partial[((int64_t)b * NCH + chunk) * a.P + p] = acc[k];
+  }
+}
+
 template <int PPT, bool MASK, bool BANDS>
 __global__ __launch_bounds__(PS_THREADS) void pose_score_kernel(const ScoreArgs a) {
   extern __shared__ float plane[];
@@ -1085,17 +1039,9 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_kernel(const ScoreArgs 
   const int NCH = gridDim.y;
   const int p_base = blockIdx.x * (PS_THREADS * PPT);
   const int tid = threadIdx.x;
-  float pc[PPT], ps[PPT], ptx[PPT], pty[PPT], acc[PPT];
-  bool pok[PPT];
-#pragma unroll
-  for (int k = 0; k < PPT; ++k) {
-    const int p = p_base + k * PS_THREADS + tid;
-    pok[k] = p < a.P;
-    acc[k] = 0.f;
-    // out-of-range slots score pose P-1 again; only the final store is guarded.
-    const f32x4 t = reinterpret_cast<const f32x4*>(a.table)[(int64_t)b * a.P + min(p, a.P - 1)];
-    pc[k] = t[0]; ps[k] = t[1]; ptx[k] = t[2]; pty[k] = t[3];
-  }
+  f32x2 pcs[PPT], pt[PPT];   // (cos, sin), (tx, ty): metres (pose_table_kernel)
+  float acc[PPT];
+  score_load_poses<PPT>(a, b, p_base, tid, pcs, pt, acc);
   const int n_begin = chunk * a.points_per_chunk;
   const int n_end = min(n_begin + a.points_per_chunk, a.Nq);
   const float Xf = (float)a.X, Yf = (float)a.Y;
@@ -1124,9 +1070,11 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_kernel(const ScoreArgs 
       __syncthreads();
 #pragma unroll
       for (int k = 0; k < PPT; ++k) {
-        // (j_t_i @ xy) / cell_size  -- Transform2D.transform, geometry.py:137-139
-        const float xm = (pc[k] * qx - ps[k] * qy) + ptx[k];
-        const float ym = (ps[k] * qx + pc[k] * qy) + pty[k];
+        // (j_t_i @ xy) / cell_size  -- Transform2D.transform, geometry.py:137-139.  This kernel keeps
+        // the reference's own sequence (divide by the cell size, four taps, four products); the
+        // LDS-DMA kernels below use score_sample / score_lerp on the cell-unit table instead.
+        const float xm = (pcs[k].x * qx - pcs[k].y * qy) + pt[k].x;
+        const float ym = (pcs[k].y * qx + pcs[k].x * qy) + pt[k].y;
         const float u = xm / a.cell, v = ym / a.cell;
         const float cu = u - 0.5f, cv = v - 0.5f;
         const float fu = floorf(cu), fv = floorf(cv);
@@ -1156,19 +1104,19 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_kernel(const ScoreArgs 
       }
     }
   }
-#pragma unroll
-  for (int k = 0; k < PPT; ++k) {
-    const int p = p_base + k * PS_THREADS + tid;
-    if (pok[k]) a.partial[((int64_t)b * NCH + chunk) * a.P + p] = acc[k];
-  }
+  score_store_partial<PPT>(a, b, NCH, chunk, p_base, tid, acc);
 }
 
-// Double-buffered variant for planes that fit twice in LDS (X*Y*4 <= 64 KiB, the
-// 128x128 map): the plane of the NEXT valid query point is streamed HBM -> LDS by
-// the LDS-DMA path (global_load_lds_dwordx4: no VGPR round trip, wave-uniform LDS
-// base + lane*16, i.e. a linear copy) while every thread gathers from the current
-// one; one barrier per point.  This keeps the HBM stream busy during the gather
-// phase -- the kernel's roofline is the single read of sim.
+// ---- the LDS-DMA scoring kernels ----------------------------------------------------------------
+// Three kernels stream a point's scores HBM -> LDS by the LDS-DMA path (global_load_lds_dwordx4: no
+// VGPR round trip, wave-uniform LDS base + lane*16, i.e. a linear copy) into one of two buffers
+// while every thread gathers from the other; one barrier per buffer.  They differ in WHAT is staged
+// -- the whole plane (pose_score_db_kernel: X*(Y+4)*4 <= 68 KiB, the 128x128 map), row bands of it
+// (pose_score_band_db_kernel) or a window around a centre pose (pose_score_window_kernel) -- and in
+// how the per-pose work is scheduled around the barrier.  The sample itself -- coordinates from the
+// cell-unit pose table, clamp, floor, weights, the 2x2 gather and the two lerps -- and the order
+// of the sums (the chunk's valid points ascending; chunks ascending in the reduce pass) are the
+// pieces below in all three: that is why their scores are the same bits.
 
 __device__ __forceinline__ float uniform_f(float v) {
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
@@ -1177,9 +1125,99 @@ constexpr int PS_DB_MAX_POINTS = 1024;  // valid points of one chunk staged in L
 constexpr int PS_DB_ROUNDS = 5;           // 16-byte DMA chunks per thread per plane (max)
 constexpr int PS_DB_PLANE_BYTES = PS_DB_ROUNDS * PS_THREADS * 16 - 12 * 1024;  // 68 KiB padded plane
 
-// YC: compile-time row length (0 = run time).  The 2x2 footprint is two ds_read2_b32 off
-// ONE address (offsets {0,1} and {YC,YC+1}); each lands as a (col j, col j+1) register
-// pair, so the coordinate and row-lerp arithmetic is packed f32 (v_pk_fma/v_pk_add).
+// The chunk's valid points [n_begin, n_end), compacted (ascending) into LDS up front by wave 0: the
+// staging loop then touches global memory ONLY through the LDS-DMA stream, so the vmcnt(0) at the
+// top of an iteration waits for exactly the buffer it is about to read and the next one's DMA
+// flies under the arithmetic (any other global load inside the loop would sit behind the in-order
+// vmcnt and serialise load and compute).  The caller's barrier publishes the list.
+__device__ __forceinline__ void score_point_list(const ScoreArgs& a, int b, int n_begin, int n_end,
+                                                 int tid, int* pt_n, float* pt_x, float* pt_y,
+                                                 int* pt_count) {
+  if (tid >= 64) return;
+  const uint8_t* vq = a.valid_q + (int64_t)b * a.Nq;
+  int count = 0;
+  for (int n0 = n_begin; n0 < n_end; n0 += 64) {
+    const int n = n0 + tid;
+    const bool v = n < n_end && vq[n] != 0;
+    const unsigned long long m = __ballot(v);
+    if (v) {
+      const int slot = count + __popcll(m & ((1ull << tid) - 1ull));
+      pt_n[slot] = n;
+      pt_x[slot] = a.q_xy[((int64_t)b * a.Nq + n) * 2 + 0];
+      pt_y[slot] = a.q_xy[((int64_t)b * a.Nq + n) * 2 + 1];
+    }
+    count += __popcll(m);
+  }
+  if (tid == 0) *pt_count = count;
+}
+
+// LDS rows are padded by one 16-byte chunk (pitch S = row + 4 floats): bank(i, j) = (4 i + j) mod
+// 32, so samples clamped to the first / last COLUMN (out-of-map poses: a large share of RANSAC
+// hypotheses) spread over 8 banks instead of all hitting one.  The DMA writes LDS contiguously but
+// each lane may fetch any global chunk, so the pad costs one duplicate chunk per row and no extra
+// instructions.  goff[k] = float offset, from the staged region's first cell, of the 16-byte chunk
+// this thread fetches in DMA round k (region-invariant).  CRP = chunks per padded row, Y = the
+// global row pitch; chunks past `clamp_to` fetch chunk clamp_to (never issued: see score_dma_issue).
+template <int ROUNDS>
+__device__ __forceinline__ void score_dma_offsets(int tid, int CRP, int Y, int clamp_to,
+                                                  int (&goff)[ROUNDS]) {
+#pragma unroll
+  for (int k = 0; k < ROUNDS; ++k) {
+    const int c = min(k * PS_THREADS + tid, clamp_to);
+    const int row = c / CRP;
+    goff[k] = row * Y + 4 * min(c - row * CRP, CRP - 2);
+  }
+}
+// the first `nchunks` chunks of a region: src = its first cell, dst = the LDS buffer
+template <int ROUNDS>
+__device__ __forceinline__ void score_dma_issue(const float* src, float* dst,
+                                                const int (&goff)[ROUNDS], int nchunks, int tid) {
+#pragma unroll
+  for (int k = 0; k < ROUNDS; ++k) {
+    const int c = k * PS_THREADS + tid;
+    if (c < nchunks)
+      lds_dma16(src + goff[k], dst + 4 * c);
+  }
+}
+
+// One sample of point (qx, qy) under pose (pcs, pt), qx2 = (qx, qx), qyn = (-qy, qy).
+// 'nearest' extension == sampling at the clamped coordinate; the cell is capped at (X-2, Y-2) = lim2
+// (weight 1 there) so the 2x2 footprint always lies inside the plane.
+struct ScoreSample {
+  f32x2 w;   // lerp weights along rows (x) and columns (y)
+  int off;   // the cell's offset in full-plane rows of pitch Sf
+  f32x2 r;   // the unclamped coordinate (mask test)
+};
+__device__ __forceinline__ ScoreSample score_sample(f32x2 pcs, f32x2 pt, f32x2 qx2, f32x2 qyn,
+                                                    f32x2 lim1, f32x2 lim2, float Sf) {
+  ScoreSample o;
+  o.r = __builtin_elementwise_fma(pcs, qx2, __builtin_elementwise_fma(pcs.yx, qyn, pt));
+  const f32x2 c = __builtin_elementwise_min(__builtin_elementwise_max(o.r, f32x2{0.f, 0.f}), lim1);
+  const f32x2 f = __builtin_elementwise_min(f32x2{floorf(c.x), floorf(c.y)}, lim2);
+  o.w = c - f;
+  o.off = (int)fmaf(f.x, Sf, f.y);
+  return o;
+}
+// The 2x2 footprint at q, rows of pitch S: two ds_read2_b32 off ONE address (offsets {0,1} and
+// {S,S+1}); each lands as a (col j, col j+1) register pair, so the row lerp is packed f32.
+struct ScoreTaps { f32x2 s0, s1; };
+__device__ __forceinline__ ScoreTaps score_fetch(const float* q, int S) {
+  ScoreTaps t;
+  t.s0 = f32x2{q[0], q[1]};
+  t.s1 = f32x2{q[S], q[S + 1]};
+  return t;
+}
+__device__ __forceinline__ float score_lerp(const ScoreTaps& tp, f32x2 w) {
+  const f32x2 t = __builtin_elementwise_fma(f32x2{w.x, w.x}, tp.s1 - tp.s0, tp.s0);
+  return fmaf(w.y, t.y - t.x, t.x);
+}
+__device__ __forceinline__ float score_gather(const float* q, int S, f32x2 w) {
+  return score_lerp(score_fetch(q, S), w);
+}
+
+// Whole plane, double-buffered: the plane of the NEXT valid query point streams in while every
+// thread gathers from the current one.  This keeps the HBM stream busy during the gather phase --
+// the kernel's roofline is the single read of sim.  YC: compile-time row length (0 = run time).
 template <int PPT, bool MASK, int YC>
 __global__ __launch_bounds__(PS_THREADS) void pose_score_db_kernel(const ScoreArgs a) {
   extern __shared__ float plane[];
@@ -1190,109 +1228,44 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_db_kernel(const ScoreAr
   const int tid = threadIdx.x;
   const int Y = YC ? YC : a.Y;
   const int XY = a.X * Y;
-  // LDS rows are padded by one 16-byte chunk (stride S = Y + 4 floats): bank(i, j) =
-  // (4 i + j) mod 32, so samples clamped to the first / last COLUMN (out-of-map poses:
-  // a large share of RANSAC hypotheses) spread over 8 banks instead of all hitting one.
-  // The DMA writes LDS contiguously but each lane may fetch any global chunk, so the pad
-  // costs one duplicate chunk per row and no extra instructions.
-  const int S = Y + 4;
+  const int S = Y + 4;                     // padded LDS row pitch
   const int CRP = (Y >> 2) + 1;            // chunks per padded row
   const int nchunks = a.X * CRP;
   const int PLANE = a.X * S;               // floats per LDS plane
   f32x2 pcs[PPT], pt[PPT];
   float acc[PPT];
-#pragma unroll
-  for (int k = 0; k < PPT; ++k) {
-    const int p = p_base + k * PS_THREADS + tid;
-    acc[k] = 0.f;
-    const f32x4 t = reinterpret_cast<const f32x4*>(a.table)[(int64_t)b * a.P + min(p, a.P - 1)];
-    pcs[k] = f32x2{t[0], t[1]};
-    pt[k] = f32x2{t[2], t[3]};
-  }
+  score_load_poses<PPT>(a, b, p_base, tid, pcs, pt, acc);
   const int n_begin = chunk * a.points_per_chunk;
   const int n_end = min(n_begin + a.points_per_chunk, a.Nq);
   const float Xf = (float)a.X, Yf = (float)Y;
   const float Sf = (float)S;
-  const f32x2 lim1 = {Xf - 1.f, Yf - 1.f}, lim2 = {Xf - 2.f, Yf - 2.f}, zero2 = {0.f, 0.f};
-  const uint8_t* vq = a.valid_q + (int64_t)b * a.Nq;
+  const f32x2 lim1 = {Xf - 1.f, Yf - 1.f}, lim2 = {Xf - 2.f, Yf - 2.f};
   const uint8_t* mvalid = a.map_valid ? a.map_valid + (int64_t)b * XY : nullptr;
 
-  // global float offset of the chunk this thread fetches in DMA round k (plane-invariant)
   int goff[PS_DB_ROUNDS];
-#pragma unroll
-  for (int k = 0; k < PS_DB_ROUNDS; ++k) {
-    const int c = min(k * PS_THREADS + tid, nchunks - 1);
-    const int row = c / CRP;
-    goff[k] = row * Y + 4 * min(c - row * CRP, CRP - 2);
-  }
+  score_dma_offsets<PS_DB_ROUNDS>(tid, CRP, Y, nchunks - 1, goff);
   auto issue = [&](int n, int buf) {
-    const float* src = a.sim + ((int64_t)b * a.Nq + n) * XY;
-    float* dst = plane + buf * PLANE;
-#pragma unroll
-    for (int k = 0; k < PS_DB_ROUNDS; ++k) {
-      const int c = k * PS_THREADS + tid;
-      if (c < nchunks)
-        lds_dma16(src + goff[k], dst + 4 * c);
-    }
+    score_dma_issue<PS_DB_ROUNDS>(a.sim + ((int64_t)b * a.Nq + n) * XY, plane + buf * PLANE, goff,
+                                  nchunks, tid);
   };
-  // The chunk's valid points, compacted (ascending) into LDS up front: the plane loop
-  // then touches global memory ONLY through the LDS-DMA stream, so the vmcnt(0) at the
-  // top of an iteration waits for exactly the plane it is about to read and the next
-  // plane's DMA flies under the arithmetic (any other global load inside the loop would
-  // sit behind the in-order vmcnt and serialise load and compute).
   __shared__ int pt_n[PS_DB_MAX_POINTS];
   __shared__ float pt_x[PS_DB_MAX_POINTS], pt_y[PS_DB_MAX_POINTS];
   __shared__ int pt_count;
-  if (tid < 64) {
-    int count = 0;
-    for (int n0 = n_begin; n0 < n_end; n0 += 64) {
-      const int n = n0 + tid;
-      const bool v = n < n_end && vq[n] != 0;
-      const unsigned long long m = __ballot(v);
-      if (v) {
-        const int slot = count + __popcll(m & ((1ull << tid) - 1ull));
-        pt_n[slot] = n;
-        pt_x[slot] = a.q_xy[((int64_t)b * a.Nq + n) * 2 + 0];
-        pt_y[slot] = a.q_xy[((int64_t)b * a.Nq + n) * 2 + 1];
-      }
-      count += __popcll(m);
-    }
-    if (tid == 0) pt_count = count;
-  }
+  score_point_list(a, b, n_begin, n_end, tid, pt_n, pt_x, pt_y, &pt_count);
   __syncthreads();
   const int count = pt_count;
   int buf = 0;
   if (count > 0) issue(pt_n[0], 0);
 
-  // One sample = coords() (pure VALU, needs only the pose and the point) + gather()
-  // (two ds_read2_b32 + lerp).  The loop is software-pipelined across the barrier: the
-  // coordinates of the first G poses for plane i+1 are computed at the end of iteration
-  // i, so every wave fires LDS reads right after the barrier instead of all 16 waves
-  // doing address arithmetic while the LDS sits idle.
-  struct Coord { f32x2 w; int off; f32x2 r; };
+  // One sample = coords() (score_sample: pure VALU, needs only the pose and the point) + fetch +
+  // blend.  The loop is software-pipelined across the barrier: the coordinates of the first G
+  // poses for plane i+1 are computed at the end of iteration i, so every wave fires LDS reads
+  // right after the barrier instead of all 16 waves doing address arithmetic while the LDS sits idle.
   auto coords = [&](int k, float qx, float qy) {
-    // 'nearest' extension == sampling at the clamped coordinate; the cell is capped at
-    // X-2 (weight 1 there) so the 2x2 footprint always lies inside the plane.
-    const f32x2 qx2 = {qx, qx}, qyn = {-qy, qy};
-    Coord o;
-    o.r = __builtin_elementwise_fma(pcs[k], qx2, __builtin_elementwise_fma(pcs[k].yx, qyn, pt[k]));
-    const f32x2 c = __builtin_elementwise_min(__builtin_elementwise_max(o.r, zero2), lim1);
-    const f32x2 f = __builtin_elementwise_min(f32x2{floorf(c.x), floorf(c.y)}, lim2);
-    o.w = c - f;
-    o.off = (int)fmaf(f.x, Sf, f.y);
-    return o;
+    return score_sample(pcs[k], pt[k], f32x2{qx, qx}, f32x2{-qy, qy}, lim1, lim2, Sf);
   };
-  struct Taps { f32x2 s0, s1; };
-  auto fetch = [&](const Coord& o, const float* pl) {
-    const float* q = pl + o.off;
-    Taps t;
-    t.s0 = f32x2{q[0], q[1]};  // one ds_read2_b32 each: (row i, cols j,j+1)
-    t.s1 = f32x2{q[S], q[S + 1]};
-    return t;
-  };
-  auto blend = [&](int k, const Coord& o, const Taps& tp) {
-    const f32x2 t = __builtin_elementwise_fma(f32x2{o.w.x, o.w.x}, tp.s1 - tp.s0, tp.s0);
-    const float val = fmaf(o.w.y, t.y - t.x, t.x);
+  auto blend = [&](int k, const ScoreSample& o, const ScoreTaps& tp) {
+    const float val = score_lerp(tp, o.w);
     bool ok = true;
     if (MASK) {
       const float u = o.r.x + 0.5f, v = o.r.y + 0.5f;
@@ -1308,7 +1281,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_db_kernel(const ScoreAr
     acc[k] += ok ? val : 0.f;
   };
   constexpr int G = PPT / 2;
-  Coord pre[G];
+  ScoreSample pre[G];
   {
     const float qx = count > 0 ? pt_x[0] : 0.f, qy = count > 0 ? pt_y[0] : 0.f;
 #pragma unroll
@@ -1325,10 +1298,10 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_db_kernel(const ScoreAr
     // group 0 reads go out back to back (addresses were ready before the barrier); group
     // 1's coordinates are computed under their latency.  Same again for group 1 with the
     // next plane's group-0 coordinates as the cover.
-    Taps tp[G];
-    Coord c1[PPT - G];
+    ScoreTaps tp[G];
+    ScoreSample c1[PPT - G];
 #pragma unroll
-    for (int k = 0; k < G; ++k) tp[k] = fetch(pre[k], pl);
+    for (int k = 0; k < G; ++k) tp[k] = score_fetch(pl + pre[k].off, S);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int k = G; k < PPT; ++k) c1[k - G] = coords(k, qx, qy);
@@ -1337,7 +1310,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_db_kernel(const ScoreAr
     for (int k = 0; k < G; ++k) blend(k, pre[k], tp[k]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int k = G; k < PPT; ++k) tp[k - G] = fetch(c1[k - G], pl);
+    for (int k = G; k < PPT; ++k) tp[k - G] = score_fetch(pl + c1[k - G].off, S);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int k = 0; k < G; ++k) pre[k] = coords(k, nqx, nqy);
@@ -1346,19 +1319,14 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_db_kernel(const ScoreAr
     for (int k = G; k < PPT; ++k) blend(k, c1[k - G], tp[k - G]);
     buf ^= 1;
   }
-#pragma unroll
-  for (int k = 0; k < PPT; ++k) {
-    const int p = p_base + k * PS_THREADS + tid;
-    if (p < a.P) a.partial[((int64_t)b * NCH + chunk) * a.P + p] = acc[k];
-  }
+  score_store_partial<PPT>(a, b, NCH, chunk, p_base, tid, acc);
 }
 
 // Banded variant for planes that do not fit LDS (256x256 maps of the eval path, BASELINE
-// configs[3]): the plane of a point streams through LDS in NB bands of RB rows (+1 halo row)
-// with the same LDS-DMA double buffering, padded rows and LDS point list as the whole-plane
-// kernel; the clamped coordinates / weights of the thread's 10 poses are computed once per
-// point and kept in registers across its bands, every band then costs a membership test, two
-// ds_read2_b32 and the lerp.  No validity mask (MASK launches take the older band kernel).
+// configs[3]): the plane of a point streams through LDS in NB bands of RB rows (+1 halo row);
+// the samples of the thread's 10 poses (score_sample) are computed once per point and kept in
+// registers across its bands, every band then costs a membership test and score_gather.  No
+// validity mask (MASK launches take the older band kernel).
 template <int PPT>
 __global__ __launch_bounds__(PS_THREADS) void pose_score_band_db_kernel(const ScoreArgs a) {
   extern __shared__ float plane[];
@@ -1375,82 +1343,43 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_band_db_kernel(const Sc
   const int PLANE = (RB + 1) * S;          // floats per LDS band buffer
   f32x2 pcs[PPT], pt[PPT];
   float acc[PPT];
-#pragma unroll
-  for (int k = 0; k < PPT; ++k) {
-    const int p = p_base + k * PS_THREADS + tid;
-    acc[k] = 0.f;
-    const f32x4 t = reinterpret_cast<const f32x4*>(a.table)[(int64_t)b * a.P + min(p, a.P - 1)];
-    pcs[k] = f32x2{t[0], t[1]};
-    pt[k] = f32x2{t[2], t[3]};
-  }
+  score_load_poses<PPT>(a, b, p_base, tid, pcs, pt, acc);
   const int n_begin = chunk * a.points_per_chunk;
   const int n_end = min(n_begin + a.points_per_chunk, a.Nq);
   const float Xf = (float)a.X, Yf = (float)Y, Sf = (float)S;
-  const f32x2 lim1 = {Xf - 1.f, Yf - 1.f}, lim2 = {Xf - 2.f, Yf - 2.f}, zero2 = {0.f, 0.f};
-  const uint8_t* vq = a.valid_q + (int64_t)b * a.Nq;
+  const f32x2 lim1 = {Xf - 1.f, Yf - 1.f}, lim2 = {Xf - 2.f, Yf - 2.f};
 
-  // chunk -> global float offset inside a band (band-invariant; rows past the band end are
-  // masked by the chunk count of the band)
+  // (band-invariant; rows past the band end are masked by the chunk count of the band)
   int goff[PS_DB_ROUNDS];
-#pragma unroll
-  for (int k = 0; k < PS_DB_ROUNDS; ++k) {
-    const int c = k * PS_THREADS + tid;
-    const int row = c / CRP;
-    goff[k] = row * Y + 4 * min(c - row * CRP, CRP - 2);
-  }
+  score_dma_offsets<PS_DB_ROUNDS>(tid, CRP, Y, INT_MAX, goff);
   auto issue = [&](int n, int band, int buf) {
     const int r0 = band * RB;
     const int rows = min(RB + 1, a.X - r0);
-    const int nchunks = rows * CRP;
-    const float* src = a.sim + ((int64_t)b * a.Nq + n) * XY + (int64_t)r0 * Y;
-    float* dst = plane + buf * PLANE;
-#pragma unroll
-    for (int k = 0; k < PS_DB_ROUNDS; ++k) {
-      const int c = k * PS_THREADS + tid;
-      if (c < nchunks)
-        lds_dma16(src + goff[k], dst + 4 * c);
-    }
+    score_dma_issue<PS_DB_ROUNDS>(a.sim + ((int64_t)b * a.Nq + n) * XY + (int64_t)r0 * Y,
+                                  plane + buf * PLANE, goff, rows * CRP, tid);
   };
   __shared__ int pt_n[PS_DB_MAX_POINTS];
   __shared__ float pt_x[PS_DB_MAX_POINTS], pt_y[PS_DB_MAX_POINTS];
   __shared__ int pt_count;
-  if (tid < 64) {
-    int count = 0;
-    for (int n0 = n_begin; n0 < n_end; n0 += 64) {
-      const int n = n0 + tid;
-      const bool v = n < n_end && vq[n] != 0;
-      const unsigned long long m = __ballot(v);
-      if (v) {
-        const int slot = count + __popcll(m & ((1ull << tid) - 1ull));
-        pt_n[slot] = n;
-        pt_x[slot] = a.q_xy[((int64_t)b * a.Nq + n) * 2 + 0];
-        pt_y[slot] = a.q_xy[((int64_t)b * a.Nq + n) * 2 + 1];
-      }
-      count += __popcll(m);
-    }
-    if (tid == 0) pt_count = count;
-  }
+  score_point_list(a, b, n_begin, n_end, tid, pt_n, pt_x, pt_y, &pt_count);
   __syncthreads();
   const int count = pt_count;
   const int steps = count * NB;            // (point, band) pairs, band fastest
   int buf = 0;
   if (steps > 0) issue(pt_n[0], 0, 0);
-  float wu[PPT], wv[PPT];
+  f32x2 w[PPT];
   int off[PPT];   // cell offset in full-plane padded rows; its row = off / S (fv < Y < S)
   int i = 0, band = 0;
   for (int t = 0; t < steps; ++t) {
     if (band == 0) {
-      // per-point state of the 10 poses: cell row, lerp weights, offset in full-plane rows
+      // per-point state of the 10 poses
       const float qx = uniform_f(pt_x[i]), qy = uniform_f(pt_y[i]);
       const f32x2 qx2 = {qx, qx}, qyn = {-qy, qy};
 #pragma unroll
       for (int k = 0; k < PPT; ++k) {
-        const f32x2 r = __builtin_elementwise_fma(pcs[k], qx2, __builtin_elementwise_fma(pcs[k].yx, qyn, pt[k]));
-        const f32x2 c = __builtin_elementwise_min(__builtin_elementwise_max(r, zero2), lim1);
-        const f32x2 f = __builtin_elementwise_min(f32x2{floorf(c.x), floorf(c.y)}, lim2);
-        wu[k] = c.x - f.x;
-        wv[k] = c.y - f.y;
-        off[k] = (int)fmaf(f.x, Sf, f.y);
+        const ScoreSample o = score_sample(pcs[k], pt[k], qx2, qyn, lim1, lim2, Sf);
+        w[k] = o.w;
+        off[k] = o.off;
       }
     }
     wait_vm<0>();
@@ -1466,21 +1395,13 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_band_db_kernel(const Sc
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
       const bool in = (unsigned)(off[k] - shift) < (unsigned)span;
-      const float* q = pl + (in ? off[k] - shift : 0);
-      const f32x2 s0 = {q[0], q[1]};
-      const f32x2 s1 = {q[S], q[S + 1]};
-      const f32x2 tt = __builtin_elementwise_fma(f32x2{wu[k], wu[k]}, s1 - s0, s0);
-      const float val = fmaf(wv[k], tt.y - tt.x, tt.x);
+      const float val = score_gather(pl + (in ? off[k] - shift : 0), S, w[k]);
       acc[k] += in ? val : 0.f;
     }
     buf ^= 1;
     if (++band == NB) { band = 0; ++i; }
   }
-#pragma unroll
-  for (int k = 0; k < PPT; ++k) {
-    const int p = p_base + k * PS_THREADS + tid;
-    if (p < a.P) a.partial[((int64_t)b * NCH + chunk) * a.P + p] = acc[k];
-  }
+  score_store_partial<PPT>(a, b, NCH, chunk, p_base, tid, acc);
 }
 
 // Windowed variant for pose sets whose samples of a point all fall within `rad` cells of ONE centre
@@ -1489,10 +1410,7 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_band_db_kernel(const Sc
 // every point through LDS once per pose chunk (256 x 256 maps: 262 KB per point and chunk, nine chunks
 // for 68 921 poses = 11 GB per scene); here a point's plane is read as ONE window of <= (2 rad + 3) rows x
 // (2 rad + 6) columns around the centre pose's image of the point (~80 x 84 cells = 27 KB): 0.14 GB per
-// pose chunk.  Arithmetic per sample (coordinates from the same cell-unit pose table, clamp, floor, the
-// two lerps) and the order of the sums (points ascending inside the same point chunks, chunks ascending in
-// the reduce pass) are those of pose_score_band_db_kernel: the scores are the same bits.  No validity
-// mask (MASK launches take the general kernels).
+// pose chunk.  No validity mask (MASK launches take the general kernels).
 struct ScoreWinArgs {
   ScoreArgs s;
   const float* ctable;   // [B, 4] the centre poses as cell-unit affine maps (pose_table_cells_kernel)
@@ -1519,29 +1437,16 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_window_kernel(const Sco
   const int PLANE = WR * S;
   f32x2 pcs[PPT], pt[PPT];
   float acc[PPT];
-#pragma unroll
-  for (int k = 0; k < PPT; ++k) {
-    const int p = p_base + k * PS_THREADS + tid;
-    acc[k] = 0.f;
-    const f32x4 t = reinterpret_cast<const f32x4*>(a.table)[(int64_t)b * a.P + min(p, a.P - 1)];
-    pcs[k] = f32x2{t[0], t[1]};
-    pt[k] = f32x2{t[2], t[3]};
-  }
+  score_load_poses<PPT>(a, b, p_base, tid, pcs, pt, acc);
   const f32x4 ct = reinterpret_cast<const f32x4*>(w.ctable)[b];
   const int n_begin = chunk * a.points_per_chunk;
   const int n_end = min(n_begin + a.points_per_chunk, a.Nq);
   const float Xf = (float)X, Yf = (float)Y, Sf = (float)S;
-  const f32x2 lim1 = {Xf - 1.f, Yf - 1.f}, lim2 = {Xf - 2.f, Yf - 2.f}, zero2 = {0.f, 0.f};
-  const uint8_t* vq = a.valid_q + (int64_t)b * a.Nq;
+  const f32x2 lim1 = {Xf - 1.f, Yf - 1.f}, lim2 = {Xf - 2.f, Yf - 2.f};
 
-  // chunk -> float offset relative to the window's first cell (window-invariant)
+  // (offsets relative to the window's first cell: window-invariant)
   int goff[PS_WIN_ROUNDS];
-#pragma unroll
-  for (int k = 0; k < PS_WIN_ROUNDS; ++k) {
-    const int c = k * PS_THREADS + tid;
-    const int row = c / CRP;
-    goff[k] = row * Y + 4 * min(c - row * CRP, CRP - 2);
-  }
+  score_dma_offsets<PS_WIN_ROUNDS>(tid, CRP, Y, INT_MAX, goff);
   const int nchunks = WR * CRP;
   // first cell (row0, col0) of the window of point (qx, qy): the centre pose's cell minus the radius,
   // one more for the floor, kept inside the plane; col0 % 4 == 0 (16-byte DMA chunks)
@@ -1553,34 +1458,13 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_window_kernel(const Sco
     return make_int2((int)ru, ((int)rv) & ~3);
   };
   auto issue = [&](int n, int2 o, int buf) {
-    const float* src = a.sim + ((int64_t)b * a.Nq + n) * XY + (int64_t)o.x * Y + o.y;
-    float* dst = plane + buf * PLANE;
-#pragma unroll
-    for (int k = 0; k < PS_WIN_ROUNDS; ++k) {
-      const int c = k * PS_THREADS + tid;
-      if (c < nchunks)
-        lds_dma16(src + goff[k], dst + 4 * c);
-    }
+    score_dma_issue<PS_WIN_ROUNDS>(a.sim + ((int64_t)b * a.Nq + n) * XY + (int64_t)o.x * Y + o.y,
+                                   plane + buf * PLANE, goff, nchunks, tid);
   };
   __shared__ int pt_n[PS_DB_MAX_POINTS];
   __shared__ float pt_x[PS_DB_MAX_POINTS], pt_y[PS_DB_MAX_POINTS];
   __shared__ int pt_count;
-  if (tid < 64) {
-    int count = 0;
-    for (int n0 = n_begin; n0 < n_end; n0 += 64) {
-      const int n = n0 + tid;
-      const bool v = n < n_end && vq[n] != 0;
-      const unsigned long long m = __ballot(v);
-      if (v) {
-        const int slot = count + __popcll(m & ((1ull << tid) - 1ull));
-        pt_n[slot] = n;
-        pt_x[slot] = a.q_xy[((int64_t)b * a.Nq + n) * 2 + 0];
-        pt_y[slot] = a.q_xy[((int64_t)b * a.Nq + n) * 2 + 1];
-      }
-      count += __popcll(m);
-    }
-    if (tid == 0) pt_count = count;
-  }
+  score_point_list(a, b, n_begin, n_end, tid, pt_n, pt_x, pt_y, &pt_count);
   __syncthreads();
   const int count = pt_count;
   int buf = 0;
@@ -1604,34 +1488,21 @@ __global__ __launch_bounds__(PS_THREADS) void pose_score_window_kernel(const Sco
     // four poses at a time: coordinates, the eight LDS reads, the lerps (per-pose state stays in 5 registers)
 #pragma unroll
     for (int g = 0; g < PPT; g += 4) {
-      float wu[4], wv[4];
+      f32x2 wt[4];
       const float* q[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int k = g + j;
-        const f32x2 r = __builtin_elementwise_fma(pcs[k], qx2, __builtin_elementwise_fma(pcs[k].yx, qyn, pt[k]));
-        const f32x2 c = __builtin_elementwise_min(__builtin_elementwise_max(r, zero2), lim1);
-        const f32x2 f = __builtin_elementwise_min(f32x2{floorf(c.x), floorf(c.y)}, lim2);
-        wu[j] = c.x - f.x;
-        wv[j] = c.y - f.y;
+        const ScoreSample o = score_sample(pcs[g + j], pt[g + j], qx2, qyn, lim1, lim2, Sf);
+        wt[j] = o.w;
         // (a pose outside the promised radius reads a clamped cell of the window: wrong, never out of bounds)
-        q[j] = pl + min(max((int)fmaf(f.x, Sf, f.y) - obase, 0), off_max);
+        q[j] = pl + min(max(o.off - obase, 0), off_max);
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x2 s0 = {q[j][0], q[j][1]};
-        const f32x2 s1 = {q[j][S], q[j][S + 1]};
-        const f32x2 tt = __builtin_elementwise_fma(f32x2{wu[j], wu[j]}, s1 - s0, s0);
-        acc[g + j] += fmaf(wv[j], tt.y - tt.x, tt.x);
-      }
+      for (int j = 0; j < 4; ++j) acc[g + j] += score_gather(q[j], S, wt[j]);
     }
     buf ^= 1;
   }
-#pragma unroll
-  for (int k = 0; k < PPT; ++k) {
-    const int p = p_base + k * PS_THREADS + tid;
-    if (p < a.P) a.partial[((int64_t)b * NCH + chunk) * a.P + p] = acc[k];
-  }
+  score_store_partial<PPT>(a, b, NCH, chunk, p_base, tid, acc);
 }
 
 __global__ void pose_score_reduce_kernel(const float* __restrict__ partial, int NCH, int P,
@@ -1659,6 +1530,44 @@ inline int score_chunks(int B, int Nq, int pose_chunks) {
 constexpr int PS_PPT = 10;
 constexpr int PS_BAND_PPT = 10;  // the banded kernel keeps per-pose sampling state in registers (128 VGPRs at 10: 20 001 hypotheses = two pose chunks, not three)
 inline int score_pose_chunks(int P) { return (P + PS_THREADS * PS_PPT - 1) / (PS_THREADS * PS_PPT); }
+
+// What both scoring entry points share on the host: the kernel arguments (whole plane as one band),
+// the point chunking -- and so the order of every sum -- and the workspace carved into the pose
+// table (16-byte aligned, first) and the per-chunk partial sums.  Returns the point chunk count.
+inline int score_setup(ScoreArgs& a, const float* sim, const float* q_xy, const uint8_t* valid_q,
+                       const uint8_t* map_valid, int B, int Nq, int X, int Y, int P, float cell_size,
+                       void* workspace) {
+  a.sim = sim; a.q_xy = q_xy; a.valid_q = valid_q; a.map_valid = map_valid;
+  a.Nq = Nq; a.X = X; a.Y = Y; a.P = P;
+  a.cell = cell_size;
+  const int nch = score_chunks(B, Nq, score_pose_chunks(P));
+  a.points_per_chunk = (Nq + nch - 1) / nch;
+  a.RB = X; a.NB = 1;
+  float* table = static_cast<float*>(workspace);
+  a.table = table;
+  a.partial = table + (size_t)B * P * 4;
+  return nch;
+}
+
+// the scoring kernel `fn` on grid (gx, nch, B) with `args` as its one parameter, then the fixed-order
+// sum of partial[B, nch, P] into scores[B, P].  Above 64 KiB of LDS the kernel's limit is raised
+// to attr_bytes first.
+inline int score_launch_and_reduce(const void* fn, int gx, int nch, int B, void* args,
+                                   size_t lds_bytes, size_t attr_bytes, const float* partial, int P,
+                                   float* scores, hipStream_t s) {
+  if (lds_bytes > 64 * 1024 &&
+      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_bytes) != hipSuccess)
+    return SNAP_ERR_LAUNCH;
+  void* kargs[] = {args};
+  if (hipLaunchKernel(fn, dim3(gx, nch, B), dim3(PS_THREADS), kargs, lds_bytes, s) != hipSuccess)
+    return SNAP_ERR_LAUNCH;
+  SNAP_CHECK_LAUNCH();
+  const int64_t total = (int64_t)B * P;
+  hipLaunchKernelGGL(pose_score_reduce_kernel, dim3((unsigned)snap_cdiv(total, 256)), dim3(256), 0,
+                     s, partial, nch, P, total, scores);
+  SNAP_CHECK_LAUNCH();
+  return SNAP_OK;
+}
 
 __global__ void refine_lattice_kernel(const float* __restrict__ init,
                                       const float* __restrict__ offs_r,
@@ -1981,41 +1890,34 @@ extern "C" int snap_pose_score_f32(const float* sim, const float* poses, const f
   if (B <= 0 || Nq <= 0 || X <= 0 || Y <= 0 || P <= 0) return SNAP_ERR_BAD_SHAPE;
   if (Y > PS_LDS_FLOATS / 2) return SNAP_ERR_UNSUPPORTED;
   if (workspace_bytes < snap_pose_score_workspace_bytes(B, Nq, P, X, Y)) return SNAP_ERR_WORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return SNAP_ERR_BAD_SHAPE;
   ScoreArgs a;
-  a.sim = sim; a.poses = poses; a.q_xy = q_xy; a.valid_q = valid_q; a.map_valid = map_valid;
-  a.B = B; a.Nq = Nq; a.X = X; a.Y = Y; a.P = P;
-  a.cell = cell_size; a.mask_oob = mask_oob;
-  const int pch = score_pose_chunks(P);
-  const int nch = score_chunks(B, Nq, pch);
-  a.points_per_chunk = (Nq + nch - 1) / nch;
-  if ((int64_t)X * Y <= PS_LDS_FLOATS) {
-    a.RB = X; a.NB = 1;
-  } else {
+  const int nch = score_setup(a, sim, q_xy, valid_q, map_valid, B, Nq, X, Y, P, cell_size, workspace);
+  if ((int64_t)X * Y > PS_LDS_FLOATS) {
     a.RB = PS_LDS_FLOATS / Y;
     a.NB = (X - 1 + (a.RB - 1) - 1) / (a.RB - 1);
   }
-  float* table = static_cast<float*>(workspace);
-  a.table = table;
-  a.partial = table + (size_t)B * P * 4;
-  if (reinterpret_cast<uintptr_t>(workspace) & 15) return SNAP_ERR_BAD_SHAPE;
-  const size_t lds = (size_t)min((int64_t)a.RB * Y, (int64_t)PS_LDS_FLOATS) * sizeof(float);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool bands = a.NB > 1;
   // double-buffered LDS-DMA variant: two whole planes must fit (2 * XY * 4 <= 128 KiB).
-  constexpr bool db_enabled = true;
-  const bool use_db = db_enabled && !bands && (Y % 4 == 0) && X >= 2 && Y >= 2 &&
+  const bool use_db = !bands && (Y % 4 == 0) && X >= 2 && Y >= 2 &&
                       ((int64_t)X * (Y + 4) * 4 <= PS_DB_PLANE_BYTES);
   // banded double-buffered variant: a plane that does not fit streams through in row bands
   const int band_rows = (int)(PS_DB_PLANE_BYTES / ((size_t)(Y + 4) * sizeof(float))) - 1;
-  const bool use_band_db = db_enabled && !use_db && !mask_oob && (Y % 4 == 0) && X >= 2 &&
-                           Y >= 2 && band_rows >= 1 && X > band_rows;
+  const bool use_band_db = !use_db && !mask_oob && (Y % 4 == 0) && X >= 2 && Y >= 2 &&
+                           band_rows >= 1 && X > band_rows;
   const void* fn = nullptr;
-  size_t lds_bytes = lds;
+  size_t lds_bytes = (size_t)min((int64_t)a.RB * Y, (int64_t)PS_LDS_FLOATS) * sizeof(float);
+  size_t attr_bytes = PS_LDS_FLOATS * sizeof(float);
+  int gx = score_pose_chunks(P);
   if (use_band_db) {
     a.RB = band_rows;
     a.NB = (X - 1 + band_rows - 1) / band_rows;     // cell rows 0 .. X-2
     fn = (const void*)&pose_score_band_db_kernel<PS_BAND_PPT>;
     lds_bytes = (size_t)2 * (band_rows + 1) * (Y + 4) * sizeof(float);
+    // (the banded kernel carries PS_BAND_PPT poses per thread; the point chunking and the partial
+    // buffer layout [B, nch, P] are the same)
+    gx = (P + PS_THREADS * PS_BAND_PPT - 1) / (PS_THREADS * PS_BAND_PPT);
   } else if (use_db) {
     if (Y == 128)
       fn = mask_oob ? (const void*)&pose_score_db_kernel<PS_PPT, true, 128>
@@ -2028,35 +1930,16 @@ extern "C" int snap_pose_score_f32(const float* sim, const float* poses, const f
                            : (const void*)&pose_score_kernel<PS_PPT, true, false>;
   else fn = bands ? (const void*)&pose_score_kernel<PS_PPT, false, true>
                   : (const void*)&pose_score_kernel<PS_PPT, false, false>;
-  if (lds_bytes > 64 * 1024) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)((use_db || use_band_db) ? 2 * PS_DB_PLANE_BYTES
-                                                          : PS_LDS_FLOATS * sizeof(float))) !=
-        hipSuccess)
-      return SNAP_ERR_LAUNCH;
-  }
   if (use_db || use_band_db) {
+    attr_bytes = 2 * PS_DB_PLANE_BYTES;
     hipLaunchKernelGGL(pose_table_cells_kernel, dim3((unsigned)snap_cdiv((int64_t)B * P, 256)),
-                       dim3(256), 0, s, poses, (int64_t)B * P, cell_size, table);
+                       dim3(256), 0, s, poses, (int64_t)B * P, cell_size, static_cast<float*>(workspace));
   } else {
     hipLaunchKernelGGL(pose_table_kernel, dim3((unsigned)snap_cdiv((int64_t)B * P, 256)),
-                       dim3(256), 0, s, poses, (int64_t)B * P, table);
+                       dim3(256), 0, s, poses, (int64_t)B * P, static_cast<float*>(workspace));
   }
   SNAP_CHECK_LAUNCH();
-  {
-    void* kargs[] = {(void*)&a};
-    // (the banded kernel carries PS_BAND_PPT poses per thread; the point chunking and the partial buffer
-    // layout [B, nch, P] are the same)
-    const int gx = use_band_db ? (P + PS_THREADS * PS_BAND_PPT - 1) / (PS_THREADS * PS_BAND_PPT) : pch;
-    if (hipLaunchKernel(fn, dim3(gx, nch, B), dim3(PS_THREADS), kargs, lds_bytes, s) != hipSuccess)
-      return SNAP_ERR_LAUNCH;
-  }
-  SNAP_CHECK_LAUNCH();
-  const int64_t total = (int64_t)B * P;
-  hipLaunchKernelGGL(pose_score_reduce_kernel, dim3((unsigned)snap_cdiv(total, 256)), dim3(256), 0,
-                     s, (const float*)a.partial, nch, P, total, scores);
-  SNAP_CHECK_LAUNCH();
-  return SNAP_OK;
+  return score_launch_and_reduce(fn, gx, nch, B, &a, lds_bytes, attr_bytes, a.partial, P, scores, s);
 }
 
 extern "C" size_t snap_pose_score_window_workspace_bytes(int32_t B, int32_t Nq, int32_t P, int32_t X,
@@ -2083,17 +1966,7 @@ extern "C" int snap_pose_score_window_f32(const float* sim, const float* poses, 
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return SNAP_ERR_BAD_SHAPE;
   ScoreWinArgs w;
   ScoreArgs& a = w.s;
-  a.sim = sim; a.poses = poses; a.q_xy = q_xy; a.valid_q = valid_q; a.map_valid = nullptr;
-  a.B = B; a.Nq = Nq; a.X = X; a.Y = Y; a.P = P;
-  a.cell = cell_size; a.mask_oob = 0;
-  // the point chunking (and so the order of every sum) of snap_pose_score_f32
-  const int pch = score_pose_chunks(P);
-  const int nch = score_chunks(B, Nq, pch);
-  a.points_per_chunk = (Nq + nch - 1) / nch;
-  a.RB = X; a.NB = 1;
-  float* table = static_cast<float*>(workspace);
-  a.table = table;
-  a.partial = table + (size_t)B * P * 4;
+  const int nch = score_setup(a, sim, q_xy, valid_q, nullptr, B, Nq, X, Y, P, cell_size, workspace);
   float* ctable = a.partial + (size_t)B * nch * P;
   ctable = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ctable) + 15) & ~(uintptr_t)15);
   w.ctable = ctable;
@@ -2102,28 +1975,15 @@ extern "C" int snap_pose_score_window_f32(const float* sim, const float* poses, 
   w.WC = min((2 * radius_cells + 6 + 3) & ~3, Y);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(pose_table_cells_kernel, dim3((unsigned)snap_cdiv((int64_t)B * P, 256)), dim3(256), 0,
-                     s, poses, (int64_t)B * P, cell_size, table);
+                     s, poses, (int64_t)B * P, cell_size, static_cast<float*>(workspace));
   SNAP_CHECK_LAUNCH();
   hipLaunchKernelGGL(pose_table_cells_kernel, dim3((unsigned)snap_cdiv((int64_t)B, 256)), dim3(256), 0, s,
                      centers, (int64_t)B, cell_size, ctable);
   SNAP_CHECK_LAUNCH();
   const size_t lds_bytes = (size_t)2 * w.WR * (w.WC + 4) * sizeof(float);
-  const void* fn = (const void*)&pose_score_window_kernel<PS_WIN_PPT>;
-  if (lds_bytes > 64 * 1024 &&
-      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-    return SNAP_ERR_LAUNCH;
-  {
-    void* kargs[] = {(void*)&w};
-    const int gx = (P + PS_THREADS * PS_WIN_PPT - 1) / (PS_THREADS * PS_WIN_PPT);
-    if (hipLaunchKernel(fn, dim3(gx, nch, B), dim3(PS_THREADS), kargs, lds_bytes, s) != hipSuccess)
-      return SNAP_ERR_LAUNCH;
-  }
-  SNAP_CHECK_LAUNCH();
-  const int64_t total = (int64_t)B * P;
-  hipLaunchKernelGGL(pose_score_reduce_kernel, dim3((unsigned)snap_cdiv(total, 256)), dim3(256), 0,
-                     s, (const float*)a.partial, nch, P, total, scores);
-  SNAP_CHECK_LAUNCH();
-  return SNAP_OK;
+  const int gx = (P + PS_THREADS * PS_WIN_PPT - 1) / (PS_THREADS * PS_WIN_PPT);
+  return score_launch_and_reduce((const void*)&pose_score_window_kernel<PS_WIN_PPT>, gx, nch, B, &w,
+                                 lds_bytes, lds_bytes, a.partial, P, scores, s);
 }
 
 extern "C" int snap_refine_lattice_f32(const float* init, const float* offs_r, const float* offs_p,
