@@ -204,7 +204,9 @@ int32_t snap_conv2d_presplit_supported(const SnapConvDesc* desc);
  * ONCE in the pre-split format: out [N*HW][C/16][hi k0-7 | hi k8-15 | lo k0-7 | lo k8-15] bf16
  * (N*HW*C*4 bytes), hi = bf16(v), lo = bf16(v - hi).  Replaces the statistics finalize launch of
  * that tensor AND the normalise / split work of every consumer tile; mu / sc (optional, both or
- * neither): the statistics as snap_group_norm_stats_from_partial_f32 defines them.  C % 16 == 0,
+ * neither): the statistics of the plain partial sums, var = (T2 - 2 mean T1 + n mean^2) / n -- WITHOUT
+ * the re-reduction snap_group_norm_stats_from_partial_f32 gives a group with mean^2 > 4 var, so on
+ * such a group the variance is off by about 2^-24 mean^2 and differs from that function's.  C % 16 == 0,
  * C <= 2048, groups a power of two <= 64. */
 int snap_gn_norm_split_f32(const float* y, const float* partial, int32_t N, int32_t HW, int32_t C,
                            int32_t groups, float eps, int32_t tile_rows, const float* gamma,
@@ -441,11 +443,16 @@ int snap_conv2d_root_pool_f32(const SnapConvDesc* desc, const float* x, const vo
                               void* stream);
 
 /* mu / sc (/ rstd) [N, C] from a conv launch's gn_partial.  tile_rows =
- * snap_conv2d_tile_rows(desc of that launch); HW = Ho*Wo of its output. */
-int snap_group_norm_stats_from_partial_f32(const float* partial, int32_t N, int32_t HW,
-                                           int32_t C, int32_t groups, float eps,
-                                           int32_t tile_rows, const float* gamma, float* mu,
-                                           float* sc, float* rstd, void* stream);
+ * snap_conv2d_tile_rows(desc of that launch); HW = Ho*Wo of its output.  y [N, HW, C]: the output that
+ * launch wrote, relu_first: the sums are those of relu(y) (gn_partial_relu).  The partial sums are plain
+ * f32 sums of y and y^2, whose variance loses about 2^-24 (1 + mean^2 / var) relative accuracy; a group
+ * with mean^2 > 4 var is therefore re-reduced from y (two-pass, fp64), every other group is not read
+ * and keeps the result of its sums. */
+int snap_group_norm_stats_from_partial_f32(const float* partial, const float* y, int32_t N,
+                                           int32_t HW, int32_t C, int32_t groups, float eps,
+                                           int32_t tile_rows, int32_t relu_first,
+                                           const float* gamma, float* mu, float* sc, float* rstd,
+                                           void* stream);
 
 /* Ascending list of the rows with mask != 0: index[0..count) (stable order,
  * deterministic), count written to *count (device).  index must hold M entries. */

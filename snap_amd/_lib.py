@@ -153,7 +153,7 @@ SIGNATURES = {
     'snap_conv2d_pack_weights_split_blocks': (c_int, [c_int, c_int, c_int]),
     'snap_conv2d_pack_weights_split_multi_bf16': (c_int, [ptr, c_int, c_int, c_int, ptr]),
     'snap_group_norm_stats_from_partial_f32': (
-        c_int, [ptr, c_int, c_int, c_int, c_int, c_float, c_int, ptr, ptr, ptr, ptr, ptr]
+        c_int, [ptr, ptr, c_int, c_int, c_int, c_int, c_float, c_int, c_int, ptr, ptr, ptr, ptr, ptr]
     ),
     'snap_compact_rows_workspace_bytes': (c_size, [c_i64]),
     'snap_compact_rows_u8': (c_int, [ptr, c_i64, ptr, ptr, ptr, c_size, ptr]),

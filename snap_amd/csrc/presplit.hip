@@ -7,8 +7,12 @@
 // snap/models/resnet.py:34-60,117-130 applied to a conv output whose per-(image, row tile,
 // channel) partial sums came out of the producing conv's epilogue.  It REPLACES the stand-alone
 // statistics finalize launch of that tensor (snap_group_norm_stats_from_partial_f32): every
-// workgroup first reduces the partial sums of its image in fp64 (fixed order; the same mean /
-// mean((v - mean)^2) / x / sqrt(var + eps) formulas), then streams its share of the image's rows.
+// workgroup first reduces the partial sums of its image in fp64 (fixed order; the plain-sum formulas
+// mean = T1 / n, var = (T2 - 2 mean T1 + n mean^2) / n, x / sqrt(var + eps)), then streams its share of
+// the image's rows.  NOT the whole of that launch: it re-reduces a group with mean^2 > 4 var from y
+// (encoder_ops.hip: kGnHazard), this kernel does not (every row workgroup would have to), so where a
+// group's mean is large against its spread the variance here carries the f32 rounding of the tiles'
+// sums of squares, about 2^-24 mean^2, and differs from the stand-alone launch's.
 // The arithmetic per element is the fused prologue's (apply_pro<SNAP_PRO_GN_RELU>), so a
 // conv_ps launch over the result multiplies the very operands conv_split would have built.
 //

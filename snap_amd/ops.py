@@ -1407,10 +1407,10 @@ def group_norm_stats(x, gamma, *, groups=32, eps=1e-5, relu_first=False, want_rs
   if fused is not None and fused[2] != bool(relu_first):
     fused = getattr(x, '_snap_gn_partial_relu', None) if relu_first else None
   if fused is not None and fused[2] == bool(relu_first) and groups == 32 and tuning().USE_FUSED_GN_STATS:
-    partial, tile_rows, _ = fused        # emitted by the conv that produced x
-    with _region('group_norm_stats', 0.0, 4.0 * partial.numel()):
+    partial, tile_rows, relu = fused     # emitted by the conv that produced x (which the kernel re-reads only
+    with _region('group_norm_stats', 0.0, 4.0 * partial.numel()):   # for groups with mean^2 > 4 var)
       st = lib.snap_group_norm_stats_from_partial_f32(
-          _p(partial), N, HW, C, groups, eps, tile_rows, _p(gamma), _p(mu), _p(sc), _p(rstd),
+          _p(partial), _p(x), N, HW, C, groups, eps, tile_rows, int(relu), _p(gamma), _p(mu), _p(sc), _p(rstd),
           _stream(),
       )
     _lib.check(st, 'snap_group_norm_stats_from_partial_f32')
