@@ -946,6 +946,32 @@ int snap_template_finalize_f32(const float* raw, const float* cnt,
                                int32_t R, int32_t Rp, float overlap_threshold,
                                int32_t use_overlap, float* scores, void* stream);
 
+/* The K best pose hypotheses of a vote volume, with non-maximum suppression: what turns the scores of
+ * exhaustive_pose_voting (snap/models/pose_exhaustive_voting.py:107-137: the volume, and one index -> one
+ * transform) into a ranked list of distinct poses.  votes[R,Ho,Wo] f32 of any shape (not tied to the voting's
+ * geometry), flat(r,a,b) = (r*Ho + a)*Wo + b.
+ *   PEAK: a cell c whose value is a number > -inf and which, for EVERY other cell n of its window
+ *     |dr| <= radius_r (circular: r-1 of 0 is R-1), |da| <= radius_xy, |db| <= radius_xy (clipped at the
+ *     border: cells outside do not exist), has v(c) > v(n) or (v(c) == v(n) and flat(c) < flat(n)).
+ *     A NaN vote is never a peak and compares like -inf as a neighbour; +inf is an ordinary large value;
+ *     == is the float comparison (-0 == +0).  Exactly one peak survives on any plateau of equal values.
+ *   SELECTION: the K peaks of greatest value, ordered by value descending, then flat ascending.
+ *   index[K,3] = (r, a, b); score[K] = the bits of the vote itself; count[2] = {peaks found, clipped to K;
+ *     NaN votes in the volume}.  Rows past the found count: index -1,-1,-1 and score -inf.
+ * Every output element is written by every call, and nothing depends on workgroup scheduling (no atomics:
+ * per-workgroup candidates are ranked by their unique (value, flat) keys and merged in a fixed order).
+ * Supported: 1 <= K <= 64, 0 <= radius_r <= 2 with 2*radius_r+1 <= R, 1 <= radius_xy <= 4, R*Ho*Wo < 2^31;
+ * anything else returns SNAP_ERR_BAD_SHAPE before any launch (a NULL pointer SNAP_ERR_NULL, a short or not
+ * 8-byte aligned workspace SNAP_ERR_WORKSPACE).  workspace: snap_vote_peaks_workspace_bytes() bytes (0 =
+ * unsupported arguments); it needs no initialisation and no launch touches a byte beyond that size.
+ * Only radius (1, 1) runs a kernel body with compile-time radii (unrolled window loops); every other setting
+ * runs the same body with run-time radii: the same results, measured separately (profiles/vote_peaks_bench.json). */
+size_t snap_vote_peaks_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t K, int32_t radius_r,
+                                       int32_t radius_xy);
+int snap_vote_peaks_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, int32_t K, int32_t radius_r,
+                        int32_t radius_xy, int32_t* index, float* score, int32_t* count, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* Confidence-weighted vertical pooling: the 'softmax' / 'weighted' modes of VerticalPooling
  * (bev_mapper.py:63-78).  score_z = vol[m,z,:] . w + bias[0] (log_sigmoid of it when
  * log_sigmoid_scores != 0, i.e. 'weighted'); weights = softmax over the valid levels (all

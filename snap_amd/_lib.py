@@ -268,6 +268,8 @@ SIGNATURES = {
     'snap_template_finalize_f32': (
         c_int, [ptr, ptr, ptr, c_int, c_int, c_int, c_int, c_float, c_int, ptr, ptr]
     ),
+    'snap_vote_peaks_workspace_bytes': (c_size, [c_int] * 6),
+    'snap_vote_peaks_f32': (c_int, [ptr, c_int, c_int, c_int, c_int, c_int, c_int, ptr, ptr, ptr, ptr, c_size, ptr]),
     'snap_vertical_pool_conf_f32': (
         c_int, [ptr, ptr, ptr, ptr, c_i64, c_int, c_int, c_int, ptr, ptr, ptr, ptr, ptr]
     ),
@@ -354,7 +356,7 @@ SIGNATURES = {
     ),
 }
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 _lib = None
 

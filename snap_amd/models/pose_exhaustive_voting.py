@@ -12,6 +12,7 @@
 
 Rotation, padding and the -inf / normalise pass are small HIP kernels (voting.hip).
 """
+import functools
 import math
 
 import numpy as np
@@ -243,3 +244,60 @@ def exhaustive_tfm_to_index(m_t_q_corner, grid, num_rotations):
   k = (-m_t_q_center.angle / (math.pi * 2) % 1) * num_rotations
   ij = (m_t_q_center.t / grid.cell_size) + torch.tensor(grid.extent, device=dev) - 1.5
   return torch.cat([k[..., None], ij], -1)
+
+
+@functools.lru_cache(maxsize=16)
+def _index_to_tfm_constants(R, extent, cell_size, device):
+  """Device constants of ``exhaustive_indices_to_tfm``, uploaded once per (rotations, grid, device): the [R, 3]
+  table (-angle, cos, sin) computed on the host in f32, the extent, the grid centre in metres, a NaN."""
+  neg_angle = -(np.arange(R) * 2 * np.pi / R).astype(np.float32)
+  table = torch.tensor(np.stack([neg_angle, np.cos(neg_angle), np.sin(neg_angle)], -1), device=device)
+  center = torch.tensor((np.asarray(extent) * cell_size / 2).astype(np.float32), device=device)
+  return table, torch.tensor(extent, device=device), center, torch.full((), float('nan'), device=device)
+
+
+def exhaustive_indices_to_tfm(indices, grid, num_rotations):
+  """``exhaustive_index_to_tfm`` for ``indices`` [K, 3] = (r, a, b) rows -> Transform2D [K]: the same +0.5 cell
+  offset and the same corner-frame conjugation c @ (-angle, xy_cell) @ c^-1, written out with c.angle = 0.
+
+  The list of poses must not depend on where it is evaluated, so nothing here is left to a device's
+  transcendentals: the cell offsets and the R angles are rounded to f32 from float64 (as the numpy restatement
+  oracle/voting.py does), cos / sin come from an R-entry host table gathered by ``r``, and the rest is f32
+  multiplies and adds in a fixed order.  A row of -1 (no peak: ``ops.vote_peaks`` past its found count) gives
+  a NaN transform, not a plausible-looking pose."""
+  indices = torch.as_tensor(indices)
+  if indices.dim() != 2 or indices.shape[-1] != 3:
+    raise ValueError(f'exhaustive_indices_to_tfm: indices [K, 3], got {tuple(indices.shape)}')
+  dev = indices.device
+  R = int(num_rotations)
+  table, extent, center, nan = _index_to_tfm_constants(R, tuple(grid.extent), float(grid.cell_size), str(dev))
+  empty = indices[:, 0] < 0
+  row = table[indices[:, 0].long().clamp(0, R - 1)]
+  xy_cell = ((indices[:, 1:].to(torch.float64) - extent + 1 + 0.5) * grid.cell_size).to(torch.float32)
+  t = center + xy_cell                                     # c @ m_t_q_center
+  bx, by = -center[0], -center[1]                          # c^-1 = (-0, -center)
+  cos, sin = row[:, 1], row[:, 2]
+  t = t + torch.stack([cos * bx + (-sin) * by, sin * bx + cos * by], -1)
+  angle = 0.0 + row[:, 0]
+  return geometry.Transform2D(torch.where(empty, nan, angle), torch.where(empty[:, None], nan, t))
+
+
+def poses_from_votes(votes, grid, num_rotations, num_peaks=16, radius_r=1, radius_xy=1):
+  """The ``num_peaks`` best distinct poses of a vote volume [R, 2H-1, 2W-1] (``ops.vote_peaks``: non-maximum
+  suppression over ``radius_r`` rotations, circular, and ``radius_xy`` cells) -> dict(map_t_query Transform2D [K],
+  index int32 [K, 3], score f32 [K], count int32 [2] = (peaks found; NaN votes)).  Best first; rows past
+  ``count[0]`` hold index -1, score -inf and a NaN transform."""
+  if votes.shape[0] != num_rotations:
+    raise ValueError(f'poses_from_votes: {votes.shape[0]} vote planes for {num_rotations} rotations')
+  index, score, count = ops.vote_peaks(votes.contiguous(), num_peaks, radius_r, radius_xy)
+  return dict(map_t_query=exhaustive_indices_to_tfm(index, grid, num_rotations), index=index, score=score,
+              count=count)
+
+
+def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, method=None, **peaks):
+  """``exhaustive_pose_voting`` followed by ``poses_from_votes(**peaks)``: the dict of the latter plus ``votes``.
+  ``['map_t_query'][0]`` is the single best pose."""
+  votes = exhaustive_pose_voting(plane_q, plane_map, num_rotations, grid, conf_q=conf_q, method=method)
+  out = poses_from_votes(votes, grid, num_rotations, **peaks)
+  out['votes'] = votes
+  return out

@@ -2206,6 +2206,35 @@ def template_finalize(raw, cnt, tcount, R, threshold, use_overlap=True):
   return scores
 
 
+def vote_peaks(votes, k, radius_r=1, radius_xy=1):
+  """The ``k`` best peaks of a vote volume: votes [R, Ho, Wo] f32 -> (index int32 [k, 3] = (r, a, b), score f32 [k],
+  count int32 [2] = (peaks found, clipped to k; NaN votes seen)).  A peak beats every other cell within
+  ``radius_r`` rotations (circular) and ``radius_xy`` cells (clipped) in the order "greater value, then smaller
+  flat index"; the list is ordered by value descending, then flat index ascending; rows past the found count
+  hold -1 / -inf (the full contract: snap_vote_peaks_f32 in include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  _f32(votes, 'votes')
+  if votes.dim() != 3:
+    raise ValueError(f'vote_peaks: votes [R, Ho, Wo], got {tuple(votes.shape)}')
+  R, Ho, Wo = votes.shape
+  k, radius_r, radius_xy = int(k), int(radius_r), int(radius_xy)
+  wsb = lib.snap_vote_peaks_workspace_bytes(R, Ho, Wo, k, radius_r, radius_xy) if votes.numel() < 2 ** 31 else 0
+  if wsb == 0:
+    raise ValueError(
+        f'vote_peaks: unsupported R={R} Ho={Ho} Wo={Wo} k={k} radius_r={radius_r} radius_xy={radius_xy} '
+        '(1 <= k <= 64, 0 <= radius_r <= 2 with 2 radius_r + 1 <= R, 1 <= radius_xy <= 4, R Ho Wo < 2^31)')
+  ws = torch.empty((wsb // 8,), dtype=torch.int64, device=votes.device)   # (whole 8-byte words, 8-byte aligned)
+  index = torch.empty((k, 3), dtype=torch.int32, device=votes.device)
+  score = torch.empty((k,), dtype=torch.float32, device=votes.device)
+  count = torch.empty((2,), dtype=torch.int32, device=votes.device)
+  # algorithmic bytes: one read of the volume (the outputs are K rows)
+  with _region('vote_peaks', 0.0, 4.0 * votes.numel()):
+    st = lib.snap_vote_peaks_f32(_p(votes), R, Ho, Wo, k, radius_r, radius_xy, _p(index), _p(score), _p(count),
+                                 _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_peaks_f32')
+  return index, score, count
+
+
 # Module attributes of the switches: aliases of the tuning in force (read) / the process default (write).
 class _OpsModule(type(sys)):
   pass

@@ -1,5 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4)
 """
 import math
 import os
@@ -80,7 +81,77 @@ def voting_c4(iters):
         f'({flop / ms / 1e9 / 157.3:.3f} of the f32 MFMA peak); algorithmic bytes {by / 1e6:.0f} MB')
 
 
+def median_ms(fn, reps):
+  """Median of ``reps`` single calls, each between its own pair of events (after the caller's warm-up)."""
+  evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+  for e0, e1 in evs:
+    e0.record()
+    fn()
+    e1.record()
+  torch.cuda.synchronize()
+  return sorted(e0.elapsed_time(e1) for e0, e1 in evs)[reps // 2]
+
+
+def torch_peaks(votes, k, radius_r, radius_xy):
+  """What a user would write without the kernel: circular pad on r, max_pool3d (-inf padded in a, b), compare, topk.
+  (Ties on a plateau all survive the compare: the composition has no order contract.)"""
+  x = torch.cat([votes[-radius_r:], votes, votes[:radius_r]], 0) if radius_r else votes
+  win = (2 * radius_r + 1, 2 * radius_xy + 1, 2 * radius_xy + 1)
+  m = torch.nn.functional.max_pool3d(x[None, None], win, stride=1, padding=(0, radius_xy, radius_xy))[0, 0]
+  val, idx = torch.topk(torch.where(votes == m, votes, float('-inf')).reshape(-1), k)
+  return idx, val
+
+
+def vote_peaks_c4(iters):
+  """Top-K peak extraction on the C4 vote volume (R = 36, 511 x 511, K = 16, radius (1, 1)): the kernel alone against
+  the torch composition on the same votes, blocks of the two alternated, medians of single calls.  One JSON line;
+  `json=<path>` as a third argument also writes it to that file."""
+  import json
+  R, Ho, Wo, K, rr, rx = 36, 511, 511, 16, 1, 1
+  g = torch.Generator(device='cuda').manual_seed(0)
+  votes = torch.randn((R, Ho, Wo), device='cuda', generator=g)       # (peak density 1 / 27: denser than real votes)
+  index, score, count = ops.vote_peaks(votes, K, rr, rx)
+  idx, val = torch_peaks(votes, K, rr, rx)
+  flat = (index[:, 0].long() * Ho + index[:, 1]) * Wo + index[:, 2]
+  assert torch.equal(flat, idx) and torch.equal(score, val), 'kernel and torch composition disagree on tie-free votes'
+  kernel = lambda: ops.vote_peaks(votes, K, rr, rx)
+  compo = lambda: torch_peaks(votes, K, rr, rx)
+  for fn in (kernel, compo):
+    for _ in range(5):
+      fn()
+  torch.cuda.synchronize()
+  ks, ts = [], []
+  for _ in range(5):
+    ks.append(median_ms(kernel, max(iters, 5)))
+    ts.append(median_ms(compo, max(iters // 2, 5)))
+  k_ms, t_ms = sorted(ks)[2], sorted(ts)[2]
+  # the other settings run the kernel's generic body (run-time radii): timed alone, on the same votes
+  generic = {}
+  for kk, r_, x_ in ((64, 2, 4), (5, 0, 2)):
+    fn = lambda: ops.vote_peaks(votes, kk, r_, x_)
+    for _ in range(5):
+      fn()
+    torch.cuda.synchronize()
+    generic[f'K{kk}_r{r_}_xy{x_}'] = round(sorted(median_ms(fn, max(iters // 2, 5)) for _ in range(3))[1], 4)
+  by = 4.0 * votes.numel()
+  pose_score_rate = 5.4e12        # B/s of pose_score_db_kernel on this chip (DESIGN.md §5)
+  res = dict(case='vote_peaks_c4', shape=[R, Ho, Wo], K=K, radius=[rr, rx], kernel_ms=round(k_ms, 4),
+             kernel_ms_blocks=[round(v, 4) for v in ks], torch_composition_ms=round(t_ms, 4),
+             torch_composition_ms_blocks=[round(v, 4) for v in ts], speedup=round(t_ms / k_ms, 2),
+             generic_body_ms=generic, volume_bytes=int(by), kernel_GBps_of_one_read=round(by / k_ms / 1e6, 1),
+             fraction_of_pose_score_hbm_rate=round(by / (k_ms * 1e-3) / pose_score_rate, 3),
+             pose_score_hbm_rate_Bps=pose_score_rate, timing='median of single calls between device events, 5 blocks '
+             'of each alternated, median block; ops.vote_peaks = both launches + its three torch.empty outputs and workspace')
+  line = json.dumps(res)
+  print(line)
+  for a in sys.argv[3:]:
+    if a.startswith('json='):
+      with open(a[5:], 'w') as f:
+        f.write(line + '\n')
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-  {'pose_score': pose_score, 'pose_score_c4': pose_score_c4, 'voting_c4': voting_c4}[which](iters)
+  {'pose_score': pose_score, 'pose_score_c4': pose_score_c4, 'voting_c4': voting_c4,
+   'vote_peaks_c4': vote_peaks_c4}[which](iters)
