@@ -16,7 +16,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
-#include "common.h"
+#include "lift_common.h"
 
 namespace {
 
@@ -39,75 +39,35 @@ struct LiftBwdArgs {
   float* dobs;           // MODE 2: their gradient
 };
 
-struct ProjB {
-  float pi, pj, depth, dist;
-  bool vis;
-};
-
-__device__ __forceinline__ ProjB project_b(const float* __restrict__ cam,
-                                           const float* __restrict__ Rt, float px, float py,
-                                           float pz, int fisheye) {
-  const float eps = 1e-3f;
-  float pv[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float r0 = Rt[0 * 3 + i], r1 = Rt[1 * 3 + i], r2 = Rt[2 * 3 + i];
-    const float tinv = -((r0 * Rt[9] + r1 * Rt[10]) + r2 * Rt[11]);
-    pv[i] = tinv + ((r0 * px + r1 * py) + r2 * pz);
-  }
-  ProjB o;
-  o.depth = pv[2];
-  bool valid = pv[2] >= eps;
-  const float z = fmaxf(pv[2], eps);
-  float x = pv[0] / z, y = pv[1] / z;
-  if (fisheye) {
-    const float radius2 = x * x + y * y;
-    const bool in_center = radius2 < eps * eps;
-    const float radius = sqrtf(in_center ? eps * eps : radius2);
-    const float theta = atanf(radius);
-    const float t2 = theta * theta;
-    const float offset = (cam[6] * t2 + cam[7] * (t2 * t2)) + cam[8] * (t2 * t2 * t2);
-    float dist = (offset + 1.f) * theta / radius;
-    dist = in_center ? 1.f : dist;
-    x *= dist;
-    y *= dist;
-    valid = valid && (in_center || ((radius < cam[10]) && (dist > 0.f)));
-  }
-  x = x * cam[2] + cam[4];
-  y = y * cam[3] + cam[5];
-  valid = valid && (x >= 0.f) && (x < cam[0]) && (y >= 0.f) && (y < cam[1]);
-  o.pi = y;
-  o.pj = x;
-  o.vis = valid;
-  const float dx = px - Rt[9], dy = py - Rt[10], dz = pz - Rt[11];
-  o.dist = sqrtf((dx * dx + dy * dy) + dz * dz);
-  return o;
+// pixel id of tap (i0, j0): the sort key of a record
+__device__ __forceinline__ unsigned lift_pixel_id(const SnapLiftDesc& d, int b, int view, int i0, int j0) {
+  return (unsigned)((((int64_t)b * d.V + view) * d.h + i0) * d.w + j0);
 }
 
-struct TapsB {
-  int i0, i1, j0, j1;
-  float w00, w01, w10, w11;
-};
+// One record's 12-float header (four tap weights | g(bin0) g(bin1) | bin0 | bin1 << 16 | i0 | i1 << 16 |
+// j0 | j1 << 16), its sort key and its share of the per-pixel count.  vec_in_dpooled sets bit 31 of the
+// key (above the bits the sort looks at): the record's vector is the voxel's row of dpooled.
+__device__ __forceinline__ void lift_bwd_header_store(float* rec_hdr, unsigned* keys, unsigned* count, int64_t rid,
+                                                      f32x4 w, float wb1, float ds, int b0, int b1, int i0,
+                                                      int i1, int j0, int j1, unsigned key, bool vec_in_dpooled) {
+  float* h = rec_hdr + rid * 12;
+  reinterpret_cast<f32x4*>(h)[0] = w;
+  reinterpret_cast<f32x4*>(h)[1] =
+      f32x4{(1.f - wb1) * ds, wb1 * ds, __int_as_float(b0 | (b1 << 16)), __int_as_float(i0 | (i1 << 16))};
+  h[8] = __int_as_float(j0 | (j1 << 16));
+  keys[rid] = vec_in_dpooled ? key | 0x80000000u : key;
+  atomicAdd(count + key, 1u);            // (integer: order-independent)
+}
 
-__device__ __forceinline__ TapsB taps_b(float pi, float pj, int h, int w, int selective) {
-  TapsB t;
-  float ci = pi - 0.5f, cj = pj - 0.5f;
-  if (selective) {
-    ci = fmaxf(fminf(ci, (float)(h - 1)), 0.f);
-    cj = fmaxf(fminf(cj, (float)(w - 1)), 0.f);
-  }
-  const float fi = floorf(ci), fj = floorf(cj);
-  const float wi1 = ci - fi, wj1 = cj - fj;
-  const float wi0 = 1.f - wi1, wj0 = 1.f - wj1;
-  t.i0 = (int)fminf(fmaxf(fi, 0.f), (float)(h - 1));
-  t.i1 = (int)fminf(fmaxf(fi + 1.f, 0.f), (float)(h - 1));
-  t.j0 = (int)fminf(fmaxf(fj, 0.f), (float)(w - 1));
-  t.j1 = (int)fminf(fmaxf(fj + 1.f, 0.f), (float)(w - 1));
-  t.w00 = wi0 * wj0;
-  t.w01 = wi0 * wj1;
-  t.w10 = wi1 * wj0;
-  t.w11 = wi1 * wj1;
-  return t;
+// The VJP of mean / variance / score_max on a lane's four channels (whichever channels those are): d score_k
+// and d f_k.  (The lane's part of d w_k = sum_c f_kc dmean_c + (f_kc - mean_c)^2 dvar_c stays written out in
+// both kernels: as a piece it cost lift_pool_bwd_kernel<1, 1> a register, 66 -> 67 -- DESIGN.md 6.)
+__device__ __forceinline__ float lift_bwd_dscore(float wgt, float dw, float dwbar, float score, float smax,
+                                                 float dsmax, int nmax) {
+  return wgt * (dw - dwbar) + ((score == smax) ? dsmax / (float)nmax : 0.f);
+}
+__device__ __forceinline__ float lift_bwd_dfeat(float wgt, float f, float mean, float dmean, float dvar) {
+  return wgt * dmean + 2.f * wgt * (f - mean) * dvar;
 }
 
 __device__ __forceinline__ float half_sum(float v) {
@@ -144,46 +104,31 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_kernel(const LiftBwdArgs a)
   const float* p = a.pts + gv * 3;
   const float px = p[0], py = p[1], pz = p[2];
 
-  ProjB pr;
-  pr.pi = pr.pj = pr.depth = 0.f;
+  LiftProj pr;
+  pr.pi = pr.pj = pr.depth = pr.vx = pr.vy = 0.f;
   pr.dist = INFINITY;
   pr.vis = false;
   if (hl < d.V)
-    pr = project_b(a.cam + ((int64_t)b * d.V + hl) * 11, a.Rt + ((int64_t)b * d.V + hl) * 12, px, py,
-                   pz, d.fisheye);
-  float key_d = (hl < d.V && pr.vis) ? pr.dist : INFINITY;
-  int key_i = (hl < d.V) ? hl : 1000 + hl;
+    pr = lift_project(a.cam + ((int64_t)b * d.V + hl) * 11, a.Rt + ((int64_t)b * d.V + hl) * 12, px, py,
+                      pz, d.fisheye);
   int sel[KMAX];
-#pragma unroll
-  for (int r = 0; r < KMAX; ++r) {
-    if (r >= nsel) { sel[r] = 0; continue; }
-    if (all_views) { sel[r] = r; continue; }
-    float bd = key_d;
-    int bi = key_i;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-      const float od = __shfl_xor(bd, o, 32);
-      const int oi = __shfl_xor(bi, o, 32);
-      if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-    }
-    sel[r] = bi;
-    if (hl == bi) { key_d = INFINITY; key_i = 1000 + hl; }
-  }
+  float min_dist;                               // (not used by the backward)
+  lift_select_halfwave<KMAX>(pr.dist, pr.vis, hl, d.V, nsel, all_views, sel, min_dist);
 
   // ---- recompute the forward quantities -----------------------------------
   f32x4 feat[KMAX];
   float score[KMAX], wb1[KMAX];
   int bin0[KMAX], bin1[KMAX], view[KMAX];
-  TapsB tp[KMAX];
+  LiftTaps tp[KMAX];
   bool ok[KMAX];
   bool any = false;
-  const float log_range = logf(d.depth_max / d.depth_min);
+  const float span = lift_depth_span(d);
 #pragma unroll
   for (int r = 0; r < KMAX; ++r) {
     feat[r] = f32x4{0.f, 0.f, 0.f, 0.f};
     score[r] = 0.f; wb1[r] = 0.f; bin0[r] = bin1[r] = 0; view[r] = 0;
     ok[r] = false;
-    tp[r] = TapsB{0, 0, 0, 0, 0.f, 0.f, 0.f, 0.f};
+    tp[r] = LiftTaps{0, 0, 0, 0, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (r >= nsel) continue;
     const int v = sel[r];
     view[r] = v;
@@ -202,9 +147,9 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_kernel(const LiftBwdArgs a)
       }
       continue;
     }
-    tp[r] = taps_b(pi, pj, d.h, d.w, all_views ? 0 : 1);
+    tp[r] = lift_taps(pi, pj, d.h, d.w, all_views ? 0 : 1);
     if constexpr (MODE == 3) continue;            // taps only
-    const TapsB& t = tp[r];
+    const LiftTaps& t = tp[r];
     const float* img = a.f + ((int64_t)b * d.V + v) * d.h * d.w * d.C;
     const float* r00 = img + ((int64_t)t.i0 * d.w + t.j0) * d.C;
     const float* r01 = img + ((int64_t)t.i0 * d.w + t.j1) * d.C;
@@ -217,18 +162,12 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_kernel(const LiftBwdArgs a)
         feat[r][e] = ((t.w00 * r00[c] + t.w01 * r01[c]) + t.w10 * r10[c]) + t.w11 * r11[c];
     }
     if (!weighted) continue;      // (scores = None: no depth-score bins in f_images)
-    const float dc = fminf(fmaxf(depth, d.depth_min), d.depth_max);
-    const float tt = logf(dc / d.depth_min) / log_range;
-    const float index = 0.5f + tt * (float)(d.num_bins - 1);
-    const float c = index - 0.5f;
-    const float fl = floorf(c);
-    wb1[r] = c - fl;
-    bin0[r] = (int)fminf(fmaxf(fl, 0.f), (float)(d.num_bins - 1));
-    bin1[r] = (int)fminf(fmaxf(fl + 1.f, 0.f), (float)(d.num_bins - 1));
-    const int c0 = fd + bin0[r], c1 = fd + bin1[r];
-    const float s0 = ((t.w00 * r00[c0] + t.w01 * r01[c0]) + t.w10 * r10[c0]) + t.w11 * r11[c0];
-    const float s1 = ((t.w00 * r00[c1] + t.w01 * r01[c1]) + t.w10 * r10[c1]) + t.w11 * r11[c1];
-    score[r] = (1.f - wb1[r]) * s0 + wb1[r] * s1;
+    const LiftBins bn = lift_depth_bins(depth, d, span);
+    wb1[r] = bn.wb1;
+    bin0[r] = bn.b0;
+    bin1[r] = bn.b1;
+    score[r] = lift_score_blend(t.w00, t.w01, t.w10, t.w11,
+                                lift_score_load(r00, r01, r10, r11, fd + bn.b0, fd + bn.b1), bn.wb1);
   }
   if constexpr (MODE == 2) {
     if (!any) {                                   // pooled == 0 (masked): no gradient
@@ -250,13 +189,14 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_kernel(const LiftBwdArgs a)
 #pragma unroll
     for (int r = 0; r < KMAX; ++r) {
       if (!ok[r] || hl != 0) continue;
-      const TapsB& t = tp[r];
+      // (this header keeps its own stores: through lift_bwd_header_store the kernel takes 2 more VGPRs)
+      const LiftTaps& t = tp[r];
       const int64_t rid = gv * nsel + r;
       float* h = a.rec_hdr + rid * 12;
       reinterpret_cast<f32x4*>(h)[0] = f32x4{t.w00, t.w01, t.w10, t.w11};
       reinterpret_cast<f32x4*>(h)[1] = f32x4{0.f, 0.f, __int_as_float(0), __int_as_float(t.i0 | (t.i1 << 16))};
       h[8] = __int_as_float(t.j0 | (t.j1 << 16));
-      const unsigned key = (unsigned)((((int64_t)b * d.V + view[r]) * d.h + t.i0) * d.w + t.j0);
+      const unsigned key = lift_pixel_id(d, b, view[r], t.i0, t.j0);
       a.keys[rid] = key;
       atomicAdd(a.count + key, 1u);
     }
@@ -264,17 +204,10 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_kernel(const LiftBwdArgs a)
   }
 
   // ---- pooling weights: softmax(where = visible, initial = 0) of the depth scores, or 1 / count
-  float m = 0.f, smax = -INFINITY;
+  float smax = -INFINITY;
   float wgt[KMAX], den = 0.f;
   if (weighted) {
-#pragma unroll
-    for (int r = 0; r < KMAX; ++r)
-      if (ok[r]) { m = fmaxf(m, score[r]); smax = fmaxf(smax, score[r]); }
-#pragma unroll
-    for (int r = 0; r < KMAX; ++r) {
-      wgt[r] = ok[r] ? expf(score[r] - m) : 0.f;
-      den += wgt[r];
-    }
+    lift_softmax_weights<KMAX>(score, ok, wgt, den, smax);
   } else {
 #pragma unroll
     for (int r = 0; r < KMAX; ++r) {
@@ -356,18 +289,18 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_kernel(const LiftBwdArgs a)
       }
       continue;
     }
-    const float ds = weighted ? wgt[r] * (dw[r] - dwbar) + ((score[r] == smax) ? dsmax / (float)nmax : 0.f) : 0.f;
+    const float ds = weighted ? lift_bwd_dscore(wgt[r], dw[r], dwbar, score[r], smax, dsmax, nmax) : 0.f;
     float dfe[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float t = wgt[r] * dmean[e] + 2.f * wgt[r] * (feat[r][e] - mean[e]) * dvar[e];
+      float t = lift_bwd_dfeat(wgt[r], feat[r][e], mean[e], dmean[e], dvar[e]);
       if (minmax) {
         if (feat[r][e] == vmx[e]) t += dmx[e] / nmx[e];
         if (feat[r][e] == vmn[e]) t += dmn[e] / nmn[e];
       }
       dfe[e] = t;
     }
-    const TapsB& t = tp[r];
+    const LiftTaps& t = tp[r];
     if constexpr (MODE == 2) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -383,17 +316,9 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_kernel(const LiftBwdArgs a)
         const int c = hl + 32 * e;
         if (c < fd) a.rec_vec[rid * fd + c] = dfe[e];
       }
-      if (hl == 0) {
-        float* h = a.rec_hdr + rid * 12;
-        reinterpret_cast<f32x4*>(h)[0] = f32x4{t.w00, t.w01, t.w10, t.w11};
-        reinterpret_cast<f32x4*>(h)[1] =
-            f32x4{(1.f - wb1[r]) * ds, wb1[r] * ds, __int_as_float(bin0[r] | (bin1[r] << 16)),
-                  __int_as_float(t.i0 | (t.i1 << 16))};
-        h[8] = __int_as_float(t.j0 | (t.j1 << 16));
-        const unsigned key = (unsigned)((((int64_t)b * d.V + view[r]) * d.h + t.i0) * d.w + t.j0);
-        a.keys[rid] = key;
-        atomicAdd(a.count + key, 1u);            // (integer: order-independent)
-      }
+      if (hl == 0)
+        lift_bwd_header_store(a.rec_hdr, a.keys, a.count, rid, f32x4{t.w00, t.w01, t.w10, t.w11}, wb1[r], ds, bin0[r],
+                              bin1[r], t.i0, t.i1, t.j0, t.j1, lift_pixel_id(d, b, view[r], t.i0, t.j0), false);
       continue;
     }
     float* img = a.df + ((int64_t)b * d.V + view[r]) * d.h * d.w * d.C;
@@ -424,7 +349,8 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_kernel(const LiftBwdArgs a)
 
 // ---------------------------------------------------------------------------
 // Batched record producer for the default fusion options (weighted, variance, no min / max; <= 4
-// selected views): the structure of the forward's lift_pool_batched_kernel (lift.hip).
+// selected views): the two phases of the forward's lift_pool_batched_kernel (lift.hip), built from the same
+// pieces of lift_common.h.
 //   phase A  lane = voxel: projection into the views, selection, tap geometry and depth bins run
 //            once per voxel on a full lane set (in the half-wave-per-voxel kernel above 4 of 32
 //            lanes do that work while 28 wait); records go to LDS.
@@ -452,7 +378,7 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_batched_kernel(const LiftBw
   const bool all_views = d.K == 0;
   const int nsel = all_views ? d.V : d.K;
   const int64_t total = (int64_t)d.B * d.N;
-  const float log_range = logf(d.depth_max / d.depth_min);
+  const float span = lift_depth_span(d);
 
   // ---------------- phase A: lane = voxel ----------------
   {
@@ -464,13 +390,14 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_batched_kernel(const LiftBw
       const float* p = a.pts + gv * 3;
       px = p[0]; py = p[1]; pz = p[2];
     }
+    // (the view loop of the forward's phase A, lift.hip, kept as a copy there and here -- DESIGN.md 6)
     float kd[KMAX], kpi[KMAX], kpj[KMAX], kdep[KMAX];
     int kv[KMAX];
 #pragma unroll
     for (int r = 0; r < KMAX; ++r) { kd[r] = INFINITY; kpi[r] = kpj[r] = kdep[r] = 0.f; kv[r] = -1; }
     for (int v = 0; v < d.V; ++v) {
-      const ProjB pr = project_b(a.cam + ((int64_t)b * d.V + v) * 11, a.Rt + ((int64_t)b * d.V + v) * 12, px, py,
-                                 pz, d.fisheye);
+      const LiftProj pr = lift_project(a.cam + ((int64_t)b * d.V + v) * 11, a.Rt + ((int64_t)b * d.V + v) * 12, px,
+                                       py, pz, d.fisheye);
       const bool vis = live && pr.vis;
       if (all_views) {
 #pragma unroll
@@ -495,27 +422,11 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_batched_kernel(const LiftBw
 #pragma unroll
     for (int r = 0; r < KMAX; ++r) {
       if (r >= nsel || kv[r] < 0) continue;
-      const TapsB t = taps_b(kpi[r], kpj[r], d.h, d.w, all_views ? 0 : 1);
-      // the 1-D weights the products of taps_b are built from (phase B rebuilds the same products)
-      float ci = kpi[r] - 0.5f, cj = kpj[r] - 0.5f;
-      if (!all_views) {
-        ci = fmaxf(fminf(ci, (float)(d.h - 1)), 0.f);
-        cj = fmaxf(fminf(cj, (float)(d.w - 1)), 0.f);
-      }
-      const float wi1 = ci - floorf(ci), wj1 = cj - floorf(cj);
-      const float dc = fminf(fmaxf(kdep[r], d.depth_min), d.depth_max);
-      const float tt = logf(dc / d.depth_min) / log_range;
-      const float index = 0.5f + tt * (float)(d.num_bins - 1);
-      const float c = index - 0.5f;
-      const float fl = floorf(c);
-      const int b0 = (int)fminf(fmaxf(fl, 0.f), (float)(d.num_bins - 1));
-      const int b1 = (int)fminf(fmaxf(fl + 1.f, 0.f), (float)(d.num_bins - 1));
-      int* rec = recs[threadIdx.x][nvis];
-      rec[0] = (int)(unsigned)((((int64_t)b * d.V + kv[r]) * d.h + t.i0) * d.w + t.j0);
-      rec[1] = kv[r] | ((t.i1 != t.i0) << 8) | ((t.j1 != t.j0) << 9) | (b0 << 10) | (b1 << 18);
-      rec[2] = __float_as_int(wi1);
-      rec[3] = __float_as_int(wj1);
-      wbs[threadIdx.x][nvis] = c - fl;
+      const LiftTaps t = lift_taps(kpi[r], kpj[r], d.h, d.w, all_views ? 0 : 1);
+      const LiftBins bn = lift_depth_bins(kdep[r], d, span);
+      // word 0: the pixel id of tap (i0, j0), which is also the sort key
+      lift_rec_pack(recs[threadIdx.x][nvis], (int)lift_pixel_id(d, b, kv[r], t.i0, t.j0), kv[r], t, bn);
+      wbs[threadIdx.x][nvis] = bn.wb1;
       ijs[threadIdx.x][nvis] = t.i0 | (t.j0 << 16);
       ++nvis;
     }
@@ -524,6 +435,8 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_batched_kernel(const LiftBw
     }
     vhdr[threadIdx.x][2] = __int_as_float(live ? (int)gv : -1);      // (B * N < 2^31: checked by the launcher)
     vhdr[threadIdx.x][3] = __int_as_float(nvis);
+    // (the counting sort of the forward's phase A, lift.hip, kept as a copy there and here: through a shared
+    //  piece the KMAX = 1 instance of this kernel takes 54 instead of 52 VGPRs -- DESIGN.md 6)
     const int key = live ? nvis : KMAX + 1;
     const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
     int rank = 0;
@@ -567,21 +480,12 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_batched_kernel(const LiftBw
         const int64_t rid = gv * nsel;
         const i32x4 q4 = *reinterpret_cast<const i32x4*>(recs[v][0]);
         const int pk = q4[1];
-        const float wi1 = __int_as_float(q4[2]), wj1 = __int_as_float(q4[3]);
-        const float wi0 = 1.f - wi1, wj0 = 1.f - wj1;
+        const LiftRecTaps q = lift_rec_decode(0u, (uint32_t)pk, __int_as_float(q4[2]), __int_as_float(q4[3]), 0u, 0u);
         const int ij = ijs[v][0];
         const int i0 = ij & 0xffff, j0 = ij >> 16;
-        const int i1 = i0 + ((pk >> 8) & 1), j1 = j0 + ((pk >> 9) & 1);
-        const float wb1 = wbs[v][0];
-        float* h = a.rec_hdr + rid * 12;
-        reinterpret_cast<f32x4*>(h)[0] = f32x4{wi0 * wj0, wi0 * wj1, wi1 * wj0, wi1 * wj1};
-        reinterpret_cast<f32x4*>(h)[1] =
-            f32x4{(1.f - wb1) * ds, wb1 * ds, __int_as_float(((pk >> 10) & 0xff) | (((pk >> 18) & 0xff) << 16)),
-                  __int_as_float(i0 | (i1 << 16))};
-        h[8] = __int_as_float(j0 | (j1 << 16));
-        const unsigned key = (unsigned)q4[0];
-        a.keys[rid] = key | 0x80000000u;
-        atomicAdd(a.count + key, 1u);            // (integer: order-independent)
+        lift_bwd_header_store(a.rec_hdr, a.keys, a.count, rid, f32x4{q.w00, q.w01, q.w10, q.w11}, wbs[v][0], ds,
+                              (int)lift_rec_bin0(pk), (int)lift_rec_bin1(pk), i0, i0 + (int)lift_rec_ei(pk), j0,
+                              j0 + (int)lift_rec_ej(pk), (unsigned)q4[0], true);
       }
       continue;
     }
@@ -592,48 +496,29 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_batched_kernel(const LiftBw
       if (r >= nvis) continue;
       const i32x4 q4 = *reinterpret_cast<const i32x4*>(recs[v][r]);
       const int pk = q4[1];
-      const float wi1 = __int_as_float(q4[2]), wj1 = __int_as_float(q4[3]);
-      const float wi0 = 1.f - wi1, wj0 = 1.f - wj1;
-      const float w00 = wi0 * wj0, w01 = wi0 * wj1, w10 = wi1 * wj0, w11 = wi1 * wj1;
+      // (word 0 is the pixel id: times Cb = the byte offset the decode takes)
+      const LiftRecTaps q = lift_rec_decode((uint32_t)q4[0] * Cb, (uint32_t)pk, __int_as_float(q4[2]),
+                                            __int_as_float(q4[3]), Cb, Wb);
+      const float w00 = q.w00, w01 = q.w01, w10 = q.w10, w11 = q.w11;
       w4[r][0] = w00; w4[r][1] = w01; w4[r][2] = w10; w4[r][3] = w11;
-      const uint32_t o00 = (uint32_t)q4[0] * Cb;
-      const uint32_t o01 = o00 + ((pk >> 9) & 1 ? Cb : 0u);
-      const uint32_t o10 = o00 + ((pk >> 8) & 1 ? Wb : 0u);
-      const uint32_t o11 = o10 + (o01 - o00);
-      const uint32_t c0 = fdb + ((pk >> 10) & 0xff) * 4u, c1 = fdb + ((pk >> 18) & 0xff) * 4u;
-      const float t00 = *reinterpret_cast<const float*>(fb + (o00 + c0));
-      const float t01 = *reinterpret_cast<const float*>(fb + (o01 + c0));
-      const float t10 = *reinterpret_cast<const float*>(fb + (o10 + c0));
-      const float t11 = *reinterpret_cast<const float*>(fb + (o11 + c0));
-      const float u00 = *reinterpret_cast<const float*>(fb + (o00 + c1));
-      const float u01 = *reinterpret_cast<const float*>(fb + (o01 + c1));
-      const float u10 = *reinterpret_cast<const float*>(fb + (o10 + c1));
-      const float u11 = *reinterpret_cast<const float*>(fb + (o11 + c1));
+      const LiftScoreTaps st = lift_score_load(fb, q, fdb + lift_rec_bin0(pk) * 4u, fdb + lift_rec_bin1(pk) * 4u);
       feat[r] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (lane_on) {
-        const f32x4 a00 = *reinterpret_cast<const f32x4*>(fb + (o00 + lane_off));
-        const f32x4 a01 = *reinterpret_cast<const f32x4*>(fb + (o01 + lane_off));
-        const f32x4 a10 = *reinterpret_cast<const f32x4*>(fb + (o10 + lane_off));
-        const f32x4 a11 = *reinterpret_cast<const f32x4*>(fb + (o11 + lane_off));
+        const f32x4 a00 = *reinterpret_cast<const f32x4*>(fb + (q.o00 + lane_off));
+        const f32x4 a01 = *reinterpret_cast<const f32x4*>(fb + (q.o01 + lane_off));
+        const f32x4 a10 = *reinterpret_cast<const f32x4*>(fb + (q.o10 + lane_off));
+        const f32x4 a11 = *reinterpret_cast<const f32x4*>(fb + (q.o11 + lane_off));
 #pragma unroll
         for (int e = 0; e < 4; ++e) feat[r][e] = ((w00 * a00[e] + w01 * a01[e]) + w10 * a10[e]) + w11 * a11[e];
       }
-      const float wb1 = wbs[v][r];
-      const float s0 = ((w00 * t00 + w01 * t01) + w10 * t10) + w11 * t11;
-      const float s1 = ((w00 * u00 + w01 * u01) + w10 * u10) + w11 * u11;
-      score[r] = (1.f - wb1) * s0 + wb1 * s1;
+      score[r] = lift_score_blend(w00, w01, w10, w11, st, wbs[v][r]);
     }
     // pooling weights: softmax(where = visible, initial = 0) of the depth scores
-    float m = 0.f, smax = -INFINITY;
+    bool ok[KMAX];
 #pragma unroll
-    for (int r = 0; r < KMAX; ++r)
-      if (r < nvis) { m = fmaxf(m, score[r]); smax = fmaxf(smax, score[r]); }
-    float wgt[KMAX], den = 0.f;
-#pragma unroll
-    for (int r = 0; r < KMAX; ++r) {
-      wgt[r] = r < nvis ? expf(score[r] - m) : 0.f;
-      den += wgt[r];
-    }
+    for (int r = 0; r < KMAX; ++r) ok[r] = r < nvis;
+    float smax, wgt[KMAX], den;
+    lift_softmax_weights<KMAX>(score, ok, wgt, den, smax);
     f32x4 mean = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int r = 0; r < KMAX; ++r) {
@@ -669,36 +554,26 @@ __global__ __launch_bounds__(256) void lift_pool_bwd_batched_kernel(const LiftBw
       dw[r] = r < nvis ? half_sum(t) : 0.f;            // (half-wave uniform condition)
       dwbar += wgt[r] * dw[r];
     }
-    const int b = (int)(gv / d.N);
 #pragma unroll
     for (int r = 0; r < KMAX; ++r) {
       if (r >= nvis) continue;
-      const float ds = wgt[r] * (dw[r] - dwbar) + ((score[r] == smax) ? dsmax / (float)nmax : 0.f);
+      const float ds = lift_bwd_dscore(wgt[r], dw[r], dwbar, score[r], smax, dsmax, nmax);
       const int64_t rid = gv * nsel + r;
       if (lane_on) {
         f32x4 dfe;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) dfe[e] = wgt[r] * dmean[e] + 2.f * wgt[r] * (feat[r][e] - mean[e]) * dvar[e];
+        for (int e = 0; e < 4; ++e) dfe[e] = lift_bwd_dfeat(wgt[r], feat[r][e], mean[e], dmean[e], dvar[e]);
         *reinterpret_cast<f32x4*>(a.rec_vec + rid * fd + 4 * hl) = dfe;
       }
       if (hl == 0) {
         const int pk = recs[v][r][1];
         const int ij = ijs[v][r];
         const int i0 = ij & 0xffff, j0 = ij >> 16;
-        const int i1 = i0 + ((pk >> 8) & 1), j1 = j0 + ((pk >> 9) & 1);
-        const float wb1 = wbs[v][r];
-        float* h = a.rec_hdr + rid * 12;
-        reinterpret_cast<f32x4*>(h)[0] = f32x4{w4[r][0], w4[r][1], w4[r][2], w4[r][3]};
-        reinterpret_cast<f32x4*>(h)[1] =
-            f32x4{(1.f - wb1) * ds, wb1 * ds, __int_as_float(((pk >> 10) & 0xff) | (((pk >> 18) & 0xff) << 16)),
-                  __int_as_float(i0 | (i1 << 16))};
-        h[8] = __int_as_float(j0 | (j1 << 16));
-        const unsigned key = (unsigned)recs[v][r][0];
-        a.keys[rid] = key;
-        atomicAdd(a.count + key, 1u);            // (integer: order-independent)
+        lift_bwd_header_store(a.rec_hdr, a.keys, a.count, rid, f32x4{w4[r][0], w4[r][1], w4[r][2], w4[r][3]}, wbs[v][r],
+                              ds, (int)lift_rec_bin0(pk), (int)lift_rec_bin1(pk), i0, i0 + (int)lift_rec_ei(pk), j0,
+                              j0 + (int)lift_rec_ej(pk), (unsigned)recs[v][r][0], false);
       }
     }
-    (void)b;
   }
 }
 
@@ -1176,23 +1051,25 @@ extern "C" int snap_lift_pool_bwd_f32(const SnapLiftDesc* desc, const float* f_i
                                       const float* dpooled, float* df_images, void* stream) {
   if (!desc || !f_images || !cam || !Rt || !points || !dpooled || !df_images) return SNAP_ERR_NULL;
   const SnapLiftDesc& d = *desc;
-  if (d.B <= 0 || d.V <= 0 || d.h <= 0 || d.w <= 0 || d.N <= 0) return SNAP_ERR_BAD_SHAPE;
-  if (d.V > 32 || d.feature_dim % 4 != 0 || d.feature_dim > 128 || d.feature_dim <= 0)
-    return SNAP_ERR_UNSUPPORTED;
-  if (d.C != d.feature_dim + d.num_bins || d.C % 4 != 0) return SNAP_ERR_BAD_SHAPE;
-  if (d.out_stride < 2 * d.feature_dim + 1 || d.out_stride % 4 != 0) return SNAP_ERR_BAD_SHAPE;
-  if (d.K < 0 || (d.K > 0 && d.K >= d.V)) return SNAP_ERR_BAD_SHAPE;
+  LiftDescChecks ck;
+  ck.read_C = true;
+  ck.bins = d.num_bins;
+  ck.read_out_stride = true;
+  ck.chans = 2 * d.feature_dim + 1;
+  ck.max8 = false;             // (more than 8 views are refused by the ladder, after df_images is zeroed)
+  const int vrc = lift_desc_validate(d, ck);
+  if (vrc != SNAP_OK) return vrc;
   if (!d.weighted || !d.use_variance || d.add_minmax) return SNAP_ERR_UNSUPPORTED;   // (the det form has them)
-  const int nsel = d.K == 0 ? d.V : d.K;
+  const int nsel = lift_nsel(d);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t bytes = (size_t)d.B * d.V * d.h * d.w * d.C * sizeof(float);
   if (hipMemsetAsync(df_images, 0, bytes, s) != hipSuccess) return SNAP_ERR_LAUNCH;
   LiftBwdArgs a{d, f_images, cam, Rt, points, dpooled, df_images};
   const dim3 grid((unsigned)snap_cdiv((int64_t)d.B * d.N, 8));
-  if (nsel <= 1) hipLaunchKernelGGL((lift_pool_bwd_kernel<1, 0>), grid, dim3(256), 0, s, a);
-  else if (nsel <= 4) hipLaunchKernelGGL((lift_pool_bwd_kernel<4, 0>), grid, dim3(256), 0, s, a);
-  else if (nsel <= 8) hipLaunchKernelGGL((lift_pool_bwd_kernel<8, 0>), grid, dim3(256), 0, s, a);
-  else return SNAP_ERR_UNSUPPORTED;
+  const int lrc = lift_nsel_ladder(nsel, [&](auto k) {
+    hipLaunchKernelGGL((lift_pool_bwd_kernel<decltype(k)::value, 0>), grid, dim3(256), 0, s, a);
+  });
+  if (lrc != SNAP_OK) return lrc;
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }
@@ -1207,7 +1084,7 @@ struct LiftDetLayout {
 };
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int lift_det_layout(const SnapLiftDesc& d, LiftDetLayout* L, bool with_vec = true) {
-  const int nsel = d.K == 0 ? d.V : d.K;
+  const int nsel = lift_nsel(d);
   L->slots = (size_t)d.B * d.N * nsel;
   L->npix = (size_t)d.B * d.V * d.h * d.w;
   if (L->slots >= 0x7fffffffULL || L->npix >= 0x7ffffffeULL || d.h > 0x7fff || d.w > 0x7fff) return SNAP_ERR_BAD_SHAPE;
@@ -1241,16 +1118,39 @@ inline int lift_det_layout(const SnapLiftDesc& d, LiftDetLayout* L, bool with_ve
 // that "workspace_bytes != 0" means "the launch will not refuse the shape" (callers fall back to the
 // scatter kernel on 0)
 static int lift_det_validate(const SnapLiftDesc& d) {
-  if (d.B <= 0 || d.V <= 0 || d.h <= 0 || d.w <= 0 || d.N <= 0) return SNAP_ERR_BAD_SHAPE;
-  if (d.V > 32 || d.feature_dim % 4 != 0 || d.feature_dim > 128 || d.feature_dim <= 0 || d.num_bins > 32)
-    return SNAP_ERR_UNSUPPORTED;
-  if (d.C != d.feature_dim + (d.weighted ? d.num_bins : 0) || d.C % 4 != 0) return SNAP_ERR_BAD_SHAPE;
-  if (d.out_stride < d.feature_dim * (1 + (d.use_variance ? 1 : 0) + (d.add_minmax ? 2 : 0)) + (d.weighted ? 1 : 0) ||
-      d.out_stride % 4 != 0)
-    return SNAP_ERR_BAD_SHAPE;
-  if (d.K < 0 || (d.K > 0 && d.K >= d.V)) return SNAP_ERR_BAD_SHAPE;
-  const int nsel = d.K == 0 ? d.V : d.K;
-  if (nsel > 8) return SNAP_ERR_UNSUPPORTED;
+  LiftDescChecks ck;
+  ck.unsupported = d.num_bins > 32;
+  ck.read_C = true;
+  ck.bins = d.weighted ? d.num_bins : 0;
+  ck.read_out_stride = true;
+  ck.chans = lift_pool_chans(d);
+  return lift_desc_validate(d, ck);
+}
+
+// The tail both deterministic entry points share, after their record kernel: a stable sort of the record
+// slots by key (ties keep slot order = voxel order), the list starts (exclusive scan of the counts), the
+// per-key sums by tap offset, then the four that land on every pixel: df_images is written exactly once.
+// a.keys / a.count / a.rec_hdr are the record kernel's; rec_vec and dpooled are where the vectors lie.
+static int lift_det_sort_gather(const SnapLiftDesc& d, const LiftDetLayout& L, char* ws, const LiftBwdArgs& a,
+                                const float* rec_vec, const float* dpooled, float* df_images, hipStream_t s) {
+  unsigned* keys_out = reinterpret_cast<unsigned*>(ws + L.off_keys_out);
+  unsigned* vals_out = reinterpret_cast<unsigned*>(ws + L.off_vals_out);
+  unsigned* start = reinterpret_cast<unsigned*>(ws + L.off_start);
+  size_t tmp = L.tmp_bytes;
+  if (rocprim::radix_sort_pairs(ws + L.off_tmp, tmp, a.keys, keys_out, rocprim::counting_iterator<unsigned>(0),
+                                vals_out, L.slots, 0, L.bits, s) != hipSuccess)
+    return SNAP_ERR_LAUNCH;
+  tmp = L.tmp_bytes;
+  if (rocprim::exclusive_scan(ws + L.off_tmp, tmp, a.count, start, 0u, L.npix + 2, rocprim::plus<unsigned>(), s) !=
+      hipSuccess)
+    return SNAP_ERR_LAUNCH;
+  LiftGatherArgs g{d, vals_out, start, keys_out, rec_vec, a.rec_hdr, dpooled, lift_nsel(d),
+                   reinterpret_cast<float*>(ws + L.off_taps), df_images, (unsigned)L.npix};
+  hipLaunchKernelGGL(lift_pool_bwd_taps_kernel, dim3((unsigned)snap_cdiv((int64_t)L.npix, 8)), dim3(256), 0, s, g);
+  SNAP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(lift_pool_bwd_combine_kernel, dim3((unsigned)snap_cdiv((int64_t)L.npix * (d.C / 4), 256)),
+                     dim3(256), 0, s, g);
+  SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }
 
@@ -1270,7 +1170,7 @@ extern "C" int snap_lift_pool_bwd_det_f32(const SnapLiftDesc* desc, const float*
   const SnapLiftDesc& d = *desc;
   const int vrc = lift_det_validate(d);
   if (vrc != SNAP_OK) return vrc;
-  const int nsel = d.K == 0 ? d.V : d.K;
+  const int nsel = lift_nsel(d);
   LiftDetLayout L;
   const int rc = lift_det_layout(d, &L);
   if (rc != SNAP_OK) return rc;
@@ -1283,9 +1183,6 @@ extern "C" int snap_lift_pool_bwd_det_f32(const SnapLiftDesc* desc, const float*
   a.keys = reinterpret_cast<unsigned*>(ws + L.off_keys);
   a.count = reinterpret_cast<unsigned*>(ws + L.off_count);
   a.npix = (unsigned)L.npix;
-  unsigned* keys_out = reinterpret_cast<unsigned*>(ws + L.off_keys_out);
-  unsigned* vals_out = reinterpret_cast<unsigned*>(ws + L.off_vals_out);
-  unsigned* start = reinterpret_cast<unsigned*>(ws + L.off_start);
   if (hipMemsetAsync(a.count, 0, (L.npix + 2) * sizeof(unsigned), s) != hipSuccess) return SNAP_ERR_LAUNCH;
   // 1. records (+ their sort keys, + the per-pixel record counts)
   const dim3 grid((unsigned)snap_cdiv((int64_t)d.B * d.N, 8));
@@ -1296,29 +1193,15 @@ extern "C" int snap_lift_pool_bwd_det_f32(const SnapLiftDesc* desc, const float*
   const dim3 gridb((unsigned)snap_cdiv((int64_t)d.B * d.N, 256));
   if (batched && nsel <= 1) hipLaunchKernelGGL((lift_pool_bwd_batched_kernel<1>), gridb, dim3(256), 0, s, a);
   else if (batched) hipLaunchKernelGGL((lift_pool_bwd_batched_kernel<4>), gridb, dim3(256), 0, s, a);
-  else if (nsel <= 1) hipLaunchKernelGGL((lift_pool_bwd_kernel<1, 1>), grid, dim3(256), 0, s, a);
-  else if (nsel <= 4) hipLaunchKernelGGL((lift_pool_bwd_kernel<4, 1>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((lift_pool_bwd_kernel<8, 1>), grid, dim3(256), 0, s, a);
+  else {
+    const int lrc = lift_nsel_ladder(nsel, [&](auto k) {
+      hipLaunchKernelGGL((lift_pool_bwd_kernel<decltype(k)::value, 1>), grid, dim3(256), 0, s, a);
+    });
+    if (lrc != SNAP_OK) return lrc;
+  }
   SNAP_CHECK_LAUNCH();
-  // 2. stable sort of the record slots by key (ties keep slot order = voxel order) and the list
-  //    starts (exclusive scan of the counts)
-  size_t tmp = L.tmp_bytes;
-  if (rocprim::radix_sort_pairs(ws + L.off_tmp, tmp, a.keys, keys_out, rocprim::counting_iterator<unsigned>(0),
-                                vals_out, L.slots, 0, L.bits, s) != hipSuccess)
-    return SNAP_ERR_LAUNCH;
-  tmp = L.tmp_bytes;
-  if (rocprim::exclusive_scan(ws + L.off_tmp, tmp, a.count, start, 0u, L.npix + 2, rocprim::plus<unsigned>(), s) !=
-      hipSuccess)
-    return SNAP_ERR_LAUNCH;
-  // 3. per-key sums by tap offset, then the four that land on every pixel: df_images written exactly once
-  LiftGatherArgs g{d, vals_out, start, keys_out, a.rec_vec, a.rec_hdr, dpooled, nsel, reinterpret_cast<float*>(ws + L.off_taps), df_images,
-                   (unsigned)L.npix};
-  hipLaunchKernelGGL(lift_pool_bwd_taps_kernel, dim3((unsigned)snap_cdiv((int64_t)L.npix, 8)), dim3(256), 0, s, g);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(lift_pool_bwd_combine_kernel, dim3((unsigned)snap_cdiv((int64_t)L.npix * (d.C / 4), 256)),
-                     dim3(256), 0, s, g);
-  SNAP_CHECK_LAUNCH();
-  return SNAP_OK;
+  // 2. sort, list starts, per-key sums, per-pixel sums
+  return lift_det_sort_gather(d, L, ws, a, a.rec_vec, dpooled, df_images, s);
 }
 
 // ---- depth_mlp fusion (streetview_encoder.py:263-267): the VJPs of its two lift passes ------------
@@ -1328,22 +1211,24 @@ extern "C" int snap_lift_pool_observations_bwd_f32(const SnapLiftDesc* desc, con
                                                    float* dobs, void* stream) {
   if (!desc || !cam || !Rt || !points || !obs_feat || !dpooled || !dobs) return SNAP_ERR_NULL;
   const SnapLiftDesc& d = *desc;
-  if (d.B <= 0 || d.V <= 0 || d.N <= 0) return SNAP_ERR_BAD_SHAPE;
-  if (d.V > 32 || d.feature_dim % 4 != 0 || d.feature_dim > 128 || d.feature_dim <= 0 || d.weighted)
-    return SNAP_ERR_UNSUPPORTED;
-  if (d.out_stride < d.feature_dim * (1 + (d.use_variance ? 1 : 0) + (d.add_minmax ? 2 : 0)) || d.out_stride % 4 != 0)
-    return SNAP_ERR_BAD_SHAPE;
-  if (d.K < 0 || (d.K > 0 && d.K >= d.V)) return SNAP_ERR_BAD_SHAPE;
-  const int nsel = d.K == 0 ? d.V : d.K;
-  if (nsel > 8) return SNAP_ERR_UNSUPPORTED;
+  // (unweighted only, so lift_pool_chans counts no score channel; h, w and C are not read)
+  LiftDescChecks ck;
+  ck.image = false;
+  ck.unsupported = d.weighted != 0;
+  ck.read_out_stride = true;
+  ck.chans = lift_pool_chans(d);
+  const int vrc = lift_desc_validate(d, ck);
+  if (vrc != SNAP_OK) return vrc;
+  const int nsel = lift_nsel(d);
   hipStream_t s = static_cast<hipStream_t>(stream);
   LiftBwdArgs a{d, nullptr, cam, Rt, points, dpooled, nullptr};
   a.obs_in = obs_feat;
   a.dobs = dobs;
   const dim3 grid((unsigned)snap_cdiv((int64_t)d.B * d.N, 8));
-  if (nsel <= 1) hipLaunchKernelGGL((lift_pool_bwd_kernel<1, 2>), grid, dim3(256), 0, s, a);
-  else if (nsel <= 4) hipLaunchKernelGGL((lift_pool_bwd_kernel<4, 2>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((lift_pool_bwd_kernel<8, 2>), grid, dim3(256), 0, s, a);
+  const int lrc = lift_nsel_ladder(nsel, [&](auto k) {
+    hipLaunchKernelGGL((lift_pool_bwd_kernel<decltype(k)::value, 2>), grid, dim3(256), 0, s, a);
+  });
+  if (lrc != SNAP_OK) return lrc;
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }
@@ -1361,12 +1246,11 @@ extern "C" int snap_lift_observations_bwd_f32(const SnapLiftDesc* desc, const fl
                                               size_t workspace_bytes, void* stream) {
   if (!desc || !cam || !Rt || !points || !dobs || !df_images || !workspace) return SNAP_ERR_NULL;
   const SnapLiftDesc& d = *desc;
-  if (d.B <= 0 || d.V <= 0 || d.h <= 0 || d.w <= 0 || d.N <= 0) return SNAP_ERR_BAD_SHAPE;
-  if (d.V > 32 || d.feature_dim % 4 != 0 || d.feature_dim > 128 || d.feature_dim <= 0 || d.C != d.feature_dim)
-    return SNAP_ERR_UNSUPPORTED;
-  if (d.K < 0 || (d.K > 0 && d.K >= d.V)) return SNAP_ERR_BAD_SHAPE;
-  const int nsel = d.K == 0 ? d.V : d.K;
-  if (nsel > 8) return SNAP_ERR_UNSUPPORTED;
+  LiftDescChecks ck;
+  ck.unsupported = d.C != d.feature_dim;
+  const int vrc = lift_desc_validate(d, ck);
+  if (vrc != SNAP_OK) return vrc;
+  const int nsel = lift_nsel(d);
   SnapLiftDesc dd = d;
   dd.num_bins = 0;                                   // (the gather writes feature channels only)
   LiftDetLayout L;
@@ -1380,31 +1264,14 @@ extern "C" int snap_lift_observations_bwd_f32(const SnapLiftDesc* desc, const fl
   a.keys = reinterpret_cast<unsigned*>(ws + L.off_keys);
   a.count = reinterpret_cast<unsigned*>(ws + L.off_count);
   a.npix = (unsigned)L.npix;
-  unsigned* keys_out = reinterpret_cast<unsigned*>(ws + L.off_keys_out);
-  unsigned* vals_out = reinterpret_cast<unsigned*>(ws + L.off_vals_out);
-  unsigned* start = reinterpret_cast<unsigned*>(ws + L.off_start);
   if (hipMemsetAsync(a.count, 0, (L.npix + 2) * sizeof(unsigned), s) != hipSuccess) return SNAP_ERR_LAUNCH;
   const dim3 grid((unsigned)snap_cdiv((int64_t)dd.B * dd.N, 8));
-  if (nsel <= 1) hipLaunchKernelGGL((lift_pool_bwd_kernel<1, 3>), grid, dim3(256), 0, s, a);
-  else if (nsel <= 4) hipLaunchKernelGGL((lift_pool_bwd_kernel<4, 3>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((lift_pool_bwd_kernel<8, 3>), grid, dim3(256), 0, s, a);
+  const int lrc = lift_nsel_ladder(nsel, [&](auto k) {
+    hipLaunchKernelGGL((lift_pool_bwd_kernel<decltype(k)::value, 3>), grid, dim3(256), 0, s, a);
+  });
+  if (lrc != SNAP_OK) return lrc;
   SNAP_CHECK_LAUNCH();
-  size_t tmp = L.tmp_bytes;
-  if (rocprim::radix_sort_pairs(ws + L.off_tmp, tmp, a.keys, keys_out, rocprim::counting_iterator<unsigned>(0),
-                                vals_out, L.slots, 0, L.bits, s) != hipSuccess)
-    return SNAP_ERR_LAUNCH;
-  tmp = L.tmp_bytes;
-  if (rocprim::exclusive_scan(ws + L.off_tmp, tmp, a.count, start, 0u, L.npix + 2, rocprim::plus<unsigned>(), s) !=
-      hipSuccess)
-    return SNAP_ERR_LAUNCH;
-  LiftGatherArgs g{dd, vals_out, start, keys_out, dobs, a.rec_hdr, nullptr, nsel, reinterpret_cast<float*>(ws + L.off_taps), df_images,
-                   (unsigned)L.npix};
-  hipLaunchKernelGGL(lift_pool_bwd_taps_kernel, dim3((unsigned)snap_cdiv((int64_t)L.npix, 8)), dim3(256), 0, s, g);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(lift_pool_bwd_combine_kernel, dim3((unsigned)snap_cdiv((int64_t)L.npix * (dd.C / 4), 256)),
-                     dim3(256), 0, s, g);
-  SNAP_CHECK_LAUNCH();
-  return SNAP_OK;
+  return lift_det_sort_gather(dd, L, ws, a, dobs, nullptr, df_images, s);   // (the record vectors ARE d obs)
 }
 
 extern "C" int snap_vertical_pool_max_bwd_arg_f32(const float* vol, const uint8_t* vvalid, const uint8_t* argz,

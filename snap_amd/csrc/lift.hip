@@ -18,7 +18,7 @@
 // of snap/utils/geometry.py:52-69,198-221,260-280.
 #include <stdlib.h>
 
-#include "common.h"
+#include "lift_common.h"
 
 namespace {
 
@@ -48,89 +48,6 @@ struct LiftArgs {
   uint32_t* tap_recs;
 };
 
-struct Proj {
-  float pi, pj;   // (row, col) coordinates in the feature map, corner origin
-  float depth;
-  float dist;     // distance voxel -> camera centre
-  bool vis;
-  float vx, vy;   // camera-frame x, y (z = depth): the viewing ray of the observation
-};
-
-// One (voxel, view) projection.  cam = wh f c k(3) max_fov pad; Rt = R(9) t(3).
-__device__ __forceinline__ Proj project_one(const float* __restrict__ cam,
-                                            const float* __restrict__ Rt, float px, float py,
-                                            float pz, int fisheye) {
-  const float eps = 1e-3f;
-  // Transform3D.inv: R_inv = R^T, t_inv = -(R^T t); then t_inv + R_inv p.
-  float pv[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float r0 = Rt[0 * 3 + i], r1 = Rt[1 * 3 + i], r2 = Rt[2 * 3 + i];
-    const float tinv = -((r0 * Rt[9] + r1 * Rt[10]) + r2 * Rt[11]);
-    pv[i] = tinv + ((r0 * px + r1 * py) + r2 * pz);
-  }
-  Proj o;
-  o.vx = pv[0];
-  o.vy = pv[1];
-  o.depth = pv[2];
-  bool valid = pv[2] >= eps;
-  const float z = fmaxf(pv[2], eps);
-  float x = pv[0] / z, y = pv[1] / z;
-  if (fisheye) {
-    const float radius2 = x * x + y * y;
-    const bool in_center = radius2 < eps * eps;
-    const float radius = sqrtf(in_center ? eps * eps : radius2);
-    const float theta = atanf(radius);
-    const float t2 = theta * theta;
-    const float offset = (cam[6] * t2 + cam[7] * (t2 * t2)) + cam[8] * (t2 * t2 * t2);
-    float dist = (offset + 1.f) * theta / radius;
-    dist = in_center ? 1.f : dist;
-    x *= dist;
-    y *= dist;
-    valid = valid && (in_center || ((radius < cam[10]) && (dist > 0.f)));
-  }
-  x = x * cam[2] + cam[4];
-  y = y * cam[3] + cam[5];
-  valid = valid && (x >= 0.f) && (x < cam[0]) && (y >= 0.f) && (y < cam[1]);
-  o.pi = y;  // xy -> ij
-  o.pj = x;
-  o.vis = valid;
-  const float dx = px - Rt[9], dy = py - Rt[10], dz = pz - Rt[11];
-  o.dist = sqrtf((dx * dx + dy * dy) + dz * dz);
-  return o;
-}
-
-struct Taps {
-  int i0, i1, j0, j1;
-  float w00, w01, w10, w11;
-  float wi1, wj1;   // the 1-D weights the four products are built from
-};
-
-// selective != 0: streetview_encoder.py:93-105 (clip the point, floor, +1);
-// selective == 0: grids.interpolate_nd / map_coordinates (clip each tap index).
-__device__ __forceinline__ Taps make_taps(float pi, float pj, int h, int w, int selective) {
-  Taps t;
-  float ci = pi - 0.5f, cj = pj - 0.5f;
-  if (selective) {
-    ci = fmaxf(fminf(ci, (float)(h - 1)), 0.f);
-    cj = fmaxf(fminf(cj, (float)(w - 1)), 0.f);
-  }
-  const float fi = floorf(ci), fj = floorf(cj);
-  const float wi1 = ci - fi, wj1 = cj - fj;
-  const float wi0 = 1.f - wi1, wj0 = 1.f - wj1;
-  t.i0 = (int)fminf(fmaxf(fi, 0.f), (float)(h - 1));
-  t.i1 = (int)fminf(fmaxf(fi + 1.f, 0.f), (float)(h - 1));
-  t.j0 = (int)fminf(fmaxf(fj, 0.f), (float)(w - 1));
-  t.j1 = (int)fminf(fmaxf(fj + 1.f, 0.f), (float)(w - 1));
-  t.w00 = wi0 * wj0;
-  t.w01 = wi0 * wj1;
-  t.w10 = wi1 * wj0;
-  t.w11 = wi1 * wj1;
-  t.wi1 = wi1;
-  t.wj1 = wj1;
-  return t;
-}
-
 // Pooling for the NON-default fusion options of pool_multiview_features
 // (streetview_encoder.py:141-178): unweighted statistics (scores = None: plain mean / variance over
 // the valid views, no score channel), fusion_use_variance = False, fusion_add_minmax = True.
@@ -148,17 +65,8 @@ __device__ __forceinline__ void pool_generic(const SnapLiftDesc& d, const f32x4 
   if (nvis > 0) {
     float wgt[KMAX];
     if (d.weighted) {
-      float m = 0.f;
-      smax = -INFINITY;
-#pragma unroll
-      for (int r = 0; r < KMAX; ++r)
-        if (ok[r]) { m = fmaxf(m, score[r]); smax = fmaxf(smax, score[r]); }
-      float den = 0.f;
-#pragma unroll
-      for (int r = 0; r < KMAX; ++r) {
-        wgt[r] = ok[r] ? expf(score[r] - m) : 0.f;
-        den += wgt[r];
-      }
+      float den;
+      lift_softmax_weights<KMAX>(score, ok, wgt, den, smax);
 #pragma unroll
       for (int r = 0; r < KMAX; ++r) wgt[r] = wgt[r] / den;
 #pragma unroll
@@ -248,52 +156,26 @@ __global__ __launch_bounds__(256) void lift_pool_kernel(const LiftArgs a) {
   const float px = p[0], py = p[1], pz = p[2];
 
   // ---- k1: lane v projects into view v -----------------------------------
-  Proj pr;
+  LiftProj pr;
   pr.pi = pr.pj = pr.depth = pr.vx = pr.vy = 0.f;
   pr.dist = INFINITY;
   pr.vis = false;
   if (hl < d.V) {
-    pr = project_one(a.cam + ((int64_t)b * d.V + hl) * 11, a.Rt + ((int64_t)b * d.V + hl) * 12, px,
-                     py, pz, d.fisheye);
+    pr = lift_project(a.cam + ((int64_t)b * d.V + hl) * 11, a.Rt + ((int64_t)b * d.V + hl) * 12, px,
+                      py, pz, d.fisheye);
   }
-  float key_d = (hl < d.V && pr.vis) ? pr.dist : INFINITY;
-  int key_i = (hl < d.V) ? hl : 1000 + hl;
 
   // ---- k2: selection ---------------------------------------------------------
   int sel[KMAX];
-  float min_dist = INFINITY;
-#pragma unroll
-  for (int r = 0; r < KMAX; ++r) {
-    if (r >= nsel) { sel[r] = 0; continue; }
-    if (all_views) {
-      sel[r] = r;
-      continue;
-    }
-    float bd = key_d;
-    int bi = key_i;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-      const float od = __shfl_xor(bd, o, 32);
-      const int oi = __shfl_xor(bi, o, 32);
-      if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-    }
-    if (r == 0) min_dist = bd;
-    sel[r] = bi;            // bi < V always while r < nsel <= V
-    if (hl == bi) { key_d = INFINITY; key_i = 1000 + hl; }
-  }
-  if (all_views) {
-    float md = key_d;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) md = fminf(md, __shfl_xor(md, o, 32));
-    min_dist = md;
-  }
+  float min_dist;
+  lift_select_halfwave<KMAX>(pr.dist, pr.vis, hl, d.V, nsel, all_views, sel, min_dist);
 
   // ---- k3/k4: gather selected observations ----------------------------------
   f32x4 feat[KMAX];
   float score[KMAX];
   bool ok[KMAX];
   bool any = false;
-  const float log_range = logf(d.depth_max / d.depth_min);
+  const float span = lift_depth_span(d);
 #pragma unroll
   for (int r = 0; r < KMAX; ++r) {
     feat[r] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -325,7 +207,7 @@ __global__ __launch_bounds__(256) void lift_pool_kernel(const LiftArgs a) {
       if (hl < nq) feat[r] = *reinterpret_cast<const f32x4*>(a.obs_in + (gv * nsel + r) * (int64_t)fd + 4 * hl);
       continue;
     }
-    const Taps t = make_taps(pi, pj, d.h, d.w, all_views ? 0 : 1);
+    const LiftTaps t = lift_taps(pi, pj, d.h, d.w, all_views ? 0 : 1);
     const float* img = a.f + ((int64_t)b * d.V + v) * d.h * d.w * d.C;
     const float* r00 = img + ((int64_t)t.i0 * d.w + t.j0) * d.C;
     const float* r01 = img + ((int64_t)t.i0 * d.w + t.j1) * d.C;
@@ -342,15 +224,11 @@ __global__ __launch_bounds__(256) void lift_pool_kernel(const LiftArgs a) {
     }
     if (!d.weighted) continue;           // (scores = None: no depth-score bins in f_images)
     // depth score: two neighbouring log-depth bins, each bilinearly gathered.
-    const float dc = fminf(fmaxf(depth, d.depth_min), d.depth_max);
-    const float tt = logf(dc / d.depth_min) / log_range;
-    const float index = 0.5f + tt * (float)(d.num_bins - 1);
-    const float c = index - 0.5f;
-    const float fl = floorf(c);
-    const float wb1 = c - fl, wb0 = 1.f - wb1;
-    const int b0 = (int)fminf(fmaxf(fl, 0.f), (float)(d.num_bins - 1));
-    const int b1 = (int)fminf(fmaxf(fl + 1.f, 0.f), (float)(d.num_bins - 1));
-    const int c0 = fd + b0, c1 = fd + b1;
+    const LiftBins bn = lift_depth_bins(depth, d, span);
+    // (the blend of lift_score_blend, written out: through the pieces the KMAX = 8 instance spills 96 instead of
+    //  68 bytes -- DESIGN.md 6)
+    const float wb1 = bn.wb1, wb0 = 1.f - wb1;
+    const int c0 = fd + bn.b0, c1 = fd + bn.b1;
     const float s0 = ((t.w00 * r00[c0] + t.w01 * r01[c0]) + t.w10 * r10[c0]) + t.w11 * r11[c0];
     const float s1 = ((t.w00 * r00[c1] + t.w01 * r01[c1]) + t.w10 * r10[c1]) + t.w11 * r11[c1];
     score[r] = wb0 * s0 + wb1 * s1;
@@ -387,18 +265,8 @@ __global__ __launch_bounds__(256) void lift_pool_kernel(const LiftArgs a) {
   f32x4 mean = {0.f, 0.f, 0.f, 0.f}, var = {0.f, 0.f, 0.f, 0.f};
   float smax = 0.f;
   if (any) {
-    // jax.nn.softmax(..., where=valid, initial=0): shift = max(0, max valid score).
-    float m = 0.f;
-    smax = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < KMAX; ++r)
-      if (ok[r]) { m = fmaxf(m, score[r]); smax = fmaxf(smax, score[r]); }
-    float e[KMAX], den = 0.f;
-#pragma unroll
-    for (int r = 0; r < KMAX; ++r) {
-      e[r] = ok[r] ? expf(score[r] - m) : 0.f;
-      den += e[r];
-    }
+    float e[KMAX], den;
+    lift_softmax_weights<KMAX>(score, ok, e, den, smax);
 #pragma unroll
     for (int r = 0; r < KMAX; ++r) {
       const float wgt = e[r] / den;
@@ -436,7 +304,8 @@ __global__ __launch_bounds__(256) void lift_pool_kernel(const LiftArgs a) {
 //            voxel with 4 of 32 lanes doing useful work (it was ~60 % of the kernel's VALU
 //            issue; the kernel is VALU-bound, PMC r01).  Records go to LDS (32 B each).
 //   phase B  for each of the 32 voxels: lane q <-> channels 4q..4q+3: broadcast-read the
-//            records, gather the taps, pool.  Same arithmetic as lift_pool_kernel, same bits.
+//            records, gather the taps, pool.  Same arithmetic as lift_pool_kernel, same bits: the
+//            geometry, the score and the pooling weights are the same pieces of lift_common.h.
 // ---------------------------------------------------------------------------
 constexpr int LB_REC = 4;    // dwords per (voxel, slot) record: tap byte offset | packed | wi1 | wj1  (+ wb1 apart)
 
@@ -506,7 +375,7 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
   const int nq = fd >> 2;
   const bool all_views = d.K == 0;
   const int nsel = all_views ? d.V : d.K;
-  const float log_range = logf(d.depth_max / d.depth_min);
+  const float span = lift_depth_span(d);
 
   // ---------------- phase A: lane = voxel ----------------
   {
@@ -518,6 +387,8 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
       const float* p = a.pts + gv * 3;
       px = p[0]; py = p[1]; pz = p[2];
     }
+    // (this view loop is also lift_pool_bwd_batched_kernel's, bev_bwd.hip: as a shared piece it cost this kernel
+    //  registers and scratch -- DESIGN.md 6)
     // selected views, ascending (visible distance, view index); invisible views never
     // contribute (ok = false in the pooling), so only visible ones are kept.
     float kd[KMAX], kpi[KMAX], kpj[KMAX], kdep[KMAX];
@@ -526,8 +397,8 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
     for (int r = 0; r < KMAX; ++r) { kd[r] = INFINITY; kpi[r] = kpj[r] = kdep[r] = 0.f; kv[r] = -1; }
     float min_dist = INFINITY;
     for (int v = 0; v < d.V; ++v) {
-      const Proj pr = project_one(a.cam + ((int64_t)b * d.V + v) * 11,
-                                  a.Rt + ((int64_t)b * d.V + v) * 12, px, py, pz, d.fisheye);
+      const LiftProj pr = lift_project(a.cam + ((int64_t)b * d.V + v) * 11,
+                                       a.Rt + ((int64_t)b * d.V + v) * 12, px, py, pz, d.fisheye);
       const bool vis = live && pr.vis;
       if (all_views) {
         // slot v <-> view v
@@ -563,20 +434,12 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
       if (r >= nsel || kv[r] < 0) continue;
       int* rec = recs[hw][hl][nvis];
       float* wbp = &wbs[hw][hl][nvis++];
-      const Taps t = make_taps(kpi[r], kpj[r], d.h, d.w, all_views ? 0 : 1);
-      // depth score: two neighbouring log-depth bins
-      const float dc = fminf(fmaxf(kdep[r], d.depth_min), d.depth_max);
-      const float tt = logf(dc / d.depth_min) / log_range;
-      const float index = 0.5f + tt * (float)(d.num_bins - 1);
-      const float c = index - 0.5f;
-      const float fl = floorf(c);
-      const int b0 = (int)fminf(fmaxf(fl, 0.f), (float)(d.num_bins - 1));
-      const int b1 = (int)fminf(fmaxf(fl + 1.f, 0.f), (float)(d.num_bins - 1));
-      rec[0] = (int)(((((uint32_t)b * d.V + kv[r]) * d.h + t.i0) * d.w + t.j0) * ((uint32_t)d.C * 4u));
-      rec[1] = kv[r] | ((t.i1 != t.i0) << 8) | ((t.j1 != t.j0) << 9) | (b0 << 10) | (b1 << 18);
-      rec[2] = __float_as_int(t.wi1);
-      rec[3] = __float_as_int(t.wj1);
-      *wbp = c - fl;
+      const LiftTaps t = lift_taps(kpi[r], kpj[r], d.h, d.w, all_views ? 0 : 1);
+      const LiftBins bn = lift_depth_bins(kdep[r], d, span);
+      // word 0: the byte offset of tap (i0, j0) in f_images
+      lift_rec_pack(rec, (int)(((((uint32_t)b * d.V + kv[r]) * d.h + t.i0) * d.w + t.j0) * ((uint32_t)d.C * 4u)),
+                    kv[r], t, bn);
+      *wbp = bn.wb1;
     }
     hdr[hw][hl][3] = __int_as_float(nvis);
     if (a.tap_recs && live && nvis <= 1) {
@@ -588,30 +451,17 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
       if (nvis == 1) {
         const int* rec = recs[hw][hl][0];
         const int pk = rec[1];
-        const float wi1 = __int_as_float(rec[2]), wj1 = __int_as_float(rec[3]);
-        const float wi0 = 1.f - wi1, wj0 = 1.f - wj1;
-        const float w00 = wi0 * wj0, w01 = wi0 * wj1, w10 = wi1 * wj0, w11 = wi1 * wj1;
-        const uint32_t Cb_ = (uint32_t)d.C * 4u, Wb_ = (uint32_t)d.w * Cb_, fdb_ = (uint32_t)d.feature_dim * 4u;
-        const uint32_t o00 = (uint32_t)rec[0];
-        const uint32_t o01 = o00 + ((pk >> 9) & 1 ? Cb_ : 0u);
-        const uint32_t o10 = o00 + ((pk >> 8) & 1 ? Wb_ : 0u);
-        const uint32_t o11 = o10 + (o01 - o00);
-        const uint32_t c0 = fdb_ + ((pk >> 10) & 0xff) * 4u, c1 = fdb_ + ((pk >> 18) & 0xff) * 4u;
-        const char* fb_ = reinterpret_cast<const char*>(a.f);
-        const float t00 = *reinterpret_cast<const float*>(fb_ + (o00 + c0));
-        const float t01 = *reinterpret_cast<const float*>(fb_ + (o01 + c0));
-        const float t10 = *reinterpret_cast<const float*>(fb_ + (o10 + c0));
-        const float t11 = *reinterpret_cast<const float*>(fb_ + (o11 + c0));
-        const float u00 = *reinterpret_cast<const float*>(fb_ + (o00 + c1));
-        const float u01 = *reinterpret_cast<const float*>(fb_ + (o01 + c1));
-        const float u10 = *reinterpret_cast<const float*>(fb_ + (o10 + c1));
-        const float u11 = *reinterpret_cast<const float*>(fb_ + (o11 + c1));
-        const float wb1 = wbs[hw][hl][0], wb0 = 1.f - wb1;
-        const float s0 = ((w00 * t00 + w01 * t01) + w10 * t10) + w11 * t11;
-        const float s1 = ((w00 * u00 + w01 * u01) + w10 * u10) + w11 * u11;
-        const float score = wb0 * s0 + wb1 * s1;
+        const LiftRecTaps q = lift_rec_decode((uint32_t)rec[0], (uint32_t)pk, __int_as_float(rec[2]),
+                                              __int_as_float(rec[3]), (uint32_t)d.C * 4u,
+                                              (uint32_t)d.w * ((uint32_t)d.C * 4u));
+        const uint32_t fdb_ = (uint32_t)d.feature_dim * 4u;
+        const float score = lift_score_blend(
+            q.w00, q.w01, q.w10, q.w11,
+            lift_score_load(reinterpret_cast<const char*>(a.f), q, fdb_ + lift_rec_bin0(pk) * 4u,
+                            fdb_ + lift_rec_bin1(pk) * 4u),
+            wbs[hw][hl][0]);
         uint4* ro = reinterpret_cast<uint4*>(a.tap_recs + gv * 8);
-        ro[0] = uint4{o00, (uint32_t)pk, (uint32_t)rec[2], (uint32_t)rec[3]};
+        ro[0] = uint4{q.o00, (uint32_t)pk, (uint32_t)rec[2], (uint32_t)rec[3]};
         ro[1] = uint4{__float_as_uint(score), 0u, 0u, 0u};
       }
       a.valid[gv] = vld ? 1 : 0;
@@ -624,6 +474,8 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
     // 8 j + hw of that order: the two halves of a wave get NEIGHBOURS of the sorted list, i.e.
     // voxels of the same class except at the few class boundaries.  Rows are independent, so
     // the bits do not change.
+    // (lift_pool_bwd_batched_kernel, bev_bwd.hip, sorts the same way; as a shared piece the sort cost its
+    //  KMAX = 1 instance two registers -- DESIGN.md 6)
     const int key = live ? nvis : KMAX + 1;
     const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
     int rank = 0;
@@ -673,35 +525,21 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
       const int* rec = &recs[0][0][0][0] + (v * KMAX + r) * LB_REC;
       const i32x4 q4 = *reinterpret_cast<const i32x4*>(rec);   // byte offset | packed | wi1 | wj1
       const int pk = q4[1];
-      const float wi1 = __int_as_float(q4[2]), wj1 = __int_as_float(q4[3]);
-      const float wi0 = 1.f - wi1, wj0 = 1.f - wj1;
-      const float w00 = wi0 * wj0, w01 = wi0 * wj1, w10 = wi1 * wj0, w11 = wi1 * wj1;
-      const uint32_t o00 = (uint32_t)q4[0];
-      const uint32_t o01 = o00 + ((pk >> 9) & 1 ? Cb : 0u);
-      const uint32_t o10 = o00 + ((pk >> 8) & 1 ? Wb : 0u);
-      const uint32_t o11 = o10 + (o01 - o00);
-      const uint32_t c0 = fdb + ((pk >> 10) & 0xff) * 4u, c1 = fdb + ((pk >> 18) & 0xff) * 4u;
-      const float t00 = *reinterpret_cast<const float*>(fb + (o00 + c0));
-      const float t01 = *reinterpret_cast<const float*>(fb + (o01 + c0));
-      const float t10 = *reinterpret_cast<const float*>(fb + (o10 + c0));
-      const float t11 = *reinterpret_cast<const float*>(fb + (o11 + c0));
-      const float u00 = *reinterpret_cast<const float*>(fb + (o00 + c1));
-      const float u01 = *reinterpret_cast<const float*>(fb + (o01 + c1));
-      const float u10 = *reinterpret_cast<const float*>(fb + (o10 + c1));
-      const float u11 = *reinterpret_cast<const float*>(fb + (o11 + c1));
+      const LiftRecTaps q = lift_rec_decode((uint32_t)q4[0], (uint32_t)pk, __int_as_float(q4[2]),
+                                            __int_as_float(q4[3]), Cb, Wb);
+      const float w00 = q.w00, w01 = q.w01, w10 = q.w10, w11 = q.w11;
+      // (the eight score loads stay in front of the four feature loads)
+      const LiftScoreTaps st = lift_score_load(fb, q, fdb + lift_rec_bin0(pk) * 4u, fdb + lift_rec_bin1(pk) * 4u);
       if (FD128 || hl < nq) {
-        const f32x4 a00 = *reinterpret_cast<const f32x4*>(fb + (o00 + lane_off));
-        const f32x4 a01 = *reinterpret_cast<const f32x4*>(fb + (o01 + lane_off));
-        const f32x4 a10 = *reinterpret_cast<const f32x4*>(fb + (o10 + lane_off));
-        const f32x4 a11 = *reinterpret_cast<const f32x4*>(fb + (o11 + lane_off));
+        const f32x4 a00 = *reinterpret_cast<const f32x4*>(fb + (q.o00 + lane_off));
+        const f32x4 a01 = *reinterpret_cast<const f32x4*>(fb + (q.o01 + lane_off));
+        const f32x4 a10 = *reinterpret_cast<const f32x4*>(fb + (q.o10 + lane_off));
+        const f32x4 a11 = *reinterpret_cast<const f32x4*>(fb + (q.o11 + lane_off));
         const f32x2 p00 = {w00, w00}, p01 = {w01, w01}, p10 = {w10, w10}, p11 = {w11, w11};
         feat[r][0] = ((p00 * pair_lo(a00) + p01 * pair_lo(a01)) + p10 * pair_lo(a10)) + p11 * pair_lo(a11);
         feat[r][1] = ((p00 * pair_hi(a00) + p01 * pair_hi(a01)) + p10 * pair_hi(a10)) + p11 * pair_hi(a11);
       }
-      const float wb1 = (&wbs[0][0][0])[v * KMAX + r], wb0 = 1.f - wb1;
-      const float s0 = ((w00 * t00 + w01 * t01) + w10 * t10) + w11 * t11;
-      const float s1 = ((w00 * u00 + w01 * u01) + w10 * u10) + w11 * u11;
-      score[r] = wb0 * s0 + wb1 * s1;
+      score[r] = lift_score_blend(w00, w01, w10, w11, st, (&wbs[0][0][0])[v * KMAX + r]);
     }
     float* out = a.pooled + gv * d.out_stride;
     f32x2 mean2[2] = {{0.f, 0.f}, {0.f, 0.f}}, var2[2] = {{0.f, 0.f}, {0.f, 0.f}};
@@ -711,19 +549,11 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
       mean2[1] = feat[0][1];
       smax = score[0];
     } else if (nvis > 1) {
-      // jax.nn.softmax(..., where=valid, initial=0): shift = max(0, max valid score).
-      float m = 0.f;
-      smax = -INFINITY;
+      bool ok[KMAX];
 #pragma unroll
-      for (int r = 0; r < KMAX; ++r)
-        if (r < nvis) { m = fmaxf(m, score[r]); smax = fmaxf(smax, score[r]); }
-      float e[KMAX], den = 0.f;
-#pragma unroll
-      for (int r = 0; r < KMAX; ++r) {
-        if (r >= nvis) continue;
-        e[r] = expf(score[r] - m);
-        den += e[r];             // (the invisible slots of the masked form add +0: same sum)
-      }
+      for (int r = 0; r < KMAX; ++r) ok[r] = r < nvis;
+      float e[KMAX], den;
+      lift_softmax_weights<KMAX>(score, ok, e, den, smax);
       float wgt[KMAX];
 #pragma unroll
       for (int r = 0; r < KMAX; ++r) {
@@ -814,8 +644,8 @@ __global__ void project_points_kernel(int B, int V, int N, int fisheye,
   const int64_t bn = i / V;
   const int b = (int)(bn / N);
   const float* p = pts + bn * 3;
-  const Proj pr = project_one(cam + ((int64_t)b * V + v) * 11, Rt + ((int64_t)b * V + v) * 12, p[0],
-                              p[1], p[2], fisheye);
+  const LiftProj pr = lift_project(cam + ((int64_t)b * V + v) * 11, Rt + ((int64_t)b * V + v) * 12, p[0],
+                                   p[1], p[2], fisheye);
   p2d[i * 2 + 0] = pr.pi;
   p2d[i * 2 + 1] = pr.pj;
   vis[i] = pr.vis ? 1 : 0;
@@ -833,17 +663,20 @@ static int lift_pool_launch(const SnapLiftDesc* desc, const float* f_images,
   if (tap_recs && (!d.class_rows || !d.out_split || !d.valid_rows_only ||
                    (reinterpret_cast<uintptr_t>(tap_recs) & 15)))
     return SNAP_ERR_UNSUPPORTED;
-  if (d.B <= 0 || d.V <= 0 || d.h <= 0 || d.w <= 0 || d.N <= 0) return SNAP_ERR_BAD_SHAPE;
-  if (d.V > 32) return SNAP_ERR_UNSUPPORTED;
-  if (d.feature_dim % 4 != 0 || d.feature_dim > 128 || d.feature_dim <= 0) return SNAP_ERR_UNSUPPORTED;
   const bool dflt = d.weighted && d.use_variance && !d.add_minmax;
-  const int bins = d.weighted ? d.num_bins : 0;
-  if (d.C != d.feature_dim + bins || d.C % 4 != 0 || (d.weighted && d.num_bins < 1)) return SNAP_ERR_BAD_SHAPE;
-  const int chans = d.feature_dim * (1 + (d.use_variance ? 1 : 0) + (d.add_minmax ? 2 : 0)) + (d.weighted ? 1 : 0);
-  if (d.out_stride < chans || d.out_stride % 4 != 0) return SNAP_ERR_BAD_SHAPE;
+  const int chans = lift_pool_chans(d);
+  // (K and the limit of 8 selected views are checked further down, between this entry point's own)
+  LiftDescChecks ck;
+  ck.read_C = true;
+  ck.bins = d.weighted ? d.num_bins : 0;
+  ck.read_out_stride = true;
+  ck.chans = chans;
+  ck.selection = false;
+  const int vrc = lift_desc_validate(d, ck);
+  if (vrc != SNAP_OK) return vrc;
+  if (d.weighted && d.num_bins < 1) return SNAP_ERR_BAD_SHAPE;
   if (d.out_split) {      // default options' batched kernel only; whole slabs; score_max on a slab boundary
-    const int nsel_ = d.K == 0 ? d.V : d.K;
-    if (!dflt || nsel_ > 4 || d.feature_dim % 8 != 0 || d.out_stride < ((chans + 15) / 16) * 16 ||
+    if (!dflt || lift_nsel(d) > 4 || d.feature_dim % 8 != 0 || d.out_stride < ((chans + 15) / 16) * 16 ||
         (int64_t)d.B * d.V * d.h * d.w * d.C * 4 >= (1LL << 32))
       return SNAP_ERR_UNSUPPORTED;
   }
@@ -852,7 +685,7 @@ static int lift_pool_launch(const SnapLiftDesc* desc, const float* f_images,
   if (!(d.depth_max > d.depth_min) || !(d.depth_min > 0.f)) return SNAP_ERR_BAD_SHAPE;
   if ((reinterpret_cast<uintptr_t>(f_images) & 15) || (reinterpret_cast<uintptr_t>(pooled) & 15))
     return SNAP_ERR_BAD_SHAPE;
-  const int nsel = d.K == 0 ? d.V : d.K;
+  const int nsel = lift_nsel(d);
   constexpr int xcd_group = 64;     // workgroups per XCD-owned chunk (section 5h of DESIGN.md: settled)
   LiftArgs a{xcd_group, 0, 3, 3, 0, 0, 0, d, f_images, cam, Rt, points, pooled, valid, nullptr, nullptr, nullptr, tap_recs};
   const int64_t total = (int64_t)d.B * d.N;
@@ -861,7 +694,6 @@ static int lift_pool_launch(const SnapLiftDesc* desc, const float* f_images,
   if (d.grid_y > 0 && d.N % (d.grid_y * d.grid_z) != 0) return SNAP_ERR_BAD_SHAPE;
   const dim3 grid((unsigned)snap_cdiv(total, 8));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  constexpr bool batched = true;    // (the one-voxel-per-half-wave kernel remains for > 4 selected views)
   // 8 half-waves x 32 voxels per workgroup; with XCD groups the grid is padded to whole
   // (8 XCDs x G) rounds -- workgroups past the range exit at once
   const int64_t nb = snap_cdiv(total, 256);
@@ -885,21 +717,19 @@ static int lift_pool_launch(const SnapLiftDesc* desc, const float* f_images,
   // (the batched kernels address the taps by 32-bit byte offsets: f_images < 4 GB)
   const bool small = (int64_t)d.B * d.V * d.h * d.w * d.C * 4 < (1LL << 32);
   const bool fd128 = d.feature_dim == 128;
-  const bool use_b = (batched || d.out_split) && dflt && small;   // (out_split exists there only)
+  // (the one-voxel-per-half-wave kernel remains for > 4 selected views and the other fusion options)
+  const bool use_b = dflt && small;
   if (use_b && nsel <= 1) {
     if (fd128) hipLaunchKernelGGL((lift_pool_batched_kernel<1, true>), bgrid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((lift_pool_batched_kernel<1, false>), bgrid, dim3(256), 0, s, a);
   } else if (use_b && nsel <= 4) {
     if (fd128) hipLaunchKernelGGL((lift_pool_batched_kernel<4, true>), bgrid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((lift_pool_batched_kernel<4, false>), bgrid, dim3(256), 0, s, a);
-  } else if (nsel <= 1) {
-    hipLaunchKernelGGL(lift_pool_kernel<1>, grid, dim3(256), 0, s, a);
-  } else if (nsel <= 4) {
-    hipLaunchKernelGGL(lift_pool_kernel<4>, grid, dim3(256), 0, s, a);
-  } else if (nsel <= 8) {
-    hipLaunchKernelGGL(lift_pool_kernel<8>, grid, dim3(256), 0, s, a);
   } else {
-    return SNAP_ERR_UNSUPPORTED;
+    const int lrc = lift_nsel_ladder(nsel, [&](auto k) {
+      hipLaunchKernelGGL(lift_pool_kernel<decltype(k)::value>, grid, dim3(256), 0, s, a);
+    });
+    if (lrc != SNAP_OK) return lrc;
   }
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
@@ -934,9 +764,10 @@ static int launch_obs(const SnapLiftDesc& d, const float* f_images, const float*
   if (nsel > 8) return SNAP_ERR_UNSUPPORTED;
   LiftArgs a{0, 0, 3, 3, 0, 0, 0, d, f_images, cam, Rt, points, pooled, valid, obs_out, obs_feat, obs_in, nullptr};
   const dim3 grid((unsigned)snap_cdiv((int64_t)d.B * d.N, 8));
-  if (nsel <= 1) hipLaunchKernelGGL(lift_pool_kernel<1>, grid, dim3(256), 0, s, a);
-  else if (nsel <= 4) hipLaunchKernelGGL(lift_pool_kernel<4>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(lift_pool_kernel<8>, grid, dim3(256), 0, s, a);
+  const int lrc = lift_nsel_ladder(nsel, [&](auto k) {
+    hipLaunchKernelGGL(lift_pool_kernel<decltype(k)::value>, grid, dim3(256), 0, s, a);
+  });
+  if (lrc != SNAP_OK) return lrc;
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }

@@ -30,6 +30,7 @@
 //          order-independent, so the result is deterministic); a finalize pass turns untouched
 //          columns into zeros / valid = 0 (the reference's where(any valid, max, 0)).
 #include "conv_common.h"
+#include "lift_common.h"
 
 namespace {
 
@@ -142,13 +143,11 @@ __global__ __launch_bounds__(256, 2) void mlp2_pool_kernel(const MlpPoolArgs a) 
       const uint4* rp = reinterpret_cast<const uint4*>(a.recs + (int64_t)a.rows[r_ok[i] ? m : m0] * 8);
       const uint4 r0 = rp[0];
       g_s[i] = __uint_as_float(rp[1].x);
-      const float wi1 = __uint_as_float(r0.z), wj1 = __uint_as_float(r0.w);
-      const float wi0 = 1.f - wi1, wj0 = 1.f - wj1;                 // (lift.hip phase B, the same products)
-      g_w[i][0] = wi0 * wj0; g_w[i][1] = wi0 * wj1; g_w[i][2] = wi1 * wj0; g_w[i][3] = wi1 * wj1;
-      const uint32_t o00 = r0.x + 16u * (tid & 3);
-      const uint32_t o01 = o00 + ((r0.y >> 9) & 1u ? a.Cb : 0u);
-      const uint32_t o10 = o00 + ((r0.y >> 8) & 1u ? a.Wb : 0u);
-      g_o[i][0] = o00; g_o[i][1] = o01; g_o[i][2] = o10; g_o[i][3] = o10 + (o01 - o00);
+      // (lift_rec_decode: the weights and offsets lift.hip's phase B takes from the same four dwords)
+      const LiftRecTaps q = lift_rec_decode(r0.x + 16u * (tid & 3), r0.y, __uint_as_float(r0.z),
+                                            __uint_as_float(r0.w), a.Cb, a.Wb);
+      g_w[i][0] = q.w00; g_w[i][1] = q.w01; g_w[i][2] = q.w10; g_w[i][3] = q.w11;
+      g_o[i][0] = q.o00; g_o[i][1] = q.o01; g_o[i][2] = q.o10; g_o[i][3] = q.o11;
     }
   }
   auto load_a = [&](int ct) {

@@ -783,6 +783,27 @@ def test_lift_pool_full_width_and_maxdist():
   helpers.report('lift pooled fd128', pg.cpu()[~mism], pw[~mism], atol=2e-4, rtol=1e-4)
 
 
+@pytest.mark.parametrize('K,V,fd,nb', [(0, 3, 32, 8), (2, 5, 32, 8), (0, 4, 128, 32)])
+def test_lift_half_wave_and_batched_forward_kernels_agree_bitwise(K, V, fd, nb):
+  """The default options take lift_pool_batched_kernel, add_minmax takes lift_pool_kernel (one half-wave per
+  voxel, row = mean | var | max | min | score_max): same validity, and mean, variance and score_max are the
+  same bits -- both kernels build them from the same pieces of csrc/lift_common.h.  N = 1500 + 37: a ragged
+  last workgroup, and voxels with no, one and several observations all occur."""
+  f, cam, Rt, pts = _lift_scene(1, V, 12, 16, fd, nb, 1500 + 37, seed=90 + V)
+  kw = dict(K=K, fisheye=True, feature_dim=fd, num_bins=nb, depth_min_max=(1.0, 16.0))
+  args = [t.to(DEV) for t in (f, cam, Rt, pts)]
+  _, vis, _ = ops.project_points(args[1], args[2], args[3], True)
+  nobs = vis.sum(-1)
+  if K:
+    nobs = nobs.clamp(max=K)
+  assert int((nobs == 0).sum()) > 0 and int((nobs == 1).sum()) > 0 and int((nobs > 1).sum()) > 0
+  pb, vb = ops.lift_pool(*args, **kw)
+  ph, vh = ops.lift_pool(*args, add_minmax=True, **kw)
+  assert torch.equal(vb, vh)
+  assert torch.equal(pb[..., :2 * fd], ph[..., :2 * fd]), float((pb[..., :2 * fd] - ph[..., :2 * fd]).abs().max())
+  assert torch.equal(pb[..., 2 * fd], ph[..., 4 * fd])
+
+
 @pytest.mark.parametrize('X,Y,Z,K,V', [(11, 13, 7, 0, 3), (16, 8, 60, 0, 4), (9, 24, 60, 2, 5), (8, 8, 3, 0, 1),
                                        (301, 1, 60, 0, 1), (70, 3, 7, 0, 3), (33, 2, 9, 2, 4)])
 def test_lift_bev_tiled_traversal_is_a_pure_reordering(X, Y, Z, K, V):
