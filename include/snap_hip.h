@@ -972,6 +972,48 @@ int snap_vote_peaks_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, i
                         int32_t radius_xy, int32_t* index, float* score, int32_t* count, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* The pose DISTRIBUTION of a vote volume: what the exhaustive path (snap/models/pose_exhaustive_voting.py:108-124:
+ * the volume) needs to report a normalised posterior, its xy heat map and yaw histogram (snap/utils/grids.py:140-153:
+ * the interpolation of a grid at a continuous index) and the negative log-likelihood of a ground-truth pose, the
+ * counterpart of the sampled path's localization/nll (snap/models/bev_localizer.py:244-278).
+ * votes[R,Ho,Wo] f32 unnormalised log-scores, flat(r,a,b) = (r*Ho + a)*Wo + b; scale: a finite float > 0 (the
+ * temperature multiplier) with |scale * v| below the f32 maximum for every finite v (not checked; beyond it the
+ * cell still counts as contributing and the outputs are NaN).
+ *   A cell CONTRIBUTES iff its vote is finite.  -inf cells are masked and silently excluded (template_finalize's
+ *   low-overlap mark); NaN and +inf cells are excluded and counted.  With x = scale * v over the contributing set F:
+ *   log_z = log sum_F exp(x);
+ *   log_prob_xy[Ho,Wo]: log sum_r exp(x[r,a,b]) - log_z, -inf where no rotation contributes;
+ *   log_prob_r[R]:      log sum_ab exp(x[r,a,b]) - log_z, -inf where no pixel contributes (a rotation's cells
+ *     enter its sum as f32 weights relative to their 256-pixel tile's maximum: a cell more than ~87 below that
+ *     maximum underflows, so a rotation ALL of whose cells lie that far below their tiles' maxima also reads -inf;
+ *     its probability is then below R*Ho*Wo*2^-126);
+ *   with p = exp(x - log_z): E[a], E[b]; the central second moments Var a, Cov ab, Var b (index units);
+ *   C = E[cos(2 pi r / R)], S = E[sin(2 pi r / R)]; the circular mean rotation index atan2(S, C) R / (2 pi) wrapped
+ *   into [0, R); the resultant length hypot(C, S); the entropy log_z - E[x].
+ *   stats[16] = { 0: log_z, 1: max x over F, 2: E[a], 3: E[b], 4: Var a, 5: Cov ab, 6: Var b, 7: C, 8: S,
+ *                 9: mean rotation index, 10: resultant length, 11: entropy, 12: log_prob_gt, 13-15: written as 0 }.
+ *   count[3] = { contributing cells; NaN or +inf cells; 1 if the ground-truth sample is valid, else 0 }.
+ *   gt_index: NULL, or a DEVICE pointer to f32 [3] = (k, i, j) as exhaustive_tfm_to_index returns it, read by the
+ *   kernel (no host synchronisation).  log_prob_gt = the trilinear interpolation of x at (k, i, j) minus log_z:
+ *   circular in k (taps floor(k) mod R and (floor(k) + 1) mod R), taps floor and floor + 1 in i and j; a tap of
+ *   weight exactly 0 is not read (so i = Ho-1 and j = Wo-1 are inside).  Valid iff k, i, j are finite,
+ *   0 <= i <= Ho-1, 0 <= j <= Wo-1 and every tap of non-zero weight contributes; otherwise (and with NULL)
+ *   log_prob_gt = NaN and count[2] = 0.
+ *   F empty: log_z = max x = -inf, both marginals all -inf, stats[2..12] NaN.
+ * The volume is read from HBM once (each workgroup walks its own 256 pixels' cells twice).  Sums of one pixel's
+ * <= R terms and of one wave's 64 pixels of one rotation are f32, everything above is float64; every output is a
+ * float64 expression rounded to f32 once.  No atomics: every reduction order is fixed by (R, Ho, Wo), so two calls
+ * give the same bits.  Every output element is written by every call.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31; anything else returns SNAP_ERR_BAD_SHAPE before any launch
+ * (a NULL pointer other than gt_index SNAP_ERR_NULL; a scale that is not a finite number > 0 SNAP_ERR_UNSUPPORTED; a
+ * short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE).  workspace: snap_vote_posterior_workspace_bytes() bytes
+ * (0 = unsupported shape); it needs no initialisation and no launch touches a byte beyond that size.  Asynchronous
+ * on `stream`; the caller owns every buffer. */
+size_t snap_vote_posterior_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo);
+int snap_vote_posterior_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, float scale,
+                            const float* gt_index, float* log_prob_xy, float* log_prob_r, float* stats,
+                            int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Confidence-weighted vertical pooling: the 'softmax' / 'weighted' modes of VerticalPooling
  * (bev_mapper.py:63-78).  score_z = vol[m,z,:] . w + bias[0] (log_sigmoid of it when
  * log_sigmoid_scores != 0, i.e. 'weighted'); weights = softmax over the valid levels (all

@@ -294,10 +294,46 @@ def poses_from_votes(votes, grid, num_rotations, num_peaks=16, radius_r=1, radiu
               count=count)
 
 
-def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, method=None, **peaks):
+def posterior_from_votes(votes, grid, num_rotations, temperature=1.0, m_t_q_gt=None):
+  """The pose distribution p = softmax(temperature * votes) of a vote volume [R, 2H-1, 2W-1] over its finite cells
+  (``ops.vote_posterior``; ``temperature`` is the multiplier of the log-scores: exp(learned temperature), or 1) ->
+  dict of device tensors, nothing synchronised:
+
+  ``log_prob_xy`` [2H-1, 2W-1] / ``log_prob_r`` [R]: the xy heat map and the yaw histogram, in log space;
+  ``log_z``, ``entropy``; ``map_t_query_expected``: ``exhaustive_index_to_tfm`` of the continuous index (circular
+  mean rotation index, E[a], E[b]) -- the same +0.5 cell offset and corner-frame conjugation; ``cov_xy`` [2, 2]: the
+  covariance of the cell offset in metres^2, rows / columns in the map's (x, y) = index (a, b) order;
+  ``yaw_resultant``: the resultant length of the rotation distribution (1 = one rotation, 0 = no preferred one);
+  ``count`` int32 [3] = (finite cells, NaN / +inf cells, ground-truth sample valid); ``stats``: the op's raw row.
+  With ``m_t_q_gt`` (a Transform2D, map corner frame): ``nll`` = -log p interpolated at ``exhaustive_tfm_to_index``
+  of it (computed and read on the device) and ``nll_valid`` (bool; ``nll`` is NaN where it is False: the pose lies
+  outside the volume or touches a masked cell)."""
+  if votes.shape[0] != num_rotations:
+    raise ValueError(f'posterior_from_votes: {votes.shape[0]} vote planes for {num_rotations} rotations')
+  gt = None
+  if m_t_q_gt is not None:
+    gt = exhaustive_tfm_to_index(m_t_q_gt, grid, num_rotations).to(device=votes.device, dtype=torch.float32)
+    gt = gt.reshape(3).contiguous()
+  log_prob_xy, log_prob_r, stats, count = ops.vote_posterior(votes.contiguous(), temperature, gt)
+  cell2 = float(grid.cell_size) ** 2
+  out = dict(
+      log_prob_xy=log_prob_xy, log_prob_r=log_prob_r, log_z=stats[0], entropy=stats[11],
+      map_t_query_expected=exhaustive_index_to_tfm(torch.stack((stats[9], stats[2], stats[3])), grid, num_rotations),
+      cov_xy=torch.stack((stats[4:6], stats[5:7])) * cell2, yaw_resultant=stats[10], count=count, stats=stats)
+  if m_t_q_gt is not None:
+    out['nll'] = -stats[12]
+    out['nll_valid'] = count[2] != 0
+  return out
+
+
+def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, method=None, posterior=None, **peaks):
   """``exhaustive_pose_voting`` followed by ``poses_from_votes(**peaks)``: the dict of the latter plus ``votes``.
-  ``['map_t_query'][0]`` is the single best pose."""
+  ``['map_t_query'][0]`` is the single best pose.  ``posterior``: True, or a dict of keyword arguments of
+  ``posterior_from_votes`` (``temperature``, ``m_t_q_gt``), adds its result as ``['posterior']``."""
   votes = exhaustive_pose_voting(plane_q, plane_map, num_rotations, grid, conf_q=conf_q, method=method)
   out = poses_from_votes(votes, grid, num_rotations, **peaks)
   out['votes'] = votes
+  if posterior is not None and posterior is not False:
+    kw = {} if posterior is True else dict(posterior)
+    out['posterior'] = posterior_from_votes(votes, grid, num_rotations, **kw)
   return out

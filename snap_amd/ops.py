@@ -2235,6 +2235,43 @@ def vote_peaks(votes, k, radius_r=1, radius_xy=1):
   return index, score, count
 
 
+def vote_posterior(votes, scale=1.0, gt_index=None):
+  """The pose distribution of a vote volume: votes [R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked) ->
+  (log_prob_xy f32 [Ho, Wo], log_prob_r f32 [R], stats f32 [16], count int32 [3]) of p = softmax(scale * votes) over
+  the finite cells.  stats = (log_z, max x, E[a], E[b], Var a, Cov ab, Var b, C, S, mean rotation index, resultant
+  length, entropy, log_prob_gt, 0, 0, 0); count = (contributing cells, NaN or +inf cells, ground-truth sample valid).
+  ``gt_index``: None or a device f32 [3] = (k, i, j) (``exhaustive_tfm_to_index``), read on the device (the full
+  contract: snap_vote_posterior_f32 in include/snap_hip.h).  ``scale * v`` must stay below the f32 maximum for every
+  finite vote (not checked: that would read the volume); beyond it the outputs are NaN.  No host synchronisation."""
+  lib = _lib.load()
+  _f32(votes, 'votes')
+  if votes.dim() != 3:
+    raise ValueError(f'vote_posterior: votes [R, Ho, Wo], got {tuple(votes.shape)}')
+  R, Ho, Wo = votes.shape
+  scale = float(scale)
+  if not (scale > 0.0 and np.isfinite(scale)):
+    raise ValueError(f'vote_posterior: scale must be a finite number > 0, got {scale}')
+  if gt_index is not None:
+    _f32(gt_index, 'gt_index')
+    if tuple(gt_index.shape) != (3,) or gt_index.device != votes.device:
+      raise ValueError(f'vote_posterior: gt_index f32 [3] on {votes.device}, got {tuple(gt_index.shape)} on '
+                       f'{gt_index.device}')
+  wsb = lib.snap_vote_posterior_workspace_bytes(R, Ho, Wo) if votes.numel() < 2 ** 31 else 0
+  if wsb == 0:
+    raise ValueError(f'vote_posterior: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  ws = torch.empty((wsb // 8,), dtype=torch.int64, device=votes.device)   # (whole 8-byte words, 8-byte aligned)
+  log_prob_xy = torch.empty((Ho, Wo), dtype=torch.float32, device=votes.device)
+  log_prob_r = torch.empty((R,), dtype=torch.float32, device=votes.device)
+  stats = torch.empty((16,), dtype=torch.float32, device=votes.device)
+  count = torch.empty((3,), dtype=torch.int32, device=votes.device)
+  # algorithmic bytes: one read of the volume (the outputs are a plane and a few rows)
+  with _region('vote_posterior', 0.0, 4.0 * votes.numel()):
+    st = lib.snap_vote_posterior_f32(_p(votes), R, Ho, Wo, scale, _p(gt_index), _p(log_prob_xy), _p(log_prob_r),
+                                     _p(stats), _p(count), _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_posterior_f32')
+  return log_prob_xy, log_prob_r, stats, count
+
+
 # Module attributes of the switches: aliases of the tuning in force (read) / the process default (write).
 class _OpsModule(type(sys)):
   pass

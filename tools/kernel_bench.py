@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4)
 """
 import math
 import os
@@ -150,8 +150,82 @@ def vote_peaks_c4(iters):
         f.write(line + '\n')
 
 
+def torch_posterior(votes, scale):
+  """What a user would write without the kernel: logsumexp over the volume and along each axis, the marginals'
+  moments, the entropy from the full normalised volume (f32 throughout, centred second moments)."""
+  R, Ho, Wo = votes.shape
+  fin = torch.isfinite(votes)
+  x = torch.where(fin, votes * scale, float('-inf'))
+  log_z = torch.logsumexp(x.reshape(-1), 0)
+  lxy = torch.logsumexp(x, 0) - log_z
+  lr = torch.logsumexp(x.reshape(R, -1), 1) - log_z
+  pxy, pr = lxy.exp(), lr.exp()
+  a = torch.arange(Ho, device=votes.device, dtype=torch.float32)[:, None]
+  b = torch.arange(Wo, device=votes.device, dtype=torch.float32)[None, :]
+  ea, eb = (pxy * a).sum(), (pxy * b).sum()
+  ang = torch.arange(R, device=votes.device, dtype=torch.float32) * (2 * math.pi / R)
+  c, s = (pr * ang.cos()).sum(), (pr * ang.sin()).sum()
+  ent = log_z - ((x - log_z).exp() * torch.where(fin, x, 0.0)).sum()
+  stats = torch.stack([log_z, x.max(), ea, eb, (pxy * (a - ea) ** 2).sum(), (pxy * (a - ea) * (b - eb)).sum(),
+                       (pxy * (b - eb) ** 2).sum(), c, s, torch.atan2(s, c) * (R / (2 * math.pi)) % R,
+                       torch.hypot(c, s), ent])
+  return lxy, lr, stats, fin.sum()
+
+
+def vote_posterior_c4(iters):
+  """The pose distribution of the C4 vote volume (R = 36, 511 x 511; the border the voting masks for low overlap is
+  -inf): whole ops.vote_posterior calls against the torch composition on the same votes, blocks of the two
+  alternated, medians of single calls (kernel times: a rocprofv3 --kernel-trace --stats run of this case).  One JSON line; `json=<path>` as a third argument also writes it to that file."""
+  import json
+  R, H, scale = 36, 256, 8.0
+  Ho = Wo = 2 * H - 1
+  g = torch.Generator(device='cuda').manual_seed(0)
+  votes = torch.randn((R, Ho, Wo), device='cuda', generator=g) * 0.25
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  votes = torch.where((ov[:, None] * ov[None, :] > 0.05 * H * H)[None], votes, float('-inf')).contiguous()
+  lxy, lr, stats, count = ops.vote_posterior(votes, scale)
+  t_lxy, t_lr, t_stats, t_n = torch_posterior(votes, scale)
+  fin = torch.isfinite(t_lxy)
+  assert torch.equal(fin, torch.isfinite(lxy)) and int(count[0]) == int(t_n)
+  err = dict(log_prob_xy=float((lxy[fin] - t_lxy[fin]).abs().max()), log_prob_r=float((lr - t_lr).abs().max()),
+             stats=[float(v) for v in (stats[:12] - t_stats).abs()])
+  assert err['log_prob_xy'] < 1e-3 and err['log_prob_r'] < 1e-3 and max(err['stats'][:2]) < 1e-3, err
+  kernel = lambda: ops.vote_posterior(votes, scale)
+  compo = lambda: torch_posterior(votes, scale)
+  for fn in (kernel, compo):
+    for _ in range(5):
+      fn()
+  torch.cuda.synchronize()
+  ks, ts = [], []
+  for _ in range(5):
+    ks.append(median_ms(kernel, max(iters, 5)))
+    ts.append(median_ms(compo, max(iters // 2, 5)))
+  k_ms, t_ms = sorted(ks)[2], sorted(ts)[2]
+  by = 4.0 * votes.numel()
+  hbm_peak = 8.0e12               # B/s, the MI355X's HBM3E peak
+  res = dict(case='vote_posterior_c4', shape=[R, Ho, Wo], scale=scale, masked_fraction=round(1 - int(t_n) / votes.numel(), 4),
+             call_ms=round(k_ms, 4), call_ms_blocks=[round(v, 4) for v in ks],
+             torch_composition_ms=round(t_ms, 4), torch_composition_ms_blocks=[round(v, 4) for v in ts],
+             speedup=round(t_ms / k_ms, 2), volume_bytes=int(by), call_GBps_of_one_read=round(by / k_ms / 1e6, 1),
+             call_fraction_of_hbm_peak=round(by / (k_ms * 1e-3) / hbm_peak, 3),
+             torch_GBps_of_one_read=round(by / t_ms / 1e6, 1),
+             torch_fraction_of_hbm_peak=round(by / (t_ms * 1e-3) / hbm_peak, 3), hbm_peak_Bps=hbm_peak,
+             max_abs_difference_to_torch=err, timing='call_ms = one whole ops.vote_posterior call between device events '
+             'on an idle stream (its five torch.empty allocations, the ctypes call and both launches), NOT kernel time: '
+             'the two kernels alone are in profiles/vote_posterior_kernel_stats.csv; median of single calls, 5 blocks of '
+             'each alternated, median block', caveat='the 37.6 MB volume is read again on every repetition and fits the '
+             '256 MB Infinity Cache, so the read need not come from HBM: the fractions relate one read of the volume per '
+             'call to the HBM peak, whatever served the read')
+  line = json.dumps(res)
+  print(line)
+  for a in sys.argv[3:]:
+    if a.startswith('json='):
+      with open(a[5:], 'w') as f:
+        f.write(line + '\n')
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
   {'pose_score': pose_score, 'pose_score_c4': pose_score_c4, 'voting_c4': voting_c4,
-   'vote_peaks_c4': vote_peaks_c4}[which](iters)
+   'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4}[which](iters)
