@@ -1014,6 +1014,42 @@ int snap_vote_posterior_f32(const float* votes, int32_t R, int32_t Ho, int32_t W
                             const float* gt_index, float* log_prob_xy, float* log_prob_r, float* stats,
                             int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Multi-frame FUSION of aligned vote volumes: N query frames with known relative motion vote into the same map, and
+ * the anchor frame's pose (r, a, b) puts frame n at the index (r + dk, a + da, b + db) with (dk, da, db) a function
+ * of (n, r) alone (pose_exhaustive_voting.sequence_shift_table: the composition m_t_qn = m_t_q0 @ q0_t_qn pushed
+ * through snap/models/pose_exhaustive_voting.py:127-149).  The result is again a vote volume.
+ * volumes[N,R,Ho,Wo] f32 unnormalised log-scores (-inf = masked, as template_finalize writes it); shifts[N,R,3] f32
+ * on the DEVICE = (dk, da, db); weights[N] f32 on the DEVICE, or NULL for all 1; fused[R,Ho,Wo] f32;
+ * count[2] = { finite cells of `fused`; NaN cells of `fused` }.
+ *   POSITION.  Each of the three shifts d is split ONCE, in f32: l = floorf(d), f = d - l (one f32 subtraction; where
+ *   it rounds to 1, a tiny negative d, l += 1 and f = 0).  With these, frame n is sampled for output cell (r, a, b) at
+ *   k' = r + lk + fk, a' = a + la + fa, b' = b + lb + fb; the integer parts are exact.
+ *   TAPS.  In k: k0 = (r + lk) mod R and k1 = (k0 + 1) mod R with factors (1 - fk, fk); in a: a + la and a + la + 1
+ *   with (1 - fa, fa); in b alike; 1 - f is one f32 subtraction.  A tap's weight is the f32 product
+ *   (k factor * a factor) * b factor.  A tap one of whose factors is exactly 0 (an upper tap of an axis with f = 0) is
+ *   NOT READ: an integer shift reads one cell, and a' = Ho-1 is inside.  (A weight that underflows to 0 from non-zero
+ *   factors is still a tap.)
+ *   A frame is IN RANGE at a cell iff its shift row is finite and 0 <= a' <= Ho-1 and 0 <= b' <= Wo-1; a frame that
+ *   is not in range reads no tap.  Its sample is VALID iff it is in range and every tap is finite.
+ *   VALUE.  If any tap of any in-range frame is NaN or +inf: NaN (0x7fc00000), whatever the other frames.  Otherwise,
+ *   if any frame's sample is not valid (out of range, or a -inf tap): -inf -- the fused score exists only where EVERY
+ *   frame sees the pose.  Otherwise sum_n w_n * blend_n in f32, in this order: blend_n = fma(weight_t, tap_t, blend_n)
+ *   over the taps present in the order t = 4 kk + 2 aa + bb (k-major, then a, then b), fused = fma(w_n, blend_n, fused)
+ *   over n ascending, both starting from -0 (so a single tap of weight 1 keeps its bits).  A weight w_n = 0 still
+ *   applies the validity rule.  count is taken from the values written (an overflow to +-inf or a NaN weight counts as
+ *   what it produced).
+ * No atomics: count is the fixed-order fold of per-workgroup partials in a last small launch; two calls give the same
+ * bits.  Every element of fused and count is written by every call.
+ * Supported: 1 <= N <= 16, 1 <= R <= 64, Ho, Wo >= 1, N*R*Ho*Wo < 2^31; anything else returns SNAP_ERR_BAD_SHAPE
+ * before any launch (a NULL pointer other than weights SNAP_ERR_NULL, checked first; a short or not 8-byte aligned
+ * workspace SNAP_ERR_WORKSPACE).  workspace: snap_vote_fuse_workspace_bytes() bytes (0 = unsupported shape): the
+ * [N][R] table of 64-byte entries and the per-workgroup counts; it needs no initialisation and no launch touches a
+ * byte beyond that size.  Three launches, asynchronous on `stream`; the caller owns every buffer. */
+size_t snap_vote_fuse_workspace_bytes(int32_t N, int32_t R, int32_t Ho, int32_t Wo);
+int snap_vote_fuse_f32(const float* volumes, const float* shifts, const float* weights, int32_t N, int32_t R,
+                       int32_t Ho, int32_t Wo, float* fused, int32_t* count, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* Confidence-weighted vertical pooling: the 'softmax' / 'weighted' modes of VerticalPooling
  * (bev_mapper.py:63-78).  score_z = vol[m,z,:] . w + bias[0] (log_sigmoid of it when
  * log_sigmoid_scores != 0, i.e. 'weighted'); weights = softmax over the valid levels (all

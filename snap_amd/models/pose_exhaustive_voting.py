@@ -337,3 +337,77 @@ def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, me
     kw = {} if posterior is True else dict(posterior)
     out['posterior'] = posterior_from_votes(votes, grid, num_rotations, **kw)
   return out
+
+
+def sequence_shift_table(q0_t_q, grid, num_rotations):
+  """The shift table of ``ops.vote_fuse`` for a sequence of query frames with known relative motion: ``q0_t_q`` is a
+  Transform2D [N] in corner frames, frame n's pose in the anchor frame's coordinates, so m_t_qn = m_t_q0 @ q0_t_qn
+  (an identity for the anchor itself) -> f32 [N, R, 3] on the transform's device.
+
+  Row (n, r) = (dk, da, db): where the anchor pose has the index (r, a, b), frame n has the continuous index
+  (r + dk, a + da, b + db).  In centre frames q0_t_qn is (phi_n, rho_n) with rho_n = tau_n + (Rot(phi_n) - I) center,
+  center = grid.extent_meters / 2; composing it behind the anchor's (-2 pi r / R, xy_cell) and reading the index back
+  (``exhaustive_index_to_tfm`` / ``exhaustive_tfm_to_index``) gives dk = -phi_n R / (2 pi) wrapped into [0, R) and
+  (da, db) = Rot(-2 pi r / R) rho_n / cell_size: the +0.5 cell offsets cancel, and nothing depends on (a, b).
+  Computed in float64 and rounded to f32 once; an identity transform gives an all-zero row."""
+  R = int(num_rotations)
+  phi = torch.as_tensor(q0_t_q.angle).to(torch.float64).reshape(-1)
+  tau = torch.as_tensor(q0_t_q.t).to(torch.float64).reshape(-1, 2)
+  dev = phi.device
+  cx, cy = (float(v) / 2 for v in grid.extent_meters)
+  cos, sin = torch.cos(phi), torch.sin(phi)
+  rho_x = tau[:, 0] + (cos * cx - sin * cy - cx)
+  rho_y = tau[:, 1] + (sin * cx + cos * cy - cy)
+  theta = torch.arange(R, device=dev, dtype=torch.float64) * (2 * math.pi / R)
+  ct, st = torch.cos(theta)[None], torch.sin(theta)[None]
+  da = (ct * rho_x[:, None] + st * rho_y[:, None]) / grid.cell_size
+  db = (-st * rho_x[:, None] + ct * rho_y[:, None]) / grid.cell_size
+  dk = torch.remainder(-phi * (R / (2 * math.pi)), R).to(torch.float32)
+  dk = torch.where(dk >= R, torch.zeros_like(dk), dk)             # (a yaw just above 0 rounds up to R)
+  return (torch.stack((dk[:, None].expand(-1, R), da.to(torch.float32), db.to(torch.float32)), -1) + 0.0).contiguous()
+
+
+def fuse_votes(volumes, q0_t_q, grid, num_rotations, weights=None):
+  """Fuse the vote volumes of N query frames with known relative motion into the anchor frame's volume
+  (``ops.vote_fuse`` on ``sequence_shift_table``).  ``volumes``: f32 [N, R, 2H-1, 2W-1] or a list of N volumes;
+  ``q0_t_q``: Transform2D [N], corner frames, m_t_qn = m_t_q0 @ q0_t_qn; ``weights``: None or N per-frame factors
+  (a sequence of numbers or a tensor) -> (fused [R, 2H-1, 2W-1], count int32 [2] = (finite cells, NaN cells)).  The
+  fused score exists only where every frame sees the pose (-inf elsewhere): it is again a vote volume, for
+  ``poses_from_votes`` and ``posterior_from_votes``."""
+  if not isinstance(volumes, torch.Tensor):
+    volumes = torch.stack(list(volumes))
+  if volumes.dim() != 4 or volumes.shape[1] != num_rotations:
+    raise ValueError(f'fuse_votes: volumes [N, {num_rotations}, Ho, Wo], got {tuple(volumes.shape)}')
+  shifts = sequence_shift_table(q0_t_q, grid, num_rotations)
+  if shifts.shape[0] != volumes.shape[0]:
+    raise ValueError(f'fuse_votes: {volumes.shape[0]} volumes for {shifts.shape[0]} relative poses')
+  if weights is not None:
+    weights = torch.as_tensor(weights, dtype=torch.float32).to(volumes.device).contiguous()
+  return ops.vote_fuse(volumes.contiguous(), shifts.to(volumes.device), weights)
+
+
+def localize_sequence(planes_q, plane_map, num_rotations, grid, q0_t_q, conf_q=None, method=None, weights=None,
+                      posterior=None, **peaks):
+  """Sequence localization: ``exhaustive_pose_voting`` per query frame, ``fuse_votes`` with the frames' relative
+  poses ``q0_t_q`` (Transform2D [N], corner frames, the anchor first as an identity), then
+  ``poses_from_votes(fused, **peaks)``: the dict of ``localize_exhaustive`` with ``votes`` = the fused volume, plus
+  ``votes_frames`` [N, R, 2H-1, 2W-1], ``count_fused`` (``fuse_votes``' count) and ``map_t_query_frames``, a
+  Transform2D [K, N] = peak k composed with q0_t_qn (NaN past the found count).  ``conf_q``: None or one confidence
+  per frame; ``posterior`` as in ``localize_exhaustive``, on the fused volume."""
+  planes_q = list(planes_q)
+  conf_q = [None] * len(planes_q) if conf_q is None else list(conf_q)
+  if len(conf_q) != len(planes_q):
+    raise ValueError(f'localize_sequence: {len(conf_q)} confidences for {len(planes_q)} frames')
+  frames = torch.stack([exhaustive_pose_voting(pq, plane_map, num_rotations, grid, conf_q=cq, method=method)
+                        for pq, cq in zip(planes_q, conf_q)])
+  fused, count_fused = fuse_votes(frames, q0_t_q, grid, num_rotations, weights)
+  out = poses_from_votes(fused, grid, num_rotations, **peaks)
+  out['votes'] = fused
+  out['votes_frames'] = frames
+  out['count_fused'] = count_fused
+  rel = q0_t_q.to(device=fused.device, dtype=torch.float32)
+  out['map_t_query_frames'] = out['map_t_query'].unsqueeze(-1) @ rel.unsqueeze(0)
+  if posterior is not None and posterior is not False:
+    kw = {} if posterior is True else dict(posterior)
+    out['posterior'] = posterior_from_votes(fused, grid, num_rotations, **kw)
+  return out

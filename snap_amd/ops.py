@@ -2272,6 +2272,43 @@ def vote_posterior(votes, scale=1.0, gt_index=None):
   return log_prob_xy, log_prob_r, stats, count
 
 
+def vote_fuse(volumes, shifts, weights=None):
+  """Multi-frame fusion of aligned vote volumes: volumes [N, R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked),
+  shifts f32 [N, R, 3] = (dk, da, db) on the same device (``pose_exhaustive_voting.sequence_shift_table``), weights
+  None (all 1) or f32 [N] on the same device -> (fused f32 [R, Ho, Wo], count int32 [2]).  fused[r, a, b] =
+  sum_n w_n * (the trilinear blend, circular in k, of volume n at (r + dk, a + da, b + db)); -inf where any frame does
+  not see the pose (out of range, a non-finite shift row or a -inf tap), NaN where a tap is NaN / +inf; count =
+  (finite cells, NaN cells) of ``fused`` (the full contract: snap_vote_fuse_f32 in include/snap_hip.h).  No host
+  synchronisation."""
+  lib = _lib.load()
+  _f32(volumes, 'volumes')
+  if volumes.dim() != 4:
+    raise ValueError(f'vote_fuse: volumes [N, R, Ho, Wo], got {tuple(volumes.shape)}')
+  N, R, Ho, Wo = volumes.shape
+  for t, name, shape in ((shifts, 'shifts', (N, R, 3)), (weights, 'weights', (N,))):
+    if t is None and name == 'weights':
+      continue
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != volumes.device
+        or tuple(t.shape) != shape):
+      got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t)
+      raise ValueError(f'vote_fuse: {name} f32 {list(shape)} on {volumes.device}, got {got}')
+    _f32(t, name)
+  wsb = lib.snap_vote_fuse_workspace_bytes(N, R, Ho, Wo) if volumes.numel() < 2 ** 31 else 0
+  if wsb == 0:
+    raise ValueError(f'vote_fuse: unsupported N={N} R={R} Ho={Ho} Wo={Wo} (1 <= N <= 16, 1 <= R <= 64, Ho, Wo >= 1, '
+                     'N R Ho Wo < 2^31)')
+  ws = torch.empty((wsb // 8,), dtype=torch.int64, device=volumes.device)   # (whole 8-byte words, 8-byte aligned)
+  fused = torch.empty((R, Ho, Wo), dtype=torch.float32, device=volumes.device)
+  count = torch.empty((2,), dtype=torch.int32, device=volumes.device)
+  # algorithmic bytes: the output once and, per frame, the two source planes of every rotation (one where the table
+  # has an integer dk, which the host does not know without reading it: the upper figure is reported)
+  with _region('vote_fuse', 0.0, 4.0 * R * Ho * Wo * (1 + 2 * N)):
+    st = lib.snap_vote_fuse_f32(_p(volumes), _p(shifts), _p(weights), N, R, Ho, Wo, _p(fused), _p(count), _p(ws),
+                                ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_fuse_f32')
+  return fused, count
+
+
 # Module attributes of the switches: aliases of the tuning in force (read) / the process default (write).
 class _OpsModule(type(sys)):
   pass

@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4)
 """
 import math
 import os
@@ -224,8 +224,107 @@ def vote_posterior_c4(iters):
         f.write(line + '\n')
 
 
+def torch_fuse(volumes, shifts_host, weights_host):
+  """What a user would write without the kernel, per frame and rotation: ``roll`` in k, shifted slices in (a, b),
+  ``lerp`` along every axis with a fraction, -inf outside the slice and where any tap is -inf (finite votes otherwise: no NaN handling)."""
+  N, R, Ho, Wo = volumes.shape
+  total = torch.zeros((R, Ho, Wo), device=volumes.device)
+  dead = torch.zeros((R, Ho, Wo), dtype=torch.bool, device=volumes.device)
+  for n in range(N):
+    dk = float(shifts_host[n, 0, 0])
+    lk = math.floor(dk)
+    fk = dk - lk
+    lo = torch.roll(volumes[n], -lk, 0)
+    hi = torch.roll(volumes[n], -lk - 1, 0)
+    for r in range(R):
+      da, db = float(shifts_host[n, r, 1]), float(shifts_host[n, r, 2])
+      la, lb = math.floor(da), math.floor(db)
+      fa, fb = da - la, db - lb
+      ua, ub = int(fa > 0), int(fb > 0)                  # an upper tap only where the fraction is not 0
+      a0, a1 = max(0, -la), min(Ho, Ho - la - ua)
+      b0, b1 = max(0, -lb), min(Wo, Wo - lb - ub)
+      planes = []
+      for src in (lo[r], hi[r]) if fk > 0 else (lo[r],):
+        rows = []
+        for da_ in range(ua + 1):
+          c0 = src[a0 + la + da_:a1 + la + da_, b0 + lb:b1 + lb]
+          rows.append(torch.lerp(c0, src[a0 + la + da_:a1 + la + da_, b0 + lb + 1:b1 + lb + 1], fb) if ub else c0)
+        planes.append(torch.lerp(rows[0], rows[1], fa) if ua else rows[0])
+      bl = torch.lerp(planes[0], planes[1], fk) if fk > 0 else planes[0]
+      ok = torch.isfinite(bl)
+      inside = torch.zeros((Ho, Wo), dtype=torch.bool, device=volumes.device)
+      inside[a0:a1, b0:b1] = ok
+      dead[r] |= ~inside
+      total[r, a0:a1, b0:b1] += float(weights_host[n]) * torch.where(ok, bl, 0.0)
+  return torch.where(dead, float('-inf'), total)
+
+
+def vote_fuse_c4(iters):
+  """Multi-frame fusion at the C4 vote volume (R = 36, 511 x 511, N = 4 frames; the low-overlap border of every
+  frame's volume -inf; shifts from a motion of 1 m and 5 degrees per frame on the 256^2 grid of 0.2 m cells, all
+  fractional): whole ops.vote_fuse calls against the torch composition of the same result on the same inputs, blocks
+  of the two alternated, medians of single calls.  One JSON line; `json=<path>` as a third argument also writes it."""
+  import json
+  import numpy as np
+  from snap_amd.models import pose_exhaustive_voting as pev
+  from snap_amd.utils import geometry, grids
+  R, H, N = 36, 256, 4
+  Ho = Wo = 2 * H - 1
+  grid = grids.Grid2D((H, H), 0.2)
+  g = torch.Generator(device='cuda').manual_seed(0)
+  volumes = torch.randn((N, R, Ho, Wo), device='cuda', generator=g) * 0.25
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  volumes = torch.where((ov[:, None] * ov[None, :] > 0.05 * H * H)[None, None], volumes, float('-inf')).contiguous()
+  step = np.arange(N)
+  yaw = np.deg2rad(5.0) * step
+  q0_t_q = geometry.Transform2D(torch.tensor(yaw), torch.tensor(np.stack([0.93 * step, 0.37 * step], -1)))
+  shifts = pev.sequence_shift_table(q0_t_q, grid, R).cuda()
+  weights = torch.tensor([1.0, 0.9, 0.8, 0.7], device='cuda')
+  sh_host, w_host = shifts.cpu().numpy(), weights.cpu().numpy()
+  planes_read = sum(2 if (sh_host[n, 0, 0] % 1) else 1 for n in range(N))
+  fused, count = ops.vote_fuse(volumes, shifts, weights)
+  t_fused = torch_fuse(volumes, sh_host, w_host)
+  fin = torch.isfinite(t_fused)
+  assert torch.equal(fin, torch.isfinite(fused)) and int(count[0]) == int(fin.sum()) and int(count[1]) == 0
+  err = float((fused[fin] - t_fused[fin]).abs().max())
+  assert err < 1e-4, err
+  kernel = lambda: ops.vote_fuse(volumes, shifts, weights)
+  compo = lambda: torch_fuse(volumes, sh_host, w_host)
+  for fn, reps in ((kernel, 5), (compo, 2)):
+    for _ in range(reps):
+      fn()
+  torch.cuda.synchronize()
+  ks, ts = [], []
+  for _ in range(5):
+    ks.append(median_ms(kernel, max(iters, 5)))
+    ts.append(median_ms(compo, 3))
+  k_ms, t_ms = sorted(ks)[2], sorted(ts)[2]
+  by = 4.0 * R * Ho * Wo * (1 + planes_read)
+  hbm_peak = 8.0e12               # B/s, the MI355X's HBM3E peak
+  res = dict(case='vote_fuse_c4', shape=[N, R, Ho, Wo], masked_fraction_in=round(1 - float(torch.isfinite(volumes).float().mean()), 4),
+             masked_fraction_out=round(1 - int(count[0]) / fused.numel(), 4), planes_read=planes_read,
+             shift_rows_frame1=[[round(float(x), 4) for x in sh_host[1, r]] for r in (0, 9)],
+             call_ms=round(k_ms, 4), call_ms_blocks=[round(v, 4) for v in ks],
+             torch_composition_ms=round(t_ms, 4), torch_composition_ms_blocks=[round(v, 4) for v in ts],
+             speedup=round(t_ms / k_ms, 2), algorithmic_bytes=int(by), call_GBps_algorithmic=round(by / k_ms / 1e6, 1),
+             call_fraction_of_hbm_peak=round(by / (k_ms * 1e-3) / hbm_peak, 3), hbm_peak_Bps=hbm_peak,
+             max_abs_difference_to_torch=err, timing='call_ms = one whole ops.vote_fuse call between device events on an '
+             'idle stream (its three torch.empty allocations, the ctypes call and the three launches), NOT kernel time; '
+             'median of single calls, 5 blocks of each alternated, median block; the torch composition is N R = 144 '
+             'rounds of slices and lerps, 3 calls per block',
+             caveat='the 150 MB of volumes are read again on every repetition and fit the 256 MB Infinity Cache, so the '
+             'reads need not come from HBM: the fraction relates the algorithmic bytes of one call to the HBM peak, '
+             'whatever served them')
+  line = json.dumps(res)
+  print(line)
+  for a in sys.argv[3:]:
+    if a.startswith('json='):
+      with open(a[5:], 'w') as f:
+        f.write(line + '\n')
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
   {'pose_score': pose_score, 'pose_score_c4': pose_score_c4, 'voting_c4': voting_c4,
-   'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4}[which](iters)
+   'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4}[which](iters)
