@@ -1050,6 +1050,43 @@ int snap_vote_fuse_f32(const float* volumes, const float* shifts, const float* w
                        int32_t Ho, int32_t Wo, float* fused, int32_t* count, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* Dense plane ALIGNMENT SCORE at continuous poses: what a vote of the exhaustive voting measures (the correlation of
+ * the query plane with the map plane, normalised by the number of valid query cells), evaluated at poses that need
+ * not lie on the vote lattice (pose_exhaustive_voting.refine_poses: a lattice of sub-bin / sub-cell poses around
+ * every peak of ops.vote_peaks).
+ * fq[Hq,Wq,D] f32 / vq[Hq,Wq] u8: the query plane; fm[Hm,Wm,D] f32 / vm[Hm,Wm] u8: the map plane; poses[P,4] f32 on
+ * the DEVICE = (cos, sin, tx, ty), the map <- query transform in corner frames with tx, ty in CELL units;
+ * score[P] f32; overlap[P] i32.
+ *   SAMPLE.  For pose p and query cell (i, j) with vq[i,j] != 0, in f32 and in this order:
+ *   u = (cos*(i+0.5) - sin*(j+0.5)) + tx, v = (sin*(i+0.5) + cos*(j+0.5)) + ty (no contraction into fma).  The rest
+ *   is snap_rot_geom / snap_rot_sample of csrc/rotate_sample.h with cell = 1 on the map plane: the sample is inside iff
+ *   0 <= u < Hm and 0 <= v < Wm; with cu = u - 0.5, fu = floor(cu) the taps are rows clamp(fu), clamp(fu + 1) into
+ *   [0, Hm-1] with factors (1 - wu1, wu1), wu1 = cu - fu, columns alike, and the four weights are the f32 products of a
+ *   row and a column factor.  The cell COUNTS iff the sample is inside and all four taps are valid in vm, those of
+ *   weight zero included.
+ *   VALUE.  raw(p) = sum over the counted cells of sum_d fq[i,j,d] * mix_d, mix_d = ((w00 m00 + w01 m01) + w10 m10) +
+ *   w11 m11 of the taps' channel d; overlap(p) = the number of counted cells; tcount = the number of cells with
+ *   vq != 0; score(p) = raw(p) / tcount if overlap(p) > threshold (compared as f32), else -inf: the normaliser and the
+ *   rule of snap_template_finalize_f32, so a score compares with a vote.  (tcount = 0 with a negative threshold: NaN.)
+ *   A pose row with a non-finite entry gives score -inf and overlap 0.  A NaN / Inf feature reaches exactly the poses
+ *   one of whose counted cells has it as a tap (a zero-weight tap included: 0 * NaN) or as its own feature.
+ *   SUMMATION.  A cell's channel sum is f32: lane l of the cell's 8 lanes adds its products a_d * mix_d over the
+ *   channels d = 32 k + 4 l .. 32 k + 4 l + 3, k ascending, in one chain from 0, and the 8 lanes fold as a binary tree
+ *   (lane distance 1, 2, 4).  Everything above the cell is float64 in an order fixed by (Hq, Wq) alone (16 x 16 cell
+ *   tiles, row-major, 16 tiles per workgroup), and the score is the float64 quotient rounded to f32 once.
+ * No atomics: two calls give the same bits, and a pose's result does not depend on P or on the other rows.
+ * Every element of score and overlap is written by every call.
+ * Supported: 1 <= Hq, Wq, Hm, Wm <= 1024, D % 4 == 0 with 4 <= D <= 128, 1 <= P < 2^20, fq and fm 16-byte aligned;
+ * anything else returns SNAP_ERR_UNSUPPORTED before any launch (a NULL pointer SNAP_ERR_NULL, checked first; a short or
+ * not 8-byte aligned workspace SNAP_ERR_WORKSPACE).  workspace: snap_plane_align_score_workspace_bytes() bytes (0 =
+ * unsupported geometry): one 16-byte partial per (pose, workgroup) and tcount; it needs no initialisation and no
+ * launch touches a byte beyond that size.  Three launches, asynchronous on `stream`; the caller owns every buffer. */
+size_t snap_plane_align_score_workspace_bytes(int32_t Hq, int32_t Wq, int32_t Hm, int32_t Wm, int32_t D, int32_t P);
+int snap_plane_align_score_f32(const float* fq, const uint8_t* vq, const float* fm, const uint8_t* vm,
+                               const float* poses, int32_t Hq, int32_t Wq, int32_t Hm, int32_t Wm, int32_t D,
+                               int32_t P, float threshold, float* score, int32_t* overlap, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 /* Confidence-weighted vertical pooling: the 'softmax' / 'weighted' modes of VerticalPooling
  * (bev_mapper.py:63-78).  score_z = vol[m,z,:] . w + bias[0] (log_sigmoid of it when
  * log_sigmoid_scores != 0, i.e. 'weighted'); weights = softmax over the valid levels (all

@@ -2309,6 +2309,53 @@ def vote_fuse(volumes, shifts, weights=None):
   return fused, count
 
 
+def plane_align_score(fq, vq, fm, vm, poses, threshold):
+  """The alignment score of two BEV planes at continuous poses: fq f32 [Hq, Wq, D] / vq bool or uint8 [Hq, Wq] (the
+  query plane), fm f32 [Hm, Wm, D] / vm [Hm, Wm] (the map plane), poses f32 [P, 4] = (cos, sin, tx, ty) on the same
+  device, the map <- query transform in corner frames with tx, ty in cells -> (score f32 [P], overlap int32 [P]).
+  score = (sum over the valid query cells whose bilinear map sample is inside and has four valid taps of fq . the
+  sampled fm) / (number of valid query cells) where more than ``threshold`` cells count, -inf elsewhere and for a
+  non-finite pose row: ``template_finalize``'s normaliser and rule, so a score compares with a vote (the full contract:
+  snap_plane_align_score_f32 in include/snap_hip.h).  No atomics, the same bits on every call and for every grouping
+  of the poses.  No host synchronisation."""
+  lib = _lib.load()
+  _f32(fq, 'fq'); _f32(fm, 'fm')
+  if fq.dim() != 3 or fm.dim() != 3 or fq.shape[-1] != fm.shape[-1]:
+    raise ValueError(f'plane_align_score: fq [Hq, Wq, D] and fm [Hm, Wm, D], got {tuple(fq.shape)} / {tuple(fm.shape)}')
+  Hq, Wq, D = fq.shape
+  Hm, Wm = fm.shape[:2]
+  for t, name, shape in ((vq, 'vq', (Hq, Wq)), (vm, 'vm', (Hm, Wm))):
+    if (not isinstance(t, torch.Tensor) or t.dtype not in (torch.bool, torch.uint8) or t.device != fq.device
+        or tuple(t.shape) != shape):
+      got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t)
+      raise ValueError(f'plane_align_score: {name} bool / uint8 {list(shape)} on {fq.device}, got {got}')
+    _mask(t, name)
+  if (not isinstance(poses, torch.Tensor) or poses.dtype != torch.float32 or poses.device != fq.device
+      or fm.device != fq.device or poses.dim() != 2 or poses.shape[1] != 4):
+    got = f'{poses.dtype} {tuple(poses.shape)} on {poses.device}' if isinstance(poses, torch.Tensor) else type(poses)
+    raise ValueError(f'plane_align_score: poses f32 [P, 4] and fm on {fq.device}, got {got} / {fm.device}')
+  _f32(poses, 'poses')
+  P = poses.shape[0]
+  threshold = float(threshold)
+  if threshold != threshold:
+    raise ValueError('plane_align_score: threshold is NaN')
+  wsb = lib.snap_plane_align_score_workspace_bytes(Hq, Wq, Hm, Wm, D, P) if P < 2 ** 31 else 0
+  if wsb == 0 or fq.data_ptr() % 16 or fm.data_ptr() % 16:
+    raise ValueError(f'plane_align_score: unsupported query {Hq}x{Wq} map {Hm}x{Wm} D={D} P={P} (extents 1 .. 1024, '
+                     'D % 4 == 0 with 4 <= D <= 128, 1 <= P < 2^20, 16-byte aligned planes)')
+  ws = torch.empty((wsb // 8,), dtype=torch.int64, device=fq.device)   # (whole 8-byte words, 8-byte aligned)
+  score = torch.empty((P,), dtype=torch.float32, device=fq.device)
+  overlap = torch.empty((P,), dtype=torch.int32, device=fq.device)
+  # algorithmic work: per pose and query cell, four taps of D channels, one multiply-add each (2 * 4 * D flop);
+  # algorithmic bytes: both planes once, the poses, the outputs
+  with _region('plane_align_score', 2.0 * 4 * P * Hq * Wq * D,
+               4.0 * (fq.numel() + fm.numel()) + vq.numel() + vm.numel() + 24.0 * P):
+    st = lib.snap_plane_align_score_f32(_p(fq), _p(vq), _p(fm), _p(vm), _p(poses), Hq, Wq, Hm, Wm, D, P, threshold,
+                                        _p(score), _p(overlap), _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_plane_align_score_f32')
+  return score, overlap
+
+
 # Module attributes of the switches: aliases of the tuning in force (read) / the process default (write).
 class _OpsModule(type(sys)):
   pass

@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_refine_c4)
 """
 import math
 import os
@@ -323,8 +323,86 @@ def vote_fuse_c4(iters):
         f.write(line + '\n')
 
 
+def vote_refine_c4(iters):
+  """Peak refinement at the C4 planes (256^2 cells, D = 32, R = 36, 16 peaks x the default 11 x 9 x 9 lattice = 14 256
+  poses; 10 % / 5 % invalid cells): whole ops.plane_align_score calls, median of single calls, against the only way to
+  get the same scores without the kernel: one ops.interpolate_nd of the map at the query cells' positions and a torch
+  reduction PER POSE, timed on a subset of the poses and scaled to all of them.  One JSON line; `json=<path>` as a
+  third argument also writes it."""
+  import json
+  import numpy as np
+  from snap_amd.models import pose_exhaustive_voting as pev
+  from snap_amd.utils import grids
+  H, D, R, K = 256, 32, 36, 16
+  grid = grids.Grid2D((H, H), 0.2)
+  g = torch.Generator(device='cuda').manual_seed(0)
+  fq = torch.randn((H, H, D), device='cuda', generator=g)
+  fm = torch.randn((H, H, D), device='cuda', generator=g)
+  vq = torch.rand((H, H), device='cuda', generator=g) > 0.10
+  vm = torch.rand((H, H), device='cuda', generator=g) > 0.05
+  rng = np.random.default_rng(0)
+  index = torch.tensor(np.stack([rng.integers(0, R, K), rng.integers(H - 41, H + 40, K), rng.integers(H - 41, H + 40, K)],
+                                -1).astype(np.int32), device='cuda')
+  cont, poses = pev.refine_lattice(index, grid, R, (H, H))
+  P = poses.shape[0]
+  thr = 0.05 * H * H
+  score, overlap = ops.plane_align_score(fq, vq, fm, vm, poses, thr)
+  ii, jj = torch.meshgrid(torch.arange(H, device='cuda') + 0.5, torch.arange(H, device='cuda') + 0.5, indexing='ij')
+  fq_rows, tcount = fq.reshape(-1, D), vq.sum()
+
+  def composed(rows):
+    out = []
+    for c, s, tx, ty in rows:
+      pts = torch.stack(((c * ii - s * jj) + tx, (s * ii + c * jj) + ty), -1).reshape(-1, 2)
+      values, valid = ops.interpolate_nd(fm, pts, vm)
+      ok = valid & vq.reshape(-1)
+      raw = torch.where(ok, (fq_rows * values).sum(-1), 0.0).sum(dtype=torch.float64)
+      out.append(torch.where(ok.sum() > thr, (raw / tcount).float(), float('-inf')))
+    return torch.stack(out)
+
+  sub = list(range(0, P, P // 32))[:32]
+  sub_rows = [tuple(poses[i]) for i in sub]
+  t_score = composed(sub_rows)
+  k_sub = score[torch.tensor(sub, device='cuda')]
+  fin = torch.isfinite(t_score)
+  assert torch.equal(fin, torch.isfinite(k_sub)) and bool(fin.any())
+  err = float((t_score[fin] - k_sub[fin]).abs().max())
+  assert err < 1e-4, err
+  kernel = lambda: ops.plane_align_score(fq, vq, fm, vm, poses, thr)
+  compo = lambda: composed(sub_rows)
+  for fn in (kernel, compo):
+    for _ in range(2):
+      fn()
+  torch.cuda.synchronize()
+  ks, ts = [], []
+  for _ in range(3):
+    ks.append(median_ms(kernel, max(iters, 3)))
+    ts.append(median_ms(compo, 3))
+  k_ms, t_ms = sorted(ks)[1], sorted(ts)[1] * (P / len(sub))
+  flop = 2.0 * 4 * P * H * H * D
+  res = dict(case='vote_refine_c4', query=[H, H, D], map=[H, H, D], rotations=R, peaks=K, lattice=[11, 9, 9], poses=P,
+             valid_fraction=[round(float(vq.float().mean()), 4), round(float(vm.float().mean()), 4)],
+             finite_scores=int(torch.isfinite(score).sum()), mean_overlap=round(float(overlap.float().mean()), 1),
+             call_ms=round(k_ms, 3), call_ms_blocks=[round(v, 3) for v in ks], flop=flop,
+             call_TFLOPs=round(flop / (k_ms * 1e-3) / 1e12, 3),
+             interpolate_loop_ms_scaled=round(t_ms, 1), interpolate_loop_poses_timed=len(sub),
+             interpolate_loop_ms_per_pose=round(t_ms / P, 4), speedup=round(t_ms / k_ms, 1),
+             max_abs_difference_to_loop=err,
+             timing='call_ms = one whole ops.plane_align_score call between device events on an idle stream (its three '
+             'torch.empty allocations, the ctypes call and the three launches), NOT kernel time; median of single calls, '
+             '3 blocks alternated with the loop, median block; flop = 2 * 4 * P * Hq * Wq * D counts every query cell '
+             'of every pose, counted or not; the loop is timed on every (P / 32)-th pose and scaled by P / 32')
+  line = json.dumps(res)
+  print(line)
+  for a in sys.argv[3:]:
+    if a.startswith('json='):
+      with open(a[5:], 'w') as f:
+        f.write(line + '\n')
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
   {'pose_score': pose_score, 'pose_score_c4': pose_score_c4, 'voting_c4': voting_c4,
-   'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4}[which](iters)
+   'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4,
+   'vote_refine_c4': vote_refine_c4}[which](iters)
