@@ -1050,6 +1050,53 @@ int snap_vote_fuse_f32(const float* volumes, const float* shifts, const float* w
                        int32_t Ho, int32_t Wo, float* fused, int32_t* count, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* Recursive pose FILTER over vote volumes (a histogram filter on the (r, a, b) lattice): one belief volume is carried
+ * from frame to frame.  PREDICT transports the belief by the odometry increment and diffuses it by the odometry's
+ * uncertainty; UPDATE multiplies by the new frame's votes and normalises.  The result is again a log-space vote volume
+ * (-inf = impossible pose) for snap_vote_peaks_f32 / snap_vote_posterior_f32.
+ * belief[R,Ho,Wo] f32 log-space, or NULL (no predict: the prior is uniform, exactly as uniform_mix = 1);
+ * votes[R,Ho,Wo] f32; on the DEVICE: taps_k[Tk] f32 with first offset lk, taps_a[R,Ta] / taps_b[R,Tb] f32 and
+ * offsets[R,2] i32 = (la, lb), the first offsets per OUTPUT rotation (pose_exhaustive_voting.motion_taps);
+ * belief_out[R,Ho,Wo] f32 (must not overlap belief or votes: it holds intermediates during the call); stats[4] f32;
+ * count[4] i32.
+ *   TAPS (precondition, not checked): every tap is finite and >= 0, and either 0 or >= 2^-20.
+ *   PREDICT.  M = the largest finite value of belief (exact).  A NaN or +inf cell is a caller error: no mass, counted.
+ *   d = belief - M is ONE f32 subtraction; the cell has the mass p = fl32(exp((double)d)) iff d >= -40, else exactly 0
+ *   (-inf cells, and anything below e^-40 of the peak): with the tap precondition every partial product below is a
+ *   normal f32 number.  Three passes, in this order, each an f32 fma chain over its taps ascending, from 0, the
+ *   intermediate volumes stored as f32:
+ *     t0[r,a,b] = sum_tk taps_k[tk]   * p [(r + lk + tk) mod R, a, b]    (mathematical modulo: k is circular);
+ *     t1[r,a,b] = sum_ta taps_a[r,ta] * t0[r, a + la[r] + ta, b];
+ *     t2[r,a,b] = sum_tb taps_b[r,tb] * t1[r, a, b + lb[r] + tb];
+ *   a source row / column outside the volume contributes 0 (the mass that leaves is lost).  The rotation pass works at
+ *   the source cell and the xy passes use the output rotation's tables, as in snap_vote_fuse_f32.  S = sum t2, float64.
+ *   UPDATE, float64 per cell, n = R*Ho*Wo, eps = uniform_mix: prior = ((1 - eps) * t2) / S + eps / n (the first term
+ *   is 0 when S == 0 and with belief == NULL); u = (double)scale * votes + log(prior), log(0) = -inf; a -inf vote
+ *   gives -inf; a NaN or +inf vote gives NaN (0x7fc00000) and the cell is left out of the normalisation;
+ *   log_z = log sum exp(u) over the finite cells (float64); belief_out = fl32(u - log_z).  When no cell is finite,
+ *   log_z = -inf and every cell that is not NaN is -inf.
+ *   stats = { log_z (the log evidence of the frame under the predicted prior); S / sum p, the share of the mass that
+ *   stayed in the volume (1 with belief == NULL, 0 when no cell has mass); M (-inf with belief == NULL or without a
+ *   finite cell); the largest belief_out (NaN cells aside; -inf when there is none) }.
+ *   count = { finite cells of belief_out; NaN or +inf cells of belief; NaN cells of belief_out; cells of belief with
+ *   mass } (the belief's counts are 0 with belief == NULL).
+ * Seven launches of min(R * ceil(Ho*Wo/256), 2048) workgroups of 256 threads (the last: one workgroup; three with
+ * belief == NULL), a tile = one rotation and 256 consecutive pixels: the peak; the rotation pass with exp fused; the
+ * row pass; the column pass; the evidence (log_z); the normalisation; the statistics.  t0 and t2 live in belief_out, t1
+ * in the workspace.  No atomics: everything above the cell is float64 (counts int32) in an order fixed by (R, Ho, Wo),
+ * so two calls give the same bits.  Every element of belief_out, stats and count is written by every call.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32; anything else returns
+ * SNAP_ERR_BAD_SHAPE before any launch (a NULL pointer other than belief SNAP_ERR_NULL, checked first; a scale that is
+ * not a finite number > 0 or a uniform_mix outside [0, 1] SNAP_ERR_UNSUPPORTED; a short or not 8-byte aligned workspace
+ * SNAP_ERR_WORKSPACE).  workspace: snap_vote_filter_workspace_bytes() bytes (0 = unsupported shape): t1 and the
+ * per-workgroup partials; it needs no initialisation and no launch touches a byte beyond that size.  Asynchronous on
+ * `stream`; the caller owns every buffer. */
+size_t snap_vote_filter_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t Tk, int32_t Ta, int32_t Tb);
+int snap_vote_filter_f32(const float* belief, const float* votes, const float* taps_k, int32_t lk, const float* taps_a,
+                         const float* taps_b, const int32_t* offsets, int32_t R, int32_t Ho, int32_t Wo, int32_t Tk,
+                         int32_t Ta, int32_t Tb, float scale, float uniform_mix, float* belief_out, float* stats,
+                         int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Dense plane ALIGNMENT SCORE at continuous poses: what a vote of the exhaustive voting measures (the correlation of
  * the query plane with the map plane, normalised by the number of valid query cells), evaluated at poses that need
  * not lie on the vote lattice (pose_exhaustive_voting.refine_poses: a lattice of sub-bin / sub-cell poses around

@@ -274,6 +274,9 @@ SIGNATURES = {
     'snap_vote_posterior_f32': (c_int, [ptr, c_int, c_int, c_int, c_float, ptr, ptr, ptr, ptr, ptr, ptr, c_size, ptr]),
     'snap_vote_fuse_workspace_bytes': (c_size, [c_int] * 4),
     'snap_vote_fuse_f32': (c_int, [ptr, ptr, ptr, c_int, c_int, c_int, c_int, ptr, ptr, ptr, c_size, ptr]),
+    'snap_vote_filter_workspace_bytes': (c_size, [c_int] * 6),
+    'snap_vote_filter_f32': (
+        c_int, [ptr, ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float, c_float, ptr, ptr, ptr, ptr, c_size, ptr]),
     'snap_plane_align_score_workspace_bytes': (c_size, [c_int] * 6),
     'snap_plane_align_score_f32': (
         c_int, [ptr] * 5 + [c_int] * 6 + [c_float, ptr, ptr, ptr, c_size, ptr]),

@@ -1,0 +1,453 @@
+// Recursive pose filter over exhaustive vote volumes: snap_vote_filter_f32 (include/snap_hip.h).
+//
+// belief [R, Ho, Wo] f32 is the log-space belief after the previous frame (-inf = impossible pose), votes [R, Ho, Wo]
+// the new frame's vote volume.  PREDICT: the belief's masses p = exp(belief - M) are transported and diffused by three
+// separable tap passes (rotation, circular; rows and columns with the OUTPUT rotation's tables, as in vote_fuse) into
+// t2, S = sum t2.  UPDATE: u = scale * votes + log((1 - eps) t2 / S + eps / n), belief_out = u - logsumexp(u).
+//
+// A tile is one rotation and 256 consecutive pixels p = a * Wo + b, one cell per thread; every launch has
+// min(tiles, 2048) workgroups of 256 threads striding over the tiles (the tap rows of a tile are uniform: scalar loads).
+// Launch 1 (vote_filter_peak_kernel):   per workgroup the largest finite belief and the count of NaN / +inf cells.
+// Launch 2 (vote_filter_rotate_kernel): every workgroup folds the partial maxima into M (a maximum: exact, the same
+//   bits everywhere); t0 = the k-tap chain over p, exp fused (a source cell's exp is recomputed by each of its <= Tk
+//   readers: the re-reads of the belief are L2 hits, t0 is the only store); sum p (float64) and the count of cells
+//   with mass from each thread's own cell.  t0 lives in belief_out.
+// Launch 3 (vote_filter_rows_kernel):   t1 = the a-tap chain over t0 (each tap a wave-contiguous run of a source row),
+//   into the workspace.
+// Launch 4 (vote_filter_cols_kernel):   t2 = the b-tap chain over t1, into belief_out; per workgroup sum t2 (float64).
+// Launch 5 (vote_filter_evidence_kernel): every workgroup folds the partial sums into S; per cell u (float64), folded
+//   into a running (maximum, sum of exp relative to it) pair per thread, then per workgroup.
+// Launch 6 (vote_filter_normalise_kernel): every workgroup folds the pairs into log_z, recomputes u (the same
+//   expression: the same bits) and writes belief_out = fl32(u - log_z) over t2 in place; per workgroup the counts of
+//   finite / NaN cells written and their maximum.  Workgroup 0 writes stats[0].
+// Launch 7 (vote_filter_finish_kernel, one workgroup): the remaining stats and count.
+// With belief == NULL launches 1-4 are skipped (uniform prior).  No atomics and no inter-workgroup hand-off inside a
+// launch: every sum is a per-thread chain over its tiles, a wave tree, the four waves, then the workgroups in a strided
+// chain per thread and the same tree -- an order fixed by (R, Ho, Wo) alone.
+// HBM traffic (n = R Ho Wo cells of 4 bytes): reads belief 2 (+ L2 re-reads), t0, t1, t2 twice, votes twice; writes
+// t0, t1, t2, belief_out: 12 n cells with a belief, 3 n without.
+#include "common.h"
+
+namespace {
+
+constexpr int FL_NT = 256;                  // threads = cells of a tile
+constexpr int FL_WAVES = FL_NT / SNAP_WAVE;
+constexpr int FL_MAX_R = 64;
+constexpr int FL_MAX_TK = 16;
+constexpr int FL_MAX_TXY = 32;
+constexpr int FL_MAX_GROUPS = 2048;
+constexpr float FL_CUT = -40.f;             // a cell carries mass iff belief - M >= FL_CUT
+
+// per-workgroup partials: double [groups][4], int32 [groups][4], float [groups][2]
+enum { FL_D_SUMP = 0, FL_D_SUMT2 = 1, FL_D_LSE_M = 2, FL_D_LSE_S = 3 };
+enum { FL_I_BAD = 0, FL_I_MASS = 1, FL_I_FIN = 2, FL_I_NAN = 3 };
+enum { FL_F_PEAK = 0, FL_F_OUTMAX = 1 };
+
+__device__ __forceinline__ bool fl_finite(float v) { return fabsf(v) < INFINITY; }   // false for NaN and +-inf
+
+// ---- workgroup reductions: a wave tree (lane 0's value is used), the four waves in order; the same bits in every
+// thread.  `sh` is free again on return.
+__device__ __forceinline__ double fl_block_sum(double v, double* sh) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  __syncthreads();
+  return s;
+}
+__device__ __forceinline__ int fl_block_sum(int v, int* sh) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const int s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  __syncthreads();
+  return s;
+}
+__device__ __forceinline__ float fl_block_max(float v, float* sh) {
+  v = wave_max(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const float m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+  __syncthreads();
+  return m;
+}
+
+// (m, s) = (maximum, sum of exp(u - m)) of a set of finite u; the empty set is (-inf, 0).  Merge another set in.
+__device__ __forceinline__ void fl_lse_merge(double* m, double* s, double m2, double s2) {
+  if (m2 == -(double)INFINITY) return;
+  if (*m == -(double)INFINITY) {
+    *m = m2;
+    *s = s2;
+  } else if (m2 > *m) {
+    *s = *s * exp(*m - m2) + s2;
+    *m = m2;
+  } else {
+    *s += s2 * exp(m2 - *m);
+  }
+}
+__device__ __forceinline__ void fl_block_lse(double* m, double* s, double (*sh)[2]) {
+  for (int o = 32; o > 0; o >>= 1) {        // (lane 0 ends with the tree over all 64 lanes; only it is used)
+    const double m2 = __shfl_xor(*m, o), s2 = __shfl_xor(*s, o);
+    fl_lse_merge(m, s, m2, s2);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    sh[threadIdx.x >> 6][0] = *m;
+    sh[threadIdx.x >> 6][1] = *s;
+  }
+  __syncthreads();
+  double mm = sh[0][0], ss = sh[0][1];
+  for (int w = 1; w < FL_WAVES; ++w) fl_lse_merge(&mm, &ss, sh[w][0], sh[w][1]);
+  __syncthreads();
+  *m = mm;
+  *s = ss;
+}
+
+// The fold of one column of the per-workgroup partials, by a whole workgroup.
+__device__ __forceinline__ double fl_fold_sum(const double* __restrict__ dpart, int col, int groups, double* sh) {
+  double v = 0.0;
+  for (int g = threadIdx.x; g < groups; g += FL_NT) v += dpart[(size_t)g * 4 + col];
+  return fl_block_sum(v, sh);
+}
+__device__ __forceinline__ int fl_fold_sum(const int32_t* __restrict__ ipart, int col, int groups, int* sh) {
+  int v = 0;
+  for (int g = threadIdx.x; g < groups; g += FL_NT) v += ipart[(size_t)g * 4 + col];
+  return fl_block_sum(v, sh);
+}
+__device__ __forceinline__ float fl_fold_max(const float* __restrict__ fpart, int col, int groups, float* sh) {
+  float v = -INFINITY;
+  for (int g = threadIdx.x; g < groups; g += FL_NT) v = fmaxf(v, fpart[(size_t)g * 2 + col]);
+  return fl_block_max(v, sh);
+}
+
+// The mass of a belief cell relative to the peak M: one f32 subtraction, the cut, exp in float64 rounded once.
+__device__ __forceinline__ float fl_mass(float v, float M) {
+  const float d = v - M;
+  return (fl_finite(v) && d >= FL_CUT) ? (float)exp((double)d) : 0.f;
+}
+
+// ---- launch 1
+__global__ __launch_bounds__(FL_NT) void vote_filter_peak_kernel(const float* __restrict__ belief, int n,
+                                                                 float* __restrict__ fpart, int32_t* __restrict__ ipart) {
+  __shared__ float shf[FL_WAVES];
+  __shared__ int shi[FL_WAVES];
+  float m = -INFINITY;
+  int bad = 0;
+  for (int64_t i = (int64_t)blockIdx.x * FL_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FL_NT) {
+    const float v = belief[i];
+    if (fl_finite(v))
+      m = fmaxf(m, v);
+    else if (!(v == -INFINITY))
+      ++bad;                                // NaN or +inf
+  }
+  m = fl_block_max(m, shf);
+  bad = fl_block_sum(bad, shi);
+  if (threadIdx.x == 0) {
+    fpart[(size_t)blockIdx.x * 2 + FL_F_PEAK] = m;
+    ipart[(size_t)blockIdx.x * 4 + FL_I_BAD] = bad;
+  }
+}
+
+// ---- launch 2
+__global__ __launch_bounds__(FL_NT) void vote_filter_rotate_kernel(const float* __restrict__ belief,
+                                                                   const float* __restrict__ taps_k, int lk, int R, int P,
+                                                                   int Tk, int tiles_per_plane, int tiles,
+                                                                   const float* __restrict__ fpart, float* __restrict__ t0,
+                                                                   double* __restrict__ dpart, int32_t* __restrict__ ipart) {
+  __shared__ float shf[FL_WAVES];
+  __shared__ double shd[FL_WAVES];
+  __shared__ int shi[FL_WAVES];
+  const float M = fl_fold_max(fpart, FL_F_PEAK, gridDim.x, shf);
+  int kfirst = (int)((int64_t)lk % R);      // (r + lk) mod R, mathematically: lk mod R in [0, R) first
+  if (kfirst < 0) kfirst += R;
+  double sum_p = 0.0;
+  int n_mass = 0;
+  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int r = tile / tiles_per_plane;
+    const int64_t p64 = (int64_t)(tile - r * tiles_per_plane) * FL_NT + threadIdx.x;
+    if (p64 >= P) continue;
+    const int p = (int)p64;
+    const float own = fl_mass(belief[(int64_t)r * P + p], M);
+    sum_p += (double)own;
+    n_mass += own > 0.f ? 1 : 0;
+    int k = r + kfirst;
+    if (k >= R) k -= R;
+    float acc = 0.f;
+    for (int i = 0; i < Tk; ++i) {
+      acc = fmaf(taps_k[i], fl_mass(belief[(int64_t)k * P + p], M), acc);
+      k = k + 1 == R ? 0 : k + 1;
+    }
+    t0[(int64_t)r * P + p] = acc;
+  }
+  sum_p = fl_block_sum(sum_p, shd);
+  n_mass = fl_block_sum(n_mass, shi);
+  if (threadIdx.x == 0) {
+    dpart[(size_t)blockIdx.x * 4 + FL_D_SUMP] = sum_p;
+    ipart[(size_t)blockIdx.x * 4 + FL_I_MASS] = n_mass;
+  }
+}
+
+// ---- launch 3: t1[r, a, b] = sum_ta taps_a[r, ta] * t0[r, a + la[r] + ta, b]
+__global__ __launch_bounds__(FL_NT) void vote_filter_rows_kernel(const float* __restrict__ t0,
+                                                                 const float* __restrict__ taps_a,
+                                                                 const int32_t* __restrict__ offsets, int Ho, int Wo, int P,
+                                                                 int Ta, int tiles_per_plane, int tiles,
+                                                                 float* __restrict__ t1) {
+  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int r = tile / tiles_per_plane;
+    const int64_t p64 = (int64_t)(tile - r * tiles_per_plane) * FL_NT + threadIdx.x;
+    if (p64 >= P) continue;
+    const int p = (int)p64;
+    const int a = p / Wo, b = p - a * Wo;
+    const float* w = taps_a + (size_t)r * Ta;                     // uniform over the workgroup
+    const int64_t first = (int64_t)a + offsets[(size_t)r * 2];    // the source row of tap 0
+    const float* src = t0 + (int64_t)r * P + b;
+    float acc = 0.f;
+    for (int i = 0; i < Ta; ++i) {
+      const int64_t sa = first + i;
+      if (sa >= 0 && sa < Ho) acc = fmaf(w[i], src[sa * Wo], acc);   // (outside: + 0, the chain is unchanged)
+    }
+    t1[(int64_t)r * P + p] = acc;
+  }
+}
+
+// ---- launch 4: t2[r, a, b] = sum_tb taps_b[r, tb] * t1[r, a, b + lb[r] + tb]; sum t2
+__global__ __launch_bounds__(FL_NT) void vote_filter_cols_kernel(const float* __restrict__ t1,
+                                                                 const float* __restrict__ taps_b,
+                                                                 const int32_t* __restrict__ offsets, int Wo, int P, int Tb,
+                                                                 int tiles_per_plane, int tiles, float* __restrict__ t2,
+                                                                 double* __restrict__ dpart) {
+  __shared__ double shd[FL_WAVES];
+  double sum = 0.0;
+  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int r = tile / tiles_per_plane;
+    const int64_t p64 = (int64_t)(tile - r * tiles_per_plane) * FL_NT + threadIdx.x;
+    if (p64 >= P) continue;
+    const int p = (int)p64;
+    const int a = p / Wo, b = p - a * Wo;
+    const float* w = taps_b + (size_t)r * Tb;
+    const int64_t first = (int64_t)b + offsets[(size_t)r * 2 + 1];
+    const float* src = t1 + (int64_t)r * P + (int64_t)a * Wo;
+    float acc = 0.f;
+    for (int i = 0; i < Tb; ++i) {
+      const int64_t sb = first + i;
+      if (sb >= 0 && sb < Wo) acc = fmaf(w[i], src[sb], acc);
+    }
+    t2[(int64_t)r * P + p] = acc;
+    sum += (double)acc;
+  }
+  sum = fl_block_sum(sum, shd);
+  if (threadIdx.x == 0) dpart[(size_t)blockIdx.x * 4 + FL_D_SUMT2] = sum;
+}
+
+// The update of one cell, float64: u = scale * vote + log(prior), prior = (1 - eps) t2 / S + eps / n.  NaN for a NaN
+// or +inf vote, -inf for a -inf vote or a prior of 0.  `transported` = (1 - eps) / S is NOT folded into one factor:
+// the expression is ((1 - eps) * t2) / S + eps / n as the contract writes it.
+struct FlUpdate {
+  double scale, one_minus_eps, S, eps_over_n;
+  bool has_prior;                           // a belief was given and S > 0
+};
+__device__ __forceinline__ double fl_update(const FlUpdate& c, float t2, float vote) {
+  if (!(vote < INFINITY)) return (double)__int_as_float(0x7fc00000);   // NaN or +inf
+  if (vote == -INFINITY) return -(double)INFINITY;
+  double prior = c.eps_over_n;
+  if (c.has_prior) prior = (c.one_minus_eps * (double)t2) / c.S + c.eps_over_n;
+  if (!(prior > 0.0)) return -(double)INFINITY;
+  return c.scale * (double)vote + log(prior);
+}
+__device__ __forceinline__ FlUpdate fl_update_setup(const double* dpart, int groups, bool with_belief, float scale,
+                                                    float eps, int n, double* sh) {
+  FlUpdate c;
+  c.S = with_belief ? fl_fold_sum(dpart, FL_D_SUMT2, groups, sh) : 0.0;
+  c.has_prior = with_belief && c.S > 0.0;
+  c.scale = (double)scale;
+  // belief == NULL is the uniform prior: eps = 1
+  c.one_minus_eps = with_belief ? 1.0 - (double)eps : 0.0;
+  c.eps_over_n = (with_belief ? (double)eps : 1.0) / (double)n;
+  return c;
+}
+
+// ---- launch 5
+__global__ __launch_bounds__(FL_NT) void vote_filter_evidence_kernel(const float* __restrict__ t2,
+                                                                     const float* __restrict__ votes, int n,
+                                                                     int with_belief, float scale, float eps,
+                                                                     double* __restrict__ dpart) {
+  __shared__ double shd[FL_WAVES];
+  __shared__ double shl[FL_WAVES][2];
+  const FlUpdate c = fl_update_setup(dpart, gridDim.x, with_belief != 0, scale, eps, n, shd);
+  double m = -(double)INFINITY, s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * FL_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FL_NT) {
+    const double u = fl_update(c, with_belief ? t2[i] : 0.f, votes[i]);
+    if (fabs(u) < (double)INFINITY) {
+      if (u > m) {
+        s = s * exp(m - u) + 1.0;           // (m = -inf at the first cell: exp gives 0)
+        m = u;
+      } else {
+        s += exp(u - m);
+      }
+    }
+  }
+  fl_block_lse(&m, &s, shl);
+  if (threadIdx.x == 0) {
+    dpart[(size_t)blockIdx.x * 4 + FL_D_LSE_M] = m;
+    dpart[(size_t)blockIdx.x * 4 + FL_D_LSE_S] = s;
+  }
+}
+
+__device__ __forceinline__ double fl_fold_log_z(const double* __restrict__ dpart, int groups, double (*shl)[2]) {
+  double m = -(double)INFINITY, s = 0.0;
+  for (int g = threadIdx.x; g < groups; g += FL_NT)
+    fl_lse_merge(&m, &s, dpart[(size_t)g * 4 + FL_D_LSE_M], dpart[(size_t)g * 4 + FL_D_LSE_S]);
+  fl_block_lse(&m, &s, shl);
+  return m == -(double)INFINITY ? m : m + log(s);
+}
+
+// ---- launch 6
+__global__ __launch_bounds__(FL_NT) void vote_filter_normalise_kernel(const float* __restrict__ votes, int n,
+                                                                      int with_belief, float scale, float eps,
+                                                                      const double* __restrict__ dpart,
+                                                                      float* __restrict__ belief_out,
+                                                                      float* __restrict__ fpart, int32_t* __restrict__ ipart,
+                                                                      float* __restrict__ stats) {
+  __shared__ double shd[FL_WAVES];
+  __shared__ double shl[FL_WAVES][2];
+  __shared__ float shf[FL_WAVES];
+  __shared__ int shi[FL_WAVES];
+  const FlUpdate c = fl_update_setup(dpart, gridDim.x, with_belief != 0, scale, eps, n, shd);
+  const double log_z = fl_fold_log_z(dpart, gridDim.x, shl);
+  float top = -INFINITY;
+  int n_fin = 0, n_nan = 0;
+  for (int64_t i = (int64_t)blockIdx.x * FL_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FL_NT) {
+    const double u = fl_update(c, with_belief ? belief_out[i] : 0.f, votes[i]);   // (t2 lives in belief_out)
+    float out;
+    if (u != u)
+      out = __int_as_float(0x7fc00000);
+    else if (u == -(double)INFINITY)
+      out = -INFINITY;
+    else
+      out = (float)(u - log_z);
+    belief_out[i] = out;
+    n_fin += fl_finite(out) ? 1 : 0;
+    n_nan += out != out ? 1 : 0;
+    top = fmaxf(top, out);                  // (fmaxf drops a NaN)
+  }
+  top = fl_block_max(top, shf);
+  n_fin = fl_block_sum(n_fin, shi);
+  n_nan = fl_block_sum(n_nan, shi);
+  if (threadIdx.x == 0) {
+    fpart[(size_t)blockIdx.x * 2 + FL_F_OUTMAX] = top;
+    ipart[(size_t)blockIdx.x * 4 + FL_I_FIN] = n_fin;
+    ipart[(size_t)blockIdx.x * 4 + FL_I_NAN] = n_nan;
+    if (blockIdx.x == 0) stats[0] = (float)log_z;
+  }
+}
+
+// ---- launch 7
+__global__ __launch_bounds__(FL_NT) void vote_filter_finish_kernel(int groups, int with_belief,
+                                                                   const double* __restrict__ dpart,
+                                                                   const float* __restrict__ fpart,
+                                                                   const int32_t* __restrict__ ipart,
+                                                                   float* __restrict__ stats, int32_t* __restrict__ count) {
+  __shared__ double shd[FL_WAVES];
+  __shared__ float shf[FL_WAVES];
+  __shared__ int shi[FL_WAVES];
+  const int n_fin = fl_fold_sum(ipart, FL_I_FIN, groups, shi);
+  const int n_nan = fl_fold_sum(ipart, FL_I_NAN, groups, shi);
+  const float top = fl_fold_max(fpart, FL_F_OUTMAX, groups, shf);
+  int n_bad = 0, n_mass = 0;
+  float M = -INFINITY, kept = 1.f;
+  if (with_belief) {
+    n_bad = fl_fold_sum(ipart, FL_I_BAD, groups, shi);
+    n_mass = fl_fold_sum(ipart, FL_I_MASS, groups, shi);
+    M = fl_fold_max(fpart, FL_F_PEAK, groups, shf);
+    const double sum_p = fl_fold_sum(dpart, FL_D_SUMP, groups, shd);
+    const double S = fl_fold_sum(dpart, FL_D_SUMT2, groups, shd);
+    kept = sum_p > 0.0 ? (float)(S / sum_p) : 0.f;
+  }
+  if (threadIdx.x == 0) {
+    stats[1] = kept;
+    stats[2] = M;
+    stats[3] = top;
+    count[0] = n_fin;
+    count[1] = n_bad;
+    count[2] = n_nan;
+    count[3] = n_mass;
+  }
+}
+
+struct FlPlan {
+  int n, P, tiles_per_plane, tiles, groups;
+  size_t t1_bytes, d_bytes, i_bytes, f_bytes;
+};
+
+bool fl_plan(int R, int Ho, int Wo, int Tk, int Ta, int Tb, FlPlan* plan) {
+  if (R < 1 || R > FL_MAX_R || Ho < 1 || Wo < 1) return false;
+  if (Tk < 1 || Tk > FL_MAX_TK || Ta < 1 || Ta > FL_MAX_TXY || Tb < 1 || Tb > FL_MAX_TXY) return false;
+  if ((int64_t)R * Ho * Wo >= ((int64_t)1 << 31)) return false;
+  plan->n = R * Ho * Wo;
+  plan->P = Ho * Wo;
+  plan->tiles_per_plane = (int)snap_cdiv(plan->P, FL_NT);
+  plan->tiles = R * plan->tiles_per_plane;   // < 2^31 / 256 + 64
+  plan->groups = plan->tiles < FL_MAX_GROUPS ? plan->tiles : FL_MAX_GROUPS;
+  plan->t1_bytes = ((size_t)plan->n * sizeof(float) + 7) / 8 * 8;
+  plan->d_bytes = (size_t)plan->groups * 4 * sizeof(double);
+  plan->i_bytes = (size_t)plan->groups * 4 * sizeof(int32_t);
+  plan->f_bytes = (size_t)plan->groups * 2 * sizeof(float);
+  return true;
+}
+
+}  // namespace
+
+extern "C" size_t snap_vote_filter_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t Tk, int32_t Ta,
+                                                   int32_t Tb) {
+  FlPlan plan;
+  if (!fl_plan(R, Ho, Wo, Tk, Ta, Tb, &plan)) return 0;
+  // [R Ho Wo] f32 t1 (whole 8-byte words) | [groups][4] float64 | [groups][4] int32 | [groups][2] f32
+  return plan.t1_bytes + plan.d_bytes + plan.i_bytes + plan.f_bytes;
+}
+
+extern "C" int snap_vote_filter_f32(const float* belief, const float* votes, const float* taps_k, int32_t lk,
+                                    const float* taps_a, const float* taps_b, const int32_t* offsets, int32_t R,
+                                    int32_t Ho, int32_t Wo, int32_t Tk, int32_t Ta, int32_t Tb, float scale,
+                                    float uniform_mix, float* belief_out, float* stats, int32_t* count, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  if (!votes || !taps_k || !taps_a || !taps_b || !offsets || !belief_out || !stats || !count || !workspace)
+    return SNAP_ERR_NULL;
+  FlPlan plan;
+  if (!fl_plan(R, Ho, Wo, Tk, Ta, Tb, &plan)) return SNAP_ERR_BAD_SHAPE;
+  if (!(scale > 0.f) || !(scale < INFINITY)) return SNAP_ERR_UNSUPPORTED;
+  if (!(uniform_mix >= 0.f && uniform_mix <= 1.f)) return SNAP_ERR_UNSUPPORTED;
+  if (workspace_bytes < plan.t1_bytes + plan.d_bytes + plan.i_bytes + plan.f_bytes ||
+      reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
+    return SNAP_ERR_WORKSPACE;
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  float* t1 = reinterpret_cast<float*>(ws);
+  double* dpart = reinterpret_cast<double*>(ws + plan.t1_bytes);
+  int32_t* ipart = reinterpret_cast<int32_t*>(ws + plan.t1_bytes + plan.d_bytes);
+  float* fpart = reinterpret_cast<float*>(ws + plan.t1_bytes + plan.d_bytes + plan.i_bytes);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(plan.groups), block(FL_NT);
+  const int with_belief = belief != nullptr ? 1 : 0;
+  if (with_belief) {
+    hipLaunchKernelGGL(vote_filter_peak_kernel, grid, block, 0, s, belief, plan.n, fpart, ipart);
+    SNAP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(vote_filter_rotate_kernel, grid, block, 0, s, belief, taps_k, lk, R, plan.P, Tk,
+                       plan.tiles_per_plane, plan.tiles, fpart, belief_out, dpart, ipart);
+    SNAP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(vote_filter_rows_kernel, grid, block, 0, s, belief_out, taps_a, offsets, Ho, Wo, plan.P, Ta,
+                       plan.tiles_per_plane, plan.tiles, t1);
+    SNAP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(vote_filter_cols_kernel, grid, block, 0, s, t1, taps_b, offsets, Wo, plan.P, Tb,
+                       plan.tiles_per_plane, plan.tiles, belief_out, dpart);
+    SNAP_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(vote_filter_evidence_kernel, grid, block, 0, s, belief_out, votes, plan.n, with_belief, scale,
+                     uniform_mix, dpart);
+  SNAP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vote_filter_normalise_kernel, grid, block, 0, s, votes, plan.n, with_belief, scale, uniform_mix,
+                     dpart, belief_out, fpart, ipart, stats);
+  SNAP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vote_filter_finish_kernel, dim3(1), block, 0, s, plan.groups, with_belief, dpart, fpart, ipart,
+                     stats, count);
+  SNAP_CHECK_LAUNCH();
+  return SNAP_OK;
+}

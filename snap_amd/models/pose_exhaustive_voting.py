@@ -469,17 +469,9 @@ def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, me
   return out
 
 
-def sequence_shift_table(q0_t_q, grid, num_rotations):
-  """The shift table of ``ops.vote_fuse`` for a sequence of query frames with known relative motion: ``q0_t_q`` is a
-  Transform2D [N] in corner frames, frame n's pose in the anchor frame's coordinates, so m_t_qn = m_t_q0 @ q0_t_qn
-  (an identity for the anchor itself) -> f32 [N, R, 3] on the transform's device.
-
-  Row (n, r) = (dk, da, db): where the anchor pose has the index (r, a, b), frame n has the continuous index
-  (r + dk, a + da, b + db).  In centre frames q0_t_qn is (phi_n, rho_n) with rho_n = tau_n + (Rot(phi_n) - I) center,
-  center = grid.extent_meters / 2; composing it behind the anchor's (-2 pi r / R, xy_cell) and reading the index back
-  (``exhaustive_index_to_tfm`` / ``exhaustive_tfm_to_index``) gives dk = -phi_n R / (2 pi) wrapped into [0, R) and
-  (da, db) = Rot(-2 pi r / R) rho_n / cell_size: the +0.5 cell offsets cancel, and nothing depends on (a, b).
-  Computed in float64 and rounded to f32 once; an identity transform gives an all-zero row."""
+def _shift_table_f64(q0_t_q, grid, num_rotations):
+  """The float64 quantities of ``sequence_shift_table`` before their rounding: (dk [N] in [0, R), da [N, R],
+  db [N, R]) on the transform's device."""
   R = int(num_rotations)
   phi = torch.as_tensor(q0_t_q.angle).to(torch.float64).reshape(-1)
   tau = torch.as_tensor(q0_t_q.t).to(torch.float64).reshape(-1, 2)
@@ -492,7 +484,24 @@ def sequence_shift_table(q0_t_q, grid, num_rotations):
   ct, st = torch.cos(theta)[None], torch.sin(theta)[None]
   da = (ct * rho_x[:, None] + st * rho_y[:, None]) / grid.cell_size
   db = (-st * rho_x[:, None] + ct * rho_y[:, None]) / grid.cell_size
-  dk = torch.remainder(-phi * (R / (2 * math.pi)), R).to(torch.float32)
+  dk = torch.remainder(-phi * (R / (2 * math.pi)), R)
+  return dk, da, db
+
+
+def sequence_shift_table(q0_t_q, grid, num_rotations):
+  """The shift table of ``ops.vote_fuse`` for a sequence of query frames with known relative motion: ``q0_t_q`` is a
+  Transform2D [N] in corner frames, frame n's pose in the anchor frame's coordinates, so m_t_qn = m_t_q0 @ q0_t_qn
+  (an identity for the anchor itself) -> f32 [N, R, 3] on the transform's device.
+
+  Row (n, r) = (dk, da, db): where the anchor pose has the index (r, a, b), frame n has the continuous index
+  (r + dk, a + da, b + db).  In centre frames q0_t_qn is (phi_n, rho_n) with rho_n = tau_n + (Rot(phi_n) - I) center,
+  center = grid.extent_meters / 2; composing it behind the anchor's (-2 pi r / R, xy_cell) and reading the index back
+  (``exhaustive_index_to_tfm`` / ``exhaustive_tfm_to_index``) gives dk = -phi_n R / (2 pi) wrapped into [0, R) and
+  (da, db) = Rot(-2 pi r / R) rho_n / cell_size: the +0.5 cell offsets cancel, and nothing depends on (a, b).
+  Computed in float64 and rounded to f32 once; an identity transform gives an all-zero row."""
+  dk, da, db = _shift_table_f64(q0_t_q, grid, num_rotations)
+  R = int(num_rotations)
+  dk = dk.to(torch.float32)
   dk = torch.where(dk >= R, torch.zeros_like(dk), dk)             # (a yaw just above 0 rounds up to R)
   return (torch.stack((dk[:, None].expand(-1, R), da.to(torch.float32), db.to(torch.float32)), -1) + 0.0).contiguous()
 
@@ -541,3 +550,152 @@ def localize_sequence(planes_q, plane_map, num_rotations, grid, q0_t_q, conf_q=N
     kw = {} if posterior is True else dict(posterior)
     out['posterior'] = posterior_from_votes(fused, grid, num_rotations, **kw)
   return out
+
+
+# Limits of ops.vote_filter's tap tables (vote_filter.hip) and the smallest non-zero tap it is specified for.
+FILTER_MAX_TAPS_K = 16
+FILTER_MAX_TAPS_XY = 32
+FILTER_MIN_TAP = 2.0 ** -20
+
+
+def _axis_taps(centre, sigma, truncate, max_taps, what):
+  """One axis of ``motion_taps``: centres [M] float64 (index units) and the standard deviation ``sigma`` (index
+  units) -> (taps float64 [M, T], first offsets int64 [M]), T = 2 rho + 2 with rho = ceil(truncate * sigma)."""
+  if not (sigma >= 0 and math.isfinite(sigma)) or not (truncate >= 0 and math.isfinite(truncate)):
+    raise ValueError(f'motion_taps: {what}: sigma {sigma} (index units), truncate {truncate}')
+  if not np.isfinite(centre).all() or np.abs(centre).max(initial=0.0) >= 2 ** 30:
+    raise ValueError(f'motion_taps: {what}: shift {centre} (index units) is not a usable number')
+  rho = int(math.ceil(truncate * sigma))
+  T = 2 * rho + 2
+  if T > max_taps:
+    raise ValueError(f'motion_taps: {what}: ceil({truncate} * {sigma:.4g}) = {rho} index units needs {T} taps, '
+                     f'the kernel has {max_taps}')
+  i = np.arange(-rho, rho + 1, dtype=np.float64)
+  g = np.exp(-i * i / (2 * sigma * sigma)) if rho > 0 else np.ones(1)
+  g = g / g.sum()
+  l = np.floor(centre)
+  f = centre - l                                            # in [0, 1)
+  w = np.zeros((len(centre), T))
+  w[:, :T - 1] += (1 - f)[:, None] * g[None]
+  w[:, 1:] += f[:, None] * g[None]
+  w[w < FILTER_MIN_TAP] = 0.0
+  w = w / w.sum(-1, keepdims=True)
+  return w, l.astype(np.int64) - rho
+
+
+def motion_taps(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, truncate=3.0, device=None):
+  """The tap tables of ``ops.vote_filter``'s predict step for one odometry increment: ``cur_t_prev`` is a Transform2D
+  in corner frames, the previous frame's pose in the current frame's coordinates, so m_t_prev = m_t_cur @ cur_t_prev;
+  ``sigma_xy`` (metres) and ``sigma_yaw`` (radians) are the increment's standard deviations ->
+  (taps_k f32 [Tk], lk int, taps_a f32 [R, Ta], taps_b f32 [R, Tb], offsets int32 [R, 2] = (la, lb)) on ``device``
+  (default: the transform's).
+
+  The current pose (r, a, b) has its previous pose at the continuous index (r + dk, a + da(r), b + db(r)): row r of
+  ``sequence_shift_table(cur_t_prev)`` before its rounding, float64.  Per axis, with the centre c = l + f,
+  l = floor(c): w_j = (1 - f) g(j - l) + f g(j - l - 1) for j = l - rho .. l + rho + 1, g the Gaussian of the axis'
+  standard deviation in index units (sigma_xy / cell_size, sigma_yaw R / 2 pi) sampled at the integers -rho .. rho,
+  rho = ceil(truncate * sigma), normalised to sum 1 (a delta for sigma = 0): linear-interpolation transport followed
+  by a blur.  The taps' mean is c exactly, they are continuous in sigma at 0, and with sigma = 0 they are
+  ``ops.vote_fuse``'s own split (1 - f, f).  Entries below 2^-20 are set to 0 and the row renormalised, in float64;
+  rounded to f32 once.  Built on the host (a transform on the device is read back: one synchronisation); raises
+  ValueError where rho is beyond the kernel's tables (Tk <= 16, Ta, Tb <= 32)."""
+  R = int(num_rotations)
+  angle = torch.as_tensor(cur_t_prev.angle)
+  if angle.numel() != 1:
+    raise ValueError(f'motion_taps: one increment, got a transform of shape {tuple(angle.shape)}')
+  if device is None:
+    device = angle.device
+  host = geometry.Transform2D(angle.detach().to('cpu', torch.float64), torch.as_tensor(cur_t_prev.t).detach().to(
+      'cpu', torch.float64))
+  dk, da, db = (v.numpy() for v in _shift_table_f64(host, grid, R))
+  cell = float(grid.cell_size)
+  wk, lk = _axis_taps(dk, float(sigma_yaw) * R / (2 * math.pi), truncate, FILTER_MAX_TAPS_K, 'rotation')
+  wa, la = _axis_taps(da[0], float(sigma_xy) / cell, truncate, FILTER_MAX_TAPS_XY, 'rows')
+  wb, lb = _axis_taps(db[0], float(sigma_xy) / cell, truncate, FILTER_MAX_TAPS_XY, 'columns')
+  # one upload: the three f32 tables, then the int32 offsets
+  f32 = np.concatenate([wk.reshape(-1), wa.reshape(-1), wb.reshape(-1)]).astype(np.float32)
+  off = np.stack([la, lb], -1).astype(np.int32)
+  blob = ops.upload_table(np.concatenate([f32.view(np.uint8), off.reshape(-1).view(np.uint8)]), device)
+  tab = blob[:f32.nbytes].view(torch.float32)
+  nk, na = wk.size, wa.size
+  return (tab[:nk], int(lk[0]), tab[nk:nk + na].view(R, -1), tab[nk + na:].view(R, -1),
+          blob[f32.nbytes:].view(torch.int32).view(R, 2))
+
+
+@functools.lru_cache(maxsize=16)
+def _still_taps(R, device):
+  """One tap of weight 1 at offset 0 on every axis (the tables of a call without a predict step)."""
+  dev = torch.device(device)
+  one = torch.ones((R, 1), dtype=torch.float32, device=dev)
+  return torch.ones((1,), dtype=torch.float32, device=dev), 0, one, one.clone(), torch.zeros((R, 2), dtype=torch.int32,
+                                                                                                device=dev)
+
+
+def filter_votes(belief, votes, cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0,
+                 uniform_mix=1e-3, truncate=3.0):
+  """One step of the recursive pose filter (``ops.vote_filter`` on ``motion_taps``): ``belief`` [R, 2H-1, 2W-1] is the
+  log-space belief after the previous frame, or None to start a track (a uniform prior; ``cur_t_prev`` is then
+  ignored); ``votes`` the new frame's volume; ``cur_t_prev`` the odometry increment (Transform2D, corner frames,
+  m_t_prev = m_t_cur @ cur_t_prev) with standard deviations ``sigma_xy`` (metres) / ``sigma_yaw`` (radians);
+  ``temperature`` multiplies the votes; ``uniform_mix`` is the share of a uniform distribution mixed into the
+  predicted prior (the track can recover from a pose it had ruled out) -> dict of device tensors: ``belief``
+  [R, 2H-1, 2W-1] (normalised log-probabilities, -inf = impossible: a vote volume for ``poses_from_votes`` /
+  ``posterior_from_votes`` / ``refine_poses``), ``log_evidence`` (of the frame under the predicted prior),
+  ``mass_kept`` (the share of the previous belief that stayed inside the volume), ``count`` int32 [4] and ``stats``
+  f32 [4] (the op's raw rows)."""
+  if votes.dim() != 3 or votes.shape[0] != num_rotations:
+    raise ValueError(f'filter_votes: votes [{num_rotations}, Ho, Wo], got {tuple(votes.shape)}')
+  if belief is None:
+    taps = _still_taps(int(num_rotations), str(votes.device))
+  else:
+    taps = motion_taps(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, truncate, device=votes.device)
+    belief = belief.contiguous()
+  out, stats, count = ops.vote_filter(belief, votes.contiguous(), taps, temperature, uniform_mix)
+  return dict(belief=out, log_evidence=stats[0], mass_kept=stats[1], count=count, stats=stats)
+
+
+class VoteFilter:
+  """A track: the recursive pose filter of one vehicle on one map lattice.  Holds the grid, the number of rotations,
+  the odometry noise (``sigma_xy`` metres, ``sigma_yaw`` radians per step), ``temperature``, ``uniform_mix``,
+  ``truncate`` (``filter_votes``) and the current ``belief`` (None before the first frame and after ``reset()``)."""
+
+  def __init__(self, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0, uniform_mix=1e-3, truncate=3.0):
+    self.grid = grid
+    self.num_rotations = int(num_rotations)
+    self.sigma_xy = float(sigma_xy)
+    self.sigma_yaw = float(sigma_yaw)
+    self.temperature = float(temperature)
+    self.uniform_mix = float(uniform_mix)
+    self.truncate = float(truncate)
+    self.belief = None
+
+  def reset(self):
+    """Drop the belief: the next ``step`` starts a track from a uniform prior."""
+    self.belief = None
+
+  def step(self, votes, cur_t_prev=None):
+    """One filter step with the new frame's ``votes`` -> ``filter_votes``' dict; the belief is kept.  ``cur_t_prev``:
+    the odometry increment since the previous step (ignored by the first step of a track); None = no motion (the
+    belief is only diffused)."""
+    if self.belief is not None and cur_t_prev is None:
+      cur_t_prev = geometry.Transform2D(torch.zeros((), dtype=torch.float64), torch.zeros(2, dtype=torch.float64))
+    out = filter_votes(self.belief, votes, cur_t_prev, self.grid, self.num_rotations, self.sigma_xy, self.sigma_yaw,
+                       self.temperature, self.uniform_mix, self.truncate)
+    self.belief = out['belief']
+    return out
+
+  def localize(self, plane_q, plane_map, cur_t_prev=None, conf_q=None, method=None, posterior=None, **peaks):
+    """``exhaustive_pose_voting`` of the new frame, ``step``, then ``poses_from_votes(belief, **peaks)``: the dict of
+    ``localize_exhaustive`` with ``votes`` = the belief, plus ``votes_frame`` (the frame's own votes),
+    ``log_evidence`` and ``mass_kept``.  ``posterior`` as in ``localize_exhaustive``, on the belief."""
+    frame = exhaustive_pose_voting(plane_q, plane_map, self.num_rotations, self.grid, conf_q=conf_q, method=method)
+    step = self.step(frame, cur_t_prev)
+    out = poses_from_votes(step['belief'], self.grid, self.num_rotations, **peaks)
+    out['votes'] = step['belief']
+    out['votes_frame'] = frame
+    out['log_evidence'] = step['log_evidence']
+    out['mass_kept'] = step['mass_kept']
+    if posterior is not None and posterior is not False:
+      kw = {} if posterior is True else dict(posterior)
+      out['posterior'] = posterior_from_votes(step['belief'], self.grid, self.num_rotations, **kw)
+    return out

@@ -2309,6 +2309,63 @@ def vote_fuse(volumes, shifts, weights=None):
   return fused, count
 
 
+def vote_filter(belief, votes, taps, scale=1.0, uniform_mix=0.0):
+  """One step of the recursive pose filter on the vote lattice: belief f32 [R, Ho, Wo] (the log-space belief after the
+  previous frame, -inf = impossible pose) or None (a uniform prior: a track starts), votes f32 [R, Ho, Wo] (the new
+  frame), taps = (taps_k f32 [Tk], lk int, taps_a f32 [R, Ta], taps_b f32 [R, Tb], offsets int32 [R, 2]) on the same
+  device (``pose_exhaustive_voting.motion_taps``) -> (belief_out f32 [R, Ho, Wo], stats f32 [4], count int32 [4]).
+  The belief's masses exp(belief - max) are transported and diffused by the three tap passes (rotation, circular; rows
+  and columns per output rotation), mixed with ``uniform_mix`` of a uniform distribution, multiplied by
+  exp(scale * votes) and normalised over the finite cells.  stats = (log evidence of the frame, share of the mass that
+  stayed in the volume, largest finite belief, largest belief_out); count = (finite cells of belief_out, NaN / +inf
+  cells of belief, NaN cells of belief_out, cells of belief with mass).  Taps must be finite, >= 0 and either 0 or
+  >= 2^-20 (not checked: ``motion_taps`` guarantees it; the full contract: snap_vote_filter_f32 in
+  include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  if not isinstance(votes, torch.Tensor) or votes.dtype != torch.float32 or not votes.is_cuda or votes.dim() != 3:
+    got = f'{votes.dtype} {tuple(votes.shape)} on {votes.device}' if isinstance(votes, torch.Tensor) else type(votes)
+    raise ValueError(f'vote_filter: votes f32 [R, Ho, Wo] on a ROCm GPU, got {got}')
+  _f32(votes, 'votes')
+  R, Ho, Wo = votes.shape
+  if not isinstance(taps, (tuple, list)) or len(taps) != 5:
+    raise ValueError('vote_filter: taps = (taps_k, lk, taps_a, taps_b, offsets)')
+  taps_k, lk, taps_a, taps_b, offsets = taps
+  if isinstance(lk, bool) or not isinstance(lk, (int, np.integer)) or not -2 ** 31 <= int(lk) < 2 ** 31:
+    raise ValueError(f'vote_filter: lk must be an int32 number, got {lk!r}')
+  Tk = taps_k.shape[0] if isinstance(taps_k, torch.Tensor) and taps_k.dim() == 1 else -1
+  Ta = taps_a.shape[1] if isinstance(taps_a, torch.Tensor) and taps_a.dim() == 2 else -1
+  Tb = taps_b.shape[1] if isinstance(taps_b, torch.Tensor) and taps_b.dim() == 2 else -1
+  for t, name, dtype, shape in ((belief, 'belief', torch.float32, (R, Ho, Wo)), (taps_k, 'taps_k', torch.float32, (Tk,)),
+                                (taps_a, 'taps_a', torch.float32, (R, Ta)), (taps_b, 'taps_b', torch.float32, (R, Tb)),
+                                (offsets, 'offsets', torch.int32, (R, 2))):
+    if t is None and name == 'belief':
+      continue
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != votes.device or tuple(t.shape) != shape):
+      got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t)
+      raise ValueError(f'vote_filter: {name} {dtype} {list(shape)} on {votes.device}, got {got}')
+    _chk(t, dtype, name)
+  scale, uniform_mix = float(scale), float(uniform_mix)
+  if not (scale > 0.0 and np.isfinite(np.float32(scale))):
+    raise ValueError(f'vote_filter: scale must be a finite number > 0, got {scale}')
+  if not 0.0 <= uniform_mix <= 1.0:
+    raise ValueError(f'vote_filter: uniform_mix must lie in [0, 1], got {uniform_mix}')
+  wsb = lib.snap_vote_filter_workspace_bytes(R, Ho, Wo, Tk, Ta, Tb) if votes.numel() < 2 ** 31 else 0
+  if wsb == 0:
+    raise ValueError(f'vote_filter: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
+                     'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  ws = torch.empty((wsb // 8,), dtype=torch.int64, device=votes.device)   # (whole 8-byte words, 8-byte aligned)
+  belief_out = torch.empty((R, Ho, Wo), dtype=torch.float32, device=votes.device)
+  stats = torch.empty((4,), dtype=torch.float32, device=votes.device)
+  count = torch.empty((4,), dtype=torch.int32, device=votes.device)
+  # bytes the launches move (the kernel file's header): 12 passes over the volume with a belief, 3 without
+  with _region('vote_filter', 0.0, 4.0 * votes.numel() * (3 if belief is None else 12)):
+    st = lib.snap_vote_filter_f32(_p(belief), _p(votes), _p(taps_k), int(lk), _p(taps_a), _p(taps_b), _p(offsets),
+                                  R, Ho, Wo, Tk, Ta, Tb, scale, uniform_mix, _p(belief_out), _p(stats), _p(count),
+                                  _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_filter_f32')
+  return belief_out, stats, count
+
+
 def plane_align_score(fq, vq, fm, vm, poses, threshold):
   """The alignment score of two BEV planes at continuous poses: fq f32 [Hq, Wq, D] / vq bool or uint8 [Hq, Wq] (the
   query plane), fm f32 [Hm, Wm, D] / vm [Hm, Wm] (the map plane), poses f32 [P, 4] = (cos, sin, tx, ty) on the same

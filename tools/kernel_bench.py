@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_refine_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_refine_c4)
 """
 import math
 import os
@@ -323,6 +323,108 @@ def vote_fuse_c4(iters):
         f.write(line + '\n')
 
 
+def torch_filter(belief, votes, taps_host, scale, eps):
+  """What a user would write without the kernel: exp relative to the peak, ``roll`` in k, shifted slices per rotation
+  and tap in (a, b), then log, the vote product and ``logsumexp`` (f32 throughout; finite votes or -inf: no NaN
+  handling)."""
+  tk, lk, ta, tb, off = taps_host
+  R, Ho, Wo = belief.shape
+  fin = torch.isfinite(belief)
+  M = torch.where(fin, belief, float('-inf')).max()
+  d = belief - M
+  p = torch.where(fin & (d >= -40), d.exp(), 0.0)
+  t0 = torch.zeros_like(p)
+  for i, w in enumerate(tk):
+    t0 += float(w) * torch.roll(p, -(lk + i), 0)
+  t2 = torch.zeros_like(p)
+  for r in range(R):
+    t1 = torch.zeros_like(p[0])
+    for i, w in enumerate(ta[r]):
+      s = int(off[r, 0]) + i
+      a0, a1 = max(0, -s), min(Ho, Ho - s)
+      if a0 < a1 and w:
+        t1[a0:a1] += float(w) * t0[r, a0 + s:a1 + s]
+    for i, w in enumerate(tb[r]):
+      s = int(off[r, 1]) + i
+      b0, b1 = max(0, -s), min(Wo, Wo - s)
+      if b0 < b1 and w:
+        t2[r, :, b0:b1] += float(w) * t1[:, b0 + s:b1 + s]
+  prior = (1 - eps) * t2 / t2.sum(dtype=torch.float64).float() + eps / p.numel()
+  u = scale * votes + prior.log()
+  log_z = torch.logsumexp(u.reshape(-1), 0)
+  return u - log_z, log_z
+
+
+def vote_filter_c4(iters):
+  """One step of the recursive pose filter at the C4 vote volume (R = 36, 511 x 511; the low-overlap border of the
+  votes -inf; the belief a previous step's output; Tk = 4, Ta = Tb = 8: an increment of 1 m and 5 degrees with
+  sigma_xy = 0.2 m, sigma_yaw = 2 degrees on the 256^2 grid of 0.2 m cells): whole ops.vote_filter calls against the
+  torch composition of the same result on the same inputs, blocks of the two alternated, medians of single calls.
+  One JSON line; `json=<path>` as a third argument also writes it."""
+  import json
+  import numpy as np
+  from snap_amd.models import pose_exhaustive_voting as pev
+  from snap_amd.utils import geometry, grids
+  R, H, scale, eps = 36, 256, 8.0, 1e-3
+  Ho = Wo = 2 * H - 1
+  grid = grids.Grid2D((H, H), 0.2)
+  g = torch.Generator(device='cuda').manual_seed(0)
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  keep = (ov[:, None] * ov[None, :] > 0.05 * H * H)[None]
+  frames = [torch.where(keep, torch.randn((R, Ho, Wo), device='cuda', generator=g) * 0.25, float('-inf')).contiguous()
+            for _ in range(2)]
+  step = geometry.Transform2D(torch.tensor(np.deg2rad(5.0)), torch.tensor([0.93, 0.37], dtype=torch.float64))
+  taps = pev.motion_taps(step, grid, R, 0.2, np.deg2rad(2.0), device='cuda')
+  Tk, Ta, Tb = taps[0].shape[0], taps[2].shape[1], taps[3].shape[1]
+  assert (Tk, Ta, Tb) == (4, 8, 8), (Tk, Ta, Tb)
+  taps_host = tuple(t.cpu().numpy() if isinstance(t, torch.Tensor) else t for t in taps)
+  belief = pev.filter_votes(None, frames[0], None, grid, R, 0.2, np.deg2rad(2.0), temperature=scale)['belief']
+  votes = frames[1]
+  out, stats, count = ops.vote_filter(belief, votes, taps, scale, eps)
+  t_out, t_lz = torch_filter(belief, votes, taps_host, scale, eps)
+  fin = torch.isfinite(t_out)
+  assert torch.equal(fin, torch.isfinite(out)) and int(count[0]) == int(fin.sum()) and int(count[2]) == 0
+  err = float((out[fin] - t_out[fin]).abs().max())
+  assert err < 1e-3 and abs(float(stats[0]) - float(t_lz)) < 1e-3, (err, float(stats[0]), float(t_lz))
+  kernel = lambda: ops.vote_filter(belief, votes, taps, scale, eps)
+  start = lambda: ops.vote_filter(None, votes, taps, scale, eps)
+  compo = lambda: torch_filter(belief, votes, taps_host, scale, eps)
+  for fn, reps in ((kernel, 5), (start, 5), (compo, 2)):
+    for _ in range(reps):
+      fn()
+  torch.cuda.synchronize()
+  ks, ss, ts = [], [], []
+  for _ in range(5):
+    ks.append(median_ms(kernel, max(iters, 5)))
+    ss.append(median_ms(start, max(iters, 5)))
+    ts.append(median_ms(compo, 3))
+  k_ms, s_ms, t_ms = sorted(ks)[2], sorted(ss)[2], sorted(ts)[2]
+  n = R * Ho * Wo
+  by = 4.0 * n * 12                # vote_filter.hip's header: 12 passes over the volume with a belief, 3 without
+  hbm_peak = 8.0e12                # B/s, the MI355X's HBM3E peak
+  res = dict(case='vote_filter_c4', shape=[R, Ho, Wo], taps=[Tk, Ta, Tb], scale=scale, uniform_mix=eps,
+             masked_fraction_votes=round(1 - float(torch.isfinite(votes).float().mean()), 4),
+             cells_with_mass=int(count[3]), mass_kept=round(float(stats[1]), 6), log_evidence=round(float(stats[0]), 4),
+             call_ms=round(k_ms, 4), call_ms_blocks=[round(v, 4) for v in ks],
+             call_ms_without_belief=round(s_ms, 4), call_ms_without_belief_blocks=[round(v, 4) for v in ss],
+             torch_composition_ms=round(t_ms, 4), torch_composition_ms_blocks=[round(v, 4) for v in ts],
+             speedup=round(t_ms / k_ms, 2), launch_bytes=int(by), call_GBps_of_launch_bytes=round(by / k_ms / 1e6, 1),
+             call_fraction_of_hbm_peak=round(by / (k_ms * 1e-3) / hbm_peak, 3), hbm_peak_Bps=hbm_peak,
+             max_abs_difference_to_torch=err, timing='call_ms = one whole ops.vote_filter call between device events on '
+             'an idle stream (its four torch.empty allocations, the ctypes call and the seven launches; three without a '
+             'belief), NOT kernel time; median of single calls, 5 blocks of each alternated, median block; the torch '
+             'composition is Tk rolls and R (Ta + Tb) = 576 shifted slice updates, 3 calls per block',
+             caveat='launch_bytes counts every pass a launch makes over the 37.6 MB volume (12 with a belief); the belief, '
+             'the votes and the two intermediates together fit the 256 MB Infinity Cache, so the passes need not come '
+             'from HBM: the fraction relates the launch bytes of one call to the HBM peak, whatever served them')
+  line = json.dumps(res)
+  print(line)
+  for a in sys.argv[3:]:
+    if a.startswith('json='):
+      with open(a[5:], 'w') as f:
+        f.write(line + '\n')
+
+
 def vote_refine_c4(iters):
   """Peak refinement at the C4 planes (256^2 cells, D = 32, R = 36, 16 peaks x the default 11 x 9 x 9 lattice = 14 256
   poses; 10 % / 5 % invalid cells): whole ops.plane_align_score calls, median of single calls, against the only way to
@@ -405,4 +507,5 @@ if __name__ == '__main__':
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
   {'pose_score': pose_score, 'pose_score_c4': pose_score_c4, 'voting_c4': voting_c4,
    'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4,
+   'vote_filter_c4': vote_filter_c4,
    'vote_refine_c4': vote_refine_c4}[which](iters)
