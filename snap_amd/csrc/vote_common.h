@@ -1,0 +1,159 @@
+// Device and host pieces shared by the operators on the exhaustive vote volume (vote_peaks.hip, vote_posterior.hip,
+// vote_fuse.hip, vote_filter.hip, vote_refine.hip).  The family's contract is "no atomics; every sum's order is a
+// function of the shape alone; two calls give the same bits", and vote_filter is tested against vote_fuse and
+// vote_posterior bit for bit: the predicates, reductions, tile walk and circular indices those comparisons rest on
+// exist once, here.  No kernels.  -ffp-contract=off is in force, so one expression gives one set of bits wherever it
+// is inlined.
+#ifndef SNAP_CSRC_VOTE_COMMON_H_
+#define SNAP_CSRC_VOTE_COMMON_H_
+
+#include "common.h"
+
+__device__ __forceinline__ bool vote_finite(float v) { return fabsf(v) < INFINITY; }   // false for NaN and +-inf
+
+// ------------------------------- wave butterflies ---------------------------------------------
+// xor butterflies: the same bits in every lane.  (Not common.h's DPP wave_sum: another order, another instruction mix.)
+__device__ __forceinline__ double vote_wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ int vote_wave_sum(int v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// ------------------------------- workgroup reductions -----------------------------------------
+// The waves' partials combined in the order that is part of a float64 result: the four waves of a 256-thread
+// workgroup pairwise, (w0 + w1) + (w2 + w3); the 16 of a 1024-thread workgroup in sequence from 0.
+template <int WAVES, typename T>
+__device__ __forceinline__ T vote_waves_sum(const T* sh) {
+  if constexpr (WAVES == 4) {
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  } else {
+    T s = 0;
+    for (int w = 0; w < WAVES; ++w) s += sh[w];
+    return s;
+  }
+}
+
+// A wave tree (lane 0's value is used), then the waves: the same bits in every thread.  `sh` [WAVES] is free again on
+// return.
+template <int WAVES, typename T>
+__device__ __forceinline__ T vote_block_sum(T v, T* sh) {
+  v = vote_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const T s = vote_waves_sum<WAVES>(sh);
+  __syncthreads();
+  return s;
+}
+template <int WAVES>
+__device__ __forceinline__ float vote_block_max(float v, float* sh) {
+  v = wave_max(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  static_assert(WAVES == 4, "the 1024-thread kernels use their staging arrays once and keep their own fold");
+  const float m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+  __syncthreads();
+  return m;
+}
+// Two counts at once behind ONE barrier: thread 0 returns the workgroup's sum of c0, thread 1 that of c1 (the other
+// threads 0).  `sh` is not free again before the caller's next barrier.
+template <int WAVES>
+__device__ __forceinline__ int vote_block_count_pair(int c0, int c1, int (*sh)[2]) {
+  c0 = vote_wave_sum(c0);
+  c1 = vote_wave_sum(c1);
+  if ((threadIdx.x & 63) == 0) {
+    sh[threadIdx.x >> 6][0] = c0;
+    sh[threadIdx.x >> 6][1] = c1;
+  }
+  __syncthreads();
+  int s = 0;
+  if (threadIdx.x < 2)
+    for (int w = 0; w < WAVES; ++w) s += sh[w][threadIdx.x];
+  return s;
+}
+
+// The fold of column `col` of [groups][STRIDE] per-workgroup partials by a whole workgroup: a strided chain per
+// thread, then the workgroup reduction.
+template <int WAVES, int STRIDE, typename T>
+__device__ __forceinline__ T vote_fold_sum(const T* __restrict__ part, int col, int groups, T* sh) {
+  T v = 0;
+  for (int g = threadIdx.x; g < groups; g += WAVES * SNAP_WAVE) v += part[(size_t)g * STRIDE + col];
+  return vote_block_sum<WAVES>(v, sh);
+}
+template <int WAVES, int STRIDE>
+__device__ __forceinline__ float vote_fold_max(const float* __restrict__ part, int col, int groups, float* sh) {
+  float v = -INFINITY;
+  for (int g = threadIdx.x; g < groups; g += WAVES * SNAP_WAVE) v = fmaxf(v, part[(size_t)g * STRIDE + col]);
+  return vote_block_max<WAVES>(v, sh);
+}
+
+// ------------------------------- the tile walk ------------------------------------------------
+// A tile is one rotation and NT consecutive pixels p = a * Wo + b of its plane, one per thread; workgroups stride over
+// the tiles.  This thread's pixel of tile `tile_in_plane`: false (and p = 0) past the plane's end, in the ragged last
+// tile.
+template <int NT>
+__device__ __forceinline__ bool vote_tile_pixel(int tile_in_plane, int P, int* p) {
+  const int64_t p64 = (int64_t)tile_in_plane * NT + threadIdx.x;
+  const bool in = p64 < P;
+  *p = in ? (int)p64 : 0;
+  return in;
+}
+template <int NT>
+__device__ __forceinline__ bool vote_tile_cell(int tile, int tiles_per_plane, int P, int* r, int* p) {
+  *r = tile / tiles_per_plane;
+  return vote_tile_pixel<NT>(tile - *r * tiles_per_plane, P, p);
+}
+__device__ __forceinline__ void vote_row_col(int p, int Wo, int* a, int* b) {
+  *a = p / Wo;
+  *b = p - *a * Wo;
+}
+
+// ------------------------------- circular rotation index --------------------------------------
+__device__ __forceinline__ int vote_wrap(int r, int R) { return r < 0 ? r + R : (r >= R ? r - R : r); }   // -R <= r < 2 R
+__device__ __forceinline__ int vote_next(int k, int R) { return k + 1 == R ? 0 : k + 1; }
+__device__ __forceinline__ int vote_mod(int v, int R) {   // v mod R in [0, R), mathematically, for any v
+  const int k = (int)((int64_t)v % R);
+  return k < 0 ? k + R : k;
+}
+
+// ------------------------------- host: the launch plan ----------------------------------------
+struct VotePlan {
+  int P, tiles_per_plane, tiles, groups;
+};
+
+// Every flat index of the volume(s) is an int: false at 2^31 cells and beyond.
+inline bool vote_cells_fit(int64_t cells) { return cells < ((int64_t)1 << 31); }
+
+// `planes` planes of Ho x Wo cut into tiles of `nt` pixels, at most `max_groups` workgroups striding over them.
+inline bool vote_plan(int64_t cells, int planes, int Ho, int Wo, int nt, int max_groups, VotePlan* plan) {
+  if (!vote_cells_fit(cells)) return false;
+  plan->P = Ho * Wo;
+  plan->tiles_per_plane = (int)snap_cdiv(plan->P, nt);
+  plan->tiles = planes * plan->tiles_per_plane;   // < 2^31 / nt + planes
+  plan->groups = plan->tiles < max_groups ? plan->tiles : max_groups;
+  return true;
+}
+
+// ------------------------------- host: the workspace layout -----------------------------------
+// A running offset over the sections of a workspace, each rounded up to whole 8-byte words.  An operator describes its
+// layout ONCE, as a function of its plan that take()s the sections in order (inside one braced list: evaluated left
+// to right): with base == nullptr it yields the size (`bytes`, and null sections), with the caller's workspace the
+// pointers.
+struct VoteLayout {
+  void* base;
+  size_t bytes = 0;
+  template <typename T>
+  T* take(size_t count) {
+    T* section = base != nullptr ? reinterpret_cast<T*>(static_cast<unsigned char*>(base) + bytes) : nullptr;
+    bytes += (count * sizeof(T) + 7) / 8 * 8;
+    return section;
+  }
+};
+
+inline bool vote_workspace_ok(const void* workspace, size_t workspace_bytes, size_t need) {
+  return workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 8 == 0;
+}
+
+#endif  // SNAP_CSRC_VOTE_COMMON_H_

@@ -26,7 +26,7 @@
 // chain per thread and the same tree -- an order fixed by (R, Ho, Wo) alone.
 // HBM traffic (n = R Ho Wo cells of 4 bytes): reads belief 2 (+ L2 re-reads), t0, t1, t2 twice, votes twice; writes
 // t0, t1, t2, belief_out: 12 n cells with a belief, 3 n without.
-#include "common.h"
+#include "vote_common.h"
 
 namespace {
 
@@ -42,35 +42,6 @@ constexpr float FL_CUT = -40.f;             // a cell carries mass iff belief - 
 enum { FL_D_SUMP = 0, FL_D_SUMT2 = 1, FL_D_LSE_M = 2, FL_D_LSE_S = 3 };
 enum { FL_I_BAD = 0, FL_I_MASS = 1, FL_I_FIN = 2, FL_I_NAN = 3 };
 enum { FL_F_PEAK = 0, FL_F_OUTMAX = 1 };
-
-__device__ __forceinline__ bool fl_finite(float v) { return fabsf(v) < INFINITY; }   // false for NaN and +-inf
-
-// ---- workgroup reductions: a wave tree (lane 0's value is used), the four waves in order; the same bits in every
-// thread.  `sh` is free again on return.
-__device__ __forceinline__ double fl_block_sum(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return s;
-}
-__device__ __forceinline__ int fl_block_sum(int v, int* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const int s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return s;
-}
-__device__ __forceinline__ float fl_block_max(float v, float* sh) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-  __syncthreads();
-  return m;
-}
 
 // (m, s) = (maximum, sum of exp(u - m)) of a set of finite u; the empty set is (-inf, 0).  Merge another set in.
 __device__ __forceinline__ void fl_lse_merge(double* m, double* s, double m2, double s2) {
@@ -102,27 +73,10 @@ __device__ __forceinline__ void fl_block_lse(double* m, double* s, double (*sh)[
   *s = ss;
 }
 
-// The fold of one column of the per-workgroup partials, by a whole workgroup.
-__device__ __forceinline__ double fl_fold_sum(const double* __restrict__ dpart, int col, int groups, double* sh) {
-  double v = 0.0;
-  for (int g = threadIdx.x; g < groups; g += FL_NT) v += dpart[(size_t)g * 4 + col];
-  return fl_block_sum(v, sh);
-}
-__device__ __forceinline__ int fl_fold_sum(const int32_t* __restrict__ ipart, int col, int groups, int* sh) {
-  int v = 0;
-  for (int g = threadIdx.x; g < groups; g += FL_NT) v += ipart[(size_t)g * 4 + col];
-  return fl_block_sum(v, sh);
-}
-__device__ __forceinline__ float fl_fold_max(const float* __restrict__ fpart, int col, int groups, float* sh) {
-  float v = -INFINITY;
-  for (int g = threadIdx.x; g < groups; g += FL_NT) v = fmaxf(v, fpart[(size_t)g * 2 + col]);
-  return fl_block_max(v, sh);
-}
-
 // The mass of a belief cell relative to the peak M: one f32 subtraction, the cut, exp in float64 rounded once.
 __device__ __forceinline__ float fl_mass(float v, float M) {
   const float d = v - M;
-  return (fl_finite(v) && d >= FL_CUT) ? (float)exp((double)d) : 0.f;
+  return (vote_finite(v) && d >= FL_CUT) ? (float)exp((double)d) : 0.f;
 }
 
 // ---- launch 1
@@ -134,13 +88,13 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_peak_kernel(const float* __
   int bad = 0;
   for (int64_t i = (int64_t)blockIdx.x * FL_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FL_NT) {
     const float v = belief[i];
-    if (fl_finite(v))
+    if (vote_finite(v))
       m = fmaxf(m, v);
     else if (!(v == -INFINITY))
       ++bad;                                // NaN or +inf
   }
-  m = fl_block_max(m, shf);
-  bad = fl_block_sum(bad, shi);
+  m = vote_block_max<FL_WAVES>(m, shf);
+  bad = vote_block_sum<FL_WAVES>(bad, shi);
   if (threadIdx.x == 0) {
     fpart[(size_t)blockIdx.x * 2 + FL_F_PEAK] = m;
     ipart[(size_t)blockIdx.x * 4 + FL_I_BAD] = bad;
@@ -156,12 +110,12 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_rotate_kernel(const float* 
   __shared__ float shf[FL_WAVES];
   __shared__ double shd[FL_WAVES];
   __shared__ int shi[FL_WAVES];
-  const float M = fl_fold_max(fpart, FL_F_PEAK, gridDim.x, shf);
-  int kfirst = (int)((int64_t)lk % R);      // (r + lk) mod R, mathematically: lk mod R in [0, R) first
-  if (kfirst < 0) kfirst += R;
+  const float M = vote_fold_max<FL_WAVES, 2>(fpart, FL_F_PEAK, gridDim.x, shf);
+  const int kfirst = vote_mod(lk, R);       // (r + lk) mod R, mathematically: lk mod R in [0, R) first
   double sum_p = 0.0;
   int n_mass = 0;
   for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    // (vote_tile_cell written out: through it this kernel takes 42 VGPRs / 58 SGPRs for 40 / 56)
     const int r = tile / tiles_per_plane;
     const int64_t p64 = (int64_t)(tile - r * tiles_per_plane) * FL_NT + threadIdx.x;
     if (p64 >= P) continue;
@@ -169,17 +123,17 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_rotate_kernel(const float* 
     const float own = fl_mass(belief[(int64_t)r * P + p], M);
     sum_p += (double)own;
     n_mass += own > 0.f ? 1 : 0;
-    int k = r + kfirst;
+    int k = r + kfirst;                     // (>= 0: one side of vote_wrap)
     if (k >= R) k -= R;
     float acc = 0.f;
     for (int i = 0; i < Tk; ++i) {
       acc = fmaf(taps_k[i], fl_mass(belief[(int64_t)k * P + p], M), acc);
-      k = k + 1 == R ? 0 : k + 1;
+      k = vote_next(k, R);
     }
     t0[(int64_t)r * P + p] = acc;
   }
-  sum_p = fl_block_sum(sum_p, shd);
-  n_mass = fl_block_sum(n_mass, shi);
+  sum_p = vote_block_sum<FL_WAVES>(sum_p, shd);
+  n_mass = vote_block_sum<FL_WAVES>(n_mass, shi);
   if (threadIdx.x == 0) {
     dpart[(size_t)blockIdx.x * 4 + FL_D_SUMP] = sum_p;
     ipart[(size_t)blockIdx.x * 4 + FL_I_MASS] = n_mass;
@@ -193,11 +147,9 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_rows_kernel(const float* __
                                                                  int Ta, int tiles_per_plane, int tiles,
                                                                  float* __restrict__ t1) {
   for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int r = tile / tiles_per_plane;
-    const int64_t p64 = (int64_t)(tile - r * tiles_per_plane) * FL_NT + threadIdx.x;
-    if (p64 >= P) continue;
-    const int p = (int)p64;
-    const int a = p / Wo, b = p - a * Wo;
+    int r, p, a, b;
+    if (!vote_tile_cell<FL_NT>(tile, tiles_per_plane, P, &r, &p)) continue;
+    vote_row_col(p, Wo, &a, &b);
     const float* w = taps_a + (size_t)r * Ta;                     // uniform over the workgroup
     const int64_t first = (int64_t)a + offsets[(size_t)r * 2];    // the source row of tap 0
     const float* src = t0 + (int64_t)r * P + b;
@@ -219,11 +171,9 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_cols_kernel(const float* __
   __shared__ double shd[FL_WAVES];
   double sum = 0.0;
   for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int r = tile / tiles_per_plane;
-    const int64_t p64 = (int64_t)(tile - r * tiles_per_plane) * FL_NT + threadIdx.x;
-    if (p64 >= P) continue;
-    const int p = (int)p64;
-    const int a = p / Wo, b = p - a * Wo;
+    int r, p, a, b;
+    if (!vote_tile_cell<FL_NT>(tile, tiles_per_plane, P, &r, &p)) continue;
+    vote_row_col(p, Wo, &a, &b);
     const float* w = taps_b + (size_t)r * Tb;
     const int64_t first = (int64_t)b + offsets[(size_t)r * 2 + 1];
     const float* src = t1 + (int64_t)r * P + (int64_t)a * Wo;
@@ -235,7 +185,7 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_cols_kernel(const float* __
     t2[(int64_t)r * P + p] = acc;
     sum += (double)acc;
   }
-  sum = fl_block_sum(sum, shd);
+  sum = vote_block_sum<FL_WAVES>(sum, shd);
   if (threadIdx.x == 0) dpart[(size_t)blockIdx.x * 4 + FL_D_SUMT2] = sum;
 }
 
@@ -257,7 +207,7 @@ __device__ __forceinline__ double fl_update(const FlUpdate& c, float t2, float v
 __device__ __forceinline__ FlUpdate fl_update_setup(const double* dpart, int groups, bool with_belief, float scale,
                                                     float eps, int n, double* sh) {
   FlUpdate c;
-  c.S = with_belief ? fl_fold_sum(dpart, FL_D_SUMT2, groups, sh) : 0.0;
+  c.S = with_belief ? vote_fold_sum<FL_WAVES, 4>(dpart, FL_D_SUMT2, groups, sh) : 0.0;
   c.has_prior = with_belief && c.S > 0.0;
   c.scale = (double)scale;
   // belief == NULL is the uniform prior: eps = 1
@@ -326,13 +276,13 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_normalise_kernel(const floa
     else
       out = (float)(u - log_z);
     belief_out[i] = out;
-    n_fin += fl_finite(out) ? 1 : 0;
+    n_fin += vote_finite(out) ? 1 : 0;
     n_nan += out != out ? 1 : 0;
     top = fmaxf(top, out);                  // (fmaxf drops a NaN)
   }
-  top = fl_block_max(top, shf);
-  n_fin = fl_block_sum(n_fin, shi);
-  n_nan = fl_block_sum(n_nan, shi);
+  top = vote_block_max<FL_WAVES>(top, shf);
+  n_fin = vote_block_sum<FL_WAVES>(n_fin, shi);
+  n_nan = vote_block_sum<FL_WAVES>(n_nan, shi);
   if (threadIdx.x == 0) {
     fpart[(size_t)blockIdx.x * 2 + FL_F_OUTMAX] = top;
     ipart[(size_t)blockIdx.x * 4 + FL_I_FIN] = n_fin;
@@ -350,17 +300,17 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_finish_kernel(int groups, i
   __shared__ double shd[FL_WAVES];
   __shared__ float shf[FL_WAVES];
   __shared__ int shi[FL_WAVES];
-  const int n_fin = fl_fold_sum(ipart, FL_I_FIN, groups, shi);
-  const int n_nan = fl_fold_sum(ipart, FL_I_NAN, groups, shi);
-  const float top = fl_fold_max(fpart, FL_F_OUTMAX, groups, shf);
+  const int n_fin = vote_fold_sum<FL_WAVES, 4>(ipart, FL_I_FIN, groups, shi);
+  const int n_nan = vote_fold_sum<FL_WAVES, 4>(ipart, FL_I_NAN, groups, shi);
+  const float top = vote_fold_max<FL_WAVES, 2>(fpart, FL_F_OUTMAX, groups, shf);
   int n_bad = 0, n_mass = 0;
   float M = -INFINITY, kept = 1.f;
   if (with_belief) {
-    n_bad = fl_fold_sum(ipart, FL_I_BAD, groups, shi);
-    n_mass = fl_fold_sum(ipart, FL_I_MASS, groups, shi);
-    M = fl_fold_max(fpart, FL_F_PEAK, groups, shf);
-    const double sum_p = fl_fold_sum(dpart, FL_D_SUMP, groups, shd);
-    const double S = fl_fold_sum(dpart, FL_D_SUMT2, groups, shd);
+    n_bad = vote_fold_sum<FL_WAVES, 4>(ipart, FL_I_BAD, groups, shi);
+    n_mass = vote_fold_sum<FL_WAVES, 4>(ipart, FL_I_MASS, groups, shi);
+    M = vote_fold_max<FL_WAVES, 2>(fpart, FL_F_PEAK, groups, shf);
+    const double sum_p = vote_fold_sum<FL_WAVES, 4>(dpart, FL_D_SUMP, groups, shd);
+    const double S = vote_fold_sum<FL_WAVES, 4>(dpart, FL_D_SUMT2, groups, shd);
     kept = sum_p > 0.0 ? (float)(S / sum_p) : 0.f;
   }
   if (threadIdx.x == 0) {
@@ -374,25 +324,31 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_finish_kernel(int groups, i
   }
 }
 
-struct FlPlan {
-  int n, P, tiles_per_plane, tiles, groups;
-  size_t t1_bytes, d_bytes, i_bytes, f_bytes;
+struct FlPlan : VotePlan {
+  int n;
 };
 
 bool fl_plan(int R, int Ho, int Wo, int Tk, int Ta, int Tb, FlPlan* plan) {
   if (R < 1 || R > FL_MAX_R || Ho < 1 || Wo < 1) return false;
   if (Tk < 1 || Tk > FL_MAX_TK || Ta < 1 || Ta > FL_MAX_TXY || Tb < 1 || Tb > FL_MAX_TXY) return false;
-  if ((int64_t)R * Ho * Wo >= ((int64_t)1 << 31)) return false;
+  if (!vote_plan((int64_t)R * Ho * Wo, R, Ho, Wo, FL_NT, FL_MAX_GROUPS, plan)) return false;
   plan->n = R * Ho * Wo;
-  plan->P = Ho * Wo;
-  plan->tiles_per_plane = (int)snap_cdiv(plan->P, FL_NT);
-  plan->tiles = R * plan->tiles_per_plane;   // < 2^31 / 256 + 64
-  plan->groups = plan->tiles < FL_MAX_GROUPS ? plan->tiles : FL_MAX_GROUPS;
-  plan->t1_bytes = ((size_t)plan->n * sizeof(float) + 7) / 8 * 8;
-  plan->d_bytes = (size_t)plan->groups * 4 * sizeof(double);
-  plan->i_bytes = (size_t)plan->groups * 4 * sizeof(int32_t);
-  plan->f_bytes = (size_t)plan->groups * 2 * sizeof(float);
   return true;
+}
+
+// [R Ho Wo] f32 t1 | [groups][4] float64 | [groups][4] int32 | [groups][2] f32
+struct FlWorkspace {
+  float* t1;
+  double* dpart;
+  int32_t* ipart;
+  float* fpart;
+  size_t bytes;
+};
+
+FlWorkspace fl_workspace(const FlPlan& plan, void* workspace) {
+  VoteLayout l{workspace};
+  return {l.take<float>(plan.n), l.take<double>((size_t)plan.groups * 4), l.take<int32_t>((size_t)plan.groups * 4),
+          l.take<float>((size_t)plan.groups * 2), l.bytes};
 }
 
 }  // namespace
@@ -401,8 +357,7 @@ extern "C" size_t snap_vote_filter_workspace_bytes(int32_t R, int32_t Ho, int32_
                                                    int32_t Tb) {
   FlPlan plan;
   if (!fl_plan(R, Ho, Wo, Tk, Ta, Tb, &plan)) return 0;
-  // [R Ho Wo] f32 t1 (whole 8-byte words) | [groups][4] float64 | [groups][4] int32 | [groups][2] f32
-  return plan.t1_bytes + plan.d_bytes + plan.i_bytes + plan.f_bytes;
+  return fl_workspace(plan, nullptr).bytes;
 }
 
 extern "C" int snap_vote_filter_f32(const float* belief, const float* votes, const float* taps_k, int32_t lk,
@@ -416,38 +371,32 @@ extern "C" int snap_vote_filter_f32(const float* belief, const float* votes, con
   if (!fl_plan(R, Ho, Wo, Tk, Ta, Tb, &plan)) return SNAP_ERR_BAD_SHAPE;
   if (!(scale > 0.f) || !(scale < INFINITY)) return SNAP_ERR_UNSUPPORTED;
   if (!(uniform_mix >= 0.f && uniform_mix <= 1.f)) return SNAP_ERR_UNSUPPORTED;
-  if (workspace_bytes < plan.t1_bytes + plan.d_bytes + plan.i_bytes + plan.f_bytes ||
-      reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-    return SNAP_ERR_WORKSPACE;
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  float* t1 = reinterpret_cast<float*>(ws);
-  double* dpart = reinterpret_cast<double*>(ws + plan.t1_bytes);
-  int32_t* ipart = reinterpret_cast<int32_t*>(ws + plan.t1_bytes + plan.d_bytes);
-  float* fpart = reinterpret_cast<float*>(ws + plan.t1_bytes + plan.d_bytes + plan.i_bytes);
+  if (!vote_workspace_ok(workspace, workspace_bytes, fl_workspace(plan, nullptr).bytes)) return SNAP_ERR_WORKSPACE;
+  const FlWorkspace w = fl_workspace(plan, workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(plan.groups), block(FL_NT);
   const int with_belief = belief != nullptr ? 1 : 0;
   if (with_belief) {
-    hipLaunchKernelGGL(vote_filter_peak_kernel, grid, block, 0, s, belief, plan.n, fpart, ipart);
+    hipLaunchKernelGGL(vote_filter_peak_kernel, grid, block, 0, s, belief, plan.n, w.fpart, w.ipart);
     SNAP_CHECK_LAUNCH();
     hipLaunchKernelGGL(vote_filter_rotate_kernel, grid, block, 0, s, belief, taps_k, lk, R, plan.P, Tk,
-                       plan.tiles_per_plane, plan.tiles, fpart, belief_out, dpart, ipart);
+                       plan.tiles_per_plane, plan.tiles, w.fpart, belief_out, w.dpart, w.ipart);
     SNAP_CHECK_LAUNCH();
     hipLaunchKernelGGL(vote_filter_rows_kernel, grid, block, 0, s, belief_out, taps_a, offsets, Ho, Wo, plan.P, Ta,
-                       plan.tiles_per_plane, plan.tiles, t1);
+                       plan.tiles_per_plane, plan.tiles, w.t1);
     SNAP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(vote_filter_cols_kernel, grid, block, 0, s, t1, taps_b, offsets, Wo, plan.P, Tb,
-                       plan.tiles_per_plane, plan.tiles, belief_out, dpart);
+    hipLaunchKernelGGL(vote_filter_cols_kernel, grid, block, 0, s, w.t1, taps_b, offsets, Wo, plan.P, Tb,
+                       plan.tiles_per_plane, plan.tiles, belief_out, w.dpart);
     SNAP_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(vote_filter_evidence_kernel, grid, block, 0, s, belief_out, votes, plan.n, with_belief, scale,
-                     uniform_mix, dpart);
+                     uniform_mix, w.dpart);
   SNAP_CHECK_LAUNCH();
   hipLaunchKernelGGL(vote_filter_normalise_kernel, grid, block, 0, s, votes, plan.n, with_belief, scale, uniform_mix,
-                     dpart, belief_out, fpart, ipart, stats);
+                     w.dpart, belief_out, w.fpart, w.ipart, stats);
   SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_filter_finish_kernel, dim3(1), block, 0, s, plan.groups, with_belief, dpart, fpart, ipart,
-                     stats, count);
+  hipLaunchKernelGGL(vote_filter_finish_kernel, dim3(1), block, 0, s, plan.groups, with_belief, w.dpart, w.fpart,
+                     w.ipart, stats, count);
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }

@@ -18,7 +18,7 @@
 // Launch 3 (vote_fuse_count_kernel, one workgroup): folds the <= 2048 pairs in a fixed tree.
 // No atomics; the order of every sum is fixed (frames ascending, taps k-major then a then b), so two calls give the
 // same bits.
-#include "common.h"
+#include "vote_common.h"
 
 namespace {
 
@@ -37,8 +37,6 @@ struct VfEntry {
   float w[8];                               // tap weights, tap = 4 kk + 2 aa + bb: ((k factor) * (a factor)) * (b factor)
 };
 static_assert(sizeof(VfEntry) == 64, "one table entry is 16 dwords");
-
-__device__ __forceinline__ bool vf_finite(float v) { return fabsf(v) < INFINITY; }   // false for NaN and +-inf
 
 // d -> (floor, fraction in [0, 1)): the fraction is the ONE f32 subtraction d - floorf(d); where that rounds to 1
 // (a tiny negative d) the position is taken as the next integer.
@@ -64,7 +62,7 @@ __global__ __launch_bounds__(VF_NT) void vote_fuse_table_kernel(const float* __r
   e.amax = e.bmax = 0;
   e.o0 = e.o1 = e.kind = e.pad = 0;
   for (int t = 0; t < 8; ++t) e.w[t] = 0.f;
-  if (vf_finite(dk) && vf_finite(da) && vf_finite(db)) {
+  if (vote_finite(dk) && vote_finite(da) && vote_finite(db)) {
     float lk, fk, la, fa, lb, fb;
     vf_split(dk, &lk, &fk);
     vf_split(da, &la, &fa);
@@ -81,7 +79,7 @@ __global__ __launch_bounds__(VF_NT) void vote_fuse_table_kernel(const float* __r
       int k0 = r + (int)km;
       if (k0 >= R) k0 -= R;
       if (k0 >= R) k0 = 0;                  // (km + R rounded to R: unreachable for |lk| < 2^24, harmless beyond)
-      const int k1 = k0 + 1 == R ? 0 : k0 + 1;
+      const int k1 = vote_next(k0, R);
       const int P = Ho * Wo;
       e.o0 = k0 * P + ia * Wo + ib;
       e.o1 = k1 * P + ia * Wo + ib;
@@ -123,14 +121,12 @@ __global__ __launch_bounds__(VF_NT) void vote_fuse_kernel(const float* __restric
                                                           int tiles_per_plane, int tiles, float* __restrict__ fused,
                                                           int32_t* __restrict__ cnt) {
   __shared__ int wcnt[VF_WAVES][2];
-  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int t = threadIdx.x;
   int n_fin = 0, n_nan = 0;
   for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int r = tile / tiles_per_plane;
-    const int64_t p64 = (int64_t)(tile - r * tiles_per_plane) * VF_NT + t;
-    if (p64 >= P) continue;
-    const int p = (int)p64;
-    const int a = p / Wo, b = p - a * Wo;
+    int r, p, a, b;
+    if (!vote_tile_cell<VF_NT>(tile, tiles_per_plane, P, &r, &p)) continue;
+    vote_row_col(p, Wo, &a, &b);
     bool bad = false, masked = false;
     float acc = -0.f;
     for (int n = 0; n < N; ++n) {
@@ -161,92 +157,68 @@ __global__ __launch_bounds__(VF_NT) void vote_fuse_kernel(const float* __restric
     }
     const float out = bad ? __int_as_float(0x7fc00000) : masked ? -INFINITY : acc;
     fused[(int64_t)r * P + p] = out;
-    n_fin += vf_finite(out) ? 1 : 0;
+    n_fin += vote_finite(out) ? 1 : 0;
     n_nan += out != out ? 1 : 0;
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    n_fin += __shfl_xor(n_fin, o);
-    n_nan += __shfl_xor(n_nan, o);
-  }
-  if (lane == 0) {
-    wcnt[wave][0] = n_fin;
-    wcnt[wave][1] = n_nan;
-  }
-  __syncthreads();
-  if (t < 2) cnt[(size_t)blockIdx.x * 2 + t] = (wcnt[0][t] + wcnt[1][t]) + (wcnt[2][t] + wcnt[3][t]);
+  const int n = vote_block_count_pair<VF_WAVES>(n_fin, n_nan, wcnt);
+  if (t < 2) cnt[(size_t)blockIdx.x * 2 + t] = n;
 }
 
 __global__ __launch_bounds__(VF_NC) void vote_fuse_count_kernel(const int32_t* __restrict__ cnt, int groups,
                                                                 int32_t* __restrict__ count) {
   __shared__ int sh[VF_NC / SNAP_WAVE][2];
-  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int t = threadIdx.x;
   int c0 = 0, c1 = 0;
   for (int g = t; g < groups; g += VF_NC) {
     c0 += cnt[(size_t)g * 2];
     c1 += cnt[(size_t)g * 2 + 1];
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    c0 += __shfl_xor(c0, o);
-    c1 += __shfl_xor(c1, o);
-  }
-  if (lane == 0) {
-    sh[wave][0] = c0;
-    sh[wave][1] = c1;
-  }
-  __syncthreads();
-  if (t < 2) {
-    int s = 0;
-    for (int w = 0; w < VF_NC / SNAP_WAVE; ++w) s += sh[w][t];
-    count[t] = s;
-  }
+  const int s = vote_block_count_pair<VF_NC / SNAP_WAVE>(c0, c1, sh);
+  if (t < 2) count[t] = s;
 }
 
-struct VfPlan {
-  int P, tiles_per_plane, tiles, groups;
-  size_t table_bytes, cnt_bytes;
+bool vf_plan(int N, int R, int Ho, int Wo, VotePlan* plan) {
+  if (N < 1 || N > VF_MAX_N || R < 1 || R > VF_MAX_R || Ho < 1 || Wo < 1) return false;
+  return vote_plan((int64_t)N * R * Ho * Wo, R, Ho, Wo, VF_NT, VF_MAX_GROUPS, plan);
+}
+
+// [N][R] 64-byte table entries | [groups][2] int32 counts
+// (the table entries are 64-byte records read as dwords: the workspace's 8-byte alignment is all the kernels need)
+struct VfWorkspace {
+  VfEntry* table;
+  int32_t* cnt;
+  size_t bytes;
 };
 
-bool vf_plan(int N, int R, int Ho, int Wo, VfPlan* plan) {
-  if (N < 1 || N > VF_MAX_N || R < 1 || R > VF_MAX_R || Ho < 1 || Wo < 1) return false;
-  if ((int64_t)N * R * Ho * Wo >= ((int64_t)1 << 31)) return false;
-  plan->P = Ho * Wo;
-  plan->tiles_per_plane = (int)snap_cdiv(plan->P, VF_NT);
-  plan->tiles = R * plan->tiles_per_plane;   // < 2^31 / 256 + 64
-  plan->groups = plan->tiles < VF_MAX_GROUPS ? plan->tiles : VF_MAX_GROUPS;
-  plan->table_bytes = (size_t)N * R * sizeof(VfEntry);
-  plan->cnt_bytes = (size_t)plan->groups * 2 * sizeof(int32_t);
-  return true;
+VfWorkspace vf_workspace(const VotePlan& plan, int N, int R, void* workspace) {
+  VoteLayout l{workspace};
+  return {l.take<VfEntry>((size_t)N * R), l.take<int32_t>((size_t)plan.groups * 2), l.bytes};
 }
 
 }  // namespace
 
 extern "C" size_t snap_vote_fuse_workspace_bytes(int32_t N, int32_t R, int32_t Ho, int32_t Wo) {
-  VfPlan plan;
+  VotePlan plan;
   if (!vf_plan(N, R, Ho, Wo, &plan)) return 0;
-  // [N][R] 64-byte table entries | [groups][2] int32 counts
-  return plan.table_bytes + plan.cnt_bytes;
+  return vf_workspace(plan, N, R, nullptr).bytes;
 }
 
 extern "C" int snap_vote_fuse_f32(const float* volumes, const float* shifts, const float* weights, int32_t N, int32_t R,
                                   int32_t Ho, int32_t Wo, float* fused, int32_t* count, void* workspace,
                                   size_t workspace_bytes, void* stream) {
   if (!volumes || !shifts || !fused || !count || !workspace) return SNAP_ERR_NULL;
-  VfPlan plan;
+  VotePlan plan;
   if (!vf_plan(N, R, Ho, Wo, &plan)) return SNAP_ERR_BAD_SHAPE;
-  // (the table entries are 64-byte records read as dwords: 8-byte alignment is all the kernels need)
-  if (workspace_bytes < plan.table_bytes + plan.cnt_bytes || reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-    return SNAP_ERR_WORKSPACE;
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  VfEntry* table = reinterpret_cast<VfEntry*>(ws);
-  int32_t* cnt = reinterpret_cast<int32_t*>(ws + plan.table_bytes);
+  if (!vote_workspace_ok(workspace, workspace_bytes, vf_workspace(plan, N, R, nullptr).bytes)) return SNAP_ERR_WORKSPACE;
+  const VfWorkspace w = vf_workspace(plan, N, R, workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(vote_fuse_table_kernel, dim3((unsigned)snap_cdiv(N * R, VF_NT)), dim3(VF_NT), 0, s, shifts, N, R,
-                     Ho, Wo, table);
+                     Ho, Wo, w.table);
   SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_fuse_kernel, dim3(plan.groups), dim3(VF_NT), 0, s, volumes, table, weights, N, R, plan.P, Wo,
-                     plan.tiles_per_plane, plan.tiles, fused, cnt);
+  hipLaunchKernelGGL(vote_fuse_kernel, dim3(plan.groups), dim3(VF_NT), 0, s, volumes, w.table, weights, N, R, plan.P,
+                     Wo, plan.tiles_per_plane, plan.tiles, fused, w.cnt);
   SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_fuse_count_kernel, dim3(1), dim3(VF_NC), 0, s, cnt, plan.groups, count);
+  hipLaunchKernelGGL(vote_fuse_count_kernel, dim3(1), dim3(VF_NC), 0, s, w.cnt, plan.groups, count);
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }

@@ -20,7 +20,7 @@
 // Pass 2 (vote_peaks_merge_kernel, one workgroup, one sorted slot list per thread): K rounds of "greatest list
 // head"; then one thread per output row, the score re-read from votes[flat] (its own bits, -0 included).
 // No atomics anywhere: no result depends on the order in which workgroups or waves arrive.
-#include "common.h"
+#include "vote_common.h"
 
 namespace {
 
@@ -48,8 +48,6 @@ __device__ __forceinline__ uint32_t vp_key(float v) {
 
 __device__ __forceinline__ uint32_t vp_umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 __device__ __forceinline__ uint64_t vp_umax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
-
-__device__ __forceinline__ int vp_wrap(int r, int R) { return r < 0 ? r + R : (r >= R ? r - R : r); }
 
 // bytes of LDS in front of the staged keys: list | nbuf | per-wave counts
 constexpr size_t VP_LDS_HEAD = (size_t)(VP_LIST + VP_MAX_K) * sizeof(uint64_t) + 2 * VP_WAVES * sizeof(int);
@@ -85,7 +83,7 @@ __global__ __launch_bounds__(VP_NT) void vote_peaks_tiles_kernel(
     // ---- stage: one wave per (rotation, row) of the haloed tile; 64 body columns, then the 2 rx halo columns
     for (int row = wave; row < NP * SH; row += VP_WAVES) {
       const int p = row / SH, y = row - p * SH;
-      const int rn = vp_wrap(r + p - rr, R);
+      const int rn = vote_wrap(r + p - rr, R);
       const int a = a0 + y - rx;
       const bool row_ok = a >= 0 && a < Ho;
       const float* src = votes + ((int64_t)rn * Ho + (row_ok ? a : 0)) * Wo;
@@ -123,7 +121,7 @@ __global__ __launch_bounds__(VP_NT) void vote_peaks_tiles_kernel(
       uint32_t m = 0;
       for (int p = 0; p < NP; ++p) {
         if (p == rr) continue;
-        const uint32_t later = vp_wrap(r + p - rr, R) > r ? 1u : 0u;
+        const uint32_t later = vote_wrap(r + p - rr, R) > r ? 1u : 0u;
         const uint32_t* pl = stage + (p * SH + ty) * SW + lane;
         for (int dy = 0; dy <= 2 * rx; ++dy)
           for (int dx = 0; dx <= 2 * rx; ++dx) m = vp_umax(m, pl[dy * SW + dx] - later);
@@ -177,14 +175,10 @@ __global__ __launch_bounds__(VP_NT) void vote_peaks_tiles_kernel(
   }
 
   if (t < K) slots[(int64_t)blockIdx.x * K + t] = t < nb ? list[t] : 0;
-  for (int o = 32; o > 0; o >>= 1) nan_seen += __shfl_xor(nan_seen, o);
+  nan_seen = vote_wave_sum(nan_seen);
   if (lane == 0) wnan[wave] = nan_seen;
   __syncthreads();
-  if (t == 0) {
-    int s = 0;
-    for (int w = 0; w < VP_WAVES; ++w) s += wnan[w];
-    nan_counts[blockIdx.x] = s;
-  }
+  if (t == 0) nan_counts[blockIdx.x] = vote_waves_sum<VP_WAVES>(wnan);
 }
 
 __global__ __launch_bounds__(VP_MAX_GROUPS) void vote_peaks_merge_kernel(
@@ -213,8 +207,7 @@ __global__ __launch_bounds__(VP_MAX_GROUPS) void vote_peaks_merge_kernel(
       cur = head < K ? mylist[head] : 0;
     }
   }
-  int nan_seen = t < groups ? nan_counts[t] : 0;
-  for (int o = 32; o > 0; o >>= 1) nan_seen += __shfl_xor(nan_seen, o);
+  const int nan_seen = vote_wave_sum(t < groups ? nan_counts[t] : 0);
   if (lane == 0) wnan[wave] = nan_seen;
   __syncthreads();
   // ---- one thread per output row (the winners are sorted: the empty rows are the tail)
@@ -234,11 +227,10 @@ __global__ __launch_bounds__(VP_MAX_GROUPS) void vote_peaks_merge_kernel(
     }
   }
   if (t == 0) {
-    int found = 0, s = 0;
+    int found = 0;
     for (int j = 0; j < K; ++j) found += winner[j] != 0 ? 1 : 0;
-    for (int w = 0; w < NW; ++w) s += wnan[w];
     count[0] = found;
-    count[1] = s;
+    count[1] = vote_waves_sum<NW>(wnan);
   }
 }
 
@@ -249,12 +241,24 @@ struct VpPlan {
 bool vp_plan(int R, int Ho, int Wo, int K, int rr, int rx, VpPlan* plan) {
   if (R <= 0 || Ho <= 0 || Wo <= 0 || K < 1 || K > VP_MAX_K) return false;
   if (rr < 0 || rr > VP_MAX_RR || 2 * rr + 1 > R || rx < 1 || rx > VP_MAX_RX) return false;
-  if ((int64_t)R * Ho * Wo >= ((int64_t)1 << 31)) return false;
+  if (!vote_cells_fit((int64_t)R * Ho * Wo)) return false;
   plan->bands = (int)snap_cdiv(Ho, VP_TA);
   plan->cblocks = (int)snap_cdiv(Wo, VP_TB);
   plan->tiles = R * plan->bands * plan->cblocks;
   plan->groups = plan->tiles < VP_MAX_GROUPS ? plan->tiles : VP_MAX_GROUPS;
   return true;
+}
+
+// [groups][K] candidate keys | [groups] NaN counts
+struct VpWorkspace {
+  uint64_t* slots;
+  int32_t* nan_counts;
+  size_t bytes;
+};
+
+VpWorkspace vp_workspace(const VpPlan& plan, int K, void* workspace) {
+  VoteLayout l{workspace};
+  return {l.take<uint64_t>((size_t)plan.groups * K), l.take<int32_t>(plan.groups), l.bytes};
 }
 
 }  // namespace
@@ -263,8 +267,7 @@ extern "C" size_t snap_vote_peaks_workspace_bytes(int32_t R, int32_t Ho, int32_t
                                                   int32_t radius_xy) {
   VpPlan plan;
   if (!vp_plan(R, Ho, Wo, K, radius_r, radius_xy, &plan)) return 0;
-  // [groups][K] candidate keys | [groups] NaN counts, rounded up to whole 8-byte words
-  return (size_t)plan.groups * K * sizeof(uint64_t) + ((size_t)plan.groups * sizeof(int32_t) + 7) / 8 * 8;
+  return vp_workspace(plan, K, nullptr).bytes;
 }
 
 extern "C" int snap_vote_peaks_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, int32_t K,
@@ -273,21 +276,18 @@ extern "C" int snap_vote_peaks_f32(const float* votes, int32_t R, int32_t Ho, in
   if (!votes || !index || !score || !count || !workspace) return SNAP_ERR_NULL;
   VpPlan plan;
   if (!vp_plan(R, Ho, Wo, K, radius_r, radius_xy, &plan)) return SNAP_ERR_BAD_SHAPE;
-  if (workspace_bytes < snap_vote_peaks_workspace_bytes(R, Ho, Wo, K, radius_r, radius_xy) ||
-      reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-    return SNAP_ERR_WORKSPACE;
-  uint64_t* slots = static_cast<uint64_t*>(workspace);
-  int32_t* nan_counts = reinterpret_cast<int32_t*>(slots + (size_t)plan.groups * K);
+  if (!vote_workspace_ok(workspace, workspace_bytes, vp_workspace(plan, K, nullptr).bytes)) return SNAP_ERR_WORKSPACE;
+  const VpWorkspace w = vp_workspace(plan, K, workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t lds = vp_lds_bytes(radius_r, radius_xy);
   if (radius_r == 1 && radius_xy == 1)
     hipLaunchKernelGGL((vote_peaks_tiles_kernel<1, 1>), dim3(plan.groups), dim3(VP_NT), lds, s, votes, R, Ho, Wo, K,
-                       radius_r, radius_xy, plan.bands, plan.cblocks, plan.tiles, slots, nan_counts);
+                       radius_r, radius_xy, plan.bands, plan.cblocks, plan.tiles, w.slots, w.nan_counts);
   else
     hipLaunchKernelGGL((vote_peaks_tiles_kernel<-1, -1>), dim3(plan.groups), dim3(VP_NT), lds, s, votes, R, Ho, Wo, K,
-                       radius_r, radius_xy, plan.bands, plan.cblocks, plan.tiles, slots, nan_counts);
+                       radius_r, radius_xy, plan.bands, plan.cblocks, plan.tiles, w.slots, w.nan_counts);
   SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_peaks_merge_kernel, dim3(1), dim3(VP_MAX_GROUPS), 0, s, votes, slots, nan_counts,
+  hipLaunchKernelGGL(vote_peaks_merge_kernel, dim3(1), dim3(VP_MAX_GROUPS), 0, s, votes, w.slots, w.nan_counts,
                      plan.groups, K, R, Ho, Wo, index, score, count);
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;

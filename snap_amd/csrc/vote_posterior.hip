@@ -23,7 +23,7 @@
 //   rounded once; workgroup 0 folds the partial rows column by column (8 chunks of workgroups in order, then the
 //   chunks in order) and writes log_prob_r, the statistics, the counts and the ground-truth sample.
 // No atomics and no inter-workgroup hand-off inside a launch: every sum's order is a function of (R, Ho, Wo) alone.
-#include "common.h"
+#include "vote_common.h"
 
 namespace {
 
@@ -39,17 +39,6 @@ constexpr int PO_CHUNKS = 8;                // launch B, workgroup 0: column sum
 constexpr int PO_CHUNK_COLS = PO_NB / PO_CHUNKS;
 constexpr int PO_MAX_NORM_GROUPS = 256;
 static_assert(PO_COLS <= PO_CHUNK_COLS && PO_COLS <= PO_NT, "one thread per partial column");
-
-__device__ __forceinline__ bool po_finite(float v) { return fabsf(v) < INFINITY; }   // false for NaN and +-inf
-
-__device__ __forceinline__ double po_wave_sum(double v) {     // xor butterfly: the same bits in every lane
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ int po_wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __global__ __launch_bounds__(PO_NT) void vote_posterior_tiles_kernel(
     const float* __restrict__ votes, int R, int P, int Wo, float scale, int tiles, float* __restrict__ sum_xy,
@@ -68,9 +57,8 @@ __global__ __launch_bounds__(PO_NT) void vote_posterior_tiles_kernel(
 
   for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     __syncthreads();                        // acc / m_run_s of the previous tile; wmax, wsum, wred free again
-    const int64_t p64 = (int64_t)tile * PO_NT + t;
-    const bool in = p64 < P;
-    const int p = in ? (int)p64 : 0;
+    int p;
+    const bool in = vote_tile_pixel<PO_NT>(tile, P, &p);
     const float* src = votes + p;
     // ---- walk 1: the pixel's maximum and counts
     float m_p = -INFINITY;
@@ -78,7 +66,7 @@ __global__ __launch_bounds__(PO_NT) void vote_posterior_tiles_kernel(
 #pragma unroll 4
       for (int r = 0; r < R; ++r) {
         const float v = src[(size_t)r * P];
-        if (po_finite(v)) {
+        if (vote_finite(v)) {
           m_p = fmaxf(m_p, scale * v);
           ++n_ok;
         } else if (!(v == -INFINITY)) {
@@ -87,7 +75,7 @@ __global__ __launch_bounds__(PO_NT) void vote_posterior_tiles_kernel(
       }
       pix_m[p] = m_p;
     }
-    const float wm = wave_max(m_p);
+    const float wm = wave_max(m_p);          // (vote_block_max written out: wmax needs no second barrier here)
     if (lane == 0) wmax[wave] = wm;
     __syncthreads();
     const float m_t = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
@@ -103,7 +91,7 @@ __global__ __launch_bounds__(PO_NT) void vote_posterior_tiles_kernel(
       float e = 0.f;
       if (live) {
         const float v = src[(size_t)r * P];
-        if (po_finite(v)) {
+        if (vote_finite(v)) {
           const float d = fmaf(scale, v, -m_p);
           e = expf(d);
           s_p += e;
@@ -117,7 +105,8 @@ __global__ __launch_bounds__(PO_NT) void vote_posterior_tiles_kernel(
     // ---- float64 above the pixel
     double val[PO_HEAD - 1];
     {
-      const int a = p / Wo, b = p - a * Wo;
+      int a, b;
+      vote_row_col(p, Wo, &a, &b);
       const double fd = (double)f_p, sd = (double)s_p, da = (double)a, db = (double)b;
       const double W = live ? sd * fd : 0.0;
       val[0] = W;
@@ -130,7 +119,7 @@ __global__ __launch_bounds__(PO_NT) void vote_posterior_tiles_kernel(
     }
 #pragma unroll
     for (int i = 0; i < PO_HEAD - 1; ++i) {
-      const double s = po_wave_sum(val[i]);
+      const double s = vote_wave_sum(val[i]);
       if (lane == 0) wred[wave][i] = s;
     }
     __syncthreads();
@@ -162,8 +151,8 @@ __global__ __launch_bounds__(PO_NT) void vote_posterior_tiles_kernel(
   }
   __syncthreads();
   if (t < cols) part[(size_t)blockIdx.x * cols + t] = t == 0 ? (double)m_run_s : acc[t];
-  n_ok = po_wave_sum(n_ok);
-  n_bad = po_wave_sum(n_bad);
+  n_ok = vote_wave_sum(n_ok);
+  n_bad = vote_wave_sum(n_bad);
   if (lane == 0) {
     wcnt[wave][0] = n_ok;
     wcnt[wave][1] = n_bad;
@@ -191,17 +180,17 @@ __global__ __launch_bounds__(PO_NB) void vote_posterior_finish_kernel(
   // ---- the global maximum and Z' = sum_g exp(m_g - M) W_g: one fixed tree, the same in every workgroup
   const float m_g = t < groups ? (float)part[(size_t)t * cols] : -INFINITY;
   const double W_g = t < groups ? part[(size_t)t * cols + 1] : 0.0;
+  // (vote_block_max / vote_block_sum written out: shm and shz are used once, so neither needs a second barrier)
   const float wm = wave_max(m_g);
   if (lane == 0) shm[wave] = wm;
   __syncthreads();
   float M = -INFINITY;
   for (int w = 0; w < PO_NB_WAVES; ++w) M = fmaxf(M, shm[w]);
   const double f = m_g > -INFINITY ? exp((double)m_g - (double)M) : 0.0;
-  const double zs = po_wave_sum(f * W_g);
+  const double zs = vote_wave_sum(f * W_g);
   if (lane == 0) shz[wave] = zs;
   __syncthreads();
-  double Zp = 0.0;
-  for (int w = 0; w < PO_NB_WAVES; ++w) Zp += shz[w];
+  const double Zp = vote_waves_sum<PO_NB_WAVES>(shz);   // (the 16 waves in sequence)
   const bool empty = !(M > -INFINITY);
   const double logZp = empty ? 0.0 : log(Zp);
 
@@ -216,9 +205,9 @@ __global__ __launch_bounds__(PO_NB) void vote_posterior_finish_kernel(
 
   // ---- workgroup 0: counts, the column sums, log_prob_r, the statistics, the ground-truth sample
   {
-    int c0 = t < groups ? cnt[(size_t)t * 2] : 0, c1 = t < groups ? cnt[(size_t)t * 2 + 1] : 0;
-    c0 = po_wave_sum(c0);
-    c1 = po_wave_sum(c1);
+    // (written out, not vote_block_count_pair: thread 64 stores both counts with its stats, one dwordx2)
+    const int c0 = vote_wave_sum(t < groups ? cnt[(size_t)t * 2] : 0);
+    const int c1 = vote_wave_sum(t < groups ? cnt[(size_t)t * 2 + 1] : 0);
     if (lane == 0) {
       shc[wave][0] = c0;
       shc[wave][1] = c1;
@@ -310,7 +299,7 @@ __global__ __launch_bounds__(PO_NB) void vote_posterior_finish_kernel(
     int valid = 0;
     if (gt != nullptr && !empty) {
       const float k = gt[0], i = gt[1], j = gt[2];
-      if (po_finite(k) && po_finite(i) && po_finite(j) && i >= 0.f && i <= (float)(Ho - 1) && j >= 0.f &&
+      if (vote_finite(k) && vote_finite(i) && vote_finite(j) && i >= 0.f && i <= (float)(Ho - 1) && j >= 0.f &&
           j <= (float)(Wo - 1)) {
         const double kfl = floor((double)k), ifl = floor((double)i), jfl = floor((double)j);
         const double wk = (double)k - kfl, wi = (double)i - ifl, wj = (double)j - jfl;
@@ -318,7 +307,7 @@ __global__ __launch_bounds__(PO_NB) void vote_posterior_finish_kernel(
         if (km < 0.0) km += (double)R;
         int k0 = (int)km;
         if (k0 >= R) k0 = 0;
-        const int k1 = k0 + 1 == R ? 0 : k0 + 1;
+        const int k1 = vote_next(k0, R);
         const int i0 = (int)ifl, j0 = (int)jfl;
         double sum = 0.0;
         bool ok = true;
@@ -332,7 +321,7 @@ __global__ __launch_bounds__(PO_NB) void vote_posterior_finish_kernel(
             continue;
           }
           const float v = votes[((size_t)rr * Ho + aa) * Wo + bb];
-          if (po_finite(v))
+          if (vote_finite(v))
             sum += w * (double)(scale * v);
           else
             ok = false;
@@ -348,23 +337,30 @@ __global__ __launch_bounds__(PO_NB) void vote_posterior_finish_kernel(
   }
 }
 
-struct PoPlan {
-  int P, tiles, groups, norm_groups;
-  size_t part_bytes, pix_bytes, cnt_bytes;
+struct PoPlan : VotePlan {   // (the tiles are cut from ONE plane: every rotation of a pixel belongs to its thread)
+  int norm_groups;
 };
 
 bool po_plan(int R, int Ho, int Wo, PoPlan* plan) {
   if (R < 1 || R > PO_MAX_R || Ho < 1 || Wo < 1) return false;
-  if ((int64_t)R * Ho * Wo >= ((int64_t)1 << 31)) return false;
-  plan->P = Ho * Wo;
-  plan->tiles = (int)snap_cdiv(plan->P, PO_NT);
-  plan->groups = plan->tiles < PO_MAX_GROUPS ? plan->tiles : PO_MAX_GROUPS;
+  if (!vote_plan((int64_t)R * Ho * Wo, 1, Ho, Wo, PO_NT, PO_MAX_GROUPS, plan)) return false;
   const int64_t ng = snap_cdiv(plan->P, 4 * PO_NB);
   plan->norm_groups = (int)(ng < PO_MAX_NORM_GROUPS ? ng : PO_MAX_NORM_GROUPS);
-  plan->part_bytes = (size_t)plan->groups * (PO_HEAD + R) * sizeof(double);
-  plan->pix_bytes = ((size_t)plan->P * sizeof(float) + 7) / 8 * 8;
-  plan->cnt_bytes = (size_t)plan->groups * 2 * sizeof(int32_t);
   return true;
+}
+
+// [groups][8 + R] float64 partial rows | [Ho Wo] f32 pixel maxima | [groups][2] counts
+struct PoWorkspace {
+  double* part;
+  float* pix_m;
+  int32_t* cnt;
+  size_t bytes;
+};
+
+PoWorkspace po_workspace(const PoPlan& plan, int R, void* workspace) {
+  VoteLayout l{workspace};
+  return {l.take<double>((size_t)plan.groups * (PO_HEAD + R)), l.take<float>(plan.P),
+          l.take<int32_t>((size_t)plan.groups * 2), l.bytes};
 }
 
 }  // namespace
@@ -372,8 +368,7 @@ bool po_plan(int R, int Ho, int Wo, PoPlan* plan) {
 extern "C" size_t snap_vote_posterior_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo) {
   PoPlan plan;
   if (!po_plan(R, Ho, Wo, &plan)) return 0;
-  // [groups][8 + R] float64 partial rows | [Ho Wo] f32 pixel maxima (whole 8-byte words) | [groups][2] counts
-  return plan.part_bytes + plan.pix_bytes + plan.cnt_bytes;
+  return po_workspace(plan, R, nullptr).bytes;
 }
 
 extern "C" int snap_vote_posterior_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, float scale,
@@ -383,20 +378,15 @@ extern "C" int snap_vote_posterior_f32(const float* votes, int32_t R, int32_t Ho
   PoPlan plan;
   if (!po_plan(R, Ho, Wo, &plan)) return SNAP_ERR_BAD_SHAPE;
   if (!(scale > 0.f) || !(scale < INFINITY)) return SNAP_ERR_UNSUPPORTED;
-  if (workspace_bytes < snap_vote_posterior_workspace_bytes(R, Ho, Wo) ||
-      reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-    return SNAP_ERR_WORKSPACE;
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  double* part = reinterpret_cast<double*>(ws);
-  float* pix_m = reinterpret_cast<float*>(ws + plan.part_bytes);
-  int32_t* cnt = reinterpret_cast<int32_t*>(ws + plan.part_bytes + plan.pix_bytes);
+  if (!vote_workspace_ok(workspace, workspace_bytes, po_workspace(plan, R, nullptr).bytes)) return SNAP_ERR_WORKSPACE;
+  const PoWorkspace w = po_workspace(plan, R, workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(vote_posterior_tiles_kernel, dim3(plan.groups), dim3(PO_NT), 0, s, votes, R, plan.P, Wo, scale,
-                     plan.tiles, log_prob_xy, pix_m, part, cnt);
+                     plan.tiles, log_prob_xy, w.pix_m, w.part, w.cnt);
   SNAP_CHECK_LAUNCH();
   hipLaunchKernelGGL(vote_posterior_finish_kernel, dim3(1 + plan.norm_groups), dim3(PO_NB), 0, s, votes, R, Ho, Wo,
-                     plan.P, scale, gt_index, plan.groups, plan.norm_groups, part, pix_m, cnt, log_prob_xy, log_prob_r,
-                     stats, count);
+                     plan.P, scale, gt_index, plan.groups, plan.norm_groups, w.part, w.pix_m, w.cnt, log_prob_xy,
+                     log_prob_r, stats, count);
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }

@@ -16,7 +16,7 @@
 //   is float64: per slot over its cells in tile order, then slots, then waves.  One (raw, count) pair per workgroup.
 // Launch 3 (pas_final_kernel, one thread per pose): the chunks ascending, the division, the threshold.
 // No atomics; results do not depend on P or on the order of the poses.
-#include "common.h"
+#include "vote_common.h"
 #include "rotate_sample.h"
 
 namespace {
@@ -39,8 +39,6 @@ struct PasPartial {
 };
 static_assert(sizeof(PasPartial) == 16, "one partial is 4 dwords");
 
-__device__ __forceinline__ bool pas_finite(float v) { return fabsf(v) < INFINITY; }   // false for NaN and +-inf
-
 __device__ __forceinline__ double pas_shfl_xor(double v, int mask) {
   int lo = __double2loint(v), hi = __double2hiint(v);
   lo = __shfl_xor(lo, mask);
@@ -51,17 +49,14 @@ __device__ __forceinline__ double pas_shfl_xor(double v, int mask) {
 __global__ __launch_bounds__(PAS_NC) void pas_tcount_kernel(const uint8_t* __restrict__ vq, int cells,
                                                             int32_t* __restrict__ tcount) {
   __shared__ int sh[PAS_NC / SNAP_WAVE];
-  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int t = threadIdx.x;
   int c = 0;
   for (int g = t; g < cells; g += PAS_NC) c += vq[g] != 0 ? 1 : 0;
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-  if (lane == 0) sh[wave] = c;
+  // (written out, not vote_block_sum: every thread folding the 16 waves takes 18 VGPRs for this kernel's 17)
+  c = vote_wave_sum(c);
+  if ((t & 63) == 0) sh[t >> 6] = c;
   __syncthreads();
-  if (t == 0) {
-    int s = 0;
-    for (int w = 0; w < PAS_NC / SNAP_WAVE; ++w) s += sh[w];
-    tcount[0] = s;
-  }
+  if (t == 0) tcount[0] = vote_waves_sum<PAS_NC / SNAP_WAVE>(sh);
 }
 
 __global__ __launch_bounds__(PAS_NT) void pas_partial_kernel(const float* __restrict__ fq,
@@ -79,7 +74,7 @@ __global__ __launch_bounds__(PAS_NT) void pas_partial_kernel(const float* __rest
   float tfm[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) tfm[k] = poses[(size_t)p * 4 + k];
-  const bool pose_ok = pas_finite(tfm[0]) && pas_finite(tfm[1]) && pas_finite(tfm[2]) && pas_finite(tfm[3]);
+  const bool pose_ok = vote_finite(tfm[0]) && vote_finite(tfm[1]) && vote_finite(tfm[2]) && vote_finite(tfm[3]);
   double acc = 0.0;
   int cnt = 0;
   const int tile_end = min(tiles, (chunk + 1) * PAS_CHUNK);
@@ -132,8 +127,8 @@ __global__ __launch_bounds__(PAS_NT) void pas_partial_kernel(const float* __rest
   __syncthreads();
   if (t == 0) {
     PasPartial out;
-    out.raw = (wraw[0] + wraw[1]) + (wraw[2] + wraw[3]);
-    out.cnt = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+    out.raw = vote_waves_sum<PAS_WAVES>(wraw);
+    out.cnt = vote_waves_sum<PAS_WAVES>(wcnt);
     out.pad = 0;
     partial[blockIdx.x] = out;
   }
@@ -147,7 +142,7 @@ __global__ __launch_bounds__(PAS_NT) void pas_final_kernel(const PasPartial* __r
   const int p = blockIdx.x * PAS_NT + threadIdx.x;
   if (p >= P) return;
   bool pose_ok = true;
-  for (int k = 0; k < 4; ++k) pose_ok = pose_ok && pas_finite(poses[(size_t)p * 4 + k]);
+  for (int k = 0; k < 4; ++k) pose_ok = pose_ok && vote_finite(poses[(size_t)p * 4 + k]);
   double raw = 0.0;
   int cnt = 0;
   for (int c = 0; c < chunks; ++c) {
@@ -162,7 +157,6 @@ __global__ __launch_bounds__(PAS_NT) void pas_final_kernel(const PasPartial* __r
 
 struct PasPlan {
   int tiles_j, tiles, chunks;
-  size_t partial_bytes;
 };
 
 bool pas_plan(int Hq, int Wq, int Hm, int Wm, int D, int P, PasPlan* plan) {
@@ -173,8 +167,19 @@ bool pas_plan(int Hq, int Wq, int Hm, int Wm, int D, int P, PasPlan* plan) {
   plan->tiles_j = (int)snap_cdiv(Wq, PAS_TILE);
   plan->tiles = (int)snap_cdiv(Hq, PAS_TILE) * plan->tiles_j;       // <= 4096
   plan->chunks = (int)snap_cdiv(plan->tiles, PAS_CHUNK);            // <= 256: P * chunks < 2^28
-  plan->partial_bytes = (size_t)P * plan->chunks * sizeof(PasPartial);
   return true;
+}
+
+// [P][chunks] 16-byte partials | tcount (one 8-byte word)
+struct PasWorkspace {
+  PasPartial* partial;
+  int32_t* tcount;
+  size_t bytes;
+};
+
+PasWorkspace pas_workspace(const PasPlan& plan, int P, void* workspace) {
+  VoteLayout l{workspace};
+  return {l.take<PasPartial>((size_t)P * plan.chunks), l.take<int32_t>(1), l.bytes};
 }
 
 }  // namespace
@@ -183,8 +188,7 @@ extern "C" size_t snap_plane_align_score_workspace_bytes(int32_t Hq, int32_t Wq,
                                                          int32_t P) {
   PasPlan plan;
   if (!pas_plan(Hq, Wq, Hm, Wm, D, P, &plan)) return 0;
-  // [P][chunks] 16-byte partials | tcount (8 bytes)
-  return plan.partial_bytes + 8;
+  return pas_workspace(plan, P, nullptr).bytes;
 }
 
 extern "C" int snap_plane_align_score_f32(const float* fq, const uint8_t* vq, const float* fm, const uint8_t* vm,
@@ -194,22 +198,19 @@ extern "C" int snap_plane_align_score_f32(const float* fq, const uint8_t* vq, co
   if (!fq || !vq || !fm || !vm || !poses || !score || !overlap || !workspace) return SNAP_ERR_NULL;
   PasPlan plan;
   if (!pas_plan(Hq, Wq, Hm, Wm, D, P, &plan)) return SNAP_ERR_UNSUPPORTED;
-  if (workspace_bytes < plan.partial_bytes + 8 || reinterpret_cast<uintptr_t>(workspace) % 8 != 0)
-    return SNAP_ERR_WORKSPACE;
+  if (!vote_workspace_ok(workspace, workspace_bytes, pas_workspace(plan, P, nullptr).bytes)) return SNAP_ERR_WORKSPACE;
   // (the feature rows are read as float4: D % 4 == 0 keeps every row 16-byte aligned when the planes are)
   if (reinterpret_cast<uintptr_t>(fq) % 16 != 0 || reinterpret_cast<uintptr_t>(fm) % 16 != 0)
     return SNAP_ERR_UNSUPPORTED;
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  PasPartial* partial = reinterpret_cast<PasPartial*>(ws);
-  int32_t* tcount = reinterpret_cast<int32_t*>(ws + plan.partial_bytes);
+  const PasWorkspace w = pas_workspace(plan, P, workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(pas_tcount_kernel, dim3(1), dim3(PAS_NC), 0, s, vq, Hq * Wq, tcount);
+  hipLaunchKernelGGL(pas_tcount_kernel, dim3(1), dim3(PAS_NC), 0, s, vq, Hq * Wq, w.tcount);
   SNAP_CHECK_LAUNCH();
   hipLaunchKernelGGL(pas_partial_kernel, dim3((unsigned)(P * plan.chunks)), dim3(PAS_NT), 0, s, fq, vq, fm, vm, poses,
-                     Hq, Wq, Hm, Wm, D, plan.tiles_j, plan.tiles, plan.chunks, partial);
+                     Hq, Wq, Hm, Wm, D, plan.tiles_j, plan.tiles, plan.chunks, w.partial);
   SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(pas_final_kernel, dim3((unsigned)snap_cdiv(P, PAS_NT)), dim3(PAS_NT), 0, s, partial, poses,
-                     tcount, P, plan.chunks, threshold, score, overlap);
+  hipLaunchKernelGGL(pas_final_kernel, dim3((unsigned)snap_cdiv(P, PAS_NT)), dim3(PAS_NT), 0, s, w.partial, poses,
+                     w.tcount, P, plan.chunks, threshold, score, overlap);
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }

@@ -357,6 +357,27 @@ def _mask(t, name):
   return _chk(t, torch.uint8, name)
 
 
+def _arg_chk(t, name, dtypes, shape, device, want, also=True, tail=''):
+  """Argument ``t`` is a tensor of one of ``dtypes`` and of ``shape`` (None: any extent) on ``device`` (None: any ROCm
+  GPU), and ``also`` holds: else ValueError(f'{want}, got <what it is>{tail}').  Then the usual ``_chk``."""
+  if (not isinstance(t, torch.Tensor) or t.dtype not in dtypes
+      or (not t.is_cuda if device is None else t.device != device) or t.dim() != len(shape)
+      or any(s is not None and s != d for s, d in zip(shape, t.shape)) or not also):
+    got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t)
+    raise ValueError(f'{want}, got {got}{tail}')
+  return _chk(t, t.dtype, name)
+
+
+def _workspace_words(nbytes_fn, args, numel, unsupported):
+  """The workspace of one call in whole 8-byte words (the caller allocates them as int64: 8-byte aligned, and the
+  allocation stays at the wrapper's own site): ``nbytes_fn(*args)`` bytes.  The C side is not asked where ``numel``
+  does not fit its int32 arguments; 0 bytes is its refusal: ValueError(unsupported)."""
+  nbytes = nbytes_fn(*args) if numel < 2 ** 31 else 0
+  if nbytes == 0:
+    raise ValueError(unsupported)
+  return nbytes // 8
+
+
 # ----------------------------------------------------------------------------
 # encoder
 # ----------------------------------------------------------------------------
@@ -2218,12 +2239,11 @@ def vote_peaks(votes, k, radius_r=1, radius_xy=1):
     raise ValueError(f'vote_peaks: votes [R, Ho, Wo], got {tuple(votes.shape)}')
   R, Ho, Wo = votes.shape
   k, radius_r, radius_xy = int(k), int(radius_r), int(radius_xy)
-  wsb = lib.snap_vote_peaks_workspace_bytes(R, Ho, Wo, k, radius_r, radius_xy) if votes.numel() < 2 ** 31 else 0
-  if wsb == 0:
-    raise ValueError(
-        f'vote_peaks: unsupported R={R} Ho={Ho} Wo={Wo} k={k} radius_r={radius_r} radius_xy={radius_xy} '
-        '(1 <= k <= 64, 0 <= radius_r <= 2 with 2 radius_r + 1 <= R, 1 <= radius_xy <= 4, R Ho Wo < 2^31)')
-  ws = torch.empty((wsb // 8,), dtype=torch.int64, device=votes.device)   # (whole 8-byte words, 8-byte aligned)
+  words = _workspace_words(
+      lib.snap_vote_peaks_workspace_bytes, (R, Ho, Wo, k, radius_r, radius_xy), votes.numel(),
+      f'vote_peaks: unsupported R={R} Ho={Ho} Wo={Wo} k={k} radius_r={radius_r} radius_xy={radius_xy} '
+      '(1 <= k <= 64, 0 <= radius_r <= 2 with 2 radius_r + 1 <= R, 1 <= radius_xy <= 4, R Ho Wo < 2^31)')
+  ws = torch.empty((words,), dtype=torch.int64, device=votes.device)
   index = torch.empty((k, 3), dtype=torch.int32, device=votes.device)
   score = torch.empty((k,), dtype=torch.float32, device=votes.device)
   count = torch.empty((2,), dtype=torch.int32, device=votes.device)
@@ -2256,10 +2276,10 @@ def vote_posterior(votes, scale=1.0, gt_index=None):
     if tuple(gt_index.shape) != (3,) or gt_index.device != votes.device:
       raise ValueError(f'vote_posterior: gt_index f32 [3] on {votes.device}, got {tuple(gt_index.shape)} on '
                        f'{gt_index.device}')
-  wsb = lib.snap_vote_posterior_workspace_bytes(R, Ho, Wo) if votes.numel() < 2 ** 31 else 0
-  if wsb == 0:
-    raise ValueError(f'vote_posterior: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
-  ws = torch.empty((wsb // 8,), dtype=torch.int64, device=votes.device)   # (whole 8-byte words, 8-byte aligned)
+  words = _workspace_words(
+      lib.snap_vote_posterior_workspace_bytes, (R, Ho, Wo), votes.numel(),
+      f'vote_posterior: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  ws = torch.empty((words,), dtype=torch.int64, device=votes.device)
   log_prob_xy = torch.empty((Ho, Wo), dtype=torch.float32, device=votes.device)
   log_prob_r = torch.empty((R,), dtype=torch.float32, device=votes.device)
   stats = torch.empty((16,), dtype=torch.float32, device=votes.device)
@@ -2288,16 +2308,13 @@ def vote_fuse(volumes, shifts, weights=None):
   for t, name, shape in ((shifts, 'shifts', (N, R, 3)), (weights, 'weights', (N,))):
     if t is None and name == 'weights':
       continue
-    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != volumes.device
-        or tuple(t.shape) != shape):
-      got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t)
-      raise ValueError(f'vote_fuse: {name} f32 {list(shape)} on {volumes.device}, got {got}')
-    _f32(t, name)
-  wsb = lib.snap_vote_fuse_workspace_bytes(N, R, Ho, Wo) if volumes.numel() < 2 ** 31 else 0
-  if wsb == 0:
-    raise ValueError(f'vote_fuse: unsupported N={N} R={R} Ho={Ho} Wo={Wo} (1 <= N <= 16, 1 <= R <= 64, Ho, Wo >= 1, '
-                     'N R Ho Wo < 2^31)')
-  ws = torch.empty((wsb // 8,), dtype=torch.int64, device=volumes.device)   # (whole 8-byte words, 8-byte aligned)
+    _arg_chk(t, name, (torch.float32,), shape, volumes.device,
+             f'vote_fuse: {name} f32 {list(shape)} on {volumes.device}')
+  words = _workspace_words(
+      lib.snap_vote_fuse_workspace_bytes, (N, R, Ho, Wo), volumes.numel(),
+      f'vote_fuse: unsupported N={N} R={R} Ho={Ho} Wo={Wo} (1 <= N <= 16, 1 <= R <= 64, Ho, Wo >= 1, '
+      'N R Ho Wo < 2^31)')
+  ws = torch.empty((words,), dtype=torch.int64, device=volumes.device)
   fused = torch.empty((R, Ho, Wo), dtype=torch.float32, device=volumes.device)
   count = torch.empty((2,), dtype=torch.int32, device=volumes.device)
   # algorithmic bytes: the output once and, per frame, the two source planes of every rotation (one where the table
@@ -2322,10 +2339,8 @@ def vote_filter(belief, votes, taps, scale=1.0, uniform_mix=0.0):
   >= 2^-20 (not checked: ``motion_taps`` guarantees it; the full contract: snap_vote_filter_f32 in
   include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  if not isinstance(votes, torch.Tensor) or votes.dtype != torch.float32 or not votes.is_cuda or votes.dim() != 3:
-    got = f'{votes.dtype} {tuple(votes.shape)} on {votes.device}' if isinstance(votes, torch.Tensor) else type(votes)
-    raise ValueError(f'vote_filter: votes f32 [R, Ho, Wo] on a ROCm GPU, got {got}')
-  _f32(votes, 'votes')
+  _arg_chk(votes, 'votes', (torch.float32,), (None, None, None), None,
+           'vote_filter: votes f32 [R, Ho, Wo] on a ROCm GPU')
   R, Ho, Wo = votes.shape
   if not isinstance(taps, (tuple, list)) or len(taps) != 5:
     raise ValueError('vote_filter: taps = (taps_k, lk, taps_a, taps_b, offsets)')
@@ -2340,20 +2355,17 @@ def vote_filter(belief, votes, taps, scale=1.0, uniform_mix=0.0):
                                 (offsets, 'offsets', torch.int32, (R, 2))):
     if t is None and name == 'belief':
       continue
-    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != votes.device or tuple(t.shape) != shape):
-      got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t)
-      raise ValueError(f'vote_filter: {name} {dtype} {list(shape)} on {votes.device}, got {got}')
-    _chk(t, dtype, name)
+    _arg_chk(t, name, (dtype,), shape, votes.device, f'vote_filter: {name} {dtype} {list(shape)} on {votes.device}')
   scale, uniform_mix = float(scale), float(uniform_mix)
   if not (scale > 0.0 and np.isfinite(np.float32(scale))):
     raise ValueError(f'vote_filter: scale must be a finite number > 0, got {scale}')
   if not 0.0 <= uniform_mix <= 1.0:
     raise ValueError(f'vote_filter: uniform_mix must lie in [0, 1], got {uniform_mix}')
-  wsb = lib.snap_vote_filter_workspace_bytes(R, Ho, Wo, Tk, Ta, Tb) if votes.numel() < 2 ** 31 else 0
-  if wsb == 0:
-    raise ValueError(f'vote_filter: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
-                     'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
-  ws = torch.empty((wsb // 8,), dtype=torch.int64, device=votes.device)   # (whole 8-byte words, 8-byte aligned)
+  words = _workspace_words(
+      lib.snap_vote_filter_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), votes.numel(),
+      f'vote_filter: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
+      'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  ws = torch.empty((words,), dtype=torch.int64, device=votes.device)
   belief_out = torch.empty((R, Ho, Wo), dtype=torch.float32, device=votes.device)
   stats = torch.empty((4,), dtype=torch.float32, device=votes.device)
   count = torch.empty((4,), dtype=torch.int32, device=votes.device)
@@ -2382,25 +2394,21 @@ def plane_align_score(fq, vq, fm, vm, poses, threshold):
   Hq, Wq, D = fq.shape
   Hm, Wm = fm.shape[:2]
   for t, name, shape in ((vq, 'vq', (Hq, Wq)), (vm, 'vm', (Hm, Wm))):
-    if (not isinstance(t, torch.Tensor) or t.dtype not in (torch.bool, torch.uint8) or t.device != fq.device
-        or tuple(t.shape) != shape):
-      got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t)
-      raise ValueError(f'plane_align_score: {name} bool / uint8 {list(shape)} on {fq.device}, got {got}')
-    _mask(t, name)
-  if (not isinstance(poses, torch.Tensor) or poses.dtype != torch.float32 or poses.device != fq.device
-      or fm.device != fq.device or poses.dim() != 2 or poses.shape[1] != 4):
-    got = f'{poses.dtype} {tuple(poses.shape)} on {poses.device}' if isinstance(poses, torch.Tensor) else type(poses)
-    raise ValueError(f'plane_align_score: poses f32 [P, 4] and fm on {fq.device}, got {got} / {fm.device}')
-  _f32(poses, 'poses')
+    _arg_chk(t, name, (torch.bool, torch.uint8), shape, fq.device,
+             f'plane_align_score: {name} bool / uint8 {list(shape)} on {fq.device}')
+  _arg_chk(poses, 'poses', (torch.float32,), (None, 4), fq.device,
+           f'plane_align_score: poses f32 [P, 4] and fm on {fq.device}', also=fm.device == fq.device,
+           tail=f' / {fm.device}')
   P = poses.shape[0]
   threshold = float(threshold)
   if threshold != threshold:
     raise ValueError('plane_align_score: threshold is NaN')
-  wsb = lib.snap_plane_align_score_workspace_bytes(Hq, Wq, Hm, Wm, D, P) if P < 2 ** 31 else 0
-  if wsb == 0 or fq.data_ptr() % 16 or fm.data_ptr() % 16:
-    raise ValueError(f'plane_align_score: unsupported query {Hq}x{Wq} map {Hm}x{Wm} D={D} P={P} (extents 1 .. 1024, '
-                     'D % 4 == 0 with 4 <= D <= 128, 1 <= P < 2^20, 16-byte aligned planes)')
-  ws = torch.empty((wsb // 8,), dtype=torch.int64, device=fq.device)   # (whole 8-byte words, 8-byte aligned)
+  unsupported = (f'plane_align_score: unsupported query {Hq}x{Wq} map {Hm}x{Wm} D={D} P={P} (extents 1 .. 1024, '
+                 'D % 4 == 0 with 4 <= D <= 128, 1 <= P < 2^20, 16-byte aligned planes)')
+  if fq.data_ptr() % 16 or fm.data_ptr() % 16:
+    raise ValueError(unsupported)
+  words = _workspace_words(lib.snap_plane_align_score_workspace_bytes, (Hq, Wq, Hm, Wm, D, P), P, unsupported)
+  ws = torch.empty((words,), dtype=torch.int64, device=fq.device)
   score = torch.empty((P,), dtype=torch.float32, device=fq.device)
   overlap = torch.empty((P,), dtype=torch.int32, device=fq.device)
   # algorithmic work: per pose and query cell, four taps of D channels, one multiply-add each (2 * 4 * D flop);

@@ -92,6 +92,31 @@ def median_ms(fn, reps):
   return sorted(e0.elapsed_time(e1) for e0, e1 in evs)[reps // 2]
 
 
+def alternated_blocks(cases, blocks=5):
+  """cases = (fn, warm-up calls, calls per block), ...: warm every case up, then ``blocks`` rounds of one ``median_ms``
+  block of each case in turn -> per case (the median block, the blocks)."""
+  for fn, warm, _ in cases:
+    for _ in range(warm):
+      fn()
+  torch.cuda.synchronize()
+  out = [[] for _ in cases]
+  for _ in range(blocks):
+    for ms, (fn, _, reps) in zip(out, cases):
+      ms.append(median_ms(fn, reps))
+  return [(sorted(ms)[blocks // 2], ms) for ms in out]
+
+
+def emit_json(res):
+  """One JSON line on stdout; a `json=<path>` argument behind the iteration count also writes it to that file."""
+  import json
+  line = json.dumps(res)
+  print(line)
+  for a in sys.argv[3:]:
+    if a.startswith('json='):
+      with open(a[5:], 'w') as f:
+        f.write(line + '\n')
+
+
 def torch_peaks(votes, k, radius_r, radius_xy):
   """What a user would write without the kernel: circular pad on r, max_pool3d (-inf padded in a, b), compare, topk.
   (Ties on a plateau all survive the compare: the composition has no order contract.)"""
@@ -106,7 +131,6 @@ def vote_peaks_c4(iters):
   """Top-K peak extraction on the C4 vote volume (R = 36, 511 x 511, K = 16, radius (1, 1)): the kernel alone against
   the torch composition on the same votes, blocks of the two alternated, medians of single calls.  One JSON line;
   `json=<path>` as a third argument also writes it to that file."""
-  import json
   R, Ho, Wo, K, rr, rx = 36, 511, 511, 16, 1, 1
   g = torch.Generator(device='cuda').manual_seed(0)
   votes = torch.randn((R, Ho, Wo), device='cuda', generator=g)       # (peak density 1 / 27: denser than real votes)
@@ -116,15 +140,7 @@ def vote_peaks_c4(iters):
   assert torch.equal(flat, idx) and torch.equal(score, val), 'kernel and torch composition disagree on tie-free votes'
   kernel = lambda: ops.vote_peaks(votes, K, rr, rx)
   compo = lambda: torch_peaks(votes, K, rr, rx)
-  for fn in (kernel, compo):
-    for _ in range(5):
-      fn()
-  torch.cuda.synchronize()
-  ks, ts = [], []
-  for _ in range(5):
-    ks.append(median_ms(kernel, max(iters, 5)))
-    ts.append(median_ms(compo, max(iters // 2, 5)))
-  k_ms, t_ms = sorted(ks)[2], sorted(ts)[2]
+  (k_ms, ks), (t_ms, ts) = alternated_blocks(((kernel, 5, max(iters, 5)), (compo, 5, max(iters // 2, 5))))
   # the other settings run the kernel's generic body (run-time radii): timed alone, on the same votes
   generic = {}
   for kk, r_, x_ in ((64, 2, 4), (5, 0, 2)):
@@ -142,12 +158,7 @@ def vote_peaks_c4(iters):
              fraction_of_pose_score_hbm_rate=round(by / (k_ms * 1e-3) / pose_score_rate, 3),
              pose_score_hbm_rate_Bps=pose_score_rate, timing='median of single calls between device events, 5 blocks '
              'of each alternated, median block; ops.vote_peaks = both launches + its three torch.empty outputs and workspace')
-  line = json.dumps(res)
-  print(line)
-  for a in sys.argv[3:]:
-    if a.startswith('json='):
-      with open(a[5:], 'w') as f:
-        f.write(line + '\n')
+  emit_json(res)
 
 
 def torch_posterior(votes, scale):
@@ -176,7 +187,6 @@ def vote_posterior_c4(iters):
   """The pose distribution of the C4 vote volume (R = 36, 511 x 511; the border the voting masks for low overlap is
   -inf): whole ops.vote_posterior calls against the torch composition on the same votes, blocks of the two
   alternated, medians of single calls (kernel times: a rocprofv3 --kernel-trace --stats run of this case).  One JSON line; `json=<path>` as a third argument also writes it to that file."""
-  import json
   R, H, scale = 36, 256, 8.0
   Ho = Wo = 2 * H - 1
   g = torch.Generator(device='cuda').manual_seed(0)
@@ -192,15 +202,7 @@ def vote_posterior_c4(iters):
   assert err['log_prob_xy'] < 1e-3 and err['log_prob_r'] < 1e-3 and max(err['stats'][:2]) < 1e-3, err
   kernel = lambda: ops.vote_posterior(votes, scale)
   compo = lambda: torch_posterior(votes, scale)
-  for fn in (kernel, compo):
-    for _ in range(5):
-      fn()
-  torch.cuda.synchronize()
-  ks, ts = [], []
-  for _ in range(5):
-    ks.append(median_ms(kernel, max(iters, 5)))
-    ts.append(median_ms(compo, max(iters // 2, 5)))
-  k_ms, t_ms = sorted(ks)[2], sorted(ts)[2]
+  (k_ms, ks), (t_ms, ts) = alternated_blocks(((kernel, 5, max(iters, 5)), (compo, 5, max(iters // 2, 5))))
   by = 4.0 * votes.numel()
   hbm_peak = 8.0e12               # B/s, the MI355X's HBM3E peak
   res = dict(case='vote_posterior_c4', shape=[R, Ho, Wo], scale=scale, masked_fraction=round(1 - int(t_n) / votes.numel(), 4),
@@ -216,12 +218,7 @@ def vote_posterior_c4(iters):
              'each alternated, median block', caveat='the 37.6 MB volume is read again on every repetition and fits the '
              '256 MB Infinity Cache, so the read need not come from HBM: the fractions relate one read of the volume per '
              'call to the HBM peak, whatever served the read')
-  line = json.dumps(res)
-  print(line)
-  for a in sys.argv[3:]:
-    if a.startswith('json='):
-      with open(a[5:], 'w') as f:
-        f.write(line + '\n')
+  emit_json(res)
 
 
 def torch_fuse(volumes, shifts_host, weights_host):
@@ -264,7 +261,6 @@ def vote_fuse_c4(iters):
   frame's volume -inf; shifts from a motion of 1 m and 5 degrees per frame on the 256^2 grid of 0.2 m cells, all
   fractional): whole ops.vote_fuse calls against the torch composition of the same result on the same inputs, blocks
   of the two alternated, medians of single calls.  One JSON line; `json=<path>` as a third argument also writes it."""
-  import json
   import numpy as np
   from snap_amd.models import pose_exhaustive_voting as pev
   from snap_amd.utils import geometry, grids
@@ -290,15 +286,7 @@ def vote_fuse_c4(iters):
   assert err < 1e-4, err
   kernel = lambda: ops.vote_fuse(volumes, shifts, weights)
   compo = lambda: torch_fuse(volumes, sh_host, w_host)
-  for fn, reps in ((kernel, 5), (compo, 2)):
-    for _ in range(reps):
-      fn()
-  torch.cuda.synchronize()
-  ks, ts = [], []
-  for _ in range(5):
-    ks.append(median_ms(kernel, max(iters, 5)))
-    ts.append(median_ms(compo, 3))
-  k_ms, t_ms = sorted(ks)[2], sorted(ts)[2]
+  (k_ms, ks), (t_ms, ts) = alternated_blocks(((kernel, 5, max(iters, 5)), (compo, 2, 3)))
   by = 4.0 * R * Ho * Wo * (1 + planes_read)
   hbm_peak = 8.0e12               # B/s, the MI355X's HBM3E peak
   res = dict(case='vote_fuse_c4', shape=[N, R, Ho, Wo], masked_fraction_in=round(1 - float(torch.isfinite(volumes).float().mean()), 4),
@@ -315,12 +303,7 @@ def vote_fuse_c4(iters):
              caveat='the 150 MB of volumes are read again on every repetition and fit the 256 MB Infinity Cache, so the '
              'reads need not come from HBM: the fraction relates the algorithmic bytes of one call to the HBM peak, '
              'whatever served them')
-  line = json.dumps(res)
-  print(line)
-  for a in sys.argv[3:]:
-    if a.startswith('json='):
-      with open(a[5:], 'w') as f:
-        f.write(line + '\n')
+  emit_json(res)
 
 
 def torch_filter(belief, votes, taps_host, scale, eps):
@@ -361,7 +344,6 @@ def vote_filter_c4(iters):
   sigma_xy = 0.2 m, sigma_yaw = 2 degrees on the 256^2 grid of 0.2 m cells): whole ops.vote_filter calls against the
   torch composition of the same result on the same inputs, blocks of the two alternated, medians of single calls.
   One JSON line; `json=<path>` as a third argument also writes it."""
-  import json
   import numpy as np
   from snap_amd.models import pose_exhaustive_voting as pev
   from snap_amd.utils import geometry, grids
@@ -389,16 +371,8 @@ def vote_filter_c4(iters):
   kernel = lambda: ops.vote_filter(belief, votes, taps, scale, eps)
   start = lambda: ops.vote_filter(None, votes, taps, scale, eps)
   compo = lambda: torch_filter(belief, votes, taps_host, scale, eps)
-  for fn, reps in ((kernel, 5), (start, 5), (compo, 2)):
-    for _ in range(reps):
-      fn()
-  torch.cuda.synchronize()
-  ks, ss, ts = [], [], []
-  for _ in range(5):
-    ks.append(median_ms(kernel, max(iters, 5)))
-    ss.append(median_ms(start, max(iters, 5)))
-    ts.append(median_ms(compo, 3))
-  k_ms, s_ms, t_ms = sorted(ks)[2], sorted(ss)[2], sorted(ts)[2]
+  (k_ms, ks), (s_ms, ss), (t_ms, ts) = alternated_blocks(
+      ((kernel, 5, max(iters, 5)), (start, 5, max(iters, 5)), (compo, 2, 3)))
   n = R * Ho * Wo
   by = 4.0 * n * 12                # vote_filter.hip's header: 12 passes over the volume with a belief, 3 without
   hbm_peak = 8.0e12                # B/s, the MI355X's HBM3E peak
@@ -417,12 +391,7 @@ def vote_filter_c4(iters):
              caveat='launch_bytes counts every pass a launch makes over the 37.6 MB volume (12 with a belief); the belief, '
              'the votes and the two intermediates together fit the 256 MB Infinity Cache, so the passes need not come '
              'from HBM: the fraction relates the launch bytes of one call to the HBM peak, whatever served them')
-  line = json.dumps(res)
-  print(line)
-  for a in sys.argv[3:]:
-    if a.startswith('json='):
-      with open(a[5:], 'w') as f:
-        f.write(line + '\n')
+  emit_json(res)
 
 
 def vote_refine_c4(iters):
@@ -431,7 +400,6 @@ def vote_refine_c4(iters):
   get the same scores without the kernel: one ops.interpolate_nd of the map at the query cells' positions and a torch
   reduction PER POSE, timed on a subset of the poses and scaled to all of them.  One JSON line; `json=<path>` as a
   third argument also writes it."""
-  import json
   import numpy as np
   from snap_amd.models import pose_exhaustive_voting as pev
   from snap_amd.utils import grids
@@ -472,15 +440,8 @@ def vote_refine_c4(iters):
   assert err < 1e-4, err
   kernel = lambda: ops.plane_align_score(fq, vq, fm, vm, poses, thr)
   compo = lambda: composed(sub_rows)
-  for fn in (kernel, compo):
-    for _ in range(2):
-      fn()
-  torch.cuda.synchronize()
-  ks, ts = [], []
-  for _ in range(3):
-    ks.append(median_ms(kernel, max(iters, 3)))
-    ts.append(median_ms(compo, 3))
-  k_ms, t_ms = sorted(ks)[1], sorted(ts)[1] * (P / len(sub))
+  (k_ms, ks), (t_ms, ts) = alternated_blocks(((kernel, 2, max(iters, 3)), (compo, 2, 3)), blocks=3)
+  t_ms *= P / len(sub)
   flop = 2.0 * 4 * P * H * H * D
   res = dict(case='vote_refine_c4', query=[H, H, D], map=[H, H, D], rotations=R, peaks=K, lattice=[11, 9, 9], poses=P,
              valid_fraction=[round(float(vq.float().mean()), 4), round(float(vm.float().mean()), 4)],
@@ -494,12 +455,7 @@ def vote_refine_c4(iters):
              'torch.empty allocations, the ctypes call and the three launches), NOT kernel time; median of single calls, '
              '3 blocks alternated with the loop, median block; flop = 2 * 4 * P * Hq * Wq * D counts every query cell '
              'of every pose, counted or not; the loop is timed on every (P / 32)-th pose and scaled by P / 32')
-  line = json.dumps(res)
-  print(line)
-  for a in sys.argv[3:]:
-    if a.startswith('json='):
-      with open(a[5:], 'w') as f:
-        f.write(line + '\n')
+  emit_json(res)
 
 
 if __name__ == '__main__':
