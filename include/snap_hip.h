@@ -1097,6 +1097,62 @@ int snap_vote_filter_f32(const float* belief, const float* votes, const float* t
                          int32_t Ta, int32_t Tb, float scale, float uniform_mix, float* belief_out, float* stats,
                          int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Backward SMOOTHING step of the pose filter above (the other half of a histogram filter): from the filtered belief
+ * of frame t and the smoothed belief of frame t+1 to the smoothed belief of frame t, p(x_t | all frames).  Run over
+ * the stored beliefs of a track from the last frame (whose smoothed belief is its filtered one) to the first.
+ * belief[R,Ho,Wo] f32 = the filter's belief_out at frame t (log alpha_t); next[R,Ho,Wo] f32 = the smoothed belief of
+ * frame t+1 (log gamma_{t+1}); taps_k, lk, taps_a, taps_b, offsets: the very tables snap_vote_filter_f32 was given for
+ * the step from t to t+1 (same layout, same precondition); uniform_mix = eps of that step; smoothed[R,Ho,Wo] f32 (must
+ * not overlap belief or next: it holds intermediates during the call); stats[4] f32; count[4] i32.  n = R*Ho*Wo.
+ *   PREDICT, exactly as snap_vote_filter_f32 does it with `belief` (its PREDICT paragraph: M, the masses p, the three
+ *   passes t0, t1, t2 as f32 fma chains, S = sum t2 and sum p in float64) and per cell, float64,
+ *   prior = ((1 - eps) * t2) / S + eps / n (the first term 0 when S == 0).  Both entry points are built from one set of
+ *   device code: t2, S and prior are the bits the filter computed from the same belief and taps.
+ *   RATIO, float64 per cell: a cell has ratio mass iff next is finite and prior > 0; then lg = (double)next -
+ *   log(prior).  G = the largest lg (exact).  q = fl32(exp(lg - G)) if fl32(lg - G) >= -40, else exactly 0, and 0
+ *   without ratio mass.  A NaN or +inf cell of next is a caller error: no mass, counted.  Q = sum q, float64.
+ *   ADJOINT TRANSPORT.  Three gathers, in this order (the xy passes first, with their OWN rotation's tables; the
+ *   rotation pass last), the intermediate volumes stored as f32:
+ *     c1[r,a,b] = sum_tb taps_b[r,tb] * q [r, a, b - lb[r] - tb];
+ *     c0[r,a,b] = sum_ta taps_a[r,ta] * c1[r, a - la[r] - ta, b];
+ *     u [k,a,b] = sum_tk taps_k[tk]   * c0[(k - lk - tk) mod R, a, b]    (mathematical modulo);
+ *   a source outside the volume contributes 0.  Each is an f32 fma chain from 0 over the SOURCE cell ascending, i.e.
+ *   the tap index DESCENDING: link i = 0 .. T-1 reads the source x - l - (T-1) + i with tap T-1-i (in k: plane
+ *   (k - lk - (Tk-1) + i) mod R, ascending before the modulo).  These are the filter's passes with each tap row
+ *   reversed and first offset -l - (T-1): sum t2 * q == sum p * u up to rounding.
+ *   COMBINE, float64 per cell: h = ((1 - eps) * (sum p / S)) * u + (eps / n) * Q (the first term 0 when S == 0);
+ *   w = ((double)belief + G) + log(h); -inf for a -inf belief or h == 0; NaN (0x7fc00000) for a NaN or +inf belief,
+ *   and the cell is left out of the normalisation; log_norm = log sum exp(w) over the finite cells (float64);
+ *   smoothed = fl32(w - log_norm).  When no cell has ratio mass (or none is finite), log_norm = -inf and every cell that
+ *   is not NaN is -inf.
+ *   This is gamma_t(x) = alpha_t(x) * sum_x' K(x'|x) gamma_{t+1}(x') / prior(x') with K = (1 - eps)(sum p / S) T +
+ *   eps / n, the kernel the filter applied, its renormalisation of the mass that left the volume included; for inputs
+ *   that come from the filter with the same tables log_norm is 0 up to rounding (its size is a diagnostic of beliefs or
+ *   tables that do not belong together).
+ *   stats = { log_norm; S / sum p (0 when no cell has mass; the filter's stats[1] of that step, bit for bit); G (-inf
+ *   without ratio mass); the largest smoothed (NaN cells aside; -inf when there is none) }.
+ *   count = { finite cells of smoothed; NaN or +inf cells of belief; NaN or +inf cells of next; cells of next with
+ *   ratio mass (those below the -40 cut included) }.
+ * Eleven launches of min(R * ceil(Ho*Wo/256), 2048) workgroups of 256 threads (the last: one workgroup), a tile = one
+ * rotation and 256 consecutive pixels: the filter's peak, rotation, row and column passes; the ratio's maximum; q,
+ * written once (the float64 log and exp are per cell, not per tap); the adjoint column, row and rotation passes, the
+ * last with the sum of exp(w) fused; the normalisation; the statistics.  t0, t2, c1 and u live in smoothed; t1, q and
+ * c0 in the workspace.  22 passes over the volume (reads: belief 4, next 2, t0, t1, t2 twice, q, c1, c0, u; writes: t0,
+ * t1, t2, q, c1, c0, u, smoothed), against the filter's 12.  No atomics: everything above the cell is float64 (counts
+ * int32) in an order fixed by (R, Ho, Wo), so two calls give the same bits.  Every element of smoothed, stats and
+ * count is written by every call.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32; anything else returns
+ * SNAP_ERR_BAD_SHAPE before any launch (a NULL pointer SNAP_ERR_NULL, checked first; a uniform_mix outside [0, 1]
+ * SNAP_ERR_UNSUPPORTED; a short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE).  workspace:
+ * snap_vote_smooth_workspace_bytes() bytes (0 = unsupported shape): one volume and the per-workgroup partials; it
+ * needs no initialisation and no launch touches a byte beyond that size.  Asynchronous on `stream`; the caller owns
+ * every buffer. */
+size_t snap_vote_smooth_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t Tk, int32_t Ta, int32_t Tb);
+int snap_vote_smooth_f32(const float* belief, const float* next, const float* taps_k, int32_t lk, const float* taps_a,
+                         const float* taps_b, const int32_t* offsets, int32_t R, int32_t Ho, int32_t Wo, int32_t Tk,
+                         int32_t Ta, int32_t Tb, float uniform_mix, float* smoothed, float* stats, int32_t* count,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Dense plane ALIGNMENT SCORE at continuous poses: what a vote of the exhaustive voting measures (the correlation of
  * the query plane with the map plane, normalised by the number of valid query cells), evaluated at poses that need
  * not lie on the vote lattice (pose_exhaustive_voting.refine_poses: a lattice of sub-bin / sub-cell poses around

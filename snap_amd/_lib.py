@@ -277,6 +277,9 @@ SIGNATURES = {
     'snap_vote_filter_workspace_bytes': (c_size, [c_int] * 6),
     'snap_vote_filter_f32': (
         c_int, [ptr, ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float, c_float, ptr, ptr, ptr, ptr, c_size, ptr]),
+    'snap_vote_smooth_workspace_bytes': (c_size, [c_int] * 6),
+    'snap_vote_smooth_f32': (
+        c_int, [ptr, ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float, ptr, ptr, ptr, ptr, c_size, ptr]),
     'snap_plane_align_score_workspace_bytes': (c_size, [c_int] * 6),
     'snap_plane_align_score_f32': (
         c_int, [ptr] * 5 + [c_int] * 6 + [c_float, ptr, ptr, ptr, c_size, ptr]),

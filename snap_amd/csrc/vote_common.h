@@ -1,6 +1,6 @@
 // Device and host pieces shared by the operators on the exhaustive vote volume (vote_peaks.hip, vote_posterior.hip,
-// vote_fuse.hip, vote_filter.hip, vote_refine.hip).  The family's contract is "no atomics; every sum's order is a
-// function of the shape alone; two calls give the same bits", and vote_filter is tested against vote_fuse and
+// vote_fuse.hip, vote_filter.hip, vote_smooth.hip, vote_refine.hip).  The family's contract is "no atomics; every sum's
+// order is a function of the shape alone; two calls give the same bits", and vote_filter is tested against vote_fuse and
 // vote_posterior bit for bit: the predicates, reductions, tile walk and circular indices those comparisons rest on
 // exist once, here.  No kernels.  -ffp-contract=off is in force, so one expression gives one set of bits wherever it
 // is inlined.
@@ -87,6 +87,57 @@ __device__ __forceinline__ float vote_fold_max(const float* __restrict__ part, i
   float v = -INFINITY;
   for (int g = threadIdx.x; g < groups; g += WAVES * SNAP_WAVE) v = fmaxf(v, part[(size_t)g * STRIDE + col]);
   return vote_block_max<WAVES>(v, sh);
+}
+
+// ------------------------------- log-sum-exp pairs --------------------------------------------
+// (m, s) = (maximum, sum of exp(u - m)) of a set of finite u; the empty set is (-inf, 0).  Merge another set in.
+__device__ __forceinline__ void vote_lse_merge(double* m, double* s, double m2, double s2) {
+  if (m2 == -(double)INFINITY) return;
+  if (*m == -(double)INFINITY) {
+    *m = m2;
+    *s = s2;
+  } else if (m2 > *m) {
+    *s = *s * exp(*m - m2) + s2;
+    *m = m2;
+  } else {
+    *s += s2 * exp(m2 - *m);
+  }
+}
+// One more finite u into a thread's running pair.
+__device__ __forceinline__ void vote_lse_add(double* m, double* s, double u) {
+  if (u > *m) {
+    *s = *s * exp(*m - u) + 1.0;            // (m = -inf at the first cell: exp gives 0)
+    *m = u;
+  } else {
+    *s += exp(u - *m);
+  }
+}
+template <int WAVES>
+__device__ __forceinline__ void vote_block_lse(double* m, double* s, double (*sh)[2]) {
+  for (int o = 32; o > 0; o >>= 1) {        // (lane 0 ends with the tree over all 64 lanes; only it is used)
+    const double m2 = __shfl_xor(*m, o), s2 = __shfl_xor(*s, o);
+    vote_lse_merge(m, s, m2, s2);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    sh[threadIdx.x >> 6][0] = *m;
+    sh[threadIdx.x >> 6][1] = *s;
+  }
+  __syncthreads();
+  double mm = sh[0][0], ss = sh[0][1];
+  for (int w = 1; w < WAVES; ++w) vote_lse_merge(&mm, &ss, sh[w][0], sh[w][1]);
+  __syncthreads();
+  *m = mm;
+  *s = ss;
+}
+// The fold of the pairs in columns (col_m, col_s) of [groups][STRIDE] partials -> log sum exp (-inf for the empty set).
+template <int WAVES, int STRIDE>
+__device__ __forceinline__ double vote_fold_lse(const double* __restrict__ part, int col_m, int col_s, int groups,
+                                                double (*sh)[2]) {
+  double m = -(double)INFINITY, s = 0.0;
+  for (int g = threadIdx.x; g < groups; g += WAVES * SNAP_WAVE)
+    vote_lse_merge(&m, &s, part[(size_t)g * STRIDE + col_m], part[(size_t)g * STRIDE + col_s]);
+  vote_block_lse<WAVES>(&m, &s, sh);
+  return m == -(double)INFINITY ? m : m + log(s);
 }
 
 // ------------------------------- the tile walk ------------------------------------------------

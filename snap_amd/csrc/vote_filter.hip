@@ -26,193 +26,65 @@
 // chain per thread and the same tree -- an order fixed by (R, Ho, Wo) alone.
 // HBM traffic (n = R Ho Wo cells of 4 bytes): reads belief 2 (+ L2 re-reads), t0, t1, t2 twice, votes twice; writes
 // t0, t1, t2, belief_out: 12 n cells with a belief, 3 n without.
-#include "vote_common.h"
+#include "vote_predict.h"
 
 namespace {
 
-constexpr int FL_NT = 256;                  // threads = cells of a tile
-constexpr int FL_WAVES = FL_NT / SNAP_WAVE;
-constexpr int FL_MAX_R = 64;
-constexpr int FL_MAX_TK = 16;
-constexpr int FL_MAX_TXY = 32;
-constexpr int FL_MAX_GROUPS = 2048;
-constexpr float FL_CUT = -40.f;             // a cell carries mass iff belief - M >= FL_CUT
+constexpr int FL_NT = VP_NT;                // threads = cells of a tile
+constexpr int FL_WAVES = VP_WAVES;
 
-// per-workgroup partials: double [groups][4], int32 [groups][4], float [groups][2]
-enum { FL_D_SUMP = 0, FL_D_SUMT2 = 1, FL_D_LSE_M = 2, FL_D_LSE_S = 3 };
-enum { FL_I_BAD = 0, FL_I_MASS = 1, FL_I_FIN = 2, FL_I_NAN = 3 };
-enum { FL_F_PEAK = 0, FL_F_OUTMAX = 1 };
+// per-workgroup partials: double [groups][4], int32 [groups][4], float [groups][2]; the predict step's columns first
+enum { FL_D_SUMP = VP_D_SUMP, FL_D_SUMT2 = VP_D_SUMT2, FL_D_LSE_M = 2, FL_D_LSE_S = 3 };
+enum { FL_I_BAD = VP_I_BAD, FL_I_MASS = VP_I_MASS, FL_I_FIN = 2, FL_I_NAN = 3 };
+enum { FL_F_PEAK = VP_F_PEAK, FL_F_OUTMAX = 1 };
 
-// (m, s) = (maximum, sum of exp(u - m)) of a set of finite u; the empty set is (-inf, 0).  Merge another set in.
-__device__ __forceinline__ void fl_lse_merge(double* m, double* s, double m2, double s2) {
-  if (m2 == -(double)INFINITY) return;
-  if (*m == -(double)INFINITY) {
-    *m = m2;
-    *s = s2;
-  } else if (m2 > *m) {
-    *s = *s * exp(*m - m2) + s2;
-    *m = m2;
-  } else {
-    *s += s2 * exp(m2 - *m);
-  }
-}
-__device__ __forceinline__ void fl_block_lse(double* m, double* s, double (*sh)[2]) {
-  for (int o = 32; o > 0; o >>= 1) {        // (lane 0 ends with the tree over all 64 lanes; only it is used)
-    const double m2 = __shfl_xor(*m, o), s2 = __shfl_xor(*s, o);
-    fl_lse_merge(m, s, m2, s2);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    sh[threadIdx.x >> 6][0] = *m;
-    sh[threadIdx.x >> 6][1] = *s;
-  }
-  __syncthreads();
-  double mm = sh[0][0], ss = sh[0][1];
-  for (int w = 1; w < FL_WAVES; ++w) fl_lse_merge(&mm, &ss, sh[w][0], sh[w][1]);
-  __syncthreads();
-  *m = mm;
-  *s = ss;
-}
-
-// The mass of a belief cell relative to the peak M: one f32 subtraction, the cut, exp in float64 rounded once.
-__device__ __forceinline__ float fl_mass(float v, float M) {
-  const float d = v - M;
-  return (vote_finite(v) && d >= FL_CUT) ? (float)exp((double)d) : 0.f;
-}
-
-// ---- launch 1
+// ---- launches 1-4: the predict step (vote_predict.h)
 __global__ __launch_bounds__(FL_NT) void vote_filter_peak_kernel(const float* __restrict__ belief, int n,
                                                                  float* __restrict__ fpart, int32_t* __restrict__ ipart) {
-  __shared__ float shf[FL_WAVES];
-  __shared__ int shi[FL_WAVES];
-  float m = -INFINITY;
-  int bad = 0;
-  for (int64_t i = (int64_t)blockIdx.x * FL_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FL_NT) {
-    const float v = belief[i];
-    if (vote_finite(v))
-      m = fmaxf(m, v);
-    else if (!(v == -INFINITY))
-      ++bad;                                // NaN or +inf
-  }
-  m = vote_block_max<FL_WAVES>(m, shf);
-  bad = vote_block_sum<FL_WAVES>(bad, shi);
-  if (threadIdx.x == 0) {
-    fpart[(size_t)blockIdx.x * 2 + FL_F_PEAK] = m;
-    ipart[(size_t)blockIdx.x * 4 + FL_I_BAD] = bad;
-  }
+  vp_peak<2, 4>(belief, n, fpart, ipart);
 }
-
-// ---- launch 2
 __global__ __launch_bounds__(FL_NT) void vote_filter_rotate_kernel(const float* __restrict__ belief,
                                                                    const float* __restrict__ taps_k, int lk, int R, int P,
                                                                    int Tk, int tiles_per_plane, int tiles,
                                                                    const float* __restrict__ fpart, float* __restrict__ t0,
                                                                    double* __restrict__ dpart, int32_t* __restrict__ ipart) {
-  __shared__ float shf[FL_WAVES];
-  __shared__ double shd[FL_WAVES];
-  __shared__ int shi[FL_WAVES];
-  const float M = vote_fold_max<FL_WAVES, 2>(fpart, FL_F_PEAK, gridDim.x, shf);
-  const int kfirst = vote_mod(lk, R);       // (r + lk) mod R, mathematically: lk mod R in [0, R) first
-  double sum_p = 0.0;
-  int n_mass = 0;
-  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    // (vote_tile_cell written out: through it this kernel takes 42 VGPRs / 58 SGPRs for 40 / 56)
-    const int r = tile / tiles_per_plane;
-    const int64_t p64 = (int64_t)(tile - r * tiles_per_plane) * FL_NT + threadIdx.x;
-    if (p64 >= P) continue;
-    const int p = (int)p64;
-    const float own = fl_mass(belief[(int64_t)r * P + p], M);
-    sum_p += (double)own;
-    n_mass += own > 0.f ? 1 : 0;
-    int k = r + kfirst;                     // (>= 0: one side of vote_wrap)
-    if (k >= R) k -= R;
-    float acc = 0.f;
-    for (int i = 0; i < Tk; ++i) {
-      acc = fmaf(taps_k[i], fl_mass(belief[(int64_t)k * P + p], M), acc);
-      k = vote_next(k, R);
-    }
-    t0[(int64_t)r * P + p] = acc;
-  }
-  sum_p = vote_block_sum<FL_WAVES>(sum_p, shd);
-  n_mass = vote_block_sum<FL_WAVES>(n_mass, shi);
-  if (threadIdx.x == 0) {
-    dpart[(size_t)blockIdx.x * 4 + FL_D_SUMP] = sum_p;
-    ipart[(size_t)blockIdx.x * 4 + FL_I_MASS] = n_mass;
-  }
+  vp_rotate<2, 4, 4>(belief, taps_k, lk, R, P, Tk, tiles_per_plane, tiles, fpart, t0, dpart, ipart);
 }
-
-// ---- launch 3: t1[r, a, b] = sum_ta taps_a[r, ta] * t0[r, a + la[r] + ta, b]
 __global__ __launch_bounds__(FL_NT) void vote_filter_rows_kernel(const float* __restrict__ t0,
                                                                  const float* __restrict__ taps_a,
                                                                  const int32_t* __restrict__ offsets, int Ho, int Wo, int P,
                                                                  int Ta, int tiles_per_plane, int tiles,
                                                                  float* __restrict__ t1) {
-  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int r, p, a, b;
-    if (!vote_tile_cell<FL_NT>(tile, tiles_per_plane, P, &r, &p)) continue;
-    vote_row_col(p, Wo, &a, &b);
-    const float* w = taps_a + (size_t)r * Ta;                     // uniform over the workgroup
-    const int64_t first = (int64_t)a + offsets[(size_t)r * 2];    // the source row of tap 0
-    const float* src = t0 + (int64_t)r * P + b;
-    float acc = 0.f;
-    for (int i = 0; i < Ta; ++i) {
-      const int64_t sa = first + i;
-      if (sa >= 0 && sa < Ho) acc = fmaf(w[i], src[sa * Wo], acc);   // (outside: + 0, the chain is unchanged)
-    }
-    t1[(int64_t)r * P + p] = acc;
-  }
+  vp_rows<false>(t0, taps_a, offsets, Ho, Wo, P, Ta, tiles_per_plane, tiles, t1);
 }
-
-// ---- launch 4: t2[r, a, b] = sum_tb taps_b[r, tb] * t1[r, a, b + lb[r] + tb]; sum t2
 __global__ __launch_bounds__(FL_NT) void vote_filter_cols_kernel(const float* __restrict__ t1,
                                                                  const float* __restrict__ taps_b,
                                                                  const int32_t* __restrict__ offsets, int Wo, int P, int Tb,
                                                                  int tiles_per_plane, int tiles, float* __restrict__ t2,
                                                                  double* __restrict__ dpart) {
-  __shared__ double shd[FL_WAVES];
-  double sum = 0.0;
-  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int r, p, a, b;
-    if (!vote_tile_cell<FL_NT>(tile, tiles_per_plane, P, &r, &p)) continue;
-    vote_row_col(p, Wo, &a, &b);
-    const float* w = taps_b + (size_t)r * Tb;
-    const int64_t first = (int64_t)b + offsets[(size_t)r * 2 + 1];
-    const float* src = t1 + (int64_t)r * P + (int64_t)a * Wo;
-    float acc = 0.f;
-    for (int i = 0; i < Tb; ++i) {
-      const int64_t sb = first + i;
-      if (sb >= 0 && sb < Wo) acc = fmaf(w[i], src[sb], acc);
-    }
-    t2[(int64_t)r * P + p] = acc;
-    sum += (double)acc;
-  }
-  sum = vote_block_sum<FL_WAVES>(sum, shd);
-  if (threadIdx.x == 0) dpart[(size_t)blockIdx.x * 4 + FL_D_SUMT2] = sum;
+  vp_cols<false, true, 4>(t1, taps_b, offsets, Wo, P, Tb, tiles_per_plane, tiles, t2, dpart);
 }
 
 // The update of one cell, float64: u = scale * vote + log(prior), prior = (1 - eps) t2 / S + eps / n.  NaN for a NaN
 // or +inf vote, -inf for a -inf vote or a prior of 0.  `transported` = (1 - eps) / S is NOT folded into one factor:
 // the expression is ((1 - eps) * t2) / S + eps / n as the contract writes it.
 struct FlUpdate {
-  double scale, one_minus_eps, S, eps_over_n;
-  bool has_prior;                           // a belief was given and S > 0
+  double scale;
+  VpPrior prior;
 };
 __device__ __forceinline__ double fl_update(const FlUpdate& c, float t2, float vote) {
   if (!(vote < INFINITY)) return (double)__int_as_float(0x7fc00000);   // NaN or +inf
   if (vote == -INFINITY) return -(double)INFINITY;
-  double prior = c.eps_over_n;
-  if (c.has_prior) prior = (c.one_minus_eps * (double)t2) / c.S + c.eps_over_n;
+  const double prior = vp_prior(c.prior, t2);
   if (!(prior > 0.0)) return -(double)INFINITY;
   return c.scale * (double)vote + log(prior);
 }
 __device__ __forceinline__ FlUpdate fl_update_setup(const double* dpart, int groups, bool with_belief, float scale,
                                                     float eps, int n, double* sh) {
   FlUpdate c;
-  c.S = with_belief ? vote_fold_sum<FL_WAVES, 4>(dpart, FL_D_SUMT2, groups, sh) : 0.0;
-  c.has_prior = with_belief && c.S > 0.0;
   c.scale = (double)scale;
-  // belief == NULL is the uniform prior: eps = 1
-  c.one_minus_eps = with_belief ? 1.0 - (double)eps : 0.0;
-  c.eps_over_n = (with_belief ? (double)eps : 1.0) / (double)n;
+  c.prior = vp_prior_setup(with_belief ? vote_fold_sum<FL_WAVES, 4>(dpart, FL_D_SUMT2, groups, sh) : 0.0, with_belief,
+                           eps, n);
   return c;
 }
 
@@ -236,19 +108,11 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_evidence_kernel(const float
       }
     }
   }
-  fl_block_lse(&m, &s, shl);
+  vote_block_lse<FL_WAVES>(&m, &s, shl);
   if (threadIdx.x == 0) {
     dpart[(size_t)blockIdx.x * 4 + FL_D_LSE_M] = m;
     dpart[(size_t)blockIdx.x * 4 + FL_D_LSE_S] = s;
   }
-}
-
-__device__ __forceinline__ double fl_fold_log_z(const double* __restrict__ dpart, int groups, double (*shl)[2]) {
-  double m = -(double)INFINITY, s = 0.0;
-  for (int g = threadIdx.x; g < groups; g += FL_NT)
-    fl_lse_merge(&m, &s, dpart[(size_t)g * 4 + FL_D_LSE_M], dpart[(size_t)g * 4 + FL_D_LSE_S]);
-  fl_block_lse(&m, &s, shl);
-  return m == -(double)INFINITY ? m : m + log(s);
 }
 
 // ---- launch 6
@@ -263,7 +127,7 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_normalise_kernel(const floa
   __shared__ float shf[FL_WAVES];
   __shared__ int shi[FL_WAVES];
   const FlUpdate c = fl_update_setup(dpart, gridDim.x, with_belief != 0, scale, eps, n, shd);
-  const double log_z = fl_fold_log_z(dpart, gridDim.x, shl);
+  const double log_z = vote_fold_lse<FL_WAVES, 4>(dpart, FL_D_LSE_M, FL_D_LSE_S, gridDim.x, shl);
   float top = -INFINITY;
   int n_fin = 0, n_nan = 0;
   for (int64_t i = (int64_t)blockIdx.x * FL_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FL_NT) {
@@ -324,18 +188,6 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_finish_kernel(int groups, i
   }
 }
 
-struct FlPlan : VotePlan {
-  int n;
-};
-
-bool fl_plan(int R, int Ho, int Wo, int Tk, int Ta, int Tb, FlPlan* plan) {
-  if (R < 1 || R > FL_MAX_R || Ho < 1 || Wo < 1) return false;
-  if (Tk < 1 || Tk > FL_MAX_TK || Ta < 1 || Ta > FL_MAX_TXY || Tb < 1 || Tb > FL_MAX_TXY) return false;
-  if (!vote_plan((int64_t)R * Ho * Wo, R, Ho, Wo, FL_NT, FL_MAX_GROUPS, plan)) return false;
-  plan->n = R * Ho * Wo;
-  return true;
-}
-
 // [R Ho Wo] f32 t1 | [groups][4] float64 | [groups][4] int32 | [groups][2] f32
 struct FlWorkspace {
   float* t1;
@@ -345,7 +197,7 @@ struct FlWorkspace {
   size_t bytes;
 };
 
-FlWorkspace fl_workspace(const FlPlan& plan, void* workspace) {
+FlWorkspace fl_workspace(const VpPlan& plan, void* workspace) {
   VoteLayout l{workspace};
   return {l.take<float>(plan.n), l.take<double>((size_t)plan.groups * 4), l.take<int32_t>((size_t)plan.groups * 4),
           l.take<float>((size_t)plan.groups * 2), l.bytes};
@@ -355,8 +207,8 @@ FlWorkspace fl_workspace(const FlPlan& plan, void* workspace) {
 
 extern "C" size_t snap_vote_filter_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t Tk, int32_t Ta,
                                                    int32_t Tb) {
-  FlPlan plan;
-  if (!fl_plan(R, Ho, Wo, Tk, Ta, Tb, &plan)) return 0;
+  VpPlan plan;
+  if (!vp_plan(R, Ho, Wo, Tk, Ta, Tb, &plan)) return 0;
   return fl_workspace(plan, nullptr).bytes;
 }
 
@@ -367,8 +219,8 @@ extern "C" int snap_vote_filter_f32(const float* belief, const float* votes, con
                                     size_t workspace_bytes, void* stream) {
   if (!votes || !taps_k || !taps_a || !taps_b || !offsets || !belief_out || !stats || !count || !workspace)
     return SNAP_ERR_NULL;
-  FlPlan plan;
-  if (!fl_plan(R, Ho, Wo, Tk, Ta, Tb, &plan)) return SNAP_ERR_BAD_SHAPE;
+  VpPlan plan;
+  if (!vp_plan(R, Ho, Wo, Tk, Ta, Tb, &plan)) return SNAP_ERR_BAD_SHAPE;
   if (!(scale > 0.f) || !(scale < INFINITY)) return SNAP_ERR_UNSUPPORTED;
   if (!(uniform_mix >= 0.f && uniform_mix <= 1.f)) return SNAP_ERR_UNSUPPORTED;
   if (!vote_workspace_ok(workspace, workspace_bytes, fl_workspace(plan, nullptr).bytes)) return SNAP_ERR_WORKSPACE;

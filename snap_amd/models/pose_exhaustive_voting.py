@@ -654,12 +654,54 @@ def filter_votes(belief, votes, cur_t_prev, grid, num_rotations, sigma_xy, sigma
   return dict(belief=out, log_evidence=stats[0], mass_kept=stats[1], count=count, stats=stats)
 
 
+def _no_motion():
+  return geometry.Transform2D(torch.zeros((), dtype=torch.float64), torch.zeros(2, dtype=torch.float64))
+
+
+def smooth_votes(belief, smoothed_next, next_t_cur, grid, num_rotations, sigma_xy, sigma_yaw, uniform_mix=1e-3,
+                 truncate=3.0):
+  """One backward step of the smoother that goes with ``filter_votes`` (``ops.vote_smooth`` on ``motion_taps``):
+  ``belief`` [R, 2H-1, 2W-1] is the filter's belief after frame t, ``smoothed_next`` the smoothed belief of frame
+  t + 1 (for the last frame of a track: its filtered belief), ``next_t_cur`` the increment the filter was given at
+  frame t + 1 (its ``cur_t_prev``) and the noise parameters that step's: ``motion_taps`` is deterministic on the host,
+  so the tables are the filter's bit for bit -> dict of device tensors: ``smoothed`` [R, 2H-1, 2W-1] (normalised
+  log-probabilities of p(x_t | all frames)), ``log_norm`` (0 up to rounding where beliefs and increment belong
+  together), ``mass_kept`` (the filter's, of that step), ``count`` int32 [4] and ``stats`` f32 [4] (the op's raw rows)."""
+  if belief.dim() != 3 or belief.shape[0] != num_rotations:
+    raise ValueError(f'smooth_votes: belief [{num_rotations}, Ho, Wo], got {tuple(belief.shape)}')
+  taps = motion_taps(next_t_cur, grid, num_rotations, sigma_xy, sigma_yaw, truncate, device=belief.device)
+  out, stats, count = ops.vote_smooth(belief.contiguous(), smoothed_next.contiguous(), taps, uniform_mix)
+  return dict(smoothed=out, log_norm=stats[0], mass_kept=stats[1], count=count, stats=stats)
+
+
+def smooth_track(beliefs, increments, grid, num_rotations, sigma_xy, sigma_yaw, uniform_mix=1e-3, truncate=3.0,
+                 details=False):
+  """The backward recursion over a track: ``beliefs`` are the N filtered beliefs (``filter_votes`` in frame order),
+  ``increments`` the N increments the filter was given (entry 0 is ignored: a track starts from a uniform prior;
+  None = no motion) -> the list of the N smoothed volumes, p(x_t | frames 0 .. N-1); the last is ``beliefs[-1]``
+  itself.  With ``details`` the list holds ``smooth_votes``' dicts (None for the last frame)."""
+  beliefs, increments = list(beliefs), list(increments)
+  if not beliefs or len(beliefs) != len(increments):
+    raise ValueError(f'smooth_track: {len(beliefs)} beliefs and {len(increments)} increments')
+  smoothed, steps = [None] * len(beliefs), [None] * len(beliefs)
+  smoothed[-1] = beliefs[-1]
+  for t in range(len(beliefs) - 2, -1, -1):
+    inc = increments[t + 1] if increments[t + 1] is not None else _no_motion()
+    steps[t] = smooth_votes(beliefs[t], smoothed[t + 1], inc, grid, num_rotations, sigma_xy, sigma_yaw, uniform_mix,
+                            truncate)
+    smoothed[t] = steps[t]['smoothed']
+  return steps if details else smoothed
+
+
 class VoteFilter:
   """A track: the recursive pose filter of one vehicle on one map lattice.  Holds the grid, the number of rotations,
   the odometry noise (``sigma_xy`` metres, ``sigma_yaw`` radians per step), ``temperature``, ``uniform_mix``,
-  ``truncate`` (``filter_votes``) and the current ``belief`` (None before the first frame and after ``reset()``)."""
+  ``truncate`` (``filter_votes``) and the current ``belief`` (None before the first frame and after ``reset()``).
+  With ``keep_history`` every step's ``(belief, cur_t_prev)`` is appended to ``history`` (one volume per frame stays
+  allocated) for ``smooth()``."""
 
-  def __init__(self, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0, uniform_mix=1e-3, truncate=3.0):
+  def __init__(self, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0, uniform_mix=1e-3, truncate=3.0,
+               keep_history=False):
     self.grid = grid
     self.num_rotations = int(num_rotations)
     self.sigma_xy = float(sigma_xy)
@@ -668,20 +710,26 @@ class VoteFilter:
     self.uniform_mix = float(uniform_mix)
     self.truncate = float(truncate)
     self.belief = None
+    if keep_history:
+      self.history = []
 
   def reset(self):
-    """Drop the belief: the next ``step`` starts a track from a uniform prior."""
+    """Drop the belief (and the history): the next ``step`` starts a track from a uniform prior."""
     self.belief = None
+    if hasattr(self, 'history'):
+      self.history = []
 
   def step(self, votes, cur_t_prev=None):
     """One filter step with the new frame's ``votes`` -> ``filter_votes``' dict; the belief is kept.  ``cur_t_prev``:
     the odometry increment since the previous step (ignored by the first step of a track); None = no motion (the
     belief is only diffused)."""
     if self.belief is not None and cur_t_prev is None:
-      cur_t_prev = geometry.Transform2D(torch.zeros((), dtype=torch.float64), torch.zeros(2, dtype=torch.float64))
+      cur_t_prev = _no_motion()
     out = filter_votes(self.belief, votes, cur_t_prev, self.grid, self.num_rotations, self.sigma_xy, self.sigma_yaw,
                        self.temperature, self.uniform_mix, self.truncate)
     self.belief = out['belief']
+    if hasattr(self, 'history'):
+      self.history.append((out['belief'], cur_t_prev))
     return out
 
   def localize(self, plane_q, plane_map, cur_t_prev=None, conf_q=None, method=None, posterior=None, **peaks):
@@ -699,3 +747,25 @@ class VoteFilter:
       kw = {} if posterior is True else dict(posterior)
       out['posterior'] = posterior_from_votes(step['belief'], self.grid, self.num_rotations, **kw)
     return out
+
+  def smooth(self, posterior=None, **peaks):
+    """The backward recursion over the history (``smooth_track``; each step's taps are rebuilt by ``motion_taps``) ->
+    one dict per frame: ``poses_from_votes(smoothed, **peaks)`` plus ``votes`` (the smoothed volume; the last frame's
+    is the filter's belief itself), ``log_norm`` (None for the last frame) and, with ``posterior`` as in
+    ``localize_exhaustive``, ``posterior``.  Raises ValueError without a history."""
+    if not getattr(self, 'history', None):
+      raise ValueError('VoteFilter.smooth: no history (keep_history=True and at least one step)')
+    beliefs, increments = zip(*self.history)
+    steps = smooth_track(beliefs, increments, self.grid, self.num_rotations, self.sigma_xy, self.sigma_yaw,
+                         self.uniform_mix, self.truncate, details=True)
+    frames = []
+    for belief, step in zip(beliefs, steps):
+      votes = belief if step is None else step['smoothed']
+      out = poses_from_votes(votes, self.grid, self.num_rotations, **peaks)
+      out['votes'] = votes
+      out['log_norm'] = None if step is None else step['log_norm']
+      if posterior is not None and posterior is not False:
+        kw = {} if posterior is True else dict(posterior)
+        out['posterior'] = posterior_from_votes(votes, self.grid, self.num_rotations, **kw)
+      frames.append(out)
+    return frames

@@ -2326,6 +2326,22 @@ def vote_fuse(volumes, shifts, weights=None):
   return fused, count
 
 
+def _vote_taps(op, taps, R, device):
+  """The tap tuple of ``vote_filter`` / ``vote_smooth`` checked -> (taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb)."""
+  if not isinstance(taps, (tuple, list)) or len(taps) != 5:
+    raise ValueError(f'{op}: taps = (taps_k, lk, taps_a, taps_b, offsets)')
+  taps_k, lk, taps_a, taps_b, offsets = taps
+  if isinstance(lk, bool) or not isinstance(lk, (int, np.integer)) or not -2 ** 31 <= int(lk) < 2 ** 31:
+    raise ValueError(f'{op}: lk must be an int32 number, got {lk!r}')
+  Tk = taps_k.shape[0] if isinstance(taps_k, torch.Tensor) and taps_k.dim() == 1 else -1
+  Ta = taps_a.shape[1] if isinstance(taps_a, torch.Tensor) and taps_a.dim() == 2 else -1
+  Tb = taps_b.shape[1] if isinstance(taps_b, torch.Tensor) and taps_b.dim() == 2 else -1
+  for t, name, dtype, shape in ((taps_k, 'taps_k', torch.float32, (Tk,)), (taps_a, 'taps_a', torch.float32, (R, Ta)),
+                                (taps_b, 'taps_b', torch.float32, (R, Tb)), (offsets, 'offsets', torch.int32, (R, 2))):
+    _arg_chk(t, name, (dtype,), shape, device, f'{op}: {name} {dtype} {list(shape)} on {device}')
+  return taps_k, int(lk), taps_a, taps_b, offsets, Tk, Ta, Tb
+
+
 def vote_filter(belief, votes, taps, scale=1.0, uniform_mix=0.0):
   """One step of the recursive pose filter on the vote lattice: belief f32 [R, Ho, Wo] (the log-space belief after the
   previous frame, -inf = impossible pose) or None (a uniform prior: a track starts), votes f32 [R, Ho, Wo] (the new
@@ -2342,20 +2358,10 @@ def vote_filter(belief, votes, taps, scale=1.0, uniform_mix=0.0):
   _arg_chk(votes, 'votes', (torch.float32,), (None, None, None), None,
            'vote_filter: votes f32 [R, Ho, Wo] on a ROCm GPU')
   R, Ho, Wo = votes.shape
-  if not isinstance(taps, (tuple, list)) or len(taps) != 5:
-    raise ValueError('vote_filter: taps = (taps_k, lk, taps_a, taps_b, offsets)')
-  taps_k, lk, taps_a, taps_b, offsets = taps
-  if isinstance(lk, bool) or not isinstance(lk, (int, np.integer)) or not -2 ** 31 <= int(lk) < 2 ** 31:
-    raise ValueError(f'vote_filter: lk must be an int32 number, got {lk!r}')
-  Tk = taps_k.shape[0] if isinstance(taps_k, torch.Tensor) and taps_k.dim() == 1 else -1
-  Ta = taps_a.shape[1] if isinstance(taps_a, torch.Tensor) and taps_a.dim() == 2 else -1
-  Tb = taps_b.shape[1] if isinstance(taps_b, torch.Tensor) and taps_b.dim() == 2 else -1
-  for t, name, dtype, shape in ((belief, 'belief', torch.float32, (R, Ho, Wo)), (taps_k, 'taps_k', torch.float32, (Tk,)),
-                                (taps_a, 'taps_a', torch.float32, (R, Ta)), (taps_b, 'taps_b', torch.float32, (R, Tb)),
-                                (offsets, 'offsets', torch.int32, (R, 2))):
-    if t is None and name == 'belief':
-      continue
-    _arg_chk(t, name, (dtype,), shape, votes.device, f'vote_filter: {name} {dtype} {list(shape)} on {votes.device}')
+  if belief is not None:
+    _arg_chk(belief, 'belief', (torch.float32,), (R, Ho, Wo), votes.device,
+             f'vote_filter: belief {torch.float32} {[R, Ho, Wo]} on {votes.device}')
+  taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb = _vote_taps('vote_filter', taps, R, votes.device)
   scale, uniform_mix = float(scale), float(uniform_mix)
   if not (scale > 0.0 and np.isfinite(np.float32(scale))):
     raise ValueError(f'vote_filter: scale must be a finite number > 0, got {scale}')
@@ -2376,6 +2382,44 @@ def vote_filter(belief, votes, taps, scale=1.0, uniform_mix=0.0):
                                   _p(ws), ws.numel() * 8, _stream())
   _lib.check(st, 'snap_vote_filter_f32')
   return belief_out, stats, count
+
+
+def vote_smooth(belief, smoothed_next, taps, uniform_mix=0.0):
+  """One backward step of the smoother that goes with ``vote_filter``: belief f32 [R, Ho, Wo] (the filter's belief
+  after frame t), smoothed_next f32 [R, Ho, Wo] (the smoothed belief of frame t + 1; for the last frame of a track its
+  filtered belief), taps = the tuple ``vote_filter`` was given for the step from t to t + 1 and ``uniform_mix`` that
+  step's -> (smoothed f32 [R, Ho, Wo], stats f32 [4], count int32 [4]).  The filter's predict step is repeated on
+  ``belief`` (the same device code: the same bits), the ratio smoothed_next / prior is carried back through the
+  adjoint of the three tap passes (columns, rows, then the circular rotation pass) and multiplied into the belief;
+  normalised over the finite cells.  stats = (log_norm: 0 up to rounding for beliefs and taps that belong together,
+  share of the belief's mass that stayed in the volume, largest log ratio, largest smoothed); count = (finite cells of
+  smoothed, NaN / +inf cells of belief, NaN / +inf cells of smoothed_next, cells of smoothed_next with ratio mass)
+  (the full contract: snap_vote_smooth_f32 in include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  _arg_chk(belief, 'belief', (torch.float32,), (None, None, None), None,
+           'vote_smooth: belief f32 [R, Ho, Wo] on a ROCm GPU')
+  R, Ho, Wo = belief.shape
+  _arg_chk(smoothed_next, 'smoothed_next', (torch.float32,), (R, Ho, Wo), belief.device,
+           f'vote_smooth: smoothed_next {torch.float32} {[R, Ho, Wo]} on {belief.device}')
+  taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb = _vote_taps('vote_smooth', taps, R, belief.device)
+  uniform_mix = float(uniform_mix)
+  if not 0.0 <= uniform_mix <= 1.0:
+    raise ValueError(f'vote_smooth: uniform_mix must lie in [0, 1], got {uniform_mix}')
+  words = _workspace_words(
+      lib.snap_vote_smooth_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), belief.numel(),
+      f'vote_smooth: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
+      'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  ws = torch.empty((words,), dtype=torch.int64, device=belief.device)
+  smoothed = torch.empty((R, Ho, Wo), dtype=torch.float32, device=belief.device)
+  stats = torch.empty((4,), dtype=torch.float32, device=belief.device)
+  count = torch.empty((4,), dtype=torch.int32, device=belief.device)
+  # bytes the launches move (snap_vote_smooth_f32 in the header): 22 passes over the volume
+  with _region('vote_smooth', 0.0, 4.0 * belief.numel() * 22):
+    st = lib.snap_vote_smooth_f32(_p(belief), _p(smoothed_next), _p(taps_k), lk, _p(taps_a), _p(taps_b), _p(offsets),
+                                  R, Ho, Wo, Tk, Ta, Tb, uniform_mix, _p(smoothed), _p(stats), _p(count), _p(ws),
+                                  ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_smooth_f32')
+  return smoothed, stats, count
 
 
 def plane_align_score(fq, vq, fm, vm, poses, threshold):

@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_refine_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4)
 """
 import math
 import os
@@ -394,6 +394,59 @@ def vote_filter_c4(iters):
   emit_json(res)
 
 
+def vote_smooth_c4(iters):
+  """One backward smoothing step at the C4 vote volume: vote_filter_c4's shape, taps and data recipe, `next` one
+  filter step further than the belief (so beliefs and taps belong together: log_norm is 0 up to rounding).  Whole
+  ops.vote_smooth calls with whole ops.vote_filter calls measured alongside, blocks of the two alternated, medians of
+  single calls.  One JSON line; `json=<path>` as a third argument also writes it."""
+  import numpy as np
+  from snap_amd.models import pose_exhaustive_voting as pev
+  from snap_amd.utils import geometry, grids
+  R, H, scale, eps = 36, 256, 8.0, 1e-3
+  Ho = Wo = 2 * H - 1
+  grid = grids.Grid2D((H, H), 0.2)
+  g = torch.Generator(device='cuda').manual_seed(0)
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  keep = (ov[:, None] * ov[None, :] > 0.05 * H * H)[None]
+  frames = [torch.where(keep, torch.randn((R, Ho, Wo), device='cuda', generator=g) * 0.25, float('-inf')).contiguous()
+            for _ in range(2)]
+  step = geometry.Transform2D(torch.tensor(np.deg2rad(5.0)), torch.tensor([0.93, 0.37], dtype=torch.float64))
+  taps = pev.motion_taps(step, grid, R, 0.2, np.deg2rad(2.0), device='cuda')
+  Tk, Ta, Tb = taps[0].shape[0], taps[2].shape[1], taps[3].shape[1]
+  assert (Tk, Ta, Tb) == (4, 8, 8), (Tk, Ta, Tb)
+  belief = pev.filter_votes(None, frames[0], None, grid, R, 0.2, np.deg2rad(2.0), temperature=scale)['belief']
+  votes = frames[1]
+  nxt, f_stats, _ = ops.vote_filter(belief, votes, taps, scale, eps)
+  out, stats, count = ops.vote_smooth(belief, nxt, taps, eps)
+  fin = torch.isfinite(out)
+  total = float(out[fin].double().exp().sum())
+  assert torch.equal(fin, torch.isfinite(belief)) and int(count[0]) == int(fin.sum()) and int(count[1]) == 0
+  assert abs(float(stats[0])) < 1e-4 and abs(total - 1) < 1e-4, (float(stats[0]), total)
+  assert float(stats[1]) == float(f_stats[1])               # the filter's mass_kept of that step, the same bits
+  smooth = lambda: ops.vote_smooth(belief, nxt, taps, eps)
+  filt = lambda: ops.vote_filter(belief, votes, taps, scale, eps)
+  (k_ms, ks), (f_ms, fs) = alternated_blocks(((smooth, 5, max(iters, 5)), (filt, 5, max(iters, 5))))
+  n = R * Ho * Wo
+  by, by_f = 4.0 * n * 22, 4.0 * n * 12   # the headers of vote_smooth.hip / vote_filter.hip: passes over the volume
+  hbm_peak = 8.0e12                # B/s, the MI355X's HBM3E peak
+  res = dict(case='vote_smooth_c4', shape=[R, Ho, Wo], taps=[Tk, Ta, Tb], uniform_mix=eps,
+             cells_with_ratio_mass=int(count[3]), mass_kept=round(float(stats[1]), 6), log_norm=float(stats[0]),
+             call_ms=round(k_ms, 4), call_ms_blocks=[round(v, 4) for v in ks],
+             filter_call_ms=round(f_ms, 4), filter_call_ms_blocks=[round(v, 4) for v in fs],
+             ratio_to_filter_call=round(k_ms / f_ms, 2), launch_bytes=int(by),
+             call_GBps_of_launch_bytes=round(by / k_ms / 1e6, 1),
+             filter_launch_bytes=int(by_f), filter_call_GBps_of_launch_bytes=round(by_f / f_ms / 1e6, 1),
+             call_fraction_of_hbm_peak=round(by / (k_ms * 1e-3) / hbm_peak, 3), hbm_peak_Bps=hbm_peak,
+             timing='call_ms = one whole ops.vote_smooth call between device events on an idle stream (its four '
+             'torch.empty allocations, the ctypes call and the eleven launches), NOT kernel time; filter_call_ms the '
+             'same for ops.vote_filter (seven launches) in the same process; median of single calls, 5 blocks of each '
+             'alternated, median block',
+             caveat='launch_bytes counts every pass a launch makes over the 37.6 MB volume (22; the filter 12); the '
+             'volumes of a call together fit the 256 MB Infinity Cache, so the passes need not come from HBM: the '
+             'fraction relates the launch bytes of one call to the HBM peak, whatever served them')
+  emit_json(res)
+
+
 def vote_refine_c4(iters):
   """Peak refinement at the C4 planes (256^2 cells, D = 32, R = 36, 16 peaks x the default 11 x 9 x 9 lattice = 14 256
   poses; 10 % / 5 % invalid cells): whole ops.plane_align_score calls, median of single calls, against the only way to
@@ -463,5 +516,5 @@ if __name__ == '__main__':
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
   {'pose_score': pose_score, 'pose_score_c4': pose_score_c4, 'voting_c4': voting_c4,
    'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4,
-   'vote_filter_c4': vote_filter_c4,
+   'vote_filter_c4': vote_filter_c4, 'vote_smooth_c4': vote_smooth_c4,
    'vote_refine_c4': vote_refine_c4}[which](iters)
