@@ -1153,6 +1153,74 @@ int snap_vote_smooth_f32(const float* belief, const float* next, const float* ta
                          int32_t Ta, int32_t Tb, float uniform_mix, float* smoothed, float* stats, int32_t* count,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Most likely pose TRACK over vote volumes: one forward step of the max-product (Viterbi) recursion that goes with the
+ * filter above, with back-pointers.  score_prev[R,Ho,Wo] f32 is the log score of the best path into every pose of the
+ * previous frame (-inf = no path), or NULL (the first frame of a track); votes[R,Ho,Wo] f32; on the DEVICE:
+ * ltaps_k[Tk] f32 with first offset lk, ltaps_a[R,Ta] / ltaps_b[R,Tb] f32 and offsets[R,2] i32 = (la, lb), the layout of
+ * snap_vote_filter_f32's tables with every tap replaced by its LOGARITHM (pose_exhaustive_voting.motion_log_taps);
+ * score_out[R,Ho,Wo] f32 and back[R,Ho,Wo] i32 (neither may overlap an input: score_out holds intermediates during
+ * the call); stats[2] f32; count[6] i32.  n = R*Ho*Wo; a linear index is (r*Ho + a)*Wo + b.
+ *   LOG-TAPS (precondition, not checked): every entry is -inf (a zero tap) or a finite f32 <= 0.  They are inputs so
+ *   that no launch evaluates a transcendental function.
+ *   Every operation below is ONE IEEE f32 operation (no contraction into fma).
+ *   PEAK.  M = the largest finite value of score_prev (exact); J = the lowest linear index at which it is attained, -1
+ *   when no cell is finite.  A NaN or +inf cell is a caller error: it counts as -inf, and is counted.
+ *   d = score_prev - M; a cell that is not finite has d = -inf.  (Subtracting M at every step keeps the scores bounded
+ *   over a long track; M is returned so the caller can sum the path's total.)
+ *   MAX-PLUS PASSES, in the filter's order and with the filter's indexing (the rotation pass circular, at the source
+ *   cell; the xy passes with the OUTPUT rotation's tables; a source row / column outside the volume is -inf), the
+ *   intermediate volumes stored as f32:
+ *     m0[r,a,b] = max_tk ( ltaps_k[tk]   + d [(r + lk + tk) mod R, a, b] )    (mathematical modulo);
+ *     m1[r,a,b] = max_ta ( ltaps_a[r,ta] + m0[r, a + la[r] + ta, b] );
+ *     m2[r,a,b] = max_tb ( ltaps_b[r,tb] + m1[r, a, b + lb[r] + tb] ).
+ *   Each maximum runs over its taps ASCENDING from -inf and is replaced on a strict > only: among equal candidates the
+ *   LOWEST tap index is the chosen one.  (f32 addition is monotone, so m2 is exactly the joint maximum over all
+ *   (tk, ta, tb) of fl32(ltaps_b + fl32(ltaps_a + fl32(ltaps_k + d))).)
+ *   UPDATE.  stay = log_stay + m2; jump = log_jump if J >= 0, else -inf (the jump's predecessor is cell J, where d = 0).
+ *   best = stay if stay >= jump (the transported predecessor wins a tie), else jump.
+ *   score_out = fl32(scale * votes) + best; -inf for a -inf vote or best = -inf; -inf, and counted, for a NaN or +inf
+ *   vote.  back[x] = the linear index of the predecessor: for a transported predecessor the source reached through the
+ *   three chosen taps -- the column tap chosen at (r, a, b) gives b' = b + lb[r] + tb, the row tap chosen at (r, a, b')
+ *   gives a' = a + la[r] + ta, the rotation tap chosen at (r, a', b') gives k' = (r + lk + tk) mod R, and the
+ *   predecessor is (k', a', b') --; for a jump J; -1 wherever score_out is -inf.
+ *   With score_prev == NULL: best = 0 and back = -1 everywhere, M = -inf, J = -1; the tables are not read.
+ *   stats = { M; the largest score_out (-inf when every cell is -inf) }.
+ *   count = { finite cells of score_out; NaN or +inf cells of score_prev; NaN or +inf cells of votes; cells whose
+ *   predecessor is the jump (score_out above -inf and back = J by the jump); J; the lowest linear index of the largest
+ *   score_out, or -1 }.
+ *   Statistically this is the max-product recursion under the transition K_max(x|x') = max((1 - eps) T(x|x'), eps / n)
+ *   with log_stay = log(1 - eps), log_jump = log(eps / n) and T the filter's three tap passes; K_max lies within a
+ *   factor 2 (log 2 per step) of the filter's (1 - eps) T + eps / n.  The filter's renormalisation of the transported
+ *   mass (sum p / S) is constant over the lattice, cannot change an argmax, and is left out.
+ * Five launches of min(R * ceil(Ho*Wo/256), 2048) workgroups of 256 threads (the last: one workgroup; two with
+ * score_prev == NULL), a tile = one rotation and 256 consecutive pixels: the peak; the rotation pass with the
+ * subtraction fused; the row pass; the column pass with the update and the composition of back; the statistics.  m0
+ * lives in score_out, m1 and the rotation and row passes' chosen taps (one byte per cell each) in the workspace.  10
+ * passes over the volume in 4-byte cells (reads: score_prev 2, m0, m1, votes, the two byte volumes 1/2; writes: m0,
+ * m1, score_out, back, the two byte volumes 1/2), 3 with score_prev == NULL, against the filter's 12; no float64 and no
+ * transcendental function.  No atomics: maxima are exact and every fold keeps "the larger value, then the lower
+ * index", a total order, so two calls give the same bits whatever the fold order.  Every element of score_out, back,
+ * stats and count is written by every call.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32; anything else returns
+ * SNAP_ERR_BAD_SHAPE before any launch (a NULL pointer other than score_prev SNAP_ERR_NULL, checked first; a scale that
+ * is not a finite number > 0, or a log_stay / log_jump that is not <= 0 (-inf allowed; NaN is not) SNAP_ERR_UNSUPPORTED;
+ * a short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE).  workspace: snap_vote_viterbi_workspace_bytes() bytes
+ * (0 = unsupported shape): m1, the two byte volumes and the per-workgroup partials; it needs no initialisation and no
+ * launch touches a byte beyond that size.  Asynchronous on `stream`; the caller owns every buffer. */
+size_t snap_vote_viterbi_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t Tk, int32_t Ta, int32_t Tb);
+int snap_vote_viterbi_f32(const float* score_prev, const float* votes, const float* ltaps_k, int32_t lk,
+                          const float* ltaps_a, const float* ltaps_b, const int32_t* offsets, int32_t R, int32_t Ho,
+                          int32_t Wo, int32_t Tk, int32_t Ta, int32_t Tb, float scale, float log_stay, float log_jump,
+                          float* score_out, int32_t* back, float* stats, int32_t* count, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* One step BACK along snap_vote_viterbi_f32's back-pointers, for B independent chains at once: back[n] i32 (a step's
+ * `back`, n = R*Ho*Wo), cur[B] i32 linear indices at frame t, prev[B] i32: prev[i] = back[cur[i]] if 0 <= cur[i] < n,
+ * else -1 (a chain that has ended stays ended).  prev must not overlap back or cur.  n, B >= 1, else
+ * SNAP_ERR_BAD_SHAPE; a NULL pointer SNAP_ERR_NULL, checked first.  One launch of ceil(B / 256) workgroups, asynchronous
+ * on `stream`, no host read. */
+int snap_vote_backstep_i32(const int32_t* back, int32_t n, const int32_t* cur, int32_t* prev, int32_t B, void* stream);
+
 /* Dense plane ALIGNMENT SCORE at continuous poses: what a vote of the exhaustive voting measures (the correlation of
  * the query plane with the map plane, normalised by the number of valid query cells), evaluated at poses that need
  * not lie on the vote lattice (pose_exhaustive_voting.refine_poses: a lattice of sub-bin / sub-cell poses around

@@ -1,9 +1,9 @@
 // Device and host pieces shared by the operators on the exhaustive vote volume (vote_peaks.hip, vote_posterior.hip,
-// vote_fuse.hip, vote_filter.hip, vote_smooth.hip, vote_refine.hip).  The family's contract is "no atomics; every sum's
-// order is a function of the shape alone; two calls give the same bits", and vote_filter is tested against vote_fuse and
-// vote_posterior bit for bit: the predicates, reductions, tile walk and circular indices those comparisons rest on
-// exist once, here.  No kernels.  -ffp-contract=off is in force, so one expression gives one set of bits wherever it
-// is inlined.
+// vote_fuse.hip, vote_filter.hip, vote_smooth.hip, vote_viterbi.hip, vote_refine.hip).  The family's contract is "no
+// atomics; every sum's order is a function of the shape alone; two calls give the same bits", and vote_filter is tested
+// against vote_fuse and vote_posterior bit for bit: the predicates, reductions, tile walk and circular indices those
+// comparisons rest on exist once, here.  No kernels.  -ffp-contract=off is in force, so one expression gives one set of
+// bits wherever it is inlined.
 #ifndef SNAP_CSRC_VOTE_COMMON_H_
 #define SNAP_CSRC_VOTE_COMMON_H_
 
@@ -87,6 +87,49 @@ __device__ __forceinline__ float vote_fold_max(const float* __restrict__ part, i
   float v = -INFINITY;
   for (int g = threadIdx.x; g < groups; g += WAVES * SNAP_WAVE) v = fmaxf(v, part[(size_t)g * STRIDE + col]);
   return vote_block_max<WAVES>(v, sh);
+}
+
+// ------------------------------- (maximum, lowest index) pairs --------------------------------
+// (m, i) = (the largest value of a set, the lowest index at which it is attained); the empty set is
+// (-inf, VOTE_NO_INDEX).  No value is NaN.  "Larger value, then lower index" is a total order, so the merge is
+// associative and commutative: every fold order gives the same pair.
+constexpr int VOTE_NO_INDEX = 0x7fffffff;
+__device__ __forceinline__ void vote_argmax_merge(float* m, int* i, float m2, int i2) {
+  if (m2 > *m || (m2 == *m && i2 < *i)) {
+    *m = m2;
+    *i = i2;
+  }
+}
+// A wave butterfly, then the waves: the same pair in every thread.  `shm` / `shi` [WAVES] are free again on return.
+template <int WAVES>
+__device__ __forceinline__ void vote_block_argmax(float* m, int* i, float* shm, int* shi) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(*m, o);
+    const int i2 = __shfl_xor(*i, o);
+    vote_argmax_merge(m, i, m2, i2);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    shm[threadIdx.x >> 6] = *m;
+    shi[threadIdx.x >> 6] = *i;
+  }
+  __syncthreads();
+  float mm = shm[0];
+  int ii = shi[0];
+  for (int w = 1; w < WAVES; ++w) vote_argmax_merge(&mm, &ii, shm[w], shi[w]);
+  __syncthreads();
+  *m = mm;
+  *i = ii;
+}
+// The fold of the pairs in column fcol of [groups][FSTRIDE] float and column icol of [groups][ISTRIDE] int32 partials.
+template <int WAVES, int FSTRIDE, int ISTRIDE>
+__device__ __forceinline__ void vote_fold_argmax(const float* __restrict__ fpart, int fcol,
+                                                 const int32_t* __restrict__ ipart, int icol, int groups, float* m,
+                                                 int* i, float* shm, int* shi) {
+  *m = -INFINITY;
+  *i = VOTE_NO_INDEX;
+  for (int g = threadIdx.x; g < groups; g += WAVES * SNAP_WAVE)
+    vote_argmax_merge(m, i, fpart[(size_t)g * FSTRIDE + fcol], ipart[(size_t)g * ISTRIDE + icol]);
+  vote_block_argmax<WAVES>(m, i, shm, shi);
 }
 
 // ------------------------------- log-sum-exp pairs --------------------------------------------

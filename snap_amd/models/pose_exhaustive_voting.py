@@ -769,3 +769,217 @@ class VoteFilter:
         out['posterior'] = posterior_from_votes(votes, self.grid, self.num_rotations, **kw)
       frames.append(out)
     return frames
+
+
+def motion_log_taps(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, truncate=3.0, device=None):
+  """``motion_taps``' tables for ``ops.vote_viterbi``: the same arguments, the same float64 construction and the same
+  rounding of every tap w to f32, then float32(log(float64(w))), -inf for w = 0 -> (ltaps_k f32 [Tk], lk int, ltaps_a
+  f32 [R, Ta], ltaps_b f32 [R, Tb], offsets int32 [R, 2]) on ``device``; the offsets are ``motion_taps``' own.  Every
+  entry is -inf or a finite number <= 0.  Built on the host, one upload."""
+  R = int(num_rotations)
+  angle = torch.as_tensor(cur_t_prev.angle)
+  if angle.numel() != 1:
+    raise ValueError(f'motion_log_taps: one increment, got a transform of shape {tuple(angle.shape)}')
+  if device is None:
+    device = angle.device
+  host = geometry.Transform2D(angle.detach().to('cpu', torch.float64), torch.as_tensor(cur_t_prev.t).detach().to(
+      'cpu', torch.float64))
+  dk, da, db = (v.numpy() for v in _shift_table_f64(host, grid, R))
+  cell = float(grid.cell_size)
+  wk, lk = _axis_taps(dk, float(sigma_yaw) * R / (2 * math.pi), truncate, FILTER_MAX_TAPS_K, 'rotation')
+  wa, la = _axis_taps(da[0], float(sigma_xy) / cell, truncate, FILTER_MAX_TAPS_XY, 'rows')
+  wb, lb = _axis_taps(db[0], float(sigma_xy) / cell, truncate, FILTER_MAX_TAPS_XY, 'columns')
+  f32 = np.concatenate([wk.reshape(-1), wa.reshape(-1), wb.reshape(-1)]).astype(np.float32)   # motion_taps' bits
+  with np.errstate(divide='ignore'):
+    f32 = np.log(f32.astype(np.float64)).astype(np.float32)
+  off = np.stack([la, lb], -1).astype(np.int32)
+  blob = ops.upload_table(np.concatenate([f32.view(np.uint8), off.reshape(-1).view(np.uint8)]), device)
+  tab = blob[:f32.nbytes].view(torch.float32)
+  nk, na = wk.size, wa.size
+  return (tab[:nk], int(lk[0]), tab[nk:nk + na].view(R, -1), tab[nk + na:].view(R, -1),
+          blob[f32.nbytes:].view(torch.int32).view(R, 2))
+
+
+@functools.lru_cache(maxsize=16)
+def _still_log_taps(R, device):
+  """One log-tap of 0 at offset 0 on every axis (``_still_taps`` in the log domain)."""
+  dev = torch.device(device)
+  zero = torch.zeros((R, 1), dtype=torch.float32, device=dev)
+  return (torch.zeros((1,), dtype=torch.float32, device=dev), 0, zero, zero.clone(),
+          torch.zeros((R, 2), dtype=torch.int32, device=dev))
+
+
+def _viterbi_log_weights(uniform_mix, n):
+  """(log_stay, log_jump) = (float32(log1p(-eps)), float32(log(eps) - log(n))) as Python floats; -inf at eps = 1 / 0."""
+  eps = float(uniform_mix)
+  if not 0.0 <= eps <= 1.0:
+    raise ValueError(f'viterbi_votes: uniform_mix must lie in [0, 1], got {uniform_mix}')
+  with np.errstate(divide='ignore'):
+    return float(np.float32(np.log1p(-np.float64(eps)))), float(np.float32(np.log(np.float64(eps)) - math.log(n)))
+
+
+def viterbi_votes(score, votes, cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0,
+                  uniform_mix=1e-3, truncate=3.0):
+  """One forward step of the most-likely-track recursion (``ops.vote_viterbi`` on ``motion_log_taps``), the max-product
+  companion of ``filter_votes`` with the same arguments: ``score`` [R, 2H-1, 2W-1] is the previous step's ``score``
+  (the log score of the best path into every pose), or None to start a track (``cur_t_prev`` is then ignored) -> dict
+  of device tensors: ``score`` [R, 2H-1, 2W-1] (a vote volume for ``poses_from_votes``), ``back`` int32 [R, 2H-1, 2W-1]
+  (the linear index of every pose's best predecessor, -1 = none), ``peak_prev`` (M, the maximum of the previous score,
+  which the step subtracted: the sum of these over a track restores the path's total), ``top`` (the largest score),
+  ``count`` int32 [6] and ``stats`` f32 [2] (the op's raw rows); and what the step was run with, for
+  ``VoteViterbi.path``: ``log_taps`` (the table tuple) and ``log_weights`` = (log_stay, log_jump) as Python floats.
+  The transition is max((1 - eps) T, eps / n): log_stay = float32(log1p(-eps)), log_jump = float32(log(eps) - log(n)),
+  eps = ``uniform_mix``."""
+  if votes.dim() != 3 or votes.shape[0] != num_rotations:
+    raise ValueError(f'viterbi_votes: votes [{num_rotations}, Ho, Wo], got {tuple(votes.shape)}')
+  log_stay, log_jump = _viterbi_log_weights(uniform_mix, votes.numel())
+  if score is None:
+    taps = _still_log_taps(int(num_rotations), str(votes.device))
+  else:
+    taps = motion_log_taps(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, truncate, device=votes.device)
+    score = score.contiguous()
+  out, back, stats, count = ops.vote_viterbi(score, votes.contiguous(), taps, temperature, log_stay, log_jump)
+  return dict(score=out, back=back, peak_prev=stats[0], top=stats[1], count=count, stats=stats, log_taps=taps,
+              log_weights=(log_stay, log_jump))
+
+
+def _entered_by_jump(cur, prev, best_prev, log_taps, shape, log_stay, log_jump):
+  """Whether the step into the cells ``cur`` int32 [B] (their predecessors ``prev`` = back[cur]) was the uniform jump,
+  from the step's tables alone, on the device -> bool [B].  A jump has prev == J (``best_prev``, the previous frame's
+  best cell).  So has a transported step out of J, which the kernel takes iff log_stay + m2 >= log_jump, and then m2
+  is the f32 value of the tap triple that leads from ``cur`` to J (d = 0 there): fl(ltb + fl(lta + ltk)), the largest
+  over the rotation taps that reach J's plane.  f32 addition is monotone, so that triple's stay >= log_jump also
+  implies that the kernel did not jump: the rule below is the kernel's decision exactly."""
+  ltk, lk, lta, ltb, off = log_taps
+  R, Ho, Wo = shape
+  P = Ho * Wo
+  x, j = cur.clamp(min=0).long(), best_prev.clamp(min=0).long()
+  r, a, b = x // P, (x % P) // Wo, x % Wo
+  kj, aj, bj = j // P, (j % P) // Wo, j % Wo
+  ta, tb = aj - a - off[r, 0].long(), bj - b - off[r, 1].long()
+  inside = (ta >= 0) & (ta < lta.shape[1]) & (tb >= 0) & (tb < ltb.shape[1])
+  planes = torch.remainder(r[:, None] + lk + torch.arange(ltk.shape[0], device=cur.device)[None], R)
+  m0 = torch.where(planes == kj, ltk[None], ltk.new_full((), -math.inf)).max(-1).values
+  m2 = ltb[r, tb.clamp(0, ltb.shape[1] - 1)] + (lta[r, ta.clamp(0, lta.shape[1] - 1)] + m0)
+  transported = inside & (m2.new_tensor(log_stay) + m2 >= log_jump)
+  return (cur >= 0) & (best_prev >= 0) & (prev == best_prev) & ~transported
+
+
+def viterbi_track(volumes, increments, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0, uniform_mix=1e-3,
+                  truncate=3.0):
+  """The jointly most likely pose sequence of a track: ``volumes`` are the N frames' vote volumes [R, 2H-1, 2W-1],
+  ``increments`` the N odometry increments as ``VoteFilter.step`` takes them (entry 0 is ignored; None = no motion).
+  ``viterbi_votes`` over the frames, then the back-pointers from the last frame's best pose (``ops.vote_backstep``)
+  -> ``VoteViterbi.path()``'s dict: ``indices`` int32 [N, 3] = (r, a, b), ``linear`` int32 [N], ``m_t_q``
+  (``exhaustive_indices_to_tfm`` of the indices), ``log_score`` (float64 scalar: the last ``top`` plus the steps'
+  ``peak_prev`` for t >= 1) and ``jumps`` bool [N] (the step into frame t was the uniform jump), all on the device.
+  One int32 volume per frame is held until the trace is done."""
+  volumes, increments = list(volumes), list(increments)
+  if not volumes or len(volumes) != len(increments):
+    raise ValueError(f'viterbi_track: {len(volumes)} volumes and {len(increments)} increments')
+  for v in volumes:
+    if not isinstance(v, torch.Tensor) or v.dim() != 3 or v.shape != volumes[0].shape or v.shape[0] != num_rotations:
+      raise ValueError(f'viterbi_track: every volume [{num_rotations}, Ho, Wo] of one shape, got '
+                       f'{[tuple(getattr(u, "shape", ())) for u in volumes]}')
+  track = VoteViterbi(grid, num_rotations, sigma_xy, sigma_yaw, temperature, uniform_mix, truncate)
+  for v, inc in zip(volumes, increments):
+    track.step(v, inc)
+  return track.path()
+
+
+class VoteViterbi:
+  """A track's most likely pose sequence (the max-product companion of ``VoteFilter``, same arguments): ``step`` runs
+  ``viterbi_votes`` on each new frame and keeps the current ``score`` (None before the first frame and after
+  ``reset()``); ``path`` follows the back-pointers from the current best pose.  Every step's ``back`` is appended to
+  ``history``: one int32 volume per frame stays allocated until ``reset()``."""
+
+  def __init__(self, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0, uniform_mix=1e-3, truncate=3.0):
+    self.grid = grid
+    self.num_rotations = int(num_rotations)
+    self.sigma_xy = float(sigma_xy)
+    self.sigma_yaw = float(sigma_yaw)
+    self.temperature = float(temperature)
+    self.uniform_mix = float(uniform_mix)
+    if not 0.0 <= self.uniform_mix <= 1.0:
+      raise ValueError(f'VoteViterbi: uniform_mix must lie in [0, 1], got {uniform_mix}')
+    self.truncate = float(truncate)
+    self.score = None
+    self.history = []
+
+  def reset(self):
+    """Drop the score and the back-pointers: the next ``step`` starts a track."""
+    self.score = None
+    self.history = []
+
+  def step(self, votes, cur_t_prev=None):
+    """One forward step with the new frame's ``votes`` -> ``viterbi_votes``' dict; ``score`` is kept and ``back``
+    appended.  ``cur_t_prev`` as in ``VoteFilter.step``."""
+    if self.score is not None:
+      if tuple(votes.shape) != tuple(self.score.shape):
+        raise ValueError(f'VoteViterbi.step: votes {tuple(votes.shape)} on a track of {tuple(self.score.shape)}')
+      if cur_t_prev is None:
+        cur_t_prev = _no_motion()
+    out = viterbi_votes(self.score, votes, cur_t_prev, self.grid, self.num_rotations, self.sigma_xy, self.sigma_yaw,
+                        self.temperature, self.uniform_mix, self.truncate)
+    self.score = out['score']
+    self.history.append(out)
+    return out
+
+  def path(self, end=None):
+    """The back-pointers followed from the last frame to the first -> dict of device tensors: ``linear`` int32 [N],
+    ``indices`` int32 [N, 3] = (r, a, b) (-1 where there is no path), ``m_t_q`` (``exhaustive_indices_to_tfm`` of the
+    indices: Transform2D [N]), ``log_score`` (float64: the end pose's score plus the steps' ``peak_prev`` for t >= 1)
+    and ``jumps`` bool [N] (the step into frame t was the uniform jump; frame 0: False).  ``end``: None = the current
+    best pose (``count[5]``), or an int32 device tensor of B linear indices of the last frame (``vote_peaks`` of the
+    score, say) to trace B alternatives at once: ``linear`` [N, B], ``indices`` [N, B, 3], ``jumps`` [N, B],
+    ``log_score`` [B], ``m_t_q`` Transform2D [N * B] (frame-major).  No host synchronisation."""
+    if not self.history:
+      raise ValueError('VoteViterbi.path: no step yet')
+    last = self.history[-1]
+    single = end is None
+    if single:
+      cur = last['count'][5:6]
+    else:
+      if (not isinstance(end, torch.Tensor) or end.dtype != torch.int32 or end.dim() != 1 or end.numel() < 1
+          or end.device != self.score.device):
+        raise ValueError(f'VoteViterbi.path: end int32 [B] on {self.score.device}, got '
+                         f'{(end.dtype, tuple(end.shape), end.device) if isinstance(end, torch.Tensor) else type(end)}')
+      cur = end.contiguous()
+    shape = tuple(self.score.shape)
+    n = self.score.numel()
+    flat = self.score.reshape(-1)
+    known = (cur >= 0) & (cur < n)
+    end_score = torch.where(known, flat[cur.clamp(0, n - 1).long()], flat.new_full((), -math.inf))
+    log_score = end_score.double()
+    linear, jumps = [cur], []
+    for step in reversed(self.history[1:]):
+      prev = ops.vote_backstep(step['back'], cur)
+      jumps.append(_entered_by_jump(cur, prev, step['count'][4], step['log_taps'], shape, *step['log_weights']))
+      log_score = log_score + step['peak_prev'].double()
+      linear.append(prev)
+      cur = prev
+    jumps.append(torch.zeros_like(cur, dtype=torch.bool))
+    linear = torch.stack(linear[::-1])                       # [N, B]
+    jumps = torch.stack(jumps[::-1])
+    P = shape[1] * shape[2]
+    lin = linear.long()
+    indices = torch.stack([lin // P, (lin % P) // shape[2], lin % shape[2]], -1).to(torch.int32)
+    indices = torch.where((linear >= 0)[..., None], indices, indices.new_full((), -1))
+    m_t_q = exhaustive_indices_to_tfm(indices.reshape(-1, 3), self.grid, self.num_rotations)
+    if single:
+      linear, jumps, indices, log_score = linear[:, 0], jumps[:, 0], indices[:, 0], log_score[0]
+    return dict(indices=indices, linear=linear, m_t_q=m_t_q, log_score=log_score, jumps=jumps)
+
+  def localize(self, plane_q, plane_map, cur_t_prev=None, conf_q=None, method=None, **peaks):
+    """``exhaustive_pose_voting`` of the new frame, ``step``, then ``poses_from_votes(score, **peaks)``: the dict of
+    ``localize_exhaustive`` with ``votes`` = the current score volume, plus ``votes_frame`` (the frame's own votes),
+    ``back``, ``peak_prev`` and ``top``."""
+    frame = exhaustive_pose_voting(plane_q, plane_map, self.num_rotations, self.grid, conf_q=conf_q, method=method)
+    step = self.step(frame, cur_t_prev)
+    out = poses_from_votes(step['score'], self.grid, self.num_rotations, **peaks)
+    out['votes'] = step['score']
+    out['votes_frame'] = frame
+    out['back'] = step['back']
+    out['peak_prev'] = step['peak_prev']
+    out['top'] = step['top']
+    return out

@@ -2422,6 +2422,68 @@ def vote_smooth(belief, smoothed_next, taps, uniform_mix=0.0):
   return smoothed, stats, count
 
 
+def vote_viterbi(score_prev, votes, log_taps, scale=1.0, log_stay=0.0, log_jump=float('-inf')):
+  """One forward step of the max-product (Viterbi) recursion that goes with ``vote_filter``: score_prev f32
+  [R, Ho, Wo] (the log score of the best path into every pose of the previous frame, -inf = no path) or None (a track
+  starts), votes f32 [R, Ho, Wo] (the new frame), log_taps = ``vote_filter``'s tap tuple with every tap replaced by
+  its logarithm, -inf for a zero tap (``pose_exhaustive_voting.motion_log_taps``) -> (score f32 [R, Ho, Wo], back int32
+  [R, Ho, Wo], stats f32 [2], count int32 [6]).  score_prev minus its maximum M is carried through three max-plus tap
+  passes (rotation, circular; rows and columns per output rotation; the lowest tap index among equals);
+  best = max(log_stay + that, log_jump), the transported predecessor winning a tie and the jump coming from the previous
+  frame's best cell J; score = fl32(scale * votes) + best, back = the predecessor's linear index ((r * Ho + a) * Wo +
+  b), -1 where score is -inf.  stats = (M, largest score); count = (finite cells of score, NaN / +inf cells of
+  score_prev, NaN / +inf cells of votes, cells entered by the jump, J, the lowest index of the largest score or -1).
+  Only f32 additions, products and comparisons: bit for bit reproducible (the full contract: snap_vote_viterbi_f32 in
+  include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  _arg_chk(votes, 'votes', (torch.float32,), (None, None, None), None,
+           'vote_viterbi: votes f32 [R, Ho, Wo] on a ROCm GPU')
+  R, Ho, Wo = votes.shape
+  if score_prev is not None:
+    _arg_chk(score_prev, 'score_prev', (torch.float32,), (R, Ho, Wo), votes.device,
+             f'vote_viterbi: score_prev {torch.float32} {[R, Ho, Wo]} on {votes.device}')
+  taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb = _vote_taps('vote_viterbi', log_taps, R, votes.device)
+  scale, log_stay, log_jump = float(scale), float(log_stay), float(log_jump)
+  if not (scale > 0.0 and np.isfinite(np.float32(scale))):
+    raise ValueError(f'vote_viterbi: scale must be a finite number > 0, got {scale}')
+  if not (log_stay <= 0.0 and log_jump <= 0.0):
+    raise ValueError(f'vote_viterbi: log_stay and log_jump must be <= 0 (-inf allowed), got {log_stay}, {log_jump}')
+  words = _workspace_words(
+      lib.snap_vote_viterbi_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), votes.numel(),
+      f'vote_viterbi: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
+      'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  ws = torch.empty((words,), dtype=torch.int64, device=votes.device)
+  score = torch.empty((R, Ho, Wo), dtype=torch.float32, device=votes.device)
+  back = torch.empty((R, Ho, Wo), dtype=torch.int32, device=votes.device)
+  stats = torch.empty((2,), dtype=torch.float32, device=votes.device)
+  count = torch.empty((6,), dtype=torch.int32, device=votes.device)
+  # bytes the launches move (the kernel file's header): 10 passes over the volume with a score_prev, 3 without
+  with _region('vote_viterbi', 0.0, 4.0 * votes.numel() * (3 if score_prev is None else 10)):
+    st = lib.snap_vote_viterbi_f32(_p(score_prev), _p(votes), _p(taps_k), lk, _p(taps_a), _p(taps_b), _p(offsets),
+                                   R, Ho, Wo, Tk, Ta, Tb, scale, log_stay, log_jump, _p(score), _p(back), _p(stats),
+                                   _p(count), _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_viterbi_f32')
+  return score, back, stats, count
+
+
+def vote_backstep(back, cur):
+  """One step back along ``vote_viterbi``'s back-pointers for B chains at once: back int32 [R, Ho, Wo] (a step's
+  ``back``), cur int32 [B] linear indices on the same device -> prev int32 [B] = back.flatten()[cur], -1 where cur is
+  outside [0, R Ho Wo) (a chain that has ended stays ended).  One small launch, no host synchronisation."""
+  lib = _lib.load()
+  _arg_chk(back, 'back', (torch.int32,), (None, None, None), None,
+           'vote_backstep: back int32 [R, Ho, Wo] on a ROCm GPU')
+  _arg_chk(cur, 'cur', (torch.int32,), (None,), back.device, f'vote_backstep: cur int32 [B] on {back.device}')
+  n, B = back.numel(), cur.shape[0]
+  if not (1 <= n < 2 ** 31 and 1 <= B < 2 ** 31):
+    raise ValueError(f'vote_backstep: 1 <= R Ho Wo < 2^31 and 1 <= B < 2^31, got {n} cells and {B} chains')
+  prev = torch.empty((B,), dtype=torch.int32, device=back.device)
+  with _region('vote_backstep', 0.0, 12.0 * B):
+    st = lib.snap_vote_backstep_i32(_p(back), n, _p(cur), _p(prev), B, _stream())
+  _lib.check(st, 'snap_vote_backstep_i32')
+  return prev
+
+
 def plane_align_score(fq, vq, fm, vm, poses, threshold):
   """The alignment score of two BEV planes at continuous poses: fq f32 [Hq, Wq, D] / vq bool or uint8 [Hq, Wq] (the
   query plane), fm f32 [Hm, Wm, D] / vm [Hm, Wm] (the map plane), poses f32 [P, 4] = (cos, sin, tx, ty) on the same
