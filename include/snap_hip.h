@@ -1221,6 +1221,87 @@ int snap_vote_viterbi_f32(const float* score_prev, const float* votes, const flo
  * on `stream`, no host read. */
 int snap_vote_backstep_i32(const int32_t* back, int32_t n, const int32_t* cur, int32_t* prev, int32_t B, void* stream);
 
+/* DRAWS from a vote volume: B independent cells of p = softmax(scale * votes) over the lattice, by the project's keyed
+ * Philox.  votes[R,Ho,Wo] f32 (log-space; -inf = impossible); uniforms: NULL or float64 [B,2] on the DEVICE; index[B]
+ * i32; log_prob[B] f32; stats[2] f32; count[2] i32.  n = R*Ho*Wo; a linear index is (r*Ho + a)*Wo + b.
+ *   MASS.  s = fl32(scale * v) (one f32 product); M = the largest finite s (exact); d = fl32(s - M); the cell has the
+ *   mass p = fl32(exp((double)d)) iff s is finite and d >= -40, else exactly 0 (snap_vote_filter_f32's rule).  A NaN or
+ *   +inf s carries no mass and is counted.
+ *   UNIFORMS.  With uniforms == NULL draw i takes (x0, x1, x2, x3) = Philox4x32-10(counter = (i, stream_id, 0, 0),
+ *   key = (seed low word, seed high word)) and u0 = ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53, u1 likewise from x2, x3:
+ *   float64 in [0, 1).  Otherwise (u0, u1) = uniforms[i] (precondition: in [0, 1)).  This entry point uses u0.
+ *   DRAW.  The inverse CDF in lattice order (linear index ascending): the first cell whose inclusive prefix of p
+ *   exceeds u0 * Z, Z = sum p.  Evaluated as a descent over three levels of float64 sums -- the R plane sums, the Ho
+ *   row sums of the chosen plane, the Wo cells of the chosen row with their masses recomputed -- each level by ONE
+ *   routine: chunks of 64 entries in ascending order; inside a chunk the inclusive prefixes are a Kogge-Stone scan
+ *   (lane i: a fixed tree over entries 0 .. i of the chunk) added to the carry, the inclusive prefix of the chunk
+ *   before at its last lane; the level takes the first entry WITH MASS whose inclusive prefix exceeds the target t and
+ *   hands max(t - its exclusive prefix, 0) to the next level as its target; when no prefix exceeds t (the levels' sums
+ *   are rounded differently) it takes its LAST entry with mass.  A row sum is a chain per lane over b = lane, lane + 64,
+ *   .. and an xor butterfly over the 64 lanes; a plane sum the same over its rows; Z is the plane level's carry after
+ *   its scan, and the first target is u0 * Z.  So a cell with p == 0 is never returned, the result is a function of the
+ *   inputs alone, and it differs from the dense float64 CDF's answer only where u0 * Z lies within rounding (2^-22 Z
+ *   covers the masses' last f32 bit and every float64 sum) of a prefix.
+ *   index = the linear index; -1 for every draw when no cell has mass.  log_prob = fl32(((double)s - M) - log Z) of the
+ *   drawn cell; -inf where index is -1.
+ *   stats = { fl32(M + log Z) (the log normaliser of scale * votes; -inf without mass); M (-inf without a finite cell) }.
+ *   count = { cells with mass; NaN or +inf cells }.
+ * Four launches: the peak on min(R * ceil(Ho*Wo/256), 2048) workgroups of 256 threads; the row sums, one wave per
+ * (r, a) row; one workgroup for the plane sums, Z, stats and count; the draws, one wave per draw.  Two reads of the
+ * volume; a draw reads R plane sums, Ho row sums and Wo cells.  No atomics; two calls give the same bytes; every
+ * element of index, log_prob, stats and count is written by every call.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31, 1 <= B <= 2^20; anything else returns SNAP_ERR_BAD_SHAPE
+ * before any launch (a NULL pointer other than uniforms SNAP_ERR_NULL, checked first; a scale that is not a finite
+ * number > 0 SNAP_ERR_UNSUPPORTED; a short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE).  workspace:
+ * snap_vote_sample_workspace_bytes() bytes (0 = unsupported shape): the row sums and counts, the plane sums and the
+ * per-workgroup partials; it needs no initialisation and no launch touches a byte beyond that size.  Asynchronous on
+ * `stream`; the caller owns every buffer. */
+size_t snap_vote_sample_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo);
+int snap_vote_sample_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, float scale, int32_t B, uint64_t seed,
+                         int32_t stream_id, const double* uniforms, int32_t* index, float* log_prob, float* stats,
+                         int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One BACKWARD step of forward-filter / backward-sample for B chains: from the chains' cells at frame t+1 to cells at
+ * frame t drawn from p(x_t | x_{t+1}, frames 0 .. t), the exact conditional of snap_vote_filter_f32's own transition.
+ * Run from a draw of the last belief (snap_vote_sample_f32) down to frame 0, it yields joint tracks from
+ * p(x_0 .. x_{N-1} | all frames).  belief[R,Ho,Wo] f32 = the filter's belief_out at frame t (required); taps_k, lk,
+ * taps_a, taps_b, offsets and uniform_mix = eps: what snap_vote_filter_f32 was given for the step t -> t+1 (same
+ * layout, same precondition); next[B] i32 linear indices at frame t+1; uniforms: NULL or float64 [B,2] on the DEVICE;
+ * prev[B] i32; jumped[B] i32; stats[2] f32; count[3] i32.
+ *   PREDICT, exactly as snap_vote_filter_f32 does it with `belief` (one set of device code): M, the masses p, sum p and
+ *   S = sum t2 are the filter's bits.  The row sums, plane sums and Z of p are formed as in snap_vote_sample_f32 (scale
+ *   1).  (u0, u1) as there, with the counter (i, stream_id, 1, 0).
+ *   WINDOW of a chain at x = (r, a, b): entry (tk, ta, tb), in ascending lexicographic order, has the cell
+ *   x' = ((r + lk + tk) mod R, a + la[r] + ta, b + lb[r] + tb) and the float64 weight
+ *   (((double)taps_k[tk] * taps_a[r,ta]) * taps_b[r,tb]) * p[x'], 0 outside the volume.  The (tk, ta) row sums are
+ *   chains over tb ascending; W = the carry after the scan (the routine above) over the Tk*Ta row sums.
+ *   A = ((1 - eps) * W) / S (0 when S == 0); J = eps / n (0 when sum p == 0).
+ *   u0 * (A + J) < J selects the JUMP: prev = a draw as in snap_vote_sample_f32 from p with u1.  Otherwise prev = the
+ *   cell of the window entry found by the routine above over the row sums with the target u1 * W, then over the chosen
+ *   row's Tb entries recomputed.  Several entries may name one cell (Tk > R).
+ *   prev = -1 where next is outside [0, n) (a chain that has ended stays ended) or A + J == 0; jumped = 1 for the jump,
+ *   0 for a transported step, -1 where prev is -1.
+ *   stats = { S / sum p (0 when sum p == 0: the filter's stats[1] of that step, bit for bit); M }.
+ *   count = { chains with a predecessor; chains that jumped; NaN or +inf cells of belief }.
+ *   This is p(x' | x) proportional to (1 - eps) K(x, x') p(x') / S + (eps / n) p(x') / sum p, the filter's prior
+ *   ((1 - eps) * t2) / S + eps / n taken apart by source cell.
+ * Eight launches: the filter's peak, rotation, row and column passes on its grid; the row sums; one workgroup for the
+ * plane sums and totals; one 256-thread workgroup per chain (the row sums of the window in LDS, then one wave); the
+ * counts.  No atomics; two calls give the same bytes; every element of prev, jumped, stats and count is written by
+ * every call.
+ * Supported: the shapes of snap_vote_filter_f32 (1 <= Tk <= 16, 1 <= Ta, Tb <= 32) and 1 <= B <= 2^20; anything else
+ * returns SNAP_ERR_BAD_SHAPE before any launch (a NULL pointer other than uniforms SNAP_ERR_NULL, checked first; a
+ * uniform_mix outside [0, 1] SNAP_ERR_UNSUPPORTED; a short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE).
+ * workspace: snap_vote_sample_back_workspace_bytes() bytes (0 = unsupported shape): two volumes (t0 / t2 and t1), the
+ * row and plane sums and the per-workgroup partials; it needs no initialisation and no launch touches a byte beyond
+ * that size.  Asynchronous on `stream`; the caller owns every buffer. */
+size_t snap_vote_sample_back_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t Tk, int32_t Ta, int32_t Tb);
+int snap_vote_sample_back_f32(const float* belief, const float* taps_k, int32_t lk, const float* taps_a,
+                              const float* taps_b, const int32_t* offsets, int32_t R, int32_t Ho, int32_t Wo, int32_t Tk,
+                              int32_t Ta, int32_t Tb, float uniform_mix, const int32_t* next, int32_t B, uint64_t seed,
+                              int32_t stream_id, const double* uniforms, int32_t* prev, int32_t* jumped, float* stats,
+                              int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Dense plane ALIGNMENT SCORE at continuous poses: what a vote of the exhaustive voting measures (the correlation of
  * the query plane with the map plane, normalised by the number of valid query cells), evaluated at poses that need
  * not lie on the vote lattice (pose_exhaustive_voting.refine_poses: a lattice of sub-bin / sub-cell poses around

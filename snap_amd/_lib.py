@@ -284,6 +284,13 @@ SIGNATURES = {
     'snap_vote_viterbi_f32': (
         c_int, [ptr, ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float] * 3 + [ptr] * 5 + [c_size, ptr]),
     'snap_vote_backstep_i32': (c_int, [ptr, c_int, ptr, ptr, c_int, ptr]),
+    'snap_vote_sample_workspace_bytes': (c_size, [c_int] * 3),
+    'snap_vote_sample_f32': (
+        c_int, [ptr, c_int, c_int, c_int, c_float, c_int, c_u64, c_int] + [ptr] * 6 + [c_size, ptr]),
+    'snap_vote_sample_back_workspace_bytes': (c_size, [c_int] * 6),
+    'snap_vote_sample_back_f32': (
+        c_int, [ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float, ptr, c_int, c_u64, c_int] + [ptr] * 6
+        + [c_size, ptr]),
     'snap_plane_align_score_workspace_bytes': (c_size, [c_int] * 6),
     'snap_plane_align_score_f32': (
         c_int, [ptr] * 5 + [c_int] * 6 + [c_float, ptr, ptr, ptr, c_size, ptr]),

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -574,20 +575,8 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
 // n = floor(u1 * Nq); cell ~ softmax row n by two-level inverse CDF:
 // chunk from chunk_stats, then the 64 cells of that chunk re-evaluated.
 // One wave per sample.
+// (philox4x32_10: philox.h)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t* out) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
-    const uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += W0; k1 += W1;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // inclusive prefix sum over the 64 lanes of a wave
 __device__ __forceinline__ float wave_scan_incl(float v, int lane) {

@@ -1,6 +1,6 @@
-// The PREDICT step of the vote-volume filter (snap_vote_filter_f32) as device pieces, shared by vote_filter.hip and
-// vote_smooth.hip: the smoother's ratio is taken against the prior the filter used, so M, the masses, t0, t1, t2, S and
-// the prior have to be the filter's bits.  They are, because both files build them from the bodies below (and
+// The PREDICT step of the vote-volume filter (snap_vote_filter_f32) as device pieces, shared by vote_filter.hip,
+// vote_smooth.hip and vote_sample.hip: the smoother's ratio (and the backward sampler's conditional) is taken against
+// the prior the filter used, so M, the masses, t0, t1, t2, S and the prior have to be the filter's bits.  They are, because both files build them from the bodies below (and
 // -ffp-contract=off is in force).  Each body is the whole of a kernel; the files wrap it in a __global__ of their own
 // name.  A tile is one rotation and VP_NT consecutive pixels p = a * Wo + b, one cell per thread, on min(tiles,
 // VP_MAX_GROUPS) workgroups of VP_NT threads striding over the tiles; the tap rows of a tile are uniform (scalar loads).

@@ -770,6 +770,83 @@ class VoteFilter:
       frames.append(out)
     return frames
 
+  def sample(self, num, seed):
+    """``num`` whole tracks drawn from the joint posterior of the history's frames (``sample_tracks``: forward-filter /
+    backward-sample on the stored beliefs; each step's taps are rebuilt by ``motion_taps``) -> its dict.  Raises
+    ValueError without a history."""
+    if not getattr(self, 'history', None):
+      raise ValueError('VoteFilter.sample: no history (keep_history=True and at least one step)')
+    beliefs, increments = zip(*self.history)
+    return sample_tracks(beliefs, increments, self.grid, self.num_rotations, self.sigma_xy, self.sigma_yaw, num, seed,
+                         self.uniform_mix, self.truncate)
+
+
+def _linear_to_indices(linear, shape):
+  """Linear lattice indices int32 [...] -> (r, a, b) int32 [..., 3]; -1 rows where the index is negative."""
+  P, Wo = shape[1] * shape[2], shape[2]
+  lin = linear.long()
+  indices = torch.stack([lin // P, (lin % P) // Wo, lin % Wo], -1).to(torch.int32)
+  return torch.where((linear >= 0)[..., None], indices, indices.new_full((), -1))
+
+
+def sample_votes(votes, grid, num_rotations, num, seed, stream=0, temperature=1.0):
+  """``num`` poses drawn from the pose distribution of a vote volume or a belief (``ops.vote_sample``): ``votes``
+  [R, 2H-1, 2W-1]; ``seed`` (64 bits) and ``stream`` (int32; the frame number, say) key the Philox draws, so the same
+  arguments give the same poses; ``temperature`` multiplies the votes -> dict of device tensors: ``linear`` int32
+  [num] (the linear lattice index, -1 when no cell has mass), ``indices`` int32 [num, 3] = (r, a, b), ``m_t_q``
+  (``exhaustive_indices_to_tfm`` of the indices: Transform2D [num], the cells' centre poses, no sub-cell jitter),
+  ``log_prob`` f32 [num] (of the drawn cells), ``count`` int32 [2] and ``stats`` f32 [2] (the op's raw rows)."""
+  if votes.dim() != 3 or votes.shape[0] != num_rotations:
+    raise ValueError(f'sample_votes: votes [{num_rotations}, Ho, Wo], got {tuple(votes.shape)}')
+  linear, log_prob, stats, count = ops.vote_sample(votes.contiguous(), num, seed, stream, temperature)
+  indices = _linear_to_indices(linear, votes.shape)
+  return dict(linear=linear, indices=indices, m_t_q=exhaustive_indices_to_tfm(indices, grid, num_rotations),
+              log_prob=log_prob, count=count, stats=stats)
+
+
+def sample_back(belief, nxt, next_t_cur, grid, num_rotations, sigma_xy, sigma_yaw, seed, stream, uniform_mix=1e-3,
+                truncate=3.0):
+  """One backward step of forward-filter / backward-sample (``ops.vote_sample_back`` on ``motion_taps``): ``belief``
+  [R, 2H-1, 2W-1] is the filter's belief after frame t, ``nxt`` int32 [B] the chains' linear indices at frame t + 1,
+  ``next_t_cur`` the increment the filter was given at frame t + 1 and the noise parameters that step's (as in
+  ``smooth_votes``: the tables are the filter's bit for bit) -> dict of device tensors: ``linear`` int32 [B] (the
+  chains' cells at frame t, -1 = none), ``jumped`` int32 [B] (1: the step was the uniform jump, 0: transported, -1: no
+  predecessor), ``mass_kept``, ``count`` int32 [3] and ``stats`` f32 [2] (the op's raw rows)."""
+  if belief.dim() != 3 or belief.shape[0] != num_rotations:
+    raise ValueError(f'sample_back: belief [{num_rotations}, Ho, Wo], got {tuple(belief.shape)}')
+  taps = motion_taps(next_t_cur, grid, num_rotations, sigma_xy, sigma_yaw, truncate, device=belief.device)
+  prev, jumped, stats, count = ops.vote_sample_back(belief.contiguous(), nxt.contiguous(), taps, uniform_mix, seed,
+                                                    stream)
+  return dict(linear=prev, jumped=jumped, mass_kept=stats[0], count=count, stats=stats)
+
+
+def sample_tracks(beliefs, increments, grid, num_rotations, sigma_xy, sigma_yaw, num, seed, uniform_mix=1e-3,
+                  truncate=3.0):
+  """``num`` whole tracks drawn from p(x_0 .. x_{N-1} | all frames) by forward-filter / backward-sample: ``beliefs``
+  are the N filtered beliefs (``filter_votes`` in frame order), ``increments`` the N increments the filter was given
+  (entry 0 is ignored; None = no motion).  ``sample_votes`` on the last belief with stream N - 1, then ``sample_back``
+  down to frame 0 with stream t -> dict of device tensors with ``VoteViterbi.path(end=...)``'s shapes: ``linear`` int32
+  [N, num], ``indices`` int32 [N, num, 3] (-1 where a track has no pose), ``m_t_q`` (Transform2D [N * num],
+  frame-major) and ``jumps`` bool [N, num] (the step into frame t was the uniform jump; frame 0: False)."""
+  beliefs, increments = list(beliefs), list(increments)
+  if not beliefs or len(beliefs) != len(increments):
+    raise ValueError(f'sample_tracks: {len(beliefs)} beliefs and {len(increments)} increments')
+  N = len(beliefs)
+  cur = sample_votes(beliefs[-1], grid, num_rotations, num, seed, N - 1)['linear']
+  linear, jumps = [cur], []
+  for t in range(N - 2, -1, -1):
+    inc = increments[t + 1] if increments[t + 1] is not None else _no_motion()
+    step = sample_back(beliefs[t], cur, inc, grid, num_rotations, sigma_xy, sigma_yaw, seed, t, uniform_mix, truncate)
+    jumps.append(step['jumped'] == 1)
+    cur = step['linear']
+    linear.append(cur)
+  jumps.append(torch.zeros_like(cur, dtype=torch.bool))
+  linear = torch.stack(linear[::-1])
+  indices = _linear_to_indices(linear, beliefs[-1].shape)
+  return dict(linear=linear, indices=indices,
+              m_t_q=exhaustive_indices_to_tfm(indices.reshape(-1, 3), grid, num_rotations),
+              jumps=torch.stack(jumps[::-1]))
+
 
 def motion_log_taps(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, truncate=3.0, device=None):
   """``motion_taps``' tables for ``ops.vote_viterbi``: the same arguments, the same float64 construction and the same

@@ -2484,6 +2484,93 @@ def vote_backstep(back, cur):
   return prev
 
 
+def _vote_draws(op, num, seed, stream, uniforms, device):
+  """The draw arguments of ``vote_sample`` / ``vote_sample_back`` checked -> (B, seed, stream)."""
+  for v, name, lo, hi in ((num, 'the number of draws', 1, 2 ** 20 + 1), (seed, 'seed', 0, 2 ** 64),
+                          (stream, 'stream', -2 ** 31, 2 ** 31)):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) < hi:
+      raise ValueError(f'{op}: {name} must be an integer in [{lo}, {hi}), got {v!r}')
+  if uniforms is not None:
+    _arg_chk(uniforms, 'uniforms', (torch.float64,), (int(num), 2), device,
+             f'{op}: uniforms {torch.float64} {[int(num), 2]} on {device}')
+  return int(num), int(seed), int(stream)
+
+
+def vote_sample(votes, num, seed, stream=0, scale=1.0, uniforms=None):
+  """``num`` independent draws from the pose distribution of a vote volume: votes f32 [R, Ho, Wo] (log-space; -inf =
+  impossible) -> (index int32 [num], log_prob f32 [num], stats f32 [2], count int32 [2]) of p = softmax(scale * votes)
+  with the filter's masses (cells more than 40 below the peak carry none).  index = the linear index
+  (r * Ho + a) * Wo + b of the drawn cell, by the inverse CDF in lattice order (-1 for every draw when no cell has
+  mass); log_prob = its normalised log-probability; stats = (log normaliser of scale * votes, largest scale * vote);
+  count = (cells with mass, NaN / +inf cells).  Draw i uses the keyed Philox4x32-10 at counter (i, stream, 0, 0) with
+  the 64-bit ``seed`` as key; ``uniforms`` float64 [num, 2] on the device replaces it (column 0 is used).  The same
+  arguments give the same bytes (the full contract: snap_vote_sample_f32 in include/snap_hip.h).  No host
+  synchronisation."""
+  lib = _lib.load()
+  _arg_chk(votes, 'votes', (torch.float32,), (None, None, None), None,
+           'vote_sample: votes f32 [R, Ho, Wo] on a ROCm GPU')
+  R, Ho, Wo = votes.shape
+  B, seed, stream = _vote_draws('vote_sample', num, seed, stream, uniforms, votes.device)
+  scale = float(scale)
+  if not (scale > 0.0 and np.isfinite(np.float32(scale))):
+    raise ValueError(f'vote_sample: scale must be a finite number > 0, got {scale}')
+  words = _workspace_words(
+      lib.snap_vote_sample_workspace_bytes, (R, Ho, Wo), votes.numel(),
+      f'vote_sample: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  ws = torch.empty((words,), dtype=torch.int64, device=votes.device)
+  index = torch.empty((B,), dtype=torch.int32, device=votes.device)
+  log_prob = torch.empty((B,), dtype=torch.float32, device=votes.device)
+  stats = torch.empty((2,), dtype=torch.float32, device=votes.device)
+  count = torch.empty((2,), dtype=torch.int32, device=votes.device)
+  # bytes the launches move: two reads of the volume, the row sums written and folded, per draw a row of cells and
+  # the sums above it
+  with _region('vote_sample', 0.0, 8.0 * votes.numel() + 24.0 * R * Ho + B * (4.0 * Wo + 8.0 * (R + Ho) + 8.0)):
+    st = lib.snap_vote_sample_f32(_p(votes), R, Ho, Wo, scale, B, seed, stream, _p(uniforms), _p(index), _p(log_prob),
+                                  _p(stats), _p(count), _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_sample_f32')
+  return index, log_prob, stats, count
+
+
+def vote_sample_back(belief, nxt, taps, uniform_mix, seed, stream=0, uniforms=None):
+  """One backward step of forward-filter / backward-sample for B chains: belief f32 [R, Ho, Wo] (``vote_filter``'s
+  belief after frame t), nxt int32 [B] (the chains' linear indices at frame t + 1), taps and ``uniform_mix`` = what
+  ``vote_filter`` was given for the step from t to t + 1 -> (prev int32 [B], jumped int32 [B], stats f32 [2], count
+  int32 [3]).  prev is drawn from the exact conditional of the filter's transition given the chain's cell at t + 1: a
+  cell of the tap window weighted by taps times the belief's mass, or -- the uniform-mix share -- a draw from the
+  belief itself (jumped = 1).  prev = jumped = -1 where nxt is outside [0, R Ho Wo) (an ended chain stays ended) or
+  nothing can precede the cell.  stats = (share of the belief's mass that stayed in the volume, largest finite
+  belief); count = (chains with a predecessor, chains that jumped, NaN / +inf cells of belief).  Chain i uses Philox at
+  counter (i, stream, 1, 0); ``uniforms`` float64 [B, 2] on the device replaces it (the full contract:
+  snap_vote_sample_back_f32 in include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  _arg_chk(belief, 'belief', (torch.float32,), (None, None, None), None,
+           'vote_sample_back: belief f32 [R, Ho, Wo] on a ROCm GPU')
+  R, Ho, Wo = belief.shape
+  _arg_chk(nxt, 'nxt', (torch.int32,), (None,), belief.device, f'vote_sample_back: nxt int32 [B] on {belief.device}')
+  taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb = _vote_taps('vote_sample_back', taps, R, belief.device)
+  B, seed, stream = _vote_draws('vote_sample_back', nxt.shape[0], seed, stream, uniforms, belief.device)
+  uniform_mix = float(uniform_mix)
+  if not 0.0 <= uniform_mix <= 1.0:
+    raise ValueError(f'vote_sample_back: uniform_mix must lie in [0, 1], got {uniform_mix}')
+  words = _workspace_words(
+      lib.snap_vote_sample_back_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), belief.numel(),
+      f'vote_sample_back: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
+      'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  ws = torch.empty((words,), dtype=torch.int64, device=belief.device)
+  prev = torch.empty((B,), dtype=torch.int32, device=belief.device)
+  jumped = torch.empty((B,), dtype=torch.int32, device=belief.device)
+  stats = torch.empty((2,), dtype=torch.float32, device=belief.device)
+  count = torch.empty((3,), dtype=torch.int32, device=belief.device)
+  # bytes the launches move: the predict step's 8 passes over the volume (the filter's 12 less its update), one more
+  # read for the row sums, and per chain its window of the belief
+  with _region('vote_sample_back', 0.0, 4.0 * belief.numel() * 9 + 4.0 * B * Tk * Ta * Tb):
+    st = lib.snap_vote_sample_back_f32(_p(belief), _p(taps_k), lk, _p(taps_a), _p(taps_b), _p(offsets), R, Ho, Wo, Tk,
+                                       Ta, Tb, uniform_mix, _p(nxt), B, seed, stream, _p(uniforms), _p(prev),
+                                       _p(jumped), _p(stats), _p(count), _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_sample_back_f32')
+  return prev, jumped, stats, count
+
+
 def plane_align_score(fq, vq, fm, vm, poses, threshold):
   """The alignment score of two BEV planes at continuous poses: fq f32 [Hq, Wq, D] / vq bool or uint8 [Hq, Wq] (the
   query plane), fm f32 [Hm, Wm, D] / vm [Hm, Wm] (the map plane), poses f32 [P, 4] = (cos, sin, tx, ty) on the same
