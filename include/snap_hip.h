@@ -1153,6 +1153,51 @@ int snap_vote_smooth_f32(const float* belief, const float* next, const float* ta
                          int32_t Ta, int32_t Tb, float uniform_mix, float* smoothed, float* stats, int32_t* count,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* TAP POSTERIORS of one step of the pose filter above (the pairwise marginals of the forward-backward family, reduced
+ * to what an EM fit of the motion noise consumes): given all frames, how the vehicle moved between frame t and frame
+ * t+1.  Arguments as snap_vote_smooth_f32's: belief[R,Ho,Wo] f32 = the filter's belief_out at frame t; next[R,Ho,Wo]
+ * f32 = the smoothed belief of frame t+1; the very tables of the step from t to t+1; uniform_mix = eps of that step.
+ * Outputs, on the device: hist_k[Tk], hist_a[R,Ta], hist_b[R,Tb], stats[4] float64; count[4] i32.  n = R*Ho*Wo.
+ *   The pairwise posterior xi(x, x') = alpha_t(x) K(x'|x) gamma_{t+1}(x') / prior(x'), with K and prior the filter's
+ *   (snap_vote_smooth_f32's last paragraph), splits exactly into the JUMP branch, through the uniform share eps / n of
+ *   the prior, and the STAY branch, through the tap triple (tk, ta, tb) that carried x to x'.
+ *   PREDICT exactly as snap_vote_filter_f32 (M, the masses p, t0, t1, t2, S, sum p, prior) and RATIO exactly as
+ *   snap_vote_smooth_f32 (G, q, Q): all three entry points are built from one set of device code, the same bits.
+ *   ADJOINT, snap_vote_smooth_f32's first two gathers (named by pass here: its c1 is c0 and its c0 is c1), f32 fma
+ *   chains stored as f32:  c0[r,a,b] = sum_tb taps_b[r,tb] * q[r, a, b - lb[r] - tb];
+ *                          c1[r,a,b] = sum_ta taps_a[r,ta] * c0[r, a - la[r] - ta, b].
+ *   HISTOGRAMS, raw; a source outside the volume contributes nothing, as in the passes:
+ *     Hb[r,tb] = sum_{a,b}   fl32(fl32(taps_b[r,tb] * t1[r, a, b + lb[r] + tb]) * q [r,a,b]);
+ *     Ha[r,ta] = sum_{a,b}   fl32(fl32(taps_a[r,ta] * t0[r, a + la[r] + ta, b]) * c0[r,a,b]);
+ *     Hk[tk]   = sum_{r,a,b} fl32(fl32(taps_k[tk]   * p[(r + lk + tk) mod R, a, b]) * c1[r,a,b]);
+ *   every term two f32 products (not contracted), every sum float64.  In exact arithmetic sum Hb = sum Ha = sum Hk =
+ *   sum t2 * q.
+ *   FINISH, float64: H = sum_tk Hk[tk] in index order; c = (1 - eps) / S (0 when S == 0); stay_raw = c * H;
+ *   jump_raw = (eps / n) * Q; total = stay_raw + jump_raw.  hist_x = (c * Hx) / total for the three tables;
+ *   stats = { stay = stay_raw / total; jump = jump_raw / total; log_norm = G + log(total); S / sum p rounded to f32 (0
+ *   when no cell has mass): converted to f32 it is the filter's stats[1] of that step, bit for bit }.  total * e^G is
+ *   the sum of gamma_{t+1} over the cells with ratio mass: log_norm is 0 up to rounding for arguments that belong
+ *   together (snap_vote_smooth_f32's log_norm is this number plus the log of the sum of exp(belief), itself 0 for a
+ *   normalised belief).  When total == 0 (no ratio mass) every histogram entry, stay and jump are 0 and log_norm = -inf.
+ *   stay + jump = 1, and each table sums to stay, up to rounding.
+ *   count = { cells of belief with mass (the filter's count[3]); then as snap_vote_smooth_f32's count[1..3]: NaN or
+ *   +inf cells of belief; NaN or +inf cells of next; cells of next with ratio mass }.
+ * Twelve launches of 256 threads: the filter's four; the ratio's two; then Hb, c0, Ha, c1, Hk; one workgroup that folds
+ * the partial rows.  The predict, ratio and adjoint launches have min(R * ceil(Ho*Wo/256), 2048) workgroups; the three
+ * reductions have R * gpr, gpr = min(ceil(Ho*Wo/256), 2048 / R) workgroups per rotation striding over that rotation's
+ * tiles, so a workgroup keeps one tap row and float64 accumulators in registers over all its tiles and writes one
+ * partial row.  22 passes over the volume, as the smoother.  No atomics: every order is fixed by (R, Ho, Wo, Tk, Ta, Tb),
+ * so two calls give the same bits.  Every element of the five outputs is written by every call.
+ * Supported shapes, error codes and their order as snap_vote_smooth_f32 (belief == NULL is SNAP_ERR_NULL: a step without
+ * a previous frame has no pair).  workspace: snap_vote_pairs_workspace_bytes() bytes (0 = unsupported shape): four
+ * volumes, the per-workgroup partials and the partial rows; it needs no initialisation and no launch touches a byte
+ * beyond that size.  Asynchronous on `stream`; the caller owns every buffer. */
+size_t snap_vote_pairs_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t Tk, int32_t Ta, int32_t Tb);
+int snap_vote_pairs_f32(const float* belief, const float* next, const float* taps_k, int32_t lk, const float* taps_a,
+                        const float* taps_b, const int32_t* offsets, int32_t R, int32_t Ho, int32_t Wo, int32_t Tk,
+                        int32_t Ta, int32_t Tb, float uniform_mix, double* hist_k, double* hist_a, double* hist_b,
+                        double* stats, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Most likely pose TRACK over vote volumes: one forward step of the max-product (Viterbi) recursion that goes with the
  * filter above, with back-pointers.  score_prev[R,Ho,Wo] f32 is the log score of the best path into every pose of the
  * previous frame (-inf = no path), or NULL (the first frame of a track); votes[R,Ho,Wo] f32; on the DEVICE:

@@ -280,6 +280,9 @@ SIGNATURES = {
     'snap_vote_smooth_workspace_bytes': (c_size, [c_int] * 6),
     'snap_vote_smooth_f32': (
         c_int, [ptr, ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float, ptr, ptr, ptr, ptr, c_size, ptr]),
+    'snap_vote_pairs_workspace_bytes': (c_size, [c_int] * 6),
+    'snap_vote_pairs_f32': (
+        c_int, [ptr, ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float] + [ptr] * 6 + [c_size, ptr]),
     'snap_vote_viterbi_workspace_bytes': (c_size, [c_int] * 6),
     'snap_vote_viterbi_f32': (
         c_int, [ptr, ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float] * 3 + [ptr] * 5 + [c_size, ptr]),

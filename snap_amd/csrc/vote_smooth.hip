@@ -3,8 +3,9 @@
 // belief [R, Ho, Wo] f32 = log alpha_t, the filter's output at frame t; next [R, Ho, Wo] f32 = log gamma_{t+1}, the
 // smoothed belief of frame t + 1; the taps the filter used from t to t + 1; eps = uniform_mix; n = R Ho Wo.
 // PREDICT, the filter's own code (vote_predict.h): M, the masses p, t0, t1, t2, S = sum t2, sum p, and per cell
-// prior = ((1 - eps) t2) / S + eps / n: the filter's bits.  RATIO, float64: lg = next - log(prior) where next is finite
-// and prior > 0, G = max lg, q = fl32(exp(lg - G)) where fl32(lg - G) >= -40, else 0, Q = sum q.  ADJOINT transport,
+// prior = ((1 - eps) t2) / S + eps / n: the filter's bits.  RATIO, float64 (vote_ratio.h, shared with vote_pairs.hip):
+// lg = next - log(prior) where next is finite and prior > 0, G = max lg, q = fl32(exp(lg - G)) where
+// fl32(lg - G) >= -40, else 0, Q = sum q.  ADJOINT transport,
 // three gathers, the xy passes first with their own rotation's tables, the rotation pass last:
 //   c1[r, a, b] = sum_tb taps_b[r, tb] q [r, a, b - lb[r] - tb];
 //   c0[r, a, b] = sum_ta taps_a[r, ta] c1[r, a - la[r] - ta, b];
@@ -37,7 +38,7 @@
 // (R, Ho, Wo) alone.
 // HBM traffic (n = R Ho Wo cells of 4 bytes): reads belief 4 (+ L2 re-reads), next 2, t0, t1, t2 twice, q, c1, c0
 // (+ L2 re-reads), u; writes t0, t1, t2, q, c1, c0, u, smoothed: 22 n cells (the filter: 12).
-#include "vote_predict.h"
+#include "vote_ratio.h"
 
 namespace {
 
@@ -46,24 +47,9 @@ constexpr int SM_WAVES = VP_WAVES;
 
 // per-workgroup partials: double [groups][6], int32 [groups][5], float [groups][2]; the predict step's columns first
 constexpr int SM_DS = 6, SM_IS = 5, SM_FS = 2;
-enum { SM_D_SUMP = VP_D_SUMP, SM_D_SUMT2 = VP_D_SUMT2, SM_D_G = 2, SM_D_Q = 3, SM_D_LSE_M = 4, SM_D_LSE_S = 5 };
-enum { SM_I_BAD = VP_I_BAD, SM_I_MASS = VP_I_MASS, SM_I_BADNEXT = 2, SM_I_RATIO = 3, SM_I_FIN = 4 };
+enum { SM_D_SUMP = VP_D_SUMP, SM_D_SUMT2 = VP_D_SUMT2, SM_D_G = VR_D_G, SM_D_Q = VR_D_Q, SM_D_LSE_M = 4, SM_D_LSE_S = 5 };
+enum { SM_I_BAD = VP_I_BAD, SM_I_MASS = VP_I_MASS, SM_I_BADNEXT = VR_I_BADNEXT, SM_I_RATIO = VR_I_RATIO, SM_I_FIN = 4 };
 enum { SM_F_PEAK = VP_F_PEAK, SM_F_OUTMAX = 1 };
-
-// The largest of the workgroup's values (a maximum: exact in any order), the same bits in every thread.
-__device__ __forceinline__ double sm_block_max(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double m = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
-  __syncthreads();
-  return m;
-}
-__device__ __forceinline__ double sm_fold_max(const double* __restrict__ dpart, int col, int groups, double* sh) {
-  double v = -(double)INFINITY;
-  for (int g = threadIdx.x; g < groups; g += SM_NT) v = fmax(v, dpart[(size_t)g * SM_DS + col]);
-  return sm_block_max(v, sh);
-}
 
 // ---- launches 1-4: the predict step (vote_predict.h)
 __global__ __launch_bounds__(SM_NT) void vote_smooth_peak_kernel(const float* __restrict__ belief, int n,
@@ -95,65 +81,16 @@ __global__ __launch_bounds__(SM_NT) void vote_smooth_cols_kernel(const float* __
   vp_cols<ADJ, !ADJ, SM_DS>(src, taps_b, offsets, Wo, P, Tb, tiles_per_plane, tiles, dst, dpart);
 }
 
-// The ratio of one cell, float64: lg = next - log(prior); false where the cell has no ratio mass (next not finite, or
-// a prior of 0).
-__device__ __forceinline__ bool sm_ratio(const VpPrior& c, float t2, float next, double* lg) {
-  if (!vote_finite(next)) return false;
-  const double prior = vp_prior(c, t2);
-  if (!(prior > 0.0)) return false;
-  *lg = (double)next - log(prior);
-  return true;
-}
-
-// ---- launch 5
+// ---- launches 5 and 6: the ratio step (vote_ratio.h)
 __global__ __launch_bounds__(SM_NT) void vote_smooth_ratio_kernel(const float* __restrict__ t2,
                                                                   const float* __restrict__ next, int n, float eps,
                                                                   double* __restrict__ dpart, int32_t* __restrict__ ipart) {
-  __shared__ double shd[SM_WAVES];
-  __shared__ int shi[SM_WAVES];
-  const VpPrior c = vp_prior_setup(vote_fold_sum<SM_WAVES, SM_DS>(dpart, SM_D_SUMT2, gridDim.x, shd), true, eps, n);
-  double G = -(double)INFINITY;
-  int bad = 0, mass = 0;
-  for (int64_t i = (int64_t)blockIdx.x * SM_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * SM_NT) {
-    const float v = next[i];
-    double lg;
-    if (sm_ratio(c, t2[i], v, &lg)) {
-      G = fmax(G, lg);
-      ++mass;
-    } else if (!vote_finite(v) && !(v == -INFINITY)) {
-      ++bad;                                // NaN or +inf
-    }
-  }
-  G = sm_block_max(G, shd);
-  bad = vote_block_sum<SM_WAVES>(bad, shi);
-  mass = vote_block_sum<SM_WAVES>(mass, shi);
-  if (threadIdx.x == 0) {
-    dpart[(size_t)blockIdx.x * SM_DS + SM_D_G] = G;
-    ipart[(size_t)blockIdx.x * SM_IS + SM_I_BADNEXT] = bad;
-    ipart[(size_t)blockIdx.x * SM_IS + SM_I_RATIO] = mass;
-  }
+  vr_max<SM_DS, SM_IS>(t2, next, n, eps, dpart, ipart);
 }
-
-// ---- launch 6
 __global__ __launch_bounds__(SM_NT) void vote_smooth_mass_kernel(const float* __restrict__ t2,
                                                                  const float* __restrict__ next, int n, float eps,
                                                                  float* __restrict__ q, double* __restrict__ dpart) {
-  __shared__ double shd[SM_WAVES];
-  const VpPrior c = vp_prior_setup(vote_fold_sum<SM_WAVES, SM_DS>(dpart, SM_D_SUMT2, gridDim.x, shd), true, eps, n);
-  const double G = sm_fold_max(dpart, SM_D_G, gridDim.x, shd);
-  double sum = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * SM_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * SM_NT) {
-    double lg;
-    float m = 0.f;
-    if (sm_ratio(c, t2[i], next[i], &lg)) {   // (then G is finite and lg <= G)
-      const double d = lg - G;
-      if ((float)d >= VP_CUT) m = (float)exp(d);
-    }
-    q[i] = m;
-    sum += (double)m;
-  }
-  sum = vote_block_sum<SM_WAVES>(sum, shd);
-  if (threadIdx.x == 0) dpart[(size_t)blockIdx.x * SM_DS + SM_D_Q] = sum;
+  vr_mass<SM_DS>(t2, next, n, eps, q, dpart);
 }
 
 // The combination of one cell, float64: w = (belief + G) + log(h), h = ((1 - eps) (sum p / S)) u + (eps / n) Q.  NaN
@@ -176,7 +113,7 @@ __device__ __forceinline__ SmCombine sm_combine_setup(const double* __restrict__
   SmCombine c;
   c.carried = S > 0.0 ? (1.0 - (double)eps) * (sum_p / S) : 0.0;
   c.uniform = ((double)eps / (double)n) * Q;
-  c.G = sm_fold_max(dpart, SM_D_G, groups, sh);
+  c.G = vr_fold_max<SM_DS>(dpart, SM_D_G, groups, sh);
   return c;
 }
 
@@ -264,7 +201,7 @@ __global__ __launch_bounds__(SM_NT) void vote_smooth_finish_kernel(int groups, c
   const float top = vote_fold_max<SM_WAVES, SM_FS>(fpart, SM_F_OUTMAX, groups, shf);
   const double sum_p = vote_fold_sum<SM_WAVES, SM_DS>(dpart, SM_D_SUMP, groups, shd);
   const double S = vote_fold_sum<SM_WAVES, SM_DS>(dpart, SM_D_SUMT2, groups, shd);
-  const double G = sm_fold_max(dpart, SM_D_G, groups, shd);
+  const double G = vr_fold_max<SM_DS>(dpart, SM_D_G, groups, shd);
   if (threadIdx.x == 0) {
     stats[1] = sum_p > 0.0 ? (float)(S / sum_p) : 0.f;   // (the filter's mass_kept: the same expression)
     stats[2] = (float)G;

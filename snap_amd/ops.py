@@ -2422,6 +2422,47 @@ def vote_smooth(belief, smoothed_next, taps, uniform_mix=0.0):
   return smoothed, stats, count
 
 
+def vote_pairs(belief, smoothed_next, taps, uniform_mix=0.0):
+  """The tap posteriors of one filter step given all frames: arguments as ``vote_smooth``'s (belief f32 [R, Ho, Wo] =
+  the filter's belief after frame t, required: a step without a previous frame has no pair; smoothed_next = the
+  smoothed belief of frame t + 1; taps and ``uniform_mix`` = that step's) -> (hist_k float64 [Tk], hist_a float64
+  [R, Ta], hist_b float64 [R, Tb], stats float64 [4], count int32 [4]) on the device.  The posterior over how the pose
+  moved from t to t + 1 splits into the jump branch (the uniform share of the prior) and the stay branch by tap; the
+  histograms are the stay branch's marginals per axis (hist_a / hist_b per destination rotation), each summing to
+  ``stay``.  stats = (stay, jump: they sum to 1; log_norm: the log of their total before normalisation, 0 up to
+  rounding for arguments that belong together; mass_kept: the filter's, its bits once converted to f32); count = (cells
+  of belief with mass, NaN / +inf cells of belief, NaN / +inf cells of smoothed_next, cells of smoothed_next with ratio
+  mass).  Without ratio mass everything but mass_kept is 0 and log_norm -inf (the full contract: snap_vote_pairs_f32 in
+  include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  _arg_chk(belief, 'belief', (torch.float32,), (None, None, None), None,
+           'vote_pairs: belief f32 [R, Ho, Wo] on a ROCm GPU')
+  R, Ho, Wo = belief.shape
+  _arg_chk(smoothed_next, 'smoothed_next', (torch.float32,), (R, Ho, Wo), belief.device,
+           f'vote_pairs: smoothed_next {torch.float32} {[R, Ho, Wo]} on {belief.device}')
+  taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb = _vote_taps('vote_pairs', taps, R, belief.device)
+  uniform_mix = float(uniform_mix)
+  if not 0.0 <= uniform_mix <= 1.0:
+    raise ValueError(f'vote_pairs: uniform_mix must lie in [0, 1], got {uniform_mix}')
+  words = _workspace_words(
+      lib.snap_vote_pairs_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), belief.numel(),
+      f'vote_pairs: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
+      'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  ws = torch.empty((words,), dtype=torch.int64, device=belief.device)
+  hist_k = torch.empty((Tk,), dtype=torch.float64, device=belief.device)
+  hist_a = torch.empty((R, Ta), dtype=torch.float64, device=belief.device)
+  hist_b = torch.empty((R, Tb), dtype=torch.float64, device=belief.device)
+  stats = torch.empty((4,), dtype=torch.float64, device=belief.device)
+  count = torch.empty((4,), dtype=torch.int32, device=belief.device)
+  # bytes the launches move (snap_vote_pairs_f32 in the header): 22 passes over the volume
+  with _region('vote_pairs', 0.0, 4.0 * belief.numel() * 22):
+    st = lib.snap_vote_pairs_f32(_p(belief), _p(smoothed_next), _p(taps_k), lk, _p(taps_a), _p(taps_b), _p(offsets),
+                                 R, Ho, Wo, Tk, Ta, Tb, uniform_mix, _p(hist_k), _p(hist_a), _p(hist_b), _p(stats),
+                                 _p(count), _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_pairs_f32')
+  return hist_k, hist_a, hist_b, stats, count
+
+
 def vote_viterbi(score_prev, votes, log_taps, scale=1.0, log_stay=0.0, log_jump=float('-inf')):
   """One forward step of the max-product (Viterbi) recursion that goes with ``vote_filter``: score_prev f32
   [R, Ho, Wo] (the log score of the best path into every pose of the previous frame, -inf = no path) or None (a track
