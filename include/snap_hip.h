@@ -1198,6 +1198,66 @@ int snap_vote_pairs_f32(const float* belief, const float* next, const float* tap
                         int32_t Ta, int32_t Tb, float uniform_mix, double* hist_k, double* hist_a, double* hist_b,
                         double* stats, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Highest-density CREDIBLE REGIONS of a vote volume, and where a ground-truth pose falls among them: the summary of a
+ * multi-modal posterior that a covariance cannot give, and the statistic a calibration check needs (for a calibrated
+ * model the mass ranked above the true pose is uniform on [0, 1]).
+ * votes[R,Ho,Wo] f32 unnormalised log-scores, flat(r,a,b) = (r*Ho + a)*Wo + b; scale: a finite float > 0.
+ *   A cell CONTRIBUTES iff its vote is finite (snap_vote_posterior_f32's rule: -inf cells are masked silently, NaN and
+ *   +inf cells are excluded and counted); F is the set of contributing cells.  vmax = the largest contributing vote;
+ *   the WEIGHT of a cell is w = exp((double)scale * ((double)v - (double)vmax)); Z = sum_F w.  The ORDER of cells is the
+ *   f32 comparison of the votes themselves, with -0 = +0 (scale > 0 does not change it).
+ *   levels: a HOST array q_0 < q_1 < ... < q_{L-1}, each strictly inside (0, 1), 1 <= L <= 8; read on the host,
+ *   validated and passed to the kernels by value.
+ *   REGION l = { c in F : v_c >= tau_l }, tau_l = the largest value t taken by a contributing cell with
+ *   mass{v >= t} >= q_l * Z.  A class of tied cells is in or out as a whole, so the regions are nested.
+ *   threshold[L]: tau_l, exactly a vote value of the volume (+0 for the class of zeros).
+ *   mass[L]: mass{v >= tau_l} / Z, float64, rounded to f32 once.
+ *   table[L,8] i32 = { cells of the region; pixels (a, b) with at least one rotation in it; rotations r with at least
+ *   one pixel in it; a_min, a_max, b_min, b_max (the inclusive index bounding box); 0 }.
+ *   The LEVEL of a cell is the smallest l with v >= tau_l, and L if there is none or the cell does not contribute.
+ *   level_xy[Ho,Wo] u8: the minimum over r; level_r[R] u8: the minimum over the pixels; level_cell[R,Ho,Wo] u8, or NULL:
+ *   the cells' own levels.  One u8 plane therefore carries all L nested footprints (region l = { level <= l }).
+ *   gt_index: NULL, or a DEVICE pointer to f32 [3] = (k, i, j) as exhaustive_tfm_to_index returns it, read by the
+ *   kernels.  The ground-truth cell is (rintf(k) mod R, rintf(i), rintf(j)) (round half to even, mathematical modulo);
+ *   valid iff k, i, j are finite, |k| <= 2^20, 0 <= i <= Ho-1, 0 <= j <= Wo-1 and that cell contributes.
+ *   gt_stats[4] = { v_gt; mass{v > v_gt} / Z, the CREDIBILITY of the ground truth; mass{v >= v_gt} / Z; 0 }: the ground
+ *   truth lies in region l exactly when v_gt >= tau_l.  Invalid or NULL: the first three are NaN.
+ *   count[4] = { contributing cells; NaN or +inf cells; 1 if the ground truth is valid, else 0; the ground truth's
+ *   level (the smallest l with v_gt >= tau_l, L if none), -1 if invalid }.
+ *   F empty: thresholds and masses NaN, every table row { 0, 0, 0, -1, -1, -1, -1, 0 }, the level maps all L,
+ *   gt_stats NaN (and its last entry 0).
+ * METHOD.  The thresholds come from a most-significant-digit radix select over the monotone 32-bit key of the vote,
+ * 8 bits a pass, for all levels at once: a pass adds the cells' FIXED-POINT weights wfix = rint(w * 2^Q) (uint64,
+ * Q = 62 - the bit length of R*Ho*Wo, so no sum can overflow) into 256 bins per distinct key prefix of the levels
+ * (integer atomics, exact and order-independent: in LDS per workgroup, the non-empty bins then added to global bins),
+ * and L workgroups pick the levels' next digits with the test (double)(cumulative wfix) >= (double)q_l * (double)Zfix
+ * (Zfix = sum wfix; the conversions of the uint64 sums round to 53 bits, monotonically, and a digit's bins sum to their
+ * parent's bin as integers, so the passes stay consistent).  The selection is exact for the quantised weights up to
+ * those conversions: it returns the definition's tau_l whenever q_l differs from the normalised mass at every vote
+ * value by more than EPS = R*Ho*Wo * 2^-Q / Z + 2^-40 (the quantum is 2^-Q; the second term covers the 2^-52 relative
+ * error of the two conversions, of the product and of the float64 exp, each at most a few 2^-53 of a mass <= 1; at
+ * 36 x 511 x 511, Q = 38 and the first term is 3.4e-5 / Z with Z >= 1, and Z is of the order of the number of cells
+ * that matter).  The masses that are RETURNED (mass, gt_stats)
+ * do not pass through the fixed point: they are float64 sums of the float64 weights, exact to float64 summation error
+ * (far inside EPS).
+ * PASSES over the volume, for every L: 1 (vmax and the counts) + 4 (one per digit) + 1 final pass that writes the
+ * level maps and accumulates the masses, the tables' partials and the ground-truth tail masses = 6.  Eleven launches
+ * (max, which also zeroes the global bins; 4 x (bins, select); levels; one workgroup that folds the partial rows).
+ * No floating-point atomics anywhere (the only atomics are the integer ones above and the level pass's LDS minima,
+ * maxima and counts); per-workgroup float64 partials are folded in an order fixed by (R, Ho, Wo), so
+ * two calls with the same arguments give the same bytes.  Every element of every output is written by every call.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31, else SNAP_ERR_BAD_SHAPE; a NULL pointer other than gt_index and
+ * level_cell SNAP_ERR_NULL; a scale that is not a finite number > 0, an L outside 1..8, or levels that are not strictly
+ * increasing inside (0, 1) SNAP_ERR_UNSUPPORTED; a short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE; all before
+ * any launch, in that order.  workspace: snap_vote_credible_workspace_bytes() bytes (0 = unsupported shape or L); it
+ * needs no initialisation and no launch touches a byte beyond that size.  Asynchronous on `stream`, no host
+ * synchronisation; the caller owns every buffer. */
+size_t snap_vote_credible_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t L);
+int snap_vote_credible_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, float scale, const float* levels,
+                           int32_t L, const float* gt_index, float* threshold, float* mass, int32_t* table,
+                           uint8_t* level_xy, uint8_t* level_r, uint8_t* level_cell, float* gt_stats, int32_t* count,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* Most likely pose TRACK over vote volumes: one forward step of the max-product (Viterbi) recursion that goes with the
  * filter above, with back-pointers.  score_prev[R,Ho,Wo] f32 is the log score of the best path into every pose of the
  * previous frame (-inf = no path), or NULL (the first frame of a track); votes[R,Ho,Wo] f32; on the DEVICE:

@@ -326,6 +326,59 @@ def posterior_from_votes(votes, grid, num_rotations, temperature=1.0, m_t_q_gt=N
   return out
 
 
+def credible_from_votes(votes, grid, num_rotations, levels=(0.5, 0.9, 0.99), temperature=1.0, m_t_q_gt=None,
+                        cell_levels=False):
+  """The highest-density credible regions of p = softmax(temperature * votes) over the finite cells of a vote volume
+  [R, 2H-1, 2W-1] (``ops.vote_credible``): for every level q of ``levels`` the smallest set of whole tie classes of
+  cells that holds at least q of the probability -> dict of device tensors, nothing synchronised:
+
+  ``threshold`` / ``mass`` [L], ``table`` int32 [L, 8], ``level_xy`` uint8 [2H-1, 2W-1], ``level_r`` uint8 [R],
+  ``level_cell`` (None unless ``cell_levels``), ``gt_stats``, ``count``: the op's outputs (region l of a level map is
+  ``level <= l``); ``area_m2`` [L] = pixels * cell^2, the footprint of the region on the map; ``yaw_span_deg`` [L] =
+  rotations * 360 / R; ``volume`` [L] = cells * cell^2 * 2 pi / R (m^2 rad).
+  With ``m_t_q_gt`` (a Transform2D, map corner frame; rounded to the nearest cell of ``exhaustive_tfm_to_index`` on the
+  device): ``gt_credibility`` = the mass ranked strictly above the true pose's cell (uniform on [0, 1] for a calibrated
+  posterior; NaN where invalid), ``gt_level`` (the smallest l whose region holds it, L = none, -1 = invalid),
+  ``gt_valid`` (bool: inside the volume, on a contributing cell) and ``covered`` [L] bool."""
+  if votes.shape[0] != num_rotations:
+    raise ValueError(f'credible_from_votes: {votes.shape[0]} vote planes for {num_rotations} rotations')
+  gt = None
+  if m_t_q_gt is not None:
+    gt = exhaustive_tfm_to_index(m_t_q_gt, grid, num_rotations).to(device=votes.device, dtype=torch.float32)
+    gt = gt.reshape(3).contiguous()
+  levels = tuple(float(q) for q in levels)
+  threshold, mass, table, level_xy, level_r, level_cell, gt_stats, count = ops.vote_credible(
+      votes.contiguous(), levels, temperature, gt, cell_levels)
+  cell2 = float(grid.cell_size) ** 2
+  out = dict(
+      threshold=threshold, mass=mass, table=table, level_xy=level_xy, level_r=level_r, level_cell=level_cell,
+      gt_stats=gt_stats, count=count, area_m2=table[:, 1].to(torch.float32) * cell2,
+      yaw_span_deg=table[:, 2].to(torch.float32) * (360.0 / num_rotations),
+      volume=table[:, 0].to(torch.float32) * (cell2 * 2 * math.pi / num_rotations))
+  if m_t_q_gt is not None:
+    out['gt_credibility'] = gt_stats[1]
+    out['gt_level'] = count[3]
+    out['gt_valid'] = count[2] != 0
+    out['covered'] = (count[3] >= 0) & (count[3] <= torch.arange(len(levels), device=votes.device))
+  return out
+
+
+def coverage_table(gt_credibility, levels, valid=None):
+  """Host helper of an evaluation loop: the calibration of credible regions over many frames.  ``gt_credibility``: the
+  frames' ``credible_from_votes(...)['gt_credibility']`` (any array-like; NaN = invalid), ``valid``: an optional bool
+  mask on top -> dict(levels, coverage [L] = the fraction of valid frames with gt_credibility < q (the true pose lay
+  inside the q-region), count = the valid frames, mean_abs_error = mean |coverage - q|).  A calibrated posterior has
+  coverage = q up to the binomial noise sqrt(q (1 - q) / count)."""
+  c = np.asarray(torch.as_tensor(gt_credibility).detach().cpu(), dtype=np.float64).reshape(-1)
+  ok = np.isfinite(c)
+  if valid is not None:
+    ok &= np.asarray(torch.as_tensor(valid).detach().cpu()).reshape(-1).astype(bool)
+  q = np.asarray(levels, dtype=np.float64).reshape(-1)
+  n = int(ok.sum())
+  cov = np.array([float((c[ok] < v).mean()) if n else float('nan') for v in q])
+  return dict(levels=q, coverage=cov, count=n, mean_abs_error=float(np.abs(cov - q).mean()) if n else float('nan'))
+
+
 def _bin_cos_sin(R):
   """float64 (cos, sin) of the R bin angles 2 pi r / R -> [R, 2].  The angle is reduced to a quarter turn first
   (4 r = q R + rem: 2 pi r / R = (q + rem / R) pi / 2) and the quarter turns are applied as sign swaps, so whole
@@ -451,12 +504,14 @@ def refine_poses(plane_q, plane_map, index, grid, num_rotations, conf_q=None, mi
 
 
 def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, method=None, posterior=None,
-                        refine=None, **peaks):
+                        refine=None, credible=None, **peaks):
   """``exhaustive_pose_voting`` followed by ``poses_from_votes(**peaks)``: the dict of the latter plus ``votes``.
   ``['map_t_query'][0]`` is the single best pose.  ``posterior``: True, or a dict of keyword arguments of
   ``posterior_from_votes`` (``temperature``, ``m_t_q_gt``), adds its result as ``['posterior']``.  ``refine``: True,
   or a dict of keyword arguments of ``refine_poses`` (``min_overlap``, the lattice), adds the peaks refined to
-  continuous poses on the two planes as ``['refined']``."""
+  continuous poses on the two planes as ``['refined']``.  ``credible``: True, or a dict of keyword arguments of
+  ``credible_from_votes`` (``levels``, ``temperature``, ``m_t_q_gt``, ``cell_levels``), adds its result as
+  ``['credible']``."""
   votes = exhaustive_pose_voting(plane_q, plane_map, num_rotations, grid, conf_q=conf_q, method=method)
   out = poses_from_votes(votes, grid, num_rotations, **peaks)
   out['votes'] = votes
@@ -466,6 +521,9 @@ def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, me
   if refine is not None and refine is not False:
     kw = {} if refine is True else dict(refine)
     out['refined'] = refine_poses(plane_q, plane_map, out['index'], grid, num_rotations, conf_q=conf_q, **kw)
+  if credible is not None and credible is not False:
+    kw = {} if credible is True else dict(credible)
+    out['credible'] = credible_from_votes(votes, grid, num_rotations, **kw)
   return out
 
 
@@ -935,6 +993,14 @@ class VoteFilter:
       kw = {} if posterior is True else dict(posterior)
       out['posterior'] = posterior_from_votes(step['belief'], self.grid, self.num_rotations, **kw)
     return out
+
+  def credible(self, levels=(0.5, 0.9, 0.99), m_t_q_gt=None, cell_levels=False):
+    """``credible_from_votes`` of the belief the filter holds (log-space and normalised, so the temperature is 1) ->
+    its dict.  Raises ValueError before the first step."""
+    if self.belief is None:
+      raise ValueError('VoteFilter.credible: no belief (at least one step)')
+    return credible_from_votes(self.belief, self.grid, self.num_rotations, levels=levels, temperature=1.0,
+                               m_t_q_gt=m_t_q_gt, cell_levels=cell_levels)
 
   def smooth(self, posterior=None, **peaks):
     """The backward recursion over the history (``smooth_track``; each step's taps are rebuilt by ``motion_taps``) ->

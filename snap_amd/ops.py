@@ -2292,6 +2292,58 @@ def vote_posterior(votes, scale=1.0, gt_index=None):
   return log_prob_xy, log_prob_r, stats, count
 
 
+def vote_credible(votes, levels, scale=1.0, gt_index=None, cell_levels=False):
+  """Highest-density credible regions of a vote volume: votes [R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked),
+  ``levels`` a host sequence 0 < q_0 < ... < q_{L-1} < 1 (1 <= L <= 8) -> (threshold f32 [L], mass f32 [L], table
+  int32 [L, 8] = (cells, pixels, rotations, a_min, a_max, b_min, b_max, 0), level_xy uint8 [Ho, Wo], level_r uint8
+  [R], level_cell uint8 [R, Ho, Wo] or None (``cell_levels``), gt_stats f32 [4] = (v_gt, mass above it = the
+  credibility of the ground truth, mass at or above it, 0), count int32 [4] = (contributing cells, NaN or +inf cells,
+  ground truth valid, ground truth's level or -1)) of p = softmax(scale * votes) over the finite cells.  Region l holds
+  the cells with v >= threshold[l], the smallest set of whole tie classes with mass >= q_l; a level map holds, per
+  pixel / rotation / cell, the smallest l whose region it touches (L = none).  ``gt_index``: None or a device f32 [3]
+  = (k, i, j) (``exhaustive_tfm_to_index``), rounded to the nearest cell on the device (the full contract:
+  snap_vote_credible_f32 in include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  _f32(votes, 'votes')
+  if votes.dim() != 3:
+    raise ValueError(f'vote_credible: votes [R, Ho, Wo], got {tuple(votes.shape)}')
+  R, Ho, Wo = votes.shape
+  scale = float(scale)
+  if not (scale > 0.0 and np.isfinite(scale)):
+    raise ValueError(f'vote_credible: scale must be a finite number > 0, got {scale}')
+  q = np.asarray(levels, dtype=np.float32).reshape(-1)
+  L = int(q.size)
+  if not (1 <= L <= 8 and bool(np.all(q > 0)) and bool(np.all(q < 1)) and bool(np.all(np.diff(q) > 0))):
+    raise ValueError(f'vote_credible: levels must be 1 to 8 strictly increasing numbers inside (0, 1), got {levels}')
+  if gt_index is not None:
+    _f32(gt_index, 'gt_index')
+    if tuple(gt_index.shape) != (3,) or gt_index.device != votes.device:
+      raise ValueError(f'vote_credible: gt_index f32 [3] on {votes.device}, got {tuple(gt_index.shape)} on '
+                       f'{gt_index.device}')
+  words = _workspace_words(
+      lib.snap_vote_credible_workspace_bytes, (R, Ho, Wo, L), votes.numel(),
+      f'vote_credible: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  dev = votes.device
+  ws = torch.empty((words,), dtype=torch.int64, device=dev)
+  threshold = torch.empty((L,), dtype=torch.float32, device=dev)
+  mass = torch.empty((L,), dtype=torch.float32, device=dev)
+  table = torch.empty((L, 8), dtype=torch.int32, device=dev)
+  level_xy = torch.empty((Ho, Wo), dtype=torch.uint8, device=dev)
+  level_r = torch.empty((R,), dtype=torch.uint8, device=dev)
+  level_cell = torch.empty((R, Ho, Wo), dtype=torch.uint8, device=dev) if cell_levels else None
+  gt_stats = torch.empty((4,), dtype=torch.float32, device=dev)
+  count = torch.empty((4,), dtype=torch.int32, device=dev)
+  host_levels = (ctypes.c_float * L)(*q.tolist())
+  # algorithmic bytes: six reads of the volume for every L (snap_vote_credible_f32 in the header: the maximum, four
+  # digit passes, the level pass)
+  with _region('vote_credible', 0.0, 4.0 * votes.numel() * 6):
+    st = lib.snap_vote_credible_f32(_p(votes), R, Ho, Wo, scale, host_levels, L, _p(gt_index), _p(threshold), _p(mass),
+                                    _p(table), _p(level_xy), _p(level_r), _p(level_cell), _p(gt_stats), _p(count),
+                                    _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_credible_f32')
+  return threshold, mass, table, level_xy, level_r, level_cell, gt_stats, count
+
+
 def vote_fuse(volumes, shifts, weights=None):
   """Multi-frame fusion of aligned vote volumes: volumes [N, R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked),
   shifts f32 [N, R, 3] = (dk, da, db) on the same device (``pose_exhaustive_voting.sequence_shift_table``), weights
