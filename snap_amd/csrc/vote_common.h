@@ -4,8 +4,9 @@
 // function of the shape alone; two calls give the same bits" (vote_credible.hip alone uses atomics, INTEGER ones: uint64
 // adds of fixed-point mass and int minima / maxima / counts, exact in any order), and vote_filter is tested
 // against vote_fuse and vote_posterior bit for bit: the predicates, reductions, tile walk and circular indices those
-// comparisons rest on exist once, here.  No kernels.  -ffp-contract=off is in force, so one expression gives one set of
-// bits wherever it is inlined.
+// comparisons rest on exist once, here.  No kernels in this file (vote_predict.h and vote_ratio.h, built on it, hold the
+// kernels several operators launch).  -ffp-contract=off is in force, so one expression gives one set of bits wherever
+// it is inlined.
 #ifndef SNAP_CSRC_VOTE_COMMON_H_
 #define SNAP_CSRC_VOTE_COMMON_H_
 
@@ -183,6 +184,13 @@ __device__ __forceinline__ double vote_fold_lse(const double* __restrict__ part,
     vote_lse_merge(&m, &s, part[(size_t)g * STRIDE + col_m], part[(size_t)g * STRIDE + col_s]);
   vote_block_lse<WAVES>(&m, &s, sh);
   return m == -(double)INFINITY ? m : m + log(s);
+}
+// A float64 log-value against the log-sum-exp of its set, as the f32 that is stored: NaN -> NaN, -inf -> -inf, else
+// fl32(w - log_norm).
+__device__ __forceinline__ float vote_normalised(double w, double log_norm) {
+  if (w != w) return __int_as_float(0x7fc00000);
+  if (w == -(double)INFINITY) return -INFINITY;
+  return (float)(w - log_norm);
 }
 
 // ------------------------------- the tile walk ------------------------------------------------

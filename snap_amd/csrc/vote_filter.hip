@@ -7,14 +7,15 @@
 //
 // A tile is one rotation and 256 consecutive pixels p = a * Wo + b, one cell per thread; every launch has
 // min(tiles, 2048) workgroups of 256 threads striding over the tiles (the tap rows of a tile are uniform: scalar loads).
-// Launch 1 (vote_filter_peak_kernel):   per workgroup the largest finite belief and the count of NaN / +inf cells.
-// Launch 2 (vote_filter_rotate_kernel): every workgroup folds the partial maxima into M (a maximum: exact, the same
+// Launches 1-4 are the predict step, vp_launch_predict; its kernels live in vote_predict.h:
+// Launch 1 (vp_peak_kernel):   per workgroup the largest finite belief and the count of NaN / +inf cells.
+// Launch 2 (vp_rotate_kernel): every workgroup folds the partial maxima into M (a maximum: exact, the same
 //   bits everywhere); t0 = the k-tap chain over p, exp fused (a source cell's exp is recomputed by each of its <= Tk
 //   readers: the re-reads of the belief are L2 hits, t0 is the only store); sum p (float64) and the count of cells
 //   with mass from each thread's own cell.  t0 lives in belief_out.
-// Launch 3 (vote_filter_rows_kernel):   t1 = the a-tap chain over t0 (each tap a wave-contiguous run of a source row),
+// Launch 3 (vp_rows_kernel):   t1 = the a-tap chain over t0 (each tap a wave-contiguous run of a source row),
 //   into the workspace.
-// Launch 4 (vote_filter_cols_kernel):   t2 = the b-tap chain over t1, into belief_out; per workgroup sum t2 (float64).
+// Launch 4 (vp_cols_kernel):   t2 = the b-tap chain over t1, into belief_out; per workgroup sum t2 (float64).
 // Launch 5 (vote_filter_evidence_kernel): every workgroup folds the partial sums into S; per cell u (float64), folded
 //   into a running (maximum, sum of exp relative to it) pair per thread, then per workgroup.
 // Launch 6 (vote_filter_normalise_kernel): every workgroup folds the pairs into log_z, recomputes u (the same
@@ -34,36 +35,10 @@ constexpr int FL_NT = VP_NT;                // threads = cells of a tile
 constexpr int FL_WAVES = VP_WAVES;
 
 // per-workgroup partials: double [groups][4], int32 [groups][4], float [groups][2]; the predict step's columns first
+constexpr int FL_DS = 4, FL_IS = 4, FL_FS = 2;
 enum { FL_D_SUMP = VP_D_SUMP, FL_D_SUMT2 = VP_D_SUMT2, FL_D_LSE_M = 2, FL_D_LSE_S = 3 };
 enum { FL_I_BAD = VP_I_BAD, FL_I_MASS = VP_I_MASS, FL_I_FIN = 2, FL_I_NAN = 3 };
 enum { FL_F_PEAK = VP_F_PEAK, FL_F_OUTMAX = 1 };
-
-// ---- launches 1-4: the predict step (vote_predict.h)
-__global__ __launch_bounds__(FL_NT) void vote_filter_peak_kernel(const float* __restrict__ belief, int n,
-                                                                 float* __restrict__ fpart, int32_t* __restrict__ ipart) {
-  vp_peak<2, 4>(belief, n, fpart, ipart);
-}
-__global__ __launch_bounds__(FL_NT) void vote_filter_rotate_kernel(const float* __restrict__ belief,
-                                                                   const float* __restrict__ taps_k, int lk, int R, int P,
-                                                                   int Tk, int tiles_per_plane, int tiles,
-                                                                   const float* __restrict__ fpart, float* __restrict__ t0,
-                                                                   double* __restrict__ dpart, int32_t* __restrict__ ipart) {
-  vp_rotate<2, 4, 4>(belief, taps_k, lk, R, P, Tk, tiles_per_plane, tiles, fpart, t0, dpart, ipart);
-}
-__global__ __launch_bounds__(FL_NT) void vote_filter_rows_kernel(const float* __restrict__ t0,
-                                                                 const float* __restrict__ taps_a,
-                                                                 const int32_t* __restrict__ offsets, int Ho, int Wo, int P,
-                                                                 int Ta, int tiles_per_plane, int tiles,
-                                                                 float* __restrict__ t1) {
-  vp_rows<false>(t0, taps_a, offsets, Ho, Wo, P, Ta, tiles_per_plane, tiles, t1);
-}
-__global__ __launch_bounds__(FL_NT) void vote_filter_cols_kernel(const float* __restrict__ t1,
-                                                                 const float* __restrict__ taps_b,
-                                                                 const int32_t* __restrict__ offsets, int Wo, int P, int Tb,
-                                                                 int tiles_per_plane, int tiles, float* __restrict__ t2,
-                                                                 double* __restrict__ dpart) {
-  vp_cols<false, true, 4>(t1, taps_b, offsets, Wo, P, Tb, tiles_per_plane, tiles, t2, dpart);
-}
 
 // The update of one cell, float64: u = scale * vote + log(prior), prior = (1 - eps) t2 / S + eps / n.  NaN for a NaN
 // or +inf vote, -inf for a -inf vote or a prior of 0.  `transported` = (1 - eps) / S is NOT folded into one factor:
@@ -83,8 +58,8 @@ __device__ __forceinline__ FlUpdate fl_update_setup(const double* dpart, int gro
                                                     float eps, int n, double* sh) {
   FlUpdate c;
   c.scale = (double)scale;
-  c.prior = vp_prior_setup(with_belief ? vote_fold_sum<FL_WAVES, 4>(dpart, FL_D_SUMT2, groups, sh) : 0.0, with_belief,
-                           eps, n);
+  c.prior = vp_prior_setup(with_belief ? vote_fold_sum<FL_WAVES, FL_DS>(dpart, FL_D_SUMT2, groups, sh) : 0.0,
+                           with_belief, eps, n);
   return c;
 }
 
@@ -99,19 +74,12 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_evidence_kernel(const float
   double m = -(double)INFINITY, s = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * FL_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FL_NT) {
     const double u = fl_update(c, with_belief ? t2[i] : 0.f, votes[i]);
-    if (fabs(u) < (double)INFINITY) {
-      if (u > m) {
-        s = s * exp(m - u) + 1.0;           // (m = -inf at the first cell: exp gives 0)
-        m = u;
-      } else {
-        s += exp(u - m);
-      }
-    }
+    if (fabs(u) < (double)INFINITY) vote_lse_add(&m, &s, u);
   }
   vote_block_lse<FL_WAVES>(&m, &s, shl);
   if (threadIdx.x == 0) {
-    dpart[(size_t)blockIdx.x * 4 + FL_D_LSE_M] = m;
-    dpart[(size_t)blockIdx.x * 4 + FL_D_LSE_S] = s;
+    dpart[(size_t)blockIdx.x * FL_DS + FL_D_LSE_M] = m;
+    dpart[(size_t)blockIdx.x * FL_DS + FL_D_LSE_S] = s;
   }
 }
 
@@ -127,18 +95,12 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_normalise_kernel(const floa
   __shared__ float shf[FL_WAVES];
   __shared__ int shi[FL_WAVES];
   const FlUpdate c = fl_update_setup(dpart, gridDim.x, with_belief != 0, scale, eps, n, shd);
-  const double log_z = vote_fold_lse<FL_WAVES, 4>(dpart, FL_D_LSE_M, FL_D_LSE_S, gridDim.x, shl);
+  const double log_z = vote_fold_lse<FL_WAVES, FL_DS>(dpart, FL_D_LSE_M, FL_D_LSE_S, gridDim.x, shl);
   float top = -INFINITY;
   int n_fin = 0, n_nan = 0;
   for (int64_t i = (int64_t)blockIdx.x * FL_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * FL_NT) {
     const double u = fl_update(c, with_belief ? belief_out[i] : 0.f, votes[i]);   // (t2 lives in belief_out)
-    float out;
-    if (u != u)
-      out = __int_as_float(0x7fc00000);
-    else if (u == -(double)INFINITY)
-      out = -INFINITY;
-    else
-      out = (float)(u - log_z);
+    const float out = vote_normalised(u, log_z);
     belief_out[i] = out;
     n_fin += vote_finite(out) ? 1 : 0;
     n_nan += out != out ? 1 : 0;
@@ -148,9 +110,9 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_normalise_kernel(const floa
   n_fin = vote_block_sum<FL_WAVES>(n_fin, shi);
   n_nan = vote_block_sum<FL_WAVES>(n_nan, shi);
   if (threadIdx.x == 0) {
-    fpart[(size_t)blockIdx.x * 2 + FL_F_OUTMAX] = top;
-    ipart[(size_t)blockIdx.x * 4 + FL_I_FIN] = n_fin;
-    ipart[(size_t)blockIdx.x * 4 + FL_I_NAN] = n_nan;
+    fpart[(size_t)blockIdx.x * FL_FS + FL_F_OUTMAX] = top;
+    ipart[(size_t)blockIdx.x * FL_IS + FL_I_FIN] = n_fin;
+    ipart[(size_t)blockIdx.x * FL_IS + FL_I_NAN] = n_nan;
     if (blockIdx.x == 0) stats[0] = (float)log_z;
   }
 }
@@ -164,17 +126,17 @@ __global__ __launch_bounds__(FL_NT) void vote_filter_finish_kernel(int groups, i
   __shared__ double shd[FL_WAVES];
   __shared__ float shf[FL_WAVES];
   __shared__ int shi[FL_WAVES];
-  const int n_fin = vote_fold_sum<FL_WAVES, 4>(ipart, FL_I_FIN, groups, shi);
-  const int n_nan = vote_fold_sum<FL_WAVES, 4>(ipart, FL_I_NAN, groups, shi);
-  const float top = vote_fold_max<FL_WAVES, 2>(fpart, FL_F_OUTMAX, groups, shf);
+  const int n_fin = vote_fold_sum<FL_WAVES, FL_IS>(ipart, FL_I_FIN, groups, shi);
+  const int n_nan = vote_fold_sum<FL_WAVES, FL_IS>(ipart, FL_I_NAN, groups, shi);
+  const float top = vote_fold_max<FL_WAVES, FL_FS>(fpart, FL_F_OUTMAX, groups, shf);
   int n_bad = 0, n_mass = 0;
   float M = -INFINITY, kept = 1.f;
   if (with_belief) {
-    n_bad = vote_fold_sum<FL_WAVES, 4>(ipart, FL_I_BAD, groups, shi);
-    n_mass = vote_fold_sum<FL_WAVES, 4>(ipart, FL_I_MASS, groups, shi);
-    M = vote_fold_max<FL_WAVES, 2>(fpart, FL_F_PEAK, groups, shf);
-    const double sum_p = vote_fold_sum<FL_WAVES, 4>(dpart, FL_D_SUMP, groups, shd);
-    const double S = vote_fold_sum<FL_WAVES, 4>(dpart, FL_D_SUMT2, groups, shd);
+    n_bad = vote_fold_sum<FL_WAVES, FL_IS>(ipart, FL_I_BAD, groups, shi);
+    n_mass = vote_fold_sum<FL_WAVES, FL_IS>(ipart, FL_I_MASS, groups, shi);
+    M = vote_fold_max<FL_WAVES, FL_FS>(fpart, FL_F_PEAK, groups, shf);
+    const double sum_p = vote_fold_sum<FL_WAVES, FL_DS>(dpart, FL_D_SUMP, groups, shd);
+    const double S = vote_fold_sum<FL_WAVES, FL_DS>(dpart, FL_D_SUMT2, groups, shd);
     kept = sum_p > 0.0 ? (float)(S / sum_p) : 0.f;
   }
   if (threadIdx.x == 0) {
@@ -199,8 +161,8 @@ struct FlWorkspace {
 
 FlWorkspace fl_workspace(const VpPlan& plan, void* workspace) {
   VoteLayout l{workspace};
-  return {l.take<float>(plan.n), l.take<double>((size_t)plan.groups * 4), l.take<int32_t>((size_t)plan.groups * 4),
-          l.take<float>((size_t)plan.groups * 2), l.bytes};
+  return {l.take<float>(plan.n), l.take<double>((size_t)plan.groups * FL_DS),
+          l.take<int32_t>((size_t)plan.groups * FL_IS), l.take<float>((size_t)plan.groups * FL_FS), l.bytes};
 }
 
 }  // namespace
@@ -229,17 +191,9 @@ extern "C" int snap_vote_filter_f32(const float* belief, const float* votes, con
   const dim3 grid(plan.groups), block(FL_NT);
   const int with_belief = belief != nullptr ? 1 : 0;
   if (with_belief) {
-    hipLaunchKernelGGL(vote_filter_peak_kernel, grid, block, 0, s, belief, plan.n, w.fpart, w.ipart);
-    SNAP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(vote_filter_rotate_kernel, grid, block, 0, s, belief, taps_k, lk, R, plan.P, Tk,
-                       plan.tiles_per_plane, plan.tiles, w.fpart, belief_out, w.dpart, w.ipart);
-    SNAP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(vote_filter_rows_kernel, grid, block, 0, s, belief_out, taps_a, offsets, Ho, Wo, plan.P, Ta,
-                       plan.tiles_per_plane, plan.tiles, w.t1);
-    SNAP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(vote_filter_cols_kernel, grid, block, 0, s, w.t1, taps_b, offsets, Wo, plan.P, Tb,
-                       plan.tiles_per_plane, plan.tiles, belief_out, w.dpart);
-    SNAP_CHECK_LAUNCH();
+    const VpTaps taps = {taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb};
+    const VpParts<FL_FS, FL_DS, FL_IS> part = {w.fpart, w.dpart, w.ipart};
+    VP_CHECK(vp_launch_predict(plan, taps, belief, belief_out, w.t1, belief_out, part, s));   // t0, t1, t2
   }
   hipLaunchKernelGGL(vote_filter_evidence_kernel, grid, block, 0, s, belief_out, votes, plan.n, with_belief, scale,
                      uniform_mix, w.dpart);

@@ -7,7 +7,7 @@
 // marginals of the stay branch and the two masses, never the joint.
 // PREDICT, the filter's own code (vote_predict.h): M, the masses p, t0, t1, t2, S = sum t2, sum p and the prior: the
 // filter's bits.  RATIO, the smoother's own code (vote_ratio.h): G, q = fl32(exp(lg - G)), Q = sum q: the smoother's
-// bits.  ADJOINT, vote_predict.h's bodies with ADJ (the smoother's first two gathers; its c1 is c0 here and its c0 is c1:
+// bits.  ADJOINT, vote_predict.h's kernels with ADJ (the smoother's first two gathers; its c1 is c0 here and its c0 is c1:
 // the names below count the passes):
 //   c0[r, a, b] = sum_tb taps_b[r, tb] q [r, a, b - lb[r] - tb];
 //   c1[r, a, b] = sum_ta taps_a[r, ta] c0[r, a - la[r] - ta, b];
@@ -35,9 +35,11 @@
 // the slices in index order through 2 KiB of LDS; hist_k first (it gives the total), then hist_a and hist_b row by
 // row, scaled as they are written.  No atomics, no inter-workgroup hand-off inside a launch: every order is fixed by
 // (R, Ho, Wo, Tk, Ta, Tb) alone.
-// Launches: 1-4 the filter's (t0 -> A, t1 -> B, t2 -> C); 5-6 the smoother's ratio (q -> D); 7 Hb (reads q, t1);
-// 8 c0 = adjoint columns of q -> C; 9 Ha (reads c0, t0); 10 c1 = adjoint rows of c0 -> B; 11 Hk (reads c1, belief);
-// 12 finish.  A-D are the workspace's four volumes.
+// Launches: 1-4 the filter's (vp_launch_predict, kernels in vote_predict.h: t0 -> A, t1 -> B, t2 -> C); 5-6 the
+// smoother's ratio (vr_launch_ratio, kernels in vote_ratio.h: q -> D); 7 Hb (vote_pairs_hist_b_kernel; reads q, t1);
+// 8 c0 = adjoint columns of q -> C (vp_launch_cols<true>); 9 Ha (vote_pairs_hist_a_kernel; reads c0, t0); 10 c1 = adjoint
+// rows of c0 -> B (vp_launch_rows<true>); 11 Hk (vote_pairs_hist_k_kernel; reads c1, belief); 12 finish
+// (vote_pairs_finish_kernel).  A-D are the workspace's four volumes.
 // HBM traffic (n cells of 4 bytes): reads belief 3 (+ L2 re-reads in k, twice), next 2, t0 2, t1 2, t2 2, q 2, c0 2,
 // c1 1; writes t0, t1, t2, q, c0, c1: 22 n cells, the smoother's figure.
 #include "vote_ratio.h"
@@ -49,46 +51,6 @@ constexpr int PR_WAVES = VP_WAVES;
 
 // per-workgroup partials of the predict / ratio launches: double [groups][4], int32 [groups][4], float [groups][1]
 constexpr int PR_DS = 4, PR_IS = 4, PR_FS = 1;
-
-// ---- launches 1-4, 8, 10: the predict step and its adjoint (vote_predict.h)
-__global__ __launch_bounds__(PR_NT) void vote_pairs_peak_kernel(const float* __restrict__ belief, int n,
-                                                                float* __restrict__ fpart, int32_t* __restrict__ ipart) {
-  vp_peak<PR_FS, PR_IS>(belief, n, fpart, ipart);
-}
-__global__ __launch_bounds__(PR_NT) void vote_pairs_rotate_kernel(const float* __restrict__ belief,
-                                                                  const float* __restrict__ taps_k, int lk, int R, int P,
-                                                                  int Tk, int tiles_per_plane, int tiles,
-                                                                  const float* __restrict__ fpart, float* __restrict__ t0,
-                                                                  double* __restrict__ dpart, int32_t* __restrict__ ipart) {
-  vp_rotate<PR_FS, PR_DS, PR_IS>(belief, taps_k, lk, R, P, Tk, tiles_per_plane, tiles, fpart, t0, dpart, ipart);
-}
-template <bool ADJ>
-__global__ __launch_bounds__(PR_NT) void vote_pairs_rows_kernel(const float* __restrict__ src,
-                                                                const float* __restrict__ taps_a,
-                                                                const int32_t* __restrict__ offsets, int Ho, int Wo, int P,
-                                                                int Ta, int tiles_per_plane, int tiles,
-                                                                float* __restrict__ dst) {
-  vp_rows<ADJ>(src, taps_a, offsets, Ho, Wo, P, Ta, tiles_per_plane, tiles, dst);
-}
-template <bool ADJ>
-__global__ __launch_bounds__(PR_NT) void vote_pairs_cols_kernel(const float* __restrict__ src,
-                                                                const float* __restrict__ taps_b,
-                                                                const int32_t* __restrict__ offsets, int Wo, int P, int Tb,
-                                                                int tiles_per_plane, int tiles, float* __restrict__ dst,
-                                                                double* __restrict__ dpart) {
-  vp_cols<ADJ, !ADJ, PR_DS>(src, taps_b, offsets, Wo, P, Tb, tiles_per_plane, tiles, dst, dpart);
-}
-// ---- launches 5 and 6: the ratio step (vote_ratio.h)
-__global__ __launch_bounds__(PR_NT) void vote_pairs_ratio_kernel(const float* __restrict__ t2,
-                                                                 const float* __restrict__ next, int n, float eps,
-                                                                 double* __restrict__ dpart, int32_t* __restrict__ ipart) {
-  vr_max<PR_DS, PR_IS>(t2, next, n, eps, dpart, ipart);
-}
-__global__ __launch_bounds__(PR_NT) void vote_pairs_mass_kernel(const float* __restrict__ t2,
-                                                                const float* __restrict__ next, int n, float eps,
-                                                                float* __restrict__ q, double* __restrict__ dpart) {
-  vr_mass<PR_DS>(t2, next, n, eps, q, dpart);
-}
 
 // The workgroup's accumulators -> its partial row [T]: per tap a wave butterfly, the four waves pairwise.
 template <int MAXT>
@@ -169,7 +131,7 @@ __global__ __launch_bounds__(PR_NT) void vote_pairs_hist_a_kernel(const float* _
 }
 
 // ---- launch 11: Hk[tk] = sum_{r, a, b} (taps_k[tk] * p[(r + lk + tk) mod R, a, b]) * c1[r, a, b], per workgroup; the
-// masses are vp_mass of the belief against the fold of the peak launch's maxima, as vp_rotate forms them
+// masses are vp_mass of the belief against the fold of the peak launch's maxima, as vp_rotate_kernel forms them
 __global__ __launch_bounds__(PR_NT) void vote_pairs_hist_k_kernel(const float* __restrict__ c1,
                                                                   const float* __restrict__ belief,
                                                                   const float* __restrict__ taps_k, int lk, int R, int P,
@@ -324,35 +286,20 @@ extern "C" int snap_vote_pairs_f32(const float* belief, const float* next, const
     return SNAP_ERR_WORKSPACE;
   const PrWorkspace w = pr_workspace(plan, R, Tk, Ta, Tb, workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(plan.groups), rgrid(R * plan.gpr), block(PR_NT);
-  const int P = plan.P, tpp = plan.tiles_per_plane, tiles = plan.tiles, gpr = plan.gpr;
-  hipLaunchKernelGGL(vote_pairs_peak_kernel, grid, block, 0, s, belief, plan.n, w.fpart, w.ipart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_pairs_rotate_kernel, grid, block, 0, s, belief, taps_k, lk, R, P, Tk, tpp, tiles, w.fpart, w.A,
-                     w.dpart, w.ipart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_pairs_rows_kernel<false>, grid, block, 0, s, w.A, taps_a, offsets, Ho, Wo, P, Ta, tpp, tiles,
-                     w.B);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_pairs_cols_kernel<false>, grid, block, 0, s, w.B, taps_b, offsets, Wo, P, Tb, tpp, tiles, w.C,
-                     w.dpart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_pairs_ratio_kernel, grid, block, 0, s, w.C, next, plan.n, uniform_mix, w.dpart, w.ipart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_pairs_mass_kernel, grid, block, 0, s, w.C, next, plan.n, uniform_mix, w.D, w.dpart);
-  SNAP_CHECK_LAUNCH();
+  const dim3 rgrid(R * plan.gpr), block(PR_NT);
+  const int P = plan.P, tpp = plan.tiles_per_plane, gpr = plan.gpr;
+  const VpTaps taps = {taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb};
+  const VpParts<PR_FS, PR_DS, PR_IS> part = {w.fpart, w.dpart, w.ipart};
+  VP_CHECK(vp_launch_predict(plan, taps, belief, w.A, w.B, w.C, part, s));   // t0, t1, t2
+  VP_CHECK(vr_launch_ratio(plan, w.C, next, uniform_mix, w.D, part, s));     // q
   hipLaunchKernelGGL(vote_pairs_hist_b_kernel, rgrid, block, 0, s, w.D, w.B, taps_b, offsets, Wo, P, Tb, tpp, gpr,
                      w.part_b);
   SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_pairs_cols_kernel<true>, grid, block, 0, s, w.D, taps_b, offsets, Wo, P, Tb, tpp, tiles, w.C,
-                     w.dpart);
-  SNAP_CHECK_LAUNCH();
+  VP_CHECK(vp_launch_cols<true>(plan, taps, w.D, w.C, part, s));               // c0
   hipLaunchKernelGGL(vote_pairs_hist_a_kernel, rgrid, block, 0, s, w.C, w.A, taps_a, offsets, Ho, Wo, P, Ta, tpp, gpr,
                      w.part_a);
   SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_pairs_rows_kernel<true>, grid, block, 0, s, w.C, taps_a, offsets, Ho, Wo, P, Ta, tpp, tiles,
-                     w.B);
-  SNAP_CHECK_LAUNCH();
+  VP_CHECK(vp_launch_rows<true>(plan, taps, w.C, w.B, s));                     // c1
   hipLaunchKernelGGL(vote_pairs_hist_k_kernel, rgrid, block, 0, s, w.B, belief, taps_k, lk, R, P, Tk, tpp, gpr, w.fpart,
                      plan.groups, w.part_k);
   SNAP_CHECK_LAUNCH();

@@ -1,8 +1,9 @@
-// The RATIO step of the vote-volume smoother (snap_vote_smooth_f32) as device pieces, shared by vote_smooth.hip and
-// vote_pairs.hip: the pairwise posterior of a step is built on the very q = gamma_{t+1} / prior the smoother carries
-// back, so lg, G and q have to be the smoother's bits.  They are, because both files wrap the two bodies below (and
-// -ffp-contract=off is in force).  Each body is the whole of a kernel, on the predict step's launch shape
-// (vote_predict.h): min(tiles, VP_MAX_GROUPS) workgroups of VP_NT threads striding over the n cells.
+// The RATIO step of the vote-volume smoother (snap_vote_smooth_f32): its two kernels and the one function that launches
+// them, shared by vote_smooth.hip and vote_pairs.hip: the pairwise posterior of a step is built on the very
+// q = gamma_{t+1} / prior the smoother carries back, so lg, G and q have to be the smoother's bits.  They are, because
+// both files run the two kernels below through vr_launch_ratio (and -ffp-contract=off is in force), on the predict
+// step's launch shape and with its linkage (vote_predict.h): min(tiles, VP_MAX_GROUPS) workgroups of VP_NT threads
+// striding over the n cells.
 //
 // Float64 per cell: a cell has ratio mass iff next is finite and prior > 0; then lg = next - log(prior); G = max lg;
 // q = fl32(exp(lg - G)) iff fl32(lg - G) >= VP_CUT, else 0; Q = sum q.
@@ -95,5 +96,36 @@ __device__ __forceinline__ void vr_mass(const float* __restrict__ t2, const floa
   sum = vote_block_sum<VP_WAVES>(sum, shd);
   if (threadIdx.x == 0) dpart[(size_t)blockIdx.x * DS + VR_D_Q] = sum;
 }
+
+namespace {   // (LINKAGE, vote_predict.h)
+
+// The kernels: each is one body above.
+template <int DS, int IS>
+__global__ __launch_bounds__(VP_NT) void vr_max_kernel(const float* __restrict__ t2, const float* __restrict__ next,
+                                                       int n, float eps, double* __restrict__ dpart,
+                                                       int32_t* __restrict__ ipart) {
+  vr_max<DS, IS>(t2, next, n, eps, dpart, ipart);
+}
+template <int DS>
+__global__ __launch_bounds__(VP_NT) void vr_mass_kernel(const float* __restrict__ t2, const float* __restrict__ next,
+                                                        int n, float eps, float* __restrict__ q,
+                                                        double* __restrict__ dpart) {
+  vr_mass<DS>(t2, next, n, eps, q, dpart);
+}
+
+// Launches 5-6 of the smoother and of the tap posteriors, in this order: max (t2, next -> G), mass (-> q, Q).  q is a
+// volume of its own.  Returns SNAP_OK or SNAP_ERR_LAUNCH.
+template <int FS, int DS, int IS>
+int vr_launch_ratio(const VpPlan& plan, const float* t2, const float* next, float eps, float* q,
+                    const VpParts<FS, DS, IS>& part, hipStream_t s) {
+  const dim3 grid(plan.groups), block(VP_NT);
+  hipLaunchKernelGGL((vr_max_kernel<DS, IS>), grid, block, 0, s, t2, next, plan.n, eps, part.d, part.i);
+  SNAP_CHECK_LAUNCH();
+  hipLaunchKernelGGL((vr_mass_kernel<DS>), grid, block, 0, s, t2, next, plan.n, eps, q, part.d);
+  SNAP_CHECK_LAUNCH();
+  return SNAP_OK;
+}
+
+}  // namespace
 
 #endif  // SNAP_CSRC_VOTE_RATIO_H_

@@ -12,7 +12,7 @@
 //
 // snap_vote_sample_f32, four launches:
 // Launch 1 (vote_sample_peak_kernel):  per workgroup the largest finite scaled vote and the count of NaN / +inf cells
-//   (vp_peak with the product fused), min(tiles, 2048) workgroups of 256 threads.
+//   (vp_peak_kernel with the product fused), min(tiles, 2048) workgroups of 256 threads.
 // Launch 2 (vote_sample_rows_kernel):  every workgroup folds the partial maxima into M; one wave per (r, a) row: a chain
 //   per lane over b = lane, lane + 64, .., then the xor butterfly -> the row's sum of p (float64) and cells with mass.
 // Launch 3 (vote_sample_fold_kernel, one workgroup): one wave per plane, the same chain and butterfly over its rows ->
@@ -20,8 +20,8 @@
 // Launch 4 (vote_sample_draw_kernel):  one wave per draw: the uniforms (Philox or given), the descent, log_prob.
 // One read of the volume for M, one for the row sums; a draw reads R plane sums, Ho row sums and Wo cells.
 //
-// snap_vote_sample_back_f32, eight launches: the filter's predict step from the vote_predict.h bodies on the filter's
-// grid (peak, rotation, rows, columns with SUM: M, sum p and S are the filter's bits; t0 and t2 live in one volume of
+// snap_vote_sample_back_f32, eight launches: the filter's predict step (vp_launch_predict: the four kernels of
+// vote_predict.h on the filter's grid, so M, sum p and S are the filter's bits; t0 and t2 live in one volume of
 // the workspace, t1 in another); launches 2 and 3 above on the belief (scale 1: the product is exact); then
 // (vote_sample_chain_kernel) one 256-thread workgroup per chain: the window's (tk, ta) row sums, a chain over tb each,
 // into LDS (<= 512 float64), then wave 0 alone: W by vs_pick's scan, the branch, and either the descent above on the
@@ -143,7 +143,7 @@ __device__ __forceinline__ void vs_uniforms(const double* __restrict__ uniforms,
   }
 }
 
-// ---- launch 1 of snap_vote_sample_f32: vp_peak on fl32(scale * votes)
+// ---- launch 1 of snap_vote_sample_f32: vp_peak_kernel on fl32(scale * votes)
 __global__ __launch_bounds__(VS_NT) void vote_sample_peak_kernel(const float* __restrict__ votes, float scale, int n,
                                                                  float* __restrict__ fpart, int32_t* __restrict__ ipart) {
   __shared__ float shf[VS_WAVES];
@@ -163,35 +163,6 @@ __global__ __launch_bounds__(VS_NT) void vote_sample_peak_kernel(const float* __
     fpart[(size_t)blockIdx.x * VS_FS + VP_F_PEAK] = m;
     ipart[(size_t)blockIdx.x * VS_IS_DRAW + VP_I_BAD] = bad;
   }
-}
-
-// ---- launches 1-4 of snap_vote_sample_back_f32: the filter's predict step (vote_predict.h)
-__global__ __launch_bounds__(VS_NT) void vote_sample_back_peak_kernel(const float* __restrict__ belief, int n,
-                                                                      float* __restrict__ fpart,
-                                                                      int32_t* __restrict__ ipart) {
-  vp_peak<VS_FS, VS_IS_BACK>(belief, n, fpart, ipart);
-}
-__global__ __launch_bounds__(VS_NT) void vote_sample_back_rotate_kernel(const float* __restrict__ belief,
-                                                                        const float* __restrict__ taps_k, int lk, int R,
-                                                                        int P, int Tk, int tiles_per_plane, int tiles,
-                                                                        const float* __restrict__ fpart,
-                                                                        float* __restrict__ t0, double* __restrict__ dpart,
-                                                                        int32_t* __restrict__ ipart) {
-  vp_rotate<VS_FS, VS_DS, VS_IS_BACK>(belief, taps_k, lk, R, P, Tk, tiles_per_plane, tiles, fpart, t0, dpart, ipart);
-}
-__global__ __launch_bounds__(VS_NT) void vote_sample_back_rows_kernel(const float* __restrict__ t0,
-                                                                      const float* __restrict__ taps_a,
-                                                                      const int32_t* __restrict__ offsets, int Ho, int Wo,
-                                                                      int P, int Ta, int tiles_per_plane, int tiles,
-                                                                      float* __restrict__ t1) {
-  vp_rows<false>(t0, taps_a, offsets, Ho, Wo, P, Ta, tiles_per_plane, tiles, t1);
-}
-__global__ __launch_bounds__(VS_NT) void vote_sample_back_cols_kernel(const float* __restrict__ t1,
-                                                                      const float* __restrict__ taps_b,
-                                                                      const int32_t* __restrict__ offsets, int Wo, int P,
-                                                                      int Tb, int tiles_per_plane, int tiles,
-                                                                      float* __restrict__ t2, double* __restrict__ dpart) {
-  vp_cols<false, true, VS_DS>(t1, taps_b, offsets, Wo, P, Tb, tiles_per_plane, tiles, t2, dpart);
 }
 
 // ---- the row sums of p, one wave per (r, a) row; rowcnt (the cells with mass) may be NULL
@@ -504,19 +475,11 @@ extern "C" int snap_vote_sample_back_f32(const float* belief, const float* taps_
     return SNAP_ERR_WORKSPACE;
   const VsWorkspace w = vs_workspace(plan, R, Ho, true, workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(plan.groups), block(VS_NT);
+  const dim3 block(VS_NT);
   const int64_t rows = (int64_t)R * Ho;
-  hipLaunchKernelGGL(vote_sample_back_peak_kernel, grid, block, 0, s, belief, plan.n, w.fpart, w.ipart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_sample_back_rotate_kernel, grid, block, 0, s, belief, taps_k, lk, R, plan.P, Tk,
-                     plan.tiles_per_plane, plan.tiles, w.fpart, w.t02, w.dpart, w.ipart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_sample_back_rows_kernel, grid, block, 0, s, w.t02, taps_a, offsets, Ho, Wo, plan.P, Ta,
-                     plan.tiles_per_plane, plan.tiles, w.t1);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_sample_back_cols_kernel, grid, block, 0, s, w.t1, taps_b, offsets, Wo, plan.P, Tb,
-                     plan.tiles_per_plane, plan.tiles, w.t02, w.dpart);
-  SNAP_CHECK_LAUNCH();
+  const VpTaps taps = {taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb};
+  const VpParts<VS_FS, VS_DS, VS_IS_BACK> part = {w.fpart, w.dpart, w.ipart};
+  VP_CHECK(vp_launch_predict(plan, taps, belief, w.t02, w.t1, w.t02, part, s));   // t0, t1, t2
   hipLaunchKernelGGL(vote_sample_rows_kernel, dim3((unsigned)snap_cdiv(rows, VS_WAVES)), block, 0, s, belief, 1.f, rows,
                      Wo, w.fpart, plan.groups, w.rowsum, (int32_t*)nullptr);
   SNAP_CHECK_LAUNCH();

@@ -17,15 +17,16 @@
 //
 // A tile is one rotation and 256 consecutive pixels p = a * Wo + b, one cell per thread; every launch has
 // min(tiles, 2048) workgroups of 256 threads striding over the tiles (the tap rows of a tile are uniform: scalar loads).
-// Launches 1-4 (vote_smooth_peak / rotate / rows / cols_kernel): the filter's launches 1-4.  t0 and t2 live in
-//   `smoothed`, t1 in the workspace.
-// Launch 5 (vote_smooth_ratio_kernel):   every workgroup folds the partial sums into S; per cell lg; per workgroup the
+// Launches 1-4 (vp_launch_predict: vp_peak / rotate / rows / cols_kernel of vote_predict.h): the filter's launches
+//   1-4.  t0 and t2 live in `smoothed`, t1 in the workspace.
+// Launches 5-6 are vr_launch_ratio; its kernels live in vote_ratio.h:
+// Launch 5 (vr_max_kernel):   every workgroup folds the partial sums into S; per cell lg; per workgroup the
 //   largest lg (float64), the count of NaN / +inf cells of `next` and of cells with ratio mass.
-// Launch 6 (vote_smooth_mass_kernel):    every workgroup folds the maxima into G (a maximum: exact), recomputes lg (the
+// Launch 6 (vr_mass_kernel):  every workgroup folds the maxima into G (a maximum: exact), recomputes lg (the
 //   same expression: the same bits) and writes q into the workspace, ONCE: the float64 log and exp sit on this pass, not
 //   on the taps; per workgroup sum q (float64).
-// Launch 7 (vote_smooth_cols_kernel):    c1 = the adjoint b chain over q, into `smoothed`.
-// Launch 8 (vote_smooth_rows_kernel):    c0 = the adjoint a chain over c1, into the workspace.
+// Launch 7 (vp_launch_cols<true>: vp_cols_kernel with ADJ): c1 = the adjoint b chain over q, into `smoothed`.
+// Launch 8 (vp_launch_rows<true>: vp_rows_kernel with ADJ): c0 = the adjoint a chain over c1, into the workspace.
 // Launch 9 (vote_smooth_gather_kernel):  every workgroup folds sum p, S, Q and G; u = the adjoint k chain over c0 (the
 //   re-reads of c0 by a cell's <= Tk readers are L2 hits), into `smoothed`; per cell w (float64), folded into a running
 //   (maximum, sum of exp relative to it) pair per thread, then per workgroup.
@@ -50,48 +51,6 @@ constexpr int SM_DS = 6, SM_IS = 5, SM_FS = 2;
 enum { SM_D_SUMP = VP_D_SUMP, SM_D_SUMT2 = VP_D_SUMT2, SM_D_G = VR_D_G, SM_D_Q = VR_D_Q, SM_D_LSE_M = 4, SM_D_LSE_S = 5 };
 enum { SM_I_BAD = VP_I_BAD, SM_I_MASS = VP_I_MASS, SM_I_BADNEXT = VR_I_BADNEXT, SM_I_RATIO = VR_I_RATIO, SM_I_FIN = 4 };
 enum { SM_F_PEAK = VP_F_PEAK, SM_F_OUTMAX = 1 };
-
-// ---- launches 1-4: the predict step (vote_predict.h)
-__global__ __launch_bounds__(SM_NT) void vote_smooth_peak_kernel(const float* __restrict__ belief, int n,
-                                                                 float* __restrict__ fpart, int32_t* __restrict__ ipart) {
-  vp_peak<SM_FS, SM_IS>(belief, n, fpart, ipart);
-}
-__global__ __launch_bounds__(SM_NT) void vote_smooth_rotate_kernel(const float* __restrict__ belief,
-                                                                   const float* __restrict__ taps_k, int lk, int R, int P,
-                                                                   int Tk, int tiles_per_plane, int tiles,
-                                                                   const float* __restrict__ fpart, float* __restrict__ t0,
-                                                                   double* __restrict__ dpart, int32_t* __restrict__ ipart) {
-  vp_rotate<SM_FS, SM_DS, SM_IS>(belief, taps_k, lk, R, P, Tk, tiles_per_plane, tiles, fpart, t0, dpart, ipart);
-}
-// ---- launches 3 and 8 (ADJ): the a chain;  launches 4 and 7 (ADJ): the b chain, forward with sum t2
-template <bool ADJ>
-__global__ __launch_bounds__(SM_NT) void vote_smooth_rows_kernel(const float* __restrict__ src,
-                                                                 const float* __restrict__ taps_a,
-                                                                 const int32_t* __restrict__ offsets, int Ho, int Wo, int P,
-                                                                 int Ta, int tiles_per_plane, int tiles,
-                                                                 float* __restrict__ dst) {
-  vp_rows<ADJ>(src, taps_a, offsets, Ho, Wo, P, Ta, tiles_per_plane, tiles, dst);
-}
-template <bool ADJ>
-__global__ __launch_bounds__(SM_NT) void vote_smooth_cols_kernel(const float* __restrict__ src,
-                                                                 const float* __restrict__ taps_b,
-                                                                 const int32_t* __restrict__ offsets, int Wo, int P, int Tb,
-                                                                 int tiles_per_plane, int tiles, float* __restrict__ dst,
-                                                                 double* __restrict__ dpart) {
-  vp_cols<ADJ, !ADJ, SM_DS>(src, taps_b, offsets, Wo, P, Tb, tiles_per_plane, tiles, dst, dpart);
-}
-
-// ---- launches 5 and 6: the ratio step (vote_ratio.h)
-__global__ __launch_bounds__(SM_NT) void vote_smooth_ratio_kernel(const float* __restrict__ t2,
-                                                                  const float* __restrict__ next, int n, float eps,
-                                                                  double* __restrict__ dpart, int32_t* __restrict__ ipart) {
-  vr_max<SM_DS, SM_IS>(t2, next, n, eps, dpart, ipart);
-}
-__global__ __launch_bounds__(SM_NT) void vote_smooth_mass_kernel(const float* __restrict__ t2,
-                                                                 const float* __restrict__ next, int n, float eps,
-                                                                 float* __restrict__ q, double* __restrict__ dpart) {
-  vr_mass<SM_DS>(t2, next, n, eps, q, dpart);
-}
 
 // The combination of one cell, float64: w = (belief + G) + log(h), h = ((1 - eps) (sum p / S)) u + (eps / n) Q.  NaN
 // for a NaN or +inf belief, -inf for a -inf belief or h == 0 (then G, which may be -inf, is not read).
@@ -166,13 +125,7 @@ __global__ __launch_bounds__(SM_NT) void vote_smooth_normalise_kernel(const floa
   int n_fin = 0;
   for (int64_t i = (int64_t)blockIdx.x * SM_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * SM_NT) {
     const double w = sm_combine(c, smoothed[i], belief[i]);   // (u lives in smoothed)
-    float out;
-    if (w != w)
-      out = __int_as_float(0x7fc00000);
-    else if (w == -(double)INFINITY)
-      out = -INFINITY;
-    else
-      out = (float)(w - log_norm);
+    const float out = vote_normalised(w, log_norm);
     smoothed[i] = out;
     n_fin += vote_finite(out) ? 1 : 0;
     top = fmaxf(top, out);                  // (fmaxf drops a NaN)
@@ -251,31 +204,14 @@ extern "C" int snap_vote_smooth_f32(const float* belief, const float* next, cons
   const SmWorkspace w = sm_workspace(plan, workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(plan.groups), block(SM_NT);
-  const int P = plan.P, tpp = plan.tiles_per_plane, tiles = plan.tiles;
-  hipLaunchKernelGGL(vote_smooth_peak_kernel, grid, block, 0, s, belief, plan.n, w.fpart, w.ipart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_smooth_rotate_kernel, grid, block, 0, s, belief, taps_k, lk, R, P, Tk, tpp, tiles, w.fpart,
-                     smoothed, w.dpart, w.ipart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_smooth_rows_kernel<false>, grid, block, 0, s, smoothed, taps_a, offsets, Ho, Wo, P, Ta, tpp,
-                     tiles, w.vol);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_smooth_cols_kernel<false>, grid, block, 0, s, w.vol, taps_b, offsets, Wo, P, Tb, tpp, tiles,
-                     smoothed, w.dpart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_smooth_ratio_kernel, grid, block, 0, s, smoothed, next, plan.n, uniform_mix, w.dpart,
-                     w.ipart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_smooth_mass_kernel, grid, block, 0, s, smoothed, next, plan.n, uniform_mix, w.vol, w.dpart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_smooth_cols_kernel<true>, grid, block, 0, s, w.vol, taps_b, offsets, Wo, P, Tb, tpp, tiles,
-                     smoothed, w.dpart);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_smooth_rows_kernel<true>, grid, block, 0, s, smoothed, taps_a, offsets, Ho, Wo, P, Ta, tpp,
-                     tiles, w.vol);
-  SNAP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(vote_smooth_gather_kernel, grid, block, 0, s, w.vol, belief, taps_k, lk, R, P, Tk, tpp, tiles,
-                     uniform_mix, plan.n, smoothed, w.dpart);
+  const VpTaps taps = {taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb};
+  const VpParts<SM_FS, SM_DS, SM_IS> part = {w.fpart, w.dpart, w.ipart};
+  VP_CHECK(vp_launch_predict(plan, taps, belief, smoothed, w.vol, smoothed, part, s));   // t0, t1, t2
+  VP_CHECK(vr_launch_ratio(plan, smoothed, next, uniform_mix, w.vol, part, s));          // q
+  VP_CHECK(vp_launch_cols<true>(plan, taps, w.vol, smoothed, part, s));                    // c1
+  VP_CHECK(vp_launch_rows<true>(plan, taps, smoothed, w.vol, s));                          // c0
+  hipLaunchKernelGGL(vote_smooth_gather_kernel, grid, block, 0, s, w.vol, belief, taps_k, lk, R, plan.P, Tk,
+                     plan.tiles_per_plane, plan.tiles, uniform_mix, plan.n, smoothed, w.dpart);
   SNAP_CHECK_LAUNCH();
   hipLaunchKernelGGL(vote_smooth_normalise_kernel, grid, block, 0, s, belief, plan.n, uniform_mix, w.dpart, smoothed,
                      w.fpart, w.ipart, stats);

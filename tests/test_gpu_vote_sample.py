@@ -186,6 +186,37 @@ def test_backward_step_branch_and_predecessor(name):
     assert (jumped[inside] == 1).all()
 
 
+def test_predict_statistics_are_the_filters_bits_in_all_four_operators():
+  """``vote_filter``, ``vote_smooth``, ``vote_pairs`` and ``vote_sample_back`` run one predict step (vote_predict.h) on
+  the same belief and taps: ``mass_kept`` has the same f32 bits from all four (pairs' float64 holds that f32) and the
+  peak the same bits from the filter and the sampler.  [5, 7, 9]: a ragged last tile of 63 cells, more rotations than
+  waves; offsets that push taps off the volume on every side, so some mass is lost."""
+  rng = np.random.default_rng(41)
+  R, Ho, Wo = 5, 7, 9
+  belief = (rng.standard_normal((R, Ho, Wo)) * 3.0).astype(np.float32)
+  belief[rng.random((R, Ho, Wo)) < 0.1] = -np.inf
+  votes = rng.standard_normal((R, Ho, Wo)).astype(np.float32)
+  norm = lambda t: (t / t.sum(-1, keepdims=True)).astype(np.float32)
+  taps = (norm(rng.random(3) + 0.1), 4, norm(rng.random((R, 2)) + 0.1), norm(rng.random((R, 4)) + 0.1),
+          np.array([[-3, 2], [2, -5], [0, 7], [6, -1], [-1, 0]], np.int32))
+  eps = 1e-3
+  b, t = _dev(belief), _dev_taps(taps)
+  nxt = _dev(np.arange(0, R * Ho * Wo, 7, dtype=np.int32))
+  with guarded.scope():
+    filtered, f_stats, _ = ops.vote_filter(b, _dev(votes), t, 1.0, eps)
+    s_stats = ops.vote_smooth(b, filtered, t, eps)[1]
+    p_stats = ops.vote_pairs(b, filtered, t, eps)[3]
+    b_stats = ops.vote_sample_back(b, nxt, t, eps, 3)[2]
+    f_stats, s_stats, p_stats, b_stats = (x.cpu().numpy() for x in (f_stats, s_stats, p_stats, b_stats))
+  bits = lambda v: int(np.float32(v).view(np.int32))
+  kept = [bits(f_stats[1]), bits(s_stats[1]), bits(p_stats[3]), bits(b_stats[0])]
+  print(f'mass_kept {f_stats[1]!r}: bits {[hex(k) for k in kept]}; peak {f_stats[2]!r} / {b_stats[1]!r}')
+  assert p_stats.dtype == np.float64 and float(np.float32(p_stats[3])) == p_stats[3]
+  assert len(set(kept)) == 1
+  assert bits(f_stats[2]) == bits(b_stats[1]) and f_stats[2] == belief[np.isfinite(belief)].max()
+  assert 0.0 < f_stats[1] < 1.0
+
+
 def test_philox_path_is_the_uniforms_path():
   """uniforms=None against the reference's Philox uniforms for the same (seed, stream), given: identical bytes."""
   seed = 0x0123456789ABCDEF
