@@ -407,12 +407,16 @@ __global__ __launch_bounds__(256, KMAX > 1 ? 6 : 8) void lift_pool_batched_kerne
           if (r == v) { kv[r] = vis ? v : -1; kpi[r] = pr.pi; kpj[r] = pr.pj; kdep[r] = pr.depth; }
         if (vis) min_dist = fminf(min_dist, pr.dist);
       } else if (vis) {
-        // stable insertion (strict <): equal distances keep the lower view index first
+        // stable insertion (strict <): equal distances keep the lower view index first.  Once the new view
+        // has taken a slot the rest of the list SHIFTS: the displaced entry goes on unconditionally (compared
+        // again with <, it lost its place to an equally distant view of a higher index behind it)
         float cd = pr.dist, cpi = pr.pi, cpj = pr.pj, cdep = pr.depth;
         int cv = v;
+        bool placed = false;
 #pragma unroll
         for (int r = 0; r < KMAX; ++r) {
-          if (r < nsel && cd < kd[r]) {
+          if (r < nsel && (placed || cd < kd[r])) {
+            placed = true;
             const float td = kd[r], tpi = kpi[r], tpj = kpj[r], tdep = kdep[r];
             const int tv = kv[r];
             kd[r] = cd; kpi[r] = cpi; kpj[r] = cpj; kdep[r] = cdep; kv[r] = cv;
