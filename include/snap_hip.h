@@ -1258,6 +1258,50 @@ int snap_vote_credible_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo
                            uint8_t* level_xy, uint8_t* level_r, uint8_t* level_cell, float* gt_stats, int32_t* count,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* The MODES of a vote volume: for each of K peaks the mass, mean and covariance of the cells around it, i.e. the
+ * weight, mean and 3 x 3 covariance of one component of a Gaussian mixture over (rotation, a, b).  votes[R,Ho,Wo] f32:
+ * unnormalised log-scores in the flat order of the other vote ops; peaks[K,3] i32: a DEVICE table of (r, a, b) rows,
+ * exactly what snap_vote_peaks_f32 writes (unsorted tables are legal), read by the kernels, no host synchronisation;
+ * gt_index: NULL, or a DEVICE pointer to f32 [3] = (k, i, j) as exhaustive_tfm_to_index returns it; stats[K,16] f32;
+ * count[K,2] i32.
+ *   CONTRIBUTING CELLS.  x = (double)scale * (double)v; a cell contributes iff v is finite (snap_vote_posterior_f32's
+ *   rule): -inf cells are silently excluded, NaN and +inf cells are excluded and counted.
+ *   EMPTY ROWS.  Row k is empty iff any component lies outside [0,R) x [0,Ho) x [0,Wo) (the -1 rows of
+ *   snap_vote_peaks_f32 are the normal case).  An empty row owns nothing and no address is formed from it.
+ *   WINDOW of a non-empty peak k: |dr| <= win_r, |da| <= win_xy, |db| <= win_xy with dr = (r - r_k) wrapped into its
+ *   nearest representative (the rotation axis is circular; 2 win_r + 1 <= R makes it unique inside a window),
+ *   da = a - a_k, db = b - b_k; clipped at the borders in a and b.
+ *   OWNERSHIP, a partition: a cell inside at least one window belongs to the peak that minimises the integer
+ *   D = wr^2 (da^2 + db^2) + win_xy^2 dr^2, wr = max(win_r, 1) (the distance normalised by the window half-widths,
+ *   exact in int32), ties to the lowest k; a cell inside no window belongs to nobody.  A duplicate of an earlier peak
+ *   therefore owns nothing.
+ *   SUMS over O_k, the owned contributing cells, with offsets (dr, da, db) from the peak itself: m_k = max x,
+ *   S0 = sum exp(x - m_k), and the three first and six second offset moments under those weights; the offsets are small
+ *   integers, so the central moments E[d d'] - E[d] E[d'] cancel at most win_xy^2 against float64.
+ *   stats[k] = { log_mass = m_k + log S0 (unnormalised: the mode's part of log_z); m_k; the mean rotation index
+ *   r_k + E[dr] wrapped into [0, R) (a value that rounds to R in f32 is stored as 0); a_k + E[da]; b_k + E[db];
+ *   Var r; Cov ra; Cov rb; Var a; Cov ab; Var b (index units); nees_gt; 0; 0; 0; 0 }.
+ *   nees_gt = e^T (Sigma_k + I/12)^-1 e, the normalised estimation error squared of the ground truth under the mode:
+ *   e = gt - mean in index units (the float64 means, the rotation's after its wrap), its rotation component taken to
+ *   the nearest representative (IEEE remainder by R); I/12 is the variance of a uniform distribution over one lattice
+ *   cell, below which the lattice cannot resolve, and keeps the matrix positive definite for a mode of one rotation
+ *   or one cell; a float64 closed-form (cofactor) inverse.  NaN when gt_index is NULL or not finite.
+ *   count[k] = { owned contributing cells; owned NaN or +inf cells }.
+ *   An empty row, or O_k empty: log_mass = m_k = -inf, stats[2..11] = NaN (0x7fc00000), stats[12..15] = 0.
+ * All arithmetic above the load is float64 and every output is a float64 expression rounded to f32 once.  No atomics:
+ * K (2 win_r + 1) workgroups each reduce one rotation of one window in an order fixed by (win_xy), one thread per mode
+ * merges its planes in the order dr = -win_r .. win_r; two calls with the same arguments give the same bytes.  Every
+ * element of stats and count is written by every call; nothing beyond them and the workspace is touched.
+ * Supported: R, Ho, Wo >= 1, R*Ho*Wo < 2^31, 1 <= K <= 64, 0 <= win_r <= 4 with 2 win_r + 1 <= R, 1 <= win_xy <= 32,
+ * else SNAP_ERR_BAD_SHAPE; a NULL pointer other than gt_index SNAP_ERR_NULL; a scale that is not a finite number > 0
+ * SNAP_ERR_UNSUPPORTED; a short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE; all before any launch.  workspace:
+ * snap_vote_modes_workspace_bytes() bytes (0 = unsupported arguments); it needs no initialisation.  Asynchronous on
+ * `stream`, no host synchronisation; the caller owns every buffer. */
+size_t snap_vote_modes_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t K, int32_t win_r, int32_t win_xy);
+int snap_vote_modes_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, float scale, const int32_t* peaks,
+                        int32_t K, int32_t win_r, int32_t win_xy, const float* gt_index, float* stats, int32_t* count,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Most likely pose TRACK over vote volumes: one forward step of the max-product (Viterbi) recursion that goes with the
  * filter above, with back-pointers.  score_prev[R,Ho,Wo] f32 is the log score of the best path into every pose of the
  * previous frame (-inf = no path), or NULL (the first frame of a track); votes[R,Ho,Wo] f32; on the DEVICE:

@@ -379,6 +379,124 @@ def coverage_table(gt_credibility, levels, valid=None):
   return dict(levels=q, coverage=cov, count=n, mean_abs_error=float(np.abs(cov - q).mean()) if n else float('nan'))
 
 
+def _mode_pose_and_jacobian(index_mean, grid, num_rotations):
+  """The corner-frame pose at continuous indices [K, 3] = (k, a, b) and its derivative, in float64 on the indices'
+  device -> (angle [K], t [K, 2], J [K, 3, 3] = d (angle, tx, ty) / d (k, a, b)).  The pose is
+  ``exhaustive_index_to_tfm``'s c @ (-2 pi k / R, ((a, b) - extent + 1.5) cell) @ c^-1 written out with c = (0, centre):
+  angle = -2 pi k / R, t = centre + xy_cell - Rot(angle) centre, so the translation depends on k through the rotation
+  of the centre: d t / d angle = (sin cx + cos cy, -cos cx + sin cy)."""
+  idx = index_mean.to(torch.float64)
+  R = int(num_rotations)
+  H, W = (float(v) for v in grid.extent)
+  cell = float(grid.cell_size)
+  cx, cy = (float(v) / 2 for v in grid.extent_meters)
+  dphi = -2 * math.pi / R
+  angle = idx[:, 0] * dphi
+  cos, sin = torch.cos(angle), torch.sin(angle)
+  tx = cx + (idx[:, 1] - H + 1.5) * cell - (cos * cx - sin * cy)
+  ty = cy + (idx[:, 2] - W + 1.5) * cell - (sin * cx + cos * cy)
+  J = torch.zeros((idx.shape[0], 3, 3), dtype=torch.float64, device=idx.device)
+  J[:, 0, 0] = dphi
+  J[:, 1, 0] = (sin * cx + cos * cy) * dphi
+  J[:, 2, 0] = (-cos * cx + sin * cy) * dphi
+  J[:, 1, 1] = cell
+  J[:, 2, 2] = cell
+  return angle, torch.stack((tx, ty), -1), J
+
+
+def modes_from_votes(votes, grid, num_rotations, peaks=None, num_peaks=16, radius_r=1, radius_xy=1, win_r=None,
+                     win_xy=None, temperature=1.0, log_z=None, m_t_q_gt=None):
+  """The Gaussian mixture of a vote volume [R, 2H-1, 2W-1]: one component per peak (``ops.vote_modes``) over
+  p = softmax(temperature * votes).  ``peaks``: an int32 [K, 3] device table of (r, a, b) rows, or None:
+  ``poses_from_votes(num_peaks, radius_r, radius_xy)`` finds them.  The window (``win_r`` rotations, ``win_xy`` cells
+  around a peak) defaults to the non-maximum-suppression radii; ``log_z``: the volume's log partition sum (a tensor or
+  a number), or None: ``ops.vote_posterior`` computes it -> dict of device tensors, nothing synchronised:
+
+  ``weight`` [K] = exp(log_mass - log_z), the probability a mode owns; ``unassigned`` = 1 - sum weight, the
+  probability of the cells outside every window; ``index_mean`` [K, 3], the continuous (k, a, b) index;
+  ``map_t_query`` Transform2D [K], the pose at it (``exhaustive_index_to_tfm``'s +0.5 cell offset and corner-frame
+  conjugation), NaN for empty modes; ``cov_index`` [K, 3, 3] in index units; ``cov`` [K, 3, 3] in (angle rad, x m, y m)
+  of the corner-frame transform, the first-order propagation J Sigma J^T at the mode mean in float64 rounded once (J
+  includes the angle-dependence of the corner-frame translation); ``count`` int32 [K, 2] = (owned finite cells, owned
+  NaN / +inf cells); ``stats``, the op's raw rows; ``index``, the peak table used.  With ``m_t_q_gt`` (a Transform2D,
+  map corner frame): ``nees`` [K], the ground truth's normalised estimation error squared under each mode in index
+  units with the lattice's I/12 added to the covariance (chi^2 with 3 degrees of freedom for a consistent mode:
+  ``nees_table``)."""
+  if votes.shape[0] != num_rotations:
+    raise ValueError(f'modes_from_votes: {votes.shape[0]} vote planes for {num_rotations} rotations')
+  votes = votes.contiguous()
+  if peaks is None:
+    peaks = poses_from_votes(votes, grid, num_rotations, num_peaks, radius_r, radius_xy)['index']
+  win_r = radius_r if win_r is None else win_r
+  win_xy = radius_xy if win_xy is None else win_xy
+  gt = None
+  if m_t_q_gt is not None:
+    gt = exhaustive_tfm_to_index(m_t_q_gt, grid, num_rotations).to(device=votes.device, dtype=torch.float32)
+    gt = gt.reshape(3).contiguous()
+  if log_z is None:
+    log_z = ops.vote_posterior(votes, temperature)[2][0]
+  stats, count = ops.vote_modes(votes, peaks.contiguous(), win_r, win_xy, temperature, gt)
+  log_z = log_z.to(device=votes.device, dtype=torch.float64) if isinstance(log_z, torch.Tensor) else float(log_z)
+  weight = torch.exp(stats[:, 0].to(torch.float64) - log_z)
+  index_mean = stats[:, 2:5]
+  angle, t, J = _mode_pose_and_jacobian(index_mean, grid, num_rotations)
+  s = stats.to(torch.float64)
+  cov_index = torch.stack((s[:, 5], s[:, 6], s[:, 7], s[:, 6], s[:, 8], s[:, 9], s[:, 7], s[:, 9], s[:, 10]),
+                          -1).reshape(-1, 3, 3)
+  cov = J @ cov_index @ J.transpose(1, 2)
+  out = dict(
+      weight=weight.to(torch.float32), unassigned=(1.0 - weight.sum()).to(torch.float32), index_mean=index_mean,
+      map_t_query=geometry.Transform2D(angle.to(torch.float32), t.to(torch.float32)),
+      cov_index=cov_index.to(torch.float32), cov=cov.to(torch.float32), count=count, stats=stats, index=peaks)
+  if m_t_q_gt is not None:
+    out['nees'] = stats[:, 11]
+  return out
+
+
+def _chi2_3_cdf(x):
+  """The chi-square distribution function with 3 degrees of freedom: erf(sqrt(x / 2)) - sqrt(2 x / pi) exp(-x / 2)."""
+  return math.erf(math.sqrt(x / 2)) - math.sqrt(2 * x / math.pi) * math.exp(-x / 2)
+
+
+def chi2_3_quantile(q):
+  """The q-quantile (0 <= q < 1) of the chi-square distribution with 3 degrees of freedom, by bisection on the closed
+  form of its distribution function in float64."""
+  q = float(q)
+  if not 0.0 <= q < 1.0:
+    raise ValueError(f'chi2_3_quantile: level {q} outside [0, 1)')
+  lo, hi = 0.0, 1.0
+  while _chi2_3_cdf(hi) < q:
+    hi *= 2
+  for _ in range(200):
+    mid = 0.5 * (lo + hi)
+    if mid == lo or mid == hi:
+      break
+    if _chi2_3_cdf(mid) < q:
+      lo = mid
+    else:
+      hi = mid
+  return 0.5 * (lo + hi)
+
+
+def nees_table(nees, levels=(0.5, 0.9, 0.99), valid=None):
+  """Host helper of an evaluation loop, the Gaussian counterpart of ``coverage_table``: the consistency of the modes'
+  covariances over many frames.  ``nees``: the frames' ``modes_from_votes(...)['nees']`` of the mode that is judged
+  (any array-like; NaN = invalid), ``valid``: an optional bool mask on top -> dict(levels, quantile [L] = the chi^2_3
+  quantiles of the levels, coverage [L] = the fraction of valid samples with nees below the quantile, count = the
+  valid samples, mean_abs_error = mean |coverage - q|).  A consistent covariance has coverage = q up to the binomial
+  noise sqrt(q (1 - q) / count); a coverage below q means covariances that are too small."""
+  c = np.asarray(torch.as_tensor(nees).detach().cpu(), dtype=np.float64).reshape(-1)
+  ok = np.isfinite(c)
+  if valid is not None:
+    ok &= np.asarray(torch.as_tensor(valid).detach().cpu()).reshape(-1).astype(bool)
+  q = np.asarray(levels, dtype=np.float64).reshape(-1)
+  quant = np.array([chi2_3_quantile(v) for v in q])
+  n = int(ok.sum())
+  cov = np.array([float((c[ok] < v).mean()) if n else float('nan') for v in quant])
+  return dict(levels=q, quantile=quant, coverage=cov, count=n,
+              mean_abs_error=float(np.abs(cov - q).mean()) if n else float('nan'))
+
+
 def _bin_cos_sin(R):
   """float64 (cos, sin) of the R bin angles 2 pi r / R -> [R, 2].  The angle is reduced to a quarter turn first
   (4 r = q R + rem: 2 pi r / R = (q + rem / R) pi / 2) and the quarter turns are applied as sign swaps, so whole
@@ -504,14 +622,16 @@ def refine_poses(plane_q, plane_map, index, grid, num_rotations, conf_q=None, mi
 
 
 def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, method=None, posterior=None,
-                        refine=None, credible=None, **peaks):
+                        refine=None, credible=None, modes=None, **peaks):
   """``exhaustive_pose_voting`` followed by ``poses_from_votes(**peaks)``: the dict of the latter plus ``votes``.
   ``['map_t_query'][0]`` is the single best pose.  ``posterior``: True, or a dict of keyword arguments of
   ``posterior_from_votes`` (``temperature``, ``m_t_q_gt``), adds its result as ``['posterior']``.  ``refine``: True,
   or a dict of keyword arguments of ``refine_poses`` (``min_overlap``, the lattice), adds the peaks refined to
   continuous poses on the two planes as ``['refined']``.  ``credible``: True, or a dict of keyword arguments of
   ``credible_from_votes`` (``levels``, ``temperature``, ``m_t_q_gt``, ``cell_levels``), adds its result as
-  ``['credible']``."""
+  ``['credible']``.  ``modes``: True, or a dict of keyword arguments of ``modes_from_votes`` (``win_r``, ``win_xy``,
+  ``temperature``, ``m_t_q_gt``), adds the mixture around the peaks already found as ``['modes']`` (the window defaults
+  to the peaks' radii; the posterior's ``log_z`` is reused where both have the same temperature)."""
   votes = exhaustive_pose_voting(plane_q, plane_map, num_rotations, grid, conf_q=conf_q, method=method)
   out = poses_from_votes(votes, grid, num_rotations, **peaks)
   out['votes'] = votes
@@ -524,7 +644,22 @@ def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, me
   if credible is not None and credible is not False:
     kw = {} if credible is True else dict(credible)
     out['credible'] = credible_from_votes(votes, grid, num_rotations, **kw)
+  if modes is not None and modes is not False:
+    out['modes'] = _modes_of_peaks(out, votes, grid, num_rotations, modes, posterior, peaks)
   return out
+
+
+def _modes_of_peaks(out, votes, grid, num_rotations, modes, posterior, peaks):
+  """``modes_from_votes`` for an entry point that has run ``poses_from_votes(**peaks)`` into ``out`` and, where
+  ``posterior`` asks for it, ``posterior_from_votes`` into ``out['posterior']``."""
+  kw = {} if modes is True else dict(modes)
+  kw.setdefault('radius_r', peaks.get('radius_r', 1))
+  kw.setdefault('radius_xy', peaks.get('radius_xy', 1))
+  if 'posterior' in out and 'log_z' not in kw:
+    post_kw = {} if posterior is True else posterior
+    if float(post_kw.get('temperature', 1.0)) == float(kw.get('temperature', 1.0)):
+      kw['log_z'] = out['posterior']['log_z']
+  return modes_from_votes(votes, grid, num_rotations, peaks=out['index'], **kw)
 
 
 def _shift_table_f64(q0_t_q, grid, num_rotations):
@@ -584,13 +719,13 @@ def fuse_votes(volumes, q0_t_q, grid, num_rotations, weights=None):
 
 
 def localize_sequence(planes_q, plane_map, num_rotations, grid, q0_t_q, conf_q=None, method=None, weights=None,
-                      posterior=None, **peaks):
+                      posterior=None, modes=None, **peaks):
   """Sequence localization: ``exhaustive_pose_voting`` per query frame, ``fuse_votes`` with the frames' relative
   poses ``q0_t_q`` (Transform2D [N], corner frames, the anchor first as an identity), then
   ``poses_from_votes(fused, **peaks)``: the dict of ``localize_exhaustive`` with ``votes`` = the fused volume, plus
   ``votes_frames`` [N, R, 2H-1, 2W-1], ``count_fused`` (``fuse_votes``' count) and ``map_t_query_frames``, a
   Transform2D [K, N] = peak k composed with q0_t_qn (NaN past the found count).  ``conf_q``: None or one confidence
-  per frame; ``posterior`` as in ``localize_exhaustive``, on the fused volume."""
+  per frame; ``posterior`` and ``modes`` as in ``localize_exhaustive``, on the fused volume."""
   planes_q = list(planes_q)
   conf_q = [None] * len(planes_q) if conf_q is None else list(conf_q)
   if len(conf_q) != len(planes_q):
@@ -607,6 +742,8 @@ def localize_sequence(planes_q, plane_map, num_rotations, grid, q0_t_q, conf_q=N
   if posterior is not None and posterior is not False:
     kw = {} if posterior is True else dict(posterior)
     out['posterior'] = posterior_from_votes(fused, grid, num_rotations, **kw)
+  if modes is not None and modes is not False:
+    out['modes'] = _modes_of_peaks(out, fused, grid, num_rotations, modes, posterior, peaks)
   return out
 
 
@@ -1001,6 +1138,13 @@ class VoteFilter:
       raise ValueError('VoteFilter.credible: no belief (at least one step)')
     return credible_from_votes(self.belief, self.grid, self.num_rotations, levels=levels, temperature=1.0,
                                m_t_q_gt=m_t_q_gt, cell_levels=cell_levels)
+
+  def modes(self, **kw):
+    """``modes_from_votes(**kw)`` of the belief the filter holds (log-space and normalised, so the temperature is 1 and
+    log_z is 0) -> its dict.  Raises ValueError before the first step."""
+    if self.belief is None:
+      raise ValueError('VoteFilter.modes: no belief (at least one step)')
+    return modes_from_votes(self.belief, self.grid, self.num_rotations, temperature=1.0, log_z=0.0, **kw)
 
   def smooth(self, posterior=None, **peaks):
     """The backward recursion over the history (``smooth_track``; each step's taps are rebuilt by ``motion_taps``) ->

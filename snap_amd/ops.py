@@ -2344,6 +2344,48 @@ def vote_credible(votes, levels, scale=1.0, gt_index=None, cell_levels=False):
   return threshold, mass, table, level_xy, level_r, level_cell, gt_stats, count
 
 
+def vote_modes(votes, peaks, win_r=1, win_xy=4, scale=1.0, gt_index=None):
+  """The modes of a vote volume: votes [R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked), ``peaks`` int32
+  [K, 3] = (r, a, b) rows on the same device (``vote_peaks``' index; a row with a component out of range, such as its
+  -1 rows, is empty) -> (stats f32 [K, 16], count int32 [K, 2]).  A cell within ``win_r`` rotations (circular) and
+  ``win_xy`` cells (clipped) of at least one peak belongs to the peak nearest in window-normalised distance, ties to
+  the lowest row; over the finite cells a peak owns, with x = scale * v: stats[k] = (log_mass = log sum exp(x), max x,
+  mean rotation index in [0, R), mean a, mean b, Var r, Cov ra, Cov rb, Var a, Cov ab, Var b in index units, nees_gt,
+  0, 0, 0, 0); count[k] = (owned finite cells, owned NaN or +inf cells).  nees_gt = e^T (Sigma + I/12)^-1 e for
+  e = gt_index - mean (NaN without one).  ``gt_index``: None or a device f32 [3] = (k, i, j)
+  (``exhaustive_tfm_to_index``), read on the device.  An empty row or a mode without finite cells: -inf masses and NaN
+  moments (the full contract: snap_vote_modes_f32 in include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  _f32(votes, 'votes')
+  if votes.dim() != 3:
+    raise ValueError(f'vote_modes: votes [R, Ho, Wo], got {tuple(votes.shape)}')
+  R, Ho, Wo = votes.shape
+  _arg_chk(peaks, 'peaks', (torch.int32,), (None, 3), votes.device, f'vote_modes: peaks int32 [K, 3] on {votes.device}')
+  K, win_r, win_xy = int(peaks.shape[0]), int(win_r), int(win_xy)
+  scale = float(scale)
+  if not (scale > 0.0 and np.isfinite(scale)):
+    raise ValueError(f'vote_modes: scale must be a finite number > 0, got {scale}')
+  if gt_index is not None:
+    _f32(gt_index, 'gt_index')
+    if tuple(gt_index.shape) != (3,) or gt_index.device != votes.device:
+      raise ValueError(f'vote_modes: gt_index f32 [3] on {votes.device}, got {tuple(gt_index.shape)} on '
+                       f'{gt_index.device}')
+  words = _workspace_words(
+      lib.snap_vote_modes_workspace_bytes, (R, Ho, Wo, K, win_r, win_xy), votes.numel(),
+      f'vote_modes: unsupported R={R} Ho={Ho} Wo={Wo} K={K} win_r={win_r} win_xy={win_xy} '
+      '(1 <= K <= 64, 0 <= win_r <= 4 with 2 win_r + 1 <= R, 1 <= win_xy <= 32, R Ho Wo < 2^31)')
+  ws = torch.empty((words,), dtype=torch.int64, device=votes.device)
+  stats = torch.empty((K, 16), dtype=torch.float32, device=votes.device)
+  count = torch.empty((K, 2), dtype=torch.int32, device=votes.device)
+  # algorithmic bytes: one read of the K windows (the second walk hits in cache), the peak table, the outputs
+  window = (2 * win_r + 1) * (2 * win_xy + 1) ** 2
+  with _region('vote_modes', 0.0, 4.0 * K * window + 12.0 * K + 72.0 * K):
+    st = lib.snap_vote_modes_f32(_p(votes), R, Ho, Wo, scale, _p(peaks), K, win_r, win_xy, _p(gt_index), _p(stats),
+                                 _p(count), _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_modes_f32')
+  return stats, count
+
+
 def vote_fuse(volumes, shifts, weights=None):
   """Multi-frame fusion of aligned vote volumes: volumes [N, R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked),
   shifts f32 [N, R, 3] = (dk, da, db) on the same device (``pose_exhaustive_voting.sequence_shift_table``), weights

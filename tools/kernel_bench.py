@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4)
 """
 import math
 import os
@@ -511,10 +511,43 @@ def vote_refine_c4(iters):
   emit_json(res)
 
 
+def vote_modes_c4(iters):
+  """The modes of the C4 vote volume (R = 36, 511 x 511, the low-overlap border -inf; K = 16 peaks of ops.vote_peaks,
+  window (2, 16): ~9e4 cells, so the call is launch-bound): whole ops.vote_modes calls beside whole ops.vote_posterior
+  and ops.vote_peaks calls on the same votes, blocks alternated, medians of single calls.  One JSON line; `json=<path>`
+  as a third argument also writes it to that file."""
+  R, H, scale, K, win_r, win_xy = 36, 256, 8.0, 16, 2, 16
+  Ho = Wo = 2 * H - 1
+  g = torch.Generator(device='cuda').manual_seed(0)
+  votes = torch.randn((R, Ho, Wo), device='cuda', generator=g) * 0.25
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  votes = torch.where((ov[:, None] * ov[None, :] > 0.05 * H * H)[None], votes, float('-inf')).contiguous()
+  peaks = ops.vote_peaks(votes, K, 2, 4)[0]
+  stats, count = ops.vote_modes(votes, peaks, win_r, win_xy, scale)
+  log_z = ops.vote_posterior(votes, scale)[2][0]
+  weight = (stats[:, 0].double() - log_z.double()).exp()
+  assert bool((count[:, 0] > 0).all()) and bool(torch.isfinite(stats[:, :11]).all()) and 0 < float(weight.sum()) <= 1
+  modes = lambda: ops.vote_modes(votes, peaks, win_r, win_xy, scale)
+  post = lambda: ops.vote_posterior(votes, scale)
+  pk = lambda: ops.vote_peaks(votes, K, 2, 4)
+  n = max(iters, 5)
+  (m_ms, ms), (p_ms, ps), (k_ms, ks) = alternated_blocks(((modes, 5, n), (post, 5, n), (pk, 5, n)))
+  cells = int(count.sum())
+  res = dict(case='vote_modes_c4', shape=[R, Ho, Wo], K=K, window=[win_r, win_xy], scale=scale, owned_cells=cells,
+             mass_in_modes=round(float(weight.sum()), 6), vote_modes_call_ms=round(m_ms, 4),
+             vote_modes_call_ms_blocks=[round(v, 4) for v in ms], vote_posterior_call_ms=round(p_ms, 4),
+             vote_posterior_call_ms_blocks=[round(v, 4) for v in ps], vote_peaks_call_ms=round(k_ms, 4),
+             vote_peaks_call_ms_blocks=[round(v, 4) for v in ks],
+             timing='whole wrapper calls (torch.empty outputs and workspace, the ctypes call, the launches) between '
+             'device events on an idle stream, NOT kernel time; median of single calls, 5 blocks of each alternated, '
+             'median block; no threshold is set on this case')
+  emit_json(res)
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
   {'pose_score': pose_score, 'pose_score_c4': pose_score_c4, 'voting_c4': voting_c4,
    'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4,
    'vote_filter_c4': vote_filter_c4, 'vote_smooth_c4': vote_smooth_c4,
-   'vote_refine_c4': vote_refine_c4}[which](iters)
+   'vote_refine_c4': vote_refine_c4, 'vote_modes_c4': vote_modes_c4}[which](iters)
