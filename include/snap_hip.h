@@ -1302,6 +1302,61 @@ int snap_vote_modes_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, f
                         int32_t K, int32_t win_r, int32_t win_xy, const float* gt_index, float* stats, int32_t* count,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* The EXPECTED RECALL of a vote volume: how much posterior mass lies within (rho cells, half_r rotation bins) of a
+ * pose.  The reference scores the localizer by hit / miss at thresholds (snap/models/bev_localizer.py:268-270,
+ * loc/recall_max_{t}m and loc/recall_max_{t}deg: dt < t, dr < t; :274-277, the joint pairs (0.5 m, 1 deg), (1 m, 2 deg),
+ * (2 m, 4 deg)); under the posterior of the votes the probability of such a hit for a candidate pose is the mass of
+ * the threshold ball around it, and the cell whose ball carries the most mass maximises the expected recall.
+ * votes[R,Ho,Wo] f32: unnormalised log-scores in the flat order of the other vote ops; rho2[L], half_r[L] i32: HOST
+ * arrays, read before the call returns; centres[K,3] i32: a DEVICE table of (r, a, b) rows, exactly what
+ * snap_vote_peaks_f32 writes, or NULL with K = 0; gt_index: NULL, or a DEVICE pointer to f32 [3] = (k, i, j) as
+ * exhaustive_tfm_to_index returns it; maps[L,R,Ho,Wo] f32 or NULL.
+ *   CONTRIBUTING CELLS.  x = (double)scale * (double)v; a cell contributes iff v is finite (snap_vote_posterior_f32's
+ *   rule): -inf cells are silently excluded, NaN and +inf cells are excluded and counted.  m = max x, e = exp(x - m),
+ *   S = sum e, all float64; a cell that does not contribute has e = 0.
+ *   BALL of level l around (r, a, b): the cells (r', a', b') with |r' - r| <= half_r[l] on the circle of R rotations and
+ *   (a' - a)^2 + (b' - b)^2 <= rho2[l], clipped to the volume in a and b (there is no mass outside it).  The thresholds
+ *   are integers so that membership is exact everywhere (pose_exhaustive_voting.recall_thresholds turns metres and
+ *   degrees into them with the reference's strict <).
+ *   log_mass_l(r, a, b) = fl32(min(0, log(sum over the ball of e) - log S)), float64 above the cell and rounded once;
+ *   -inf where the sum is 0 (no contributing cell in the ball).
+ *   best_index[L,3] i32, best_log_mass[L] f32: the maximum of log_mass_l over ALL cells, compared as the stored f32
+ *   values, the greater value first and then the lower flat index (r*Ho + a)*Wo + b; (-1, -1, -1) and -inf when no
+ *   cell has a log mass above -inf.
+ *   centre_log_mass[K,L] f32: log_mass_l at row k's cell; a row with a component outside [0,R) x [0,Ho) x [0,Wo) (the
+ *   -1 rows of snap_vote_peaks_f32) is EMPTY: -inf, and no address is formed from it.
+ *   gt_log_mass[L] f32: log_mass_l at the ground-truth cell (rintf(k) mod R, rint(i), rint(j)) (round half to even,
+ *   mathematical modulo: snap_vote_credible_f32's rounding); the ground truth is valid iff k, i, j are finite,
+ *   |k| <= 2^20, 0 <= i <= Ho-1 and 0 <= j <= Wo-1 (the cell itself need not contribute: the mass near a masked truth
+ *   is a legitimate answer); NaN (0x7fc00000) when gt_index is NULL or invalid.
+ *   stats[4] f32 = { log_z = m + log S; m; 0; 0 } (both -inf when no cell contributes).
+ *   count[4] i32 = { contributing cells; NaN or +inf cells; 1 if the ground truth is valid, else 0; 0 }.
+ *   maps, when not NULL: log_mass_l at every cell.  Every other output holds the same bytes with and without maps.
+ * METHOD.  Every ball mass is a sum of NON-NEGATIVE float64 terms: no prefix sums and no sliding-window differences,
+ * which lose a low-mass ball against its row total and can go negative.  E = e as a float64 volume; per level one
+ * launch in which a wave owns 64 columns and marches down the rows: the row of sum_{|dr| <= half_r} E[r + dr] goes to
+ * LDS, a thread grows the centred spans of its column S_h = (S_{h-1} + e(b-h)) + e(b+h), h = 0 .. rho, and adds
+ * S_{isqrt(rho2 - d^2)} into the pending output rows at distance d, a ring of 2 rho + 1 rows in LDS; about 4 rho + 1
+ * additions per cell and level instead of pi rho^2.  An output row receives its spans in ascending input-row order
+ * whatever the tiling.  The centres' and the ground truth's masses are summed directly over their balls.  Values at
+ * the same cell in maps and in centre_log_mass come from different summation orders of the same non-negative terms:
+ * equal to float64 rounding before the single f32 rounding.  No atomics; per-workgroup partials are folded in an order
+ * fixed by the shape, so two calls with the same arguments give the same bytes.  Every element of every output is
+ * written by every call; the workspace needs no initialisation.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31, 0 <= K <= 64, 1 <= L <= 8, 0 <= rho2[l] <= 1024,
+ * 0 <= half_r[l] <= 4 with 2 half_r[l] + 1 <= R, else SNAP_ERR_BAD_SHAPE; a NULL pointer other than gt_index, maps and
+ * (with K = 0) centres / centre_log_mass SNAP_ERR_NULL (checked first: the thresholds are read); a scale that is not a
+ * finite number > 0 SNAP_ERR_UNSUPPORTED; a short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE; all before any
+ * launch.  workspace: snap_vote_recall_workspace_bytes() bytes (0 = unsupported shape, K or L): ONE float64 volume
+ * plus per-workgroup partials (75 MB at 36 x 511 x 511, L = 8), independent of the thresholds.  Asynchronous on
+ * `stream`, no host synchronisation; the caller owns every buffer. */
+size_t snap_vote_recall_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t K, int32_t L);
+int snap_vote_recall_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, float scale, const int32_t* rho2,
+                         const int32_t* half_r, int32_t L, const int32_t* centres, int32_t K, const float* gt_index,
+                         int32_t* best_index, float* best_log_mass, float* centre_log_mass, float* gt_log_mass,
+                         float* stats, int32_t* count, float* maps, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* Most likely pose TRACK over vote volumes: one forward step of the max-product (Viterbi) recursion that goes with the
  * filter above, with back-pointers.  score_prev[R,Ho,Wo] f32 is the log score of the best path into every pose of the
  * previous frame (-inf = no path), or NULL (the first frame of a track); votes[R,Ho,Wo] f32; on the DEVICE:

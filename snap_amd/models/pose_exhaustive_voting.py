@@ -12,6 +12,7 @@
 
 Rotation, padding and the -inf / normalise pass are small HIP kernels (voting.hip).
 """
+import fractions
 import functools
 import math
 
@@ -497,6 +498,104 @@ def nees_table(nees, levels=(0.5, 0.9, 0.99), valid=None):
               mean_abs_error=float(np.abs(cov - q).mean()) if n else float('nan'))
 
 
+RECALL_THRESHOLDS = ((0.5, 1), (1, 2), (2, 4))             # (metres, degrees): the reference's joint recall pairs
+
+
+def recall_thresholds(thresholds, grid, num_rotations):
+  """(metres, degrees) pairs -> (rho2, half_r), int32 arrays [L] of ``ops.vote_recall``: the squared xy radius in cells
+  and the rotation half-width in bins of the lattice poses STRICTLY within the thresholds of a lattice pose, as the
+  reference's recall tests dt < t and dr < t: d^2 < (t / cell)^2 for an integer d^2 is d^2 <= ceil((t / cell)^2) - 1,
+  and |dr| 360 / R < t_deg is |dr| <= ceil(t_deg R / 360) - 1.  Exact rational arithmetic on the numbers' shortest
+  decimal forms (0.25 is 1/4, 0.2 is 1/5), so a threshold that is a whole number of cells is excluded as it should
+  be.  ValueError for a pair outside the op's limits (1 to 8 pairs, 0 <= rho2 <= 1024, 0 <= half_r <= 4,
+  2 half_r + 1 <= R)."""
+  frac = lambda v: fractions.Fraction(repr(float(v)))
+  R = int(num_rotations)
+  pairs = [tuple(p) for p in thresholds]
+  if not 1 <= len(pairs) <= 8 or any(len(p) != 2 for p in pairs):
+    raise ValueError(f'recall_thresholds: 1 to 8 (metres, degrees) pairs, got {thresholds}')
+  cell = frac(grid.cell_size)
+  rho2, half_r = [], []
+  for t_m, t_deg in pairs:
+    if not (math.isfinite(t_m) and math.isfinite(t_deg) and t_m > 0 and t_deg > 0):
+      raise ValueError(f'recall_thresholds: thresholds must be finite numbers > 0, got ({t_m}, {t_deg})')
+    q = math.ceil((frac(t_m) / cell) ** 2) - 1
+    h = math.ceil(frac(t_deg) * R / 360) - 1
+    if q > 1024 or h > 4 or 2 * h + 1 > R:
+      raise ValueError(f'recall_thresholds: ({t_m} m, {t_deg} deg) is rho2={q}, half_r={h} on a {grid.cell_size} m, '
+                       f'{R}-rotation lattice: outside rho2 <= 1024, half_r <= 4, 2 half_r + 1 <= R')
+    rho2.append(q)
+    half_r.append(h)
+  return np.asarray(rho2, dtype=np.int32), np.asarray(half_r, dtype=np.int32)
+
+
+def recall_from_votes(votes, grid, num_rotations, thresholds=RECALL_THRESHOLDS, temperature=1.0, peaks=None,
+                      m_t_q_gt=None, maps=False):
+  """The expected recall under p = softmax(temperature * votes) of a vote volume [R, 2H-1, 2W-1]
+  (``ops.vote_recall``): for every (metres, degrees) pair of ``thresholds`` (``recall_thresholds``) the probability
+  that the pose lies strictly within the pair of a lattice pose -> dict of device tensors, nothing synchronised:
+
+  ``best_index`` int32 [L, 3] and ``map_t_query`` Transform2D [L]: per pair the lattice pose whose threshold ball
+  carries the most probability, i.e. the estimate that maximises the expected recall at that pair
+  (``exhaustive_indices_to_tfm``; NaN without a finite vote); ``best_recall`` [L]: that probability;
+  ``thresholds_cells`` int32 [L, 2] = (rho2, half_r) (host); ``log_z``; ``count`` int32 [4] = (finite cells, NaN / +inf
+  cells, ground truth valid, 0).  With ``peaks`` (an int32 [K, 3] device table, ``poses_from_votes(...)['index']``):
+  ``peak_recall`` [K, L], the probability that each candidate is within the thresholds (0 for a -1 row).  With
+  ``m_t_q_gt`` (a Transform2D, map corner frame; rounded to the nearest cell of ``exhaustive_tfm_to_index`` on the
+  device): ``gt_recall`` [L], the probability within the thresholds of the true pose, a smooth counterpart of the
+  hit / miss metric (NaN where the truth lies outside the volume).  With ``maps``: ``maps`` [L, R, 2H-1, 2W-1], the log
+  of that probability for every lattice pose."""
+  if votes.shape[0] != num_rotations:
+    raise ValueError(f'recall_from_votes: {votes.shape[0]} vote planes for {num_rotations} rotations')
+  rho2, half_r = recall_thresholds(thresholds, grid, num_rotations)
+  gt = None
+  if m_t_q_gt is not None:
+    gt = exhaustive_tfm_to_index(m_t_q_gt, grid, num_rotations).to(device=votes.device, dtype=torch.float32)
+    gt = gt.reshape(3).contiguous()
+  best_index, best_lm, centre_lm, gt_lm, stats, count, lm_maps = ops.vote_recall(
+      votes.contiguous(), rho2.tolist(), half_r.tolist(), None if peaks is None else peaks.contiguous(), temperature,
+      gt, maps)
+  out = dict(best_index=best_index, map_t_query=exhaustive_indices_to_tfm(best_index, grid, num_rotations),
+             best_recall=torch.exp(best_lm), thresholds_cells=np.stack([rho2, half_r], -1), log_z=stats[0],
+             count=count)
+  if peaks is not None:
+    out['peak_recall'] = torch.exp(centre_lm)
+  if m_t_q_gt is not None:
+    out['gt_recall'] = torch.exp(gt_lm)
+  if maps:
+    out['maps'] = lm_maps
+  return out
+
+
+def recall_table(pred_recall, hit, bins=10, valid=None):
+  """Host helper of an evaluation loop, the reliability table that goes with ``recall_from_votes(...)['peak_recall']``:
+  ``pred_recall``: the predicted probabilities that the judged poses are within a threshold, ``hit``: whether they
+  were (any array-likes of one shape; a NaN prediction = invalid), ``valid``: an optional bool mask on top ->
+  dict(edges [bins + 1], count [bins], mean_pred [bins], hit_rate [bins] (NaN for an empty bin), total = the valid
+  samples, ece = sum count / total |mean_pred - hit_rate|, NaN without samples).  ``bins`` equal bins on [0, 1], a
+  prediction of exactly 1 in the last; float64.  A calibrated predictor has hit_rate = mean_pred up to the binomial
+  noise sqrt(p (1 - p) / count)."""
+  p = np.asarray(torch.as_tensor(pred_recall).detach().cpu(), dtype=np.float64).reshape(-1)
+  h = np.asarray(torch.as_tensor(hit).detach().cpu()).reshape(-1).astype(np.float64)
+  bins = int(bins)
+  if bins < 1 or p.shape != h.shape:
+    raise ValueError(f'recall_table: bins >= 1 and one hit per prediction, got bins={bins}, {p.size} and {h.size}')
+  ok = np.isfinite(p)
+  if valid is not None:
+    ok &= np.asarray(torch.as_tensor(valid).detach().cpu()).reshape(-1).astype(bool)
+  p, h = p[ok], h[ok]
+  which = np.clip(np.floor(p * bins).astype(np.int64), 0, bins - 1)
+  count = np.bincount(which, minlength=bins)
+  with np.errstate(invalid='ignore'):
+    mean_pred = np.bincount(which, weights=p, minlength=bins) / count
+    hit_rate = np.bincount(which, weights=h, minlength=bins) / count
+  n = int(count.sum())
+  full = count > 0
+  ece = float((count[full] * np.abs(mean_pred[full] - hit_rate[full])).sum() / n) if n else float('nan')
+  return dict(edges=np.linspace(0.0, 1.0, bins + 1), count=count, mean_pred=mean_pred, hit_rate=hit_rate, total=n,
+              ece=ece)
+
+
 def _bin_cos_sin(R):
   """float64 (cos, sin) of the R bin angles 2 pi r / R -> [R, 2].  The angle is reduced to a quarter turn first
   (4 r = q R + rem: 2 pi r / R = (q + rem / R) pi / 2) and the quarter turns are applied as sign swaps, so whole
@@ -622,7 +721,7 @@ def refine_poses(plane_q, plane_map, index, grid, num_rotations, conf_q=None, mi
 
 
 def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, method=None, posterior=None,
-                        refine=None, credible=None, modes=None, **peaks):
+                        refine=None, credible=None, modes=None, recall=None, **peaks):
   """``exhaustive_pose_voting`` followed by ``poses_from_votes(**peaks)``: the dict of the latter plus ``votes``.
   ``['map_t_query'][0]`` is the single best pose.  ``posterior``: True, or a dict of keyword arguments of
   ``posterior_from_votes`` (``temperature``, ``m_t_q_gt``), adds its result as ``['posterior']``.  ``refine``: True,
@@ -631,7 +730,9 @@ def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, me
   ``credible_from_votes`` (``levels``, ``temperature``, ``m_t_q_gt``, ``cell_levels``), adds its result as
   ``['credible']``.  ``modes``: True, or a dict of keyword arguments of ``modes_from_votes`` (``win_r``, ``win_xy``,
   ``temperature``, ``m_t_q_gt``), adds the mixture around the peaks already found as ``['modes']`` (the window defaults
-  to the peaks' radii; the posterior's ``log_z`` is reused where both have the same temperature)."""
+  to the peaks' radii; the posterior's ``log_z`` is reused where both have the same temperature).  ``recall``: True, or
+  a dict of keyword arguments of ``recall_from_votes`` (``thresholds``, ``temperature``, ``m_t_q_gt``, ``maps``), adds
+  its result for the peaks already found as ``['recall']``."""
   votes = exhaustive_pose_voting(plane_q, plane_map, num_rotations, grid, conf_q=conf_q, method=method)
   out = poses_from_votes(votes, grid, num_rotations, **peaks)
   out['votes'] = votes
@@ -646,6 +747,9 @@ def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, me
     out['credible'] = credible_from_votes(votes, grid, num_rotations, **kw)
   if modes is not None and modes is not False:
     out['modes'] = _modes_of_peaks(out, votes, grid, num_rotations, modes, posterior, peaks)
+  if recall is not None and recall is not False:
+    kw = {} if recall is True else dict(recall)
+    out['recall'] = recall_from_votes(votes, grid, num_rotations, peaks=out['index'], **kw)
   return out
 
 
@@ -1145,6 +1249,13 @@ class VoteFilter:
     if self.belief is None:
       raise ValueError('VoteFilter.modes: no belief (at least one step)')
     return modes_from_votes(self.belief, self.grid, self.num_rotations, temperature=1.0, log_z=0.0, **kw)
+
+  def recall(self, **kw):
+    """``recall_from_votes(**kw)`` of the belief the filter holds (log-space and normalised, so the temperature is 1)
+    -> its dict.  Raises ValueError before the first step."""
+    if self.belief is None:
+      raise ValueError('VoteFilter.recall: no belief (at least one step)')
+    return recall_from_votes(self.belief, self.grid, self.num_rotations, temperature=1.0, **kw)
 
   def smooth(self, posterior=None, **peaks):
     """The backward recursion over the history (``smooth_track``; each step's taps are rebuilt by ``motion_taps``) ->

@@ -6,6 +6,7 @@ current stream.  There is no CPU or PyTorch fallback: tensors must live on a
 ROCm device and the shared library must be built, otherwise these raise.
 """
 import contextlib
+import operator
 import sys
 import ctypes
 import threading
@@ -2384,6 +2385,78 @@ def vote_modes(votes, peaks, win_r=1, win_xy=4, scale=1.0, gt_index=None):
                                  _p(count), _p(ws), ws.numel() * 8, _stream())
   _lib.check(st, 'snap_vote_modes_f32')
   return stats, count
+
+
+def vote_recall(votes, rho2, half_r, centres=None, scale=1.0, gt_index=None, maps=False):
+  """The expected recall of a vote volume: votes [R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked); ``rho2``,
+  ``half_r``: host sequences of L integers (1 <= L <= 8), the squared xy radius in cells (0..1024) and the rotation
+  half-width in bins (0..4, 2 half_r + 1 <= R) of L threshold pairs; ``centres``: None or an int32 [K, 3] table of
+  (r, a, b) rows on the same device, K <= 64 (``vote_peaks``' index; a row with a component out of range, such as its
+  -1 rows, is empty) -> (best_index int32 [L, 3], best_log_mass f32 [L], centre_log_mass f32 [K, L], gt_log_mass f32
+  [L], stats f32 [4] = (log_z, max x, 0, 0), count int32 [4] = (contributing cells, NaN or +inf cells, ground truth
+  valid, 0), maps f32 [L, R, Ho, Wo] or None).  Over the finite cells, with e = exp(scale * v - max) and S = sum e in
+  float64, the log mass of level l at a cell is fl32(min(0, log(sum of e over the ball) - log S)), the ball being the
+  cells within ``half_r[l]`` rotations (circular) and squared distance ``rho2[l]`` (clipped to the volume); -inf for a
+  ball without a finite cell.  best_index / best_log_mass: the cell of the largest log mass per level (compared as
+  f32, then the lower flat index; -1 rows and -inf without a finite cell): the pose of maximum expected recall.
+  centre_log_mass: the log mass at each centre, -inf for an empty row.  ``gt_index``: None or a device f32 [3] =
+  (k, i, j) (``exhaustive_tfm_to_index``), rounded to the nearest cell on the device as ``vote_credible`` does;
+  gt_log_mass is NaN without a valid one.  ``maps``: also return the log mass of every cell; the other outputs hold
+  the same bytes either way.  Every ball mass is a sum of non-negative terms (the full contract: snap_vote_recall_f32
+  in include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  _f32(votes, 'votes')
+  if votes.dim() != 3:
+    raise ValueError(f'vote_recall: votes [R, Ho, Wo], got {tuple(votes.shape)}')
+  R, Ho, Wo = votes.shape
+  dev = votes.device
+  scale = float(scale)
+  if not (scale > 0.0 and np.isfinite(scale)):
+    raise ValueError(f'vote_recall: scale must be a finite number > 0, got {scale}')
+  try:
+    rho2_h = [operator.index(v) for v in rho2]
+    half_h = [operator.index(v) for v in half_r]
+  except TypeError:
+    raise ValueError(f'vote_recall: rho2 and half_r must be sequences of integers, got {rho2} and {half_r}') from None
+  L = len(rho2_h)
+  if not (1 <= L <= 8 and len(half_h) == L and all(0 <= v <= 1024 for v in rho2_h)
+          and all(0 <= v <= 4 and 2 * v + 1 <= R for v in half_h)):
+    raise ValueError(f'vote_recall: 1 to 8 pairs with 0 <= rho2 <= 1024, 0 <= half_r <= 4 and 2 half_r + 1 <= R={R}, '
+                     f'got rho2={rho2_h} half_r={half_h}')
+  K = 0
+  if centres is not None:
+    _arg_chk(centres, 'centres', (torch.int32,), (None, 3), dev, f'vote_recall: centres int32 [K, 3] on {dev}')
+    K = int(centres.shape[0])
+    if K > 64:
+      raise ValueError(f'vote_recall: at most 64 centres, got {K}')
+  if gt_index is not None:
+    _f32(gt_index, 'gt_index')
+    if tuple(gt_index.shape) != (3,) or gt_index.device != dev:
+      raise ValueError(f'vote_recall: gt_index f32 [3] on {dev}, got {tuple(gt_index.shape)} on {gt_index.device}')
+  words = _workspace_words(
+      lib.snap_vote_recall_workspace_bytes, (R, Ho, Wo, K, L), votes.numel(),
+      f'vote_recall: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  ws = torch.empty((words,), dtype=torch.int64, device=dev)
+  best_index = torch.empty((L, 3), dtype=torch.int32, device=dev)
+  best_log_mass = torch.empty((L,), dtype=torch.float32, device=dev)
+  centre_log_mass = torch.empty((K, L), dtype=torch.float32, device=dev)
+  gt_log_mass = torch.empty((L,), dtype=torch.float32, device=dev)
+  stats = torch.empty((4,), dtype=torch.float32, device=dev)
+  count = torch.empty((4,), dtype=torch.int32, device=dev)
+  out_maps = torch.empty((L, R, Ho, Wo), dtype=torch.float32, device=dev) if maps else None
+  host_rho2 = (ctypes.c_int32 * L)(*rho2_h)
+  host_half = (ctypes.c_int32 * L)(*half_h)
+  # algorithmic bytes: two reads of the volume (maximum, weights), one write of the float64 weights, then per level
+  # 2 half_r + 1 reads of them (the rows' halo re-reads hit in cache) and, with maps, one f32 write
+  n = votes.numel()
+  nbytes = 4.0 * n * 2 + 8.0 * n + sum(8.0 * n * (2 * h + 1) for h in half_h) + (4.0 * n * L if maps else 0.0)
+  with _region('vote_recall', 0.0, nbytes):
+    st = lib.snap_vote_recall_f32(_p(votes), R, Ho, Wo, scale, host_rho2, host_half, L, _p(centres) if K else None, K,
+                                  _p(gt_index), _p(best_index), _p(best_log_mass), _p(centre_log_mass) if K else None,
+                                  _p(gt_log_mass), _p(stats), _p(count), _p(out_maps), _p(ws), ws.numel() * 8,
+                                  _stream())
+  _lib.check(st, 'snap_vote_recall_f32')
+  return best_index, best_log_mass, centre_log_mass, gt_log_mass, stats, count, out_maps
 
 
 def vote_fuse(volumes, shifts, weights=None):

@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4)
 """
 import math
 import os
@@ -544,10 +544,46 @@ def vote_modes_c4(iters):
   emit_json(res)
 
 
+def vote_recall_c4(iters):
+  """The expected recall of the C4 vote volume (R = 36, 511 x 511, the low-overlap border -inf; the reference's three
+  threshold pairs (0.5 m, 1 deg), (1 m, 2 deg), (2 m, 4 deg) at 0.25 m cells and 10 degree bins = rho2 (3, 15, 63),
+  half_r 0; K = 16 peaks of ops.vote_peaks as centres): whole ops.vote_recall calls, without and with the maps, beside
+  whole ops.vote_posterior calls on the same votes, blocks alternated, medians of single calls.  One JSON line;
+  `json=<path>` as a third argument also writes it to that file."""
+  R, H, scale, K = 36, 256, 8.0, 16
+  rho2, half_r = (3, 15, 63), (0, 0, 0)
+  Ho = Wo = 2 * H - 1
+  g = torch.Generator(device='cuda').manual_seed(0)
+  votes = torch.randn((R, Ho, Wo), device='cuda', generator=g) * 0.25
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  votes = torch.where((ov[:, None] * ov[None, :] > 0.05 * H * H)[None], votes, float('-inf')).contiguous()
+  peaks = ops.vote_peaks(votes, K, 2, 4)[0]
+  best_index, best_lm, centre_lm, _, stats, count, _ = ops.vote_recall(votes, rho2, half_r, peaks, scale)
+  log_z = ops.vote_posterior(votes, scale)[2][0]
+  assert abs(float(stats[0]) - float(log_z)) <= 1e-4 * abs(float(log_z)) and int(count[0]) > 0
+  assert bool((best_index >= 0).all()) and bool((best_lm <= 0).all()) and bool((best_lm[1:] >= best_lm[:-1]).all())
+  assert bool((centre_lm <= best_lm[None] + 1e-6).all()) and bool(torch.isfinite(centre_lm).all())
+  recall = lambda: ops.vote_recall(votes, rho2, half_r, peaks, scale)
+  with_maps = lambda: ops.vote_recall(votes, rho2, half_r, peaks, scale, maps=True)
+  post = lambda: ops.vote_posterior(votes, scale)
+  n = max(iters, 5)
+  (r_ms, rs), (m_ms, ms), (p_ms, ps) = alternated_blocks(((recall, 3, n), (with_maps, 3, n), (post, 3, n)))
+  res = dict(case='vote_recall_c4', shape=[R, Ho, Wo], K=K, rho2=list(rho2), half_r=list(half_r), scale=scale,
+             best_recall=[round(float(v), 6) for v in best_lm.exp()], vote_recall_call_ms=round(r_ms, 4),
+             vote_recall_call_ms_blocks=[round(v, 4) for v in rs], vote_recall_maps_call_ms=round(m_ms, 4),
+             vote_recall_maps_call_ms_blocks=[round(v, 4) for v in ms], vote_posterior_call_ms=round(p_ms, 4),
+             vote_posterior_call_ms_blocks=[round(v, 4) for v in ps], ratio_to_vote_posterior=round(r_ms / p_ms, 2),
+             workspace_bytes=int(ops._lib.load().snap_vote_recall_workspace_bytes(R, Ho, Wo, K, len(rho2))),
+             timing='whole wrapper calls (torch.empty outputs and workspace, the ctypes call, the launches) between '
+             'device events on an idle stream, NOT kernel time; median of single calls, 5 blocks of each alternated, '
+             'median block; no threshold is set on this case')
+  emit_json(res)
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
   {'pose_score': pose_score, 'pose_score_c4': pose_score_c4, 'voting_c4': voting_c4,
    'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4,
    'vote_filter_c4': vote_filter_c4, 'vote_smooth_c4': vote_smooth_c4,
-   'vote_refine_c4': vote_refine_c4, 'vote_modes_c4': vote_modes_c4}[which](iters)
+   'vote_refine_c4': vote_refine_c4, 'vote_modes_c4': vote_modes_c4, 'vote_recall_c4': vote_recall_c4}[which](iters)
