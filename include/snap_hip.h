@@ -1357,6 +1357,54 @@ int snap_vote_recall_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, 
                          float* stats, int32_t* count, float* maps, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* The MOTION BETWEEN TWO FRAMES from their votes: the joint posterior over the integer index shift between the previous
+ * frame's pose distribution and the current frame's votes, the one input every sequence operator above takes from
+ * outside.  prev[R,Ho,Wo] f32: the previous frame's log-space distribution (a belief of snap_vote_filter_f32 with
+ * scale_prev = 1, or a vote volume with its temperature); cur[R,Ho,Wo] f32: the current frame's votes; shifts[U,R,3]
+ * i32 on the DEVICE or NULL with U = 0: row (u, r) = (k, i, j), candidate increment u seen from rotation r
+ * (pose_exhaustive_voting.increment_lattice); log_table[2Kr+1,R,2S+1,2S+1] f32; log_evidence[U] f32 (may be NULL with
+ * U = 0); best[1] i32; stats[4] f32; count[6] i32.
+ *   MASSES (snap_vote_filter_f32's PREDICT rule, with a scale).  For a volume v with scale s: M = the largest finite
+ *   cell; d = v - M, ONE f32 subtraction; the cell has mass fl32(exp((double)s * (double)d)) iff v is finite and
+ *   (double)s * (double)d >= -40, else exactly 0.  NaN and +-inf cells have no mass; NaN and +inf cells are counted.
+ *   p = the masses of prev, q = those of cur, zp and zq their float64 sums.
+ *   TABLE.  For k in [-Kr, Kr], r in [0, R), i, j in [-S, S]:
+ *     T[k][r][i][j] = sum over (a, b) of q[r, a, b] * p[(r + k) mod R, a + i, b + j]   (float64; a source cell outside
+ *   the plane contributes nothing), motion_taps' indexing: the current pose (r, a, b) has its previous pose at
+ *   (r + dk, a + da(r), b + db(r)).  Both factors are f32, so every product is exact in float64 and T is a sum of
+ *   exact non-negative terms: only the order of the sum can change a bit.
+ *   log_table[k + Kr][r][i + S][j + S] = fl32((log T - log zp) - log zq); -inf where T == 0.
+ *   CANDIDATES.  A row (k, i, j) is INSIDE the window iff -Kr <= k <= Kr, -S <= i <= S and -S <= j <= S (as given: k is
+ *   not wrapped).  E[u] = sum over r = 0 .. R-1, in that order, of T[k][r][i][j] at row (u, r); a row outside the window
+ *   adds 0, is counted, and no address is formed from it.  log_evidence[u] = fl32((log E[u] - log zp) - log zq), -inf
+ *   where E[u] == 0.
+ *   best[0] = the lowest u with the largest log_evidence (compared as stored), -1 when none is finite.
+ *   stats[4] = { log zp + scale_prev * M_prev; log zq + scale_cur * M_cur (the log-sum-exp of the scaled volume over its
+ *   cells with mass); log sum over the finite u of exp((double)log_evidence[u]), as m + log sum exp(. - m) with m the
+ *   largest; log_evidence[best] }, float64 rounded once; -inf where empty.
+ *   count[6] = { cells of prev with mass; NaN or +inf cells of prev; cells of cur with mass; NaN or +inf cells of cur;
+ *   shift rows outside the window; candidates with a finite log_evidence }.
+ * METHOD.  The masses are written once as two f32 volumes.  The hot launch: a workgroup owns one (k, r) and a band of
+ * rows; per tile it stages the q tile and the (tile + 2 S) halo of p in LDS as f32; a thread keeps the accumulators of
+ * one column shift j and a block of consecutive row shifts i in float64 registers and walks the tile column by column,
+ * the p values it needs being a sliding window down one LDS column (one LDS read of p and one broadcast read of q per
+ * block of fmas); tiles whose q or p is all zero, and cells whose q is zero, are skipped (they add exact zeros).  Band
+ * partials are folded in band order by a second launch.  No atomics; every float64 sum's order is a function of
+ * (R, Ho, Wo, Kr, S, U) alone, so two calls with the same arguments give the same bytes.  Every element of every output
+ * is written by every call; the workspace needs no initialisation.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31, 0 <= Kr with 2 Kr + 1 <= R, 0 <= S <= 32, U >= 0 (with U == 0
+ * only the table is produced: best = -1, stats[2] = stats[3] = -inf), else SNAP_ERR_BAD_SHAPE; a NULL pointer other than
+ * (with U = 0) shifts / log_evidence SNAP_ERR_NULL; a scale that is not a finite number > 0 SNAP_ERR_UNSUPPORTED; a short
+ * or not 8-byte aligned workspace SNAP_ERR_WORKSPACE; all before any launch.  workspace:
+ * snap_vote_odometry_workspace_bytes() bytes (0 = unsupported arguments): the two mass volumes, the band partials and
+ * the float64 table, 105.1 MB at R = 36, 511 x 511, Kr = 2, S = 16.  Asynchronous on `stream`, no host synchronisation;
+ * the caller owns every buffer. */
+size_t snap_vote_odometry_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t Kr, int32_t S, int32_t U);
+int snap_vote_odometry_f32(const float* prev, const float* cur, float scale_prev, float scale_cur,
+                           const int32_t* shifts, int32_t R, int32_t Ho, int32_t Wo, int32_t Kr, int32_t S, int32_t U,
+                           float* log_table, float* log_evidence, int32_t* best, float* stats, int32_t* count,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* Most likely pose TRACK over vote volumes: one forward step of the max-product (Viterbi) recursion that goes with the
  * filter above, with back-pointers.  score_prev[R,Ho,Wo] f32 is the log score of the best path into every pose of the
  * previous frame (-inf = no path), or NULL (the first frame of a track); votes[R,Ho,Wo] f32; on the DEVICE:

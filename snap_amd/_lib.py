@@ -292,6 +292,9 @@ SIGNATURES = {
     'snap_vote_recall_workspace_bytes': (c_size, [c_int] * 5),
     'snap_vote_recall_f32': (
         c_int, [ptr, c_int, c_int, c_int, c_float, ptr, ptr, c_int, ptr, c_int] + [ptr] * 9 + [c_size, ptr]),
+    'snap_vote_odometry_workspace_bytes': (c_size, [c_int] * 6),
+    'snap_vote_odometry_f32': (
+        c_int, [ptr, ptr, c_float, c_float, ptr] + [c_int] * 6 + [ptr] * 6 + [c_size, ptr]),
     'snap_vote_viterbi_workspace_bytes': (c_size, [c_int] * 6),
     'snap_vote_viterbi_f32': (
         c_int, [ptr, ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float] * 3 + [ptr] * 5 + [c_size, ptr]),

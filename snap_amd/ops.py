@@ -2459,6 +2459,64 @@ def vote_recall(votes, rho2, half_r, centres=None, scale=1.0, gt_index=None, map
   return best_index, best_log_mass, centre_log_mass, gt_log_mass, stats, count, out_maps
 
 
+def vote_odometry(prev, cur, Kr, S, shifts=None, scale_prev=1.0, scale_cur=1.0):
+  """The motion between two frames from their votes: ``prev`` [R, Ho, Wo] f32 the previous frame's log-space pose
+  distribution (a filter belief, or a vote volume with its temperature as ``scale_prev``), ``cur`` [R, Ho, Wo] f32 the
+  current frame's votes, ``Kr`` / ``S`` the half-widths of the window in rotation bins (2 Kr + 1 <= R) and cells
+  (<= 32), ``shifts``: None or an int32 [U, R, 3] table of (k, i, j) rows on the same device
+  (``pose_exhaustive_voting.increment_lattice``) -> (log_table f32 [2 Kr + 1, R, 2 S + 1, 2 S + 1], log_evidence f32
+  [U], best int32 [1], stats f32 [4], count int32 [6]).  With the masses p, q of the two volumes (the filter's predict
+  rule: exp(scale * (v - max)) rounded to f32, 0 below e^-40 and for a cell that is not finite) and their sums zp, zq:
+  T[k][r][i][j] = sum_(a, b) q[r, a, b] p[(r + k) mod R, a + i, b + j] in float64, log_table = log(T / (zp zq));
+  log_evidence[u] = log(sum_r T[shifts[u, r]] / (zp zq)), a row outside the window adding 0; best = the first arg-max
+  (-1 when none is finite); stats = (log-sum-exp of scale_prev * prev, of scale_cur * cur, log sum_u
+  exp(log_evidence), log_evidence[best]); count = (cells of prev with mass, NaN / +inf cells of prev, the same two of
+  cur, shift rows outside the window, finite candidates) (the full contract: snap_vote_odometry_f32 in
+  include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  _f32(prev, 'prev')
+  _f32(cur, 'cur')
+  if prev.dim() != 3 or prev.shape != cur.shape or prev.device != cur.device:
+    raise ValueError(f'vote_odometry: prev and cur [R, Ho, Wo] on one device, got {tuple(prev.shape)} on {prev.device} '
+                     f'and {tuple(cur.shape)} on {cur.device}')
+  R, Ho, Wo = prev.shape
+  dev = prev.device
+  try:
+    Kr, S = operator.index(Kr), operator.index(S)
+  except TypeError:
+    raise ValueError(f'vote_odometry: Kr and S must be integers, got {Kr} and {S}') from None
+  if not (0 <= Kr and 2 * Kr + 1 <= R and 0 <= S <= 32):
+    raise ValueError(f'vote_odometry: 0 <= Kr with 2 Kr + 1 <= R={R} and 0 <= S <= 32, got Kr={Kr} S={S}')
+  scale_prev, scale_cur = float(scale_prev), float(scale_cur)
+  if not (scale_prev > 0.0 and np.isfinite(scale_prev) and scale_cur > 0.0 and np.isfinite(scale_cur)):
+    raise ValueError(f'vote_odometry: scales must be finite numbers > 0, got {scale_prev} and {scale_cur}')
+  U = 0
+  if shifts is not None:
+    _arg_chk(shifts, 'shifts', (torch.int32,), (None, R, 3), dev, f'vote_odometry: shifts int32 [U, {R}, 3] on {dev}')
+    U = int(shifts.shape[0])
+    if U * R * 3 >= 2 ** 31:
+      raise ValueError(f'vote_odometry: {U} candidates of {R} rows do not fit an int32 index')
+  words = _workspace_words(
+      lib.snap_vote_odometry_workspace_bytes, (R, Ho, Wo, Kr, S, U), prev.numel(),
+      f'vote_odometry: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  ws = torch.empty((words,), dtype=torch.int64, device=dev)
+  W = 2 * S + 1
+  log_table = torch.empty((2 * Kr + 1, R, W, W), dtype=torch.float32, device=dev)
+  log_evidence = torch.empty((U,), dtype=torch.float32, device=dev)
+  best = torch.empty((1,), dtype=torch.int32, device=dev)
+  stats = torch.empty((4,), dtype=torch.float32, device=dev)
+  count = torch.empty((6,), dtype=torch.int32, device=dev)
+  # float64 fmas: every cell of cur against its window of prev; algorithmic bytes: two reads of both volumes, one
+  # write and (2 Kr + 1) reads of the masses (the halo re-reads hit in cache)
+  n = prev.numel()
+  with _region('vote_odometry', 2.0 * n * (2 * Kr + 1) * W * W, 4.0 * n * (4 + 2 + 2 * (2 * Kr + 1))):
+    st = lib.snap_vote_odometry_f32(_p(prev), _p(cur), scale_prev, scale_cur, _p(shifts) if U else None, R, Ho, Wo,
+                                    Kr, S, U, _p(log_table), _p(log_evidence) if U else None, _p(best), _p(stats),
+                                    _p(count), _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_odometry_f32')
+  return log_table, log_evidence, best, stats, count
+
+
 def vote_fuse(volumes, shifts, weights=None):
   """Multi-frame fusion of aligned vote volumes: volumes [N, R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked),
   shifts f32 [N, R, 3] = (dk, da, db) on the same device (``pose_exhaustive_voting.sequence_shift_table``), weights

@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4 | vote_odometry_c4)
 """
 import math
 import os
@@ -580,10 +580,64 @@ def vote_recall_c4(iters):
   emit_json(res)
 
 
+def vote_odometry_c4(iters):
+  """The increment posterior at the C4 vote volume (R = 36, 511 x 511, the low-overlap border -inf; prev = the belief
+  of one filter step at temperature 8, cur = the next frame's votes at scale 8: every unmasked cell carries mass, the
+  dense case in which no tile is skipped; Kr = 2, S = 16, U = 5 x 33 x 33 candidates with one (k, i, j) for all
+  rotations): whole ops.vote_odometry calls beside whole ops.vote_filter calls (Tk = 4, Ta = Tb = 8) on the same
+  volumes, blocks alternated, medians of single calls.  One JSON line; `json=<path>` as a third argument also writes it
+  to that file."""
+  import numpy as np
+  from snap_amd.models import pose_exhaustive_voting as pev
+  from snap_amd.utils import geometry, grids
+  R, H, scale, Kr, S = 36, 256, 8.0, 2, 16
+  Ho = Wo = 2 * H - 1
+  grid = grids.Grid2D((H, H), 0.2)
+  g = torch.Generator(device='cuda').manual_seed(0)
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  keep = (ov[:, None] * ov[None, :] > 0.05 * H * H)[None]
+  frames = [torch.where(keep, torch.randn((R, Ho, Wo), device='cuda', generator=g) * 0.25, float('-inf')).contiguous()
+            for _ in range(2)]
+  belief = pev.filter_votes(None, frames[0], None, grid, R, 0.2, np.deg2rad(2.0), temperature=scale)['belief']
+  votes = frames[1]
+  k, i, j = torch.meshgrid(torch.arange(-Kr, Kr + 1), torch.arange(-S, S + 1), torch.arange(-S, S + 1), indexing='ij')
+  rows = torch.stack((k.reshape(-1), i.reshape(-1), j.reshape(-1)), -1).to(torch.int32)
+  shifts = rows[:, None, :].expand(-1, R, -1).contiguous().cuda()
+  U = int(shifts.shape[0])
+  log_table, log_evidence, best, stats, count = ops.vote_odometry(belief, votes, Kr, S, shifts, 1.0, scale)
+  assert U == 5 * 33 * 33 and int(count[4]) == 0 and int(count[5]) == U and bool((log_table <= 0).all())
+  # candidate u sums its table entry over the rotations
+  want = torch.logsumexp(log_table.double(), 1).reshape(-1)
+  assert float((log_evidence.double() - want).abs().max()) < 1e-5 and int(best[0]) == int(log_evidence.argmax())
+  step = geometry.Transform2D(torch.tensor(np.deg2rad(5.0)), torch.tensor([0.93, 0.37], dtype=torch.float64))
+  taps = pev.motion_taps(step, grid, R, 0.2, np.deg2rad(2.0), device='cuda')
+  odo = lambda: ops.vote_odometry(belief, votes, Kr, S, shifts, 1.0, scale)
+  flt = lambda: ops.vote_filter(belief, votes, taps, scale, 1e-3)
+  n = max(iters, 3)
+  (o_ms, os_), (f_ms, fs) = alternated_blocks(((odo, 3, n), (flt, 3, n)))
+  W = 2 * S + 1
+  fma_nominal = R * Ho * Wo * (2 * Kr + 1) * W * W           # every cell of cur against its whole window
+  fma_mass = int(count[2]) * (2 * Kr + 1) * W * W            # the cells of cur with mass: the fmas that are issued
+  peak = 78.6e12 / 2                                         # MI355X float64 vector peak, 78.6 TFLOP/s = 39.3e12 fma/s
+  res = dict(case='vote_odometry_c4', shape=[R, Ho, Wo], Kr=Kr, S=S, U=U, scale=scale,
+             cells_with_mass=[int(count[0]), int(count[2])], vote_odometry_call_ms=round(o_ms, 3),
+             vote_odometry_call_ms_blocks=[round(v, 3) for v in os_], vote_filter_call_ms=round(f_ms, 4),
+             vote_filter_call_ms_blocks=[round(v, 4) for v in fs], ratio_to_vote_filter=round(o_ms / f_ms, 1),
+             f64_fma_nominal=fma_nominal, f64_fma_on_cells_with_mass=fma_mass,
+             share_of_f64_vector_peak=round(fma_mass / (o_ms * 1e-3) / peak, 4),
+             workspace_bytes=int(ops._lib.load().snap_vote_odometry_workspace_bytes(R, Ho, Wo, Kr, S, U)),
+             timing='whole wrapper calls (torch.empty outputs and workspace, the ctypes call, the six launches) between '
+             'device events on an idle stream, NOT kernel time; median of single calls, 5 blocks of each alternated, '
+             'median block; the share counts the fmas on cells of cur with mass against 39.3e12 float64 fma/s (the '
+             '78.6 TFLOP/s vector peak of the data sheet); untuned; no threshold is set on this case')
+  emit_json(res)
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
   {'pose_score': pose_score, 'pose_score_c4': pose_score_c4, 'voting_c4': voting_c4,
    'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4,
    'vote_filter_c4': vote_filter_c4, 'vote_smooth_c4': vote_smooth_c4,
-   'vote_refine_c4': vote_refine_c4, 'vote_modes_c4': vote_modes_c4, 'vote_recall_c4': vote_recall_c4}[which](iters)
+   'vote_refine_c4': vote_refine_c4, 'vote_modes_c4': vote_modes_c4, 'vote_recall_c4': vote_recall_c4,
+   'vote_odometry_c4': vote_odometry_c4}[which](iters)
