@@ -1,12 +1,14 @@
 // Device and host pieces shared by the operators on the exhaustive vote volume (vote_peaks.hip, vote_posterior.hip,
 // vote_fuse.hip, vote_filter.hip, vote_smooth.hip, vote_pairs.hip, vote_viterbi.hip, vote_sample.hip, vote_refine.hip,
-// vote_credible.hip, vote_modes.hip, vote_recall.hip, vote_odometry.hip).  The family's contract is "no floating-point atomics; every floating-point sum's order is a
-// function of the shape alone; two calls give the same bits" (vote_credible.hip alone uses atomics, INTEGER ones: uint64
-// adds of fixed-point mass and int minima / maxima / counts, exact in any order), and vote_filter is tested
-// against vote_fuse and vote_posterior bit for bit: the predicates, reductions, tile walk and circular indices those
-// comparisons rest on exist once, here.  No kernels in this file (vote_predict.h and vote_ratio.h, built on it, hold the
-// kernels several operators launch).  -ffp-contract=off is in force, so one expression gives one set of bits wherever
-// it is inlined.
+// vote_credible.hip, vote_modes.hip, vote_recall.hip, vote_odometry.hip).  The family's contract is "no floating-point
+// atomics; every floating-point sum's order is a function of the shape alone; two calls give the same bits"
+// (vote_credible.hip alone uses atomics, INTEGER ones: uint64 adds of fixed-point mass and int minima / maxima /
+// counts, exact in any order), and vote_filter is tested against vote_fuse and vote_posterior bit for bit: the
+// predicates, reductions, tile walk and circular indices those comparisons rest on exist once, here.  So do the two
+// pieces vote_credible.hip and vote_recall.hip share: the scan for the largest finite vote and the counts
+// (vote_scan_max) and the rounding of a ground-truth index to its cell (vote_gt_cell).  No kernels in this file
+// (vote_predict.h and vote_ratio.h, built on it, hold the kernels several operators launch).  -ffp-contract=off is in
+// force, so one expression gives one set of bits wherever it is inlined.
 #ifndef SNAP_CSRC_VOTE_COMMON_H_
 #define SNAP_CSRC_VOTE_COMMON_H_
 
@@ -220,6 +222,50 @@ __device__ __forceinline__ int vote_next(int k, int R) { return k + 1 == R ? 0 :
 __device__ __forceinline__ int vote_mod(int v, int R) {   // v mod R in [0, R), mathematically, for any v
   const int k = (int)((int64_t)v % R);
   return k < 0 ? k + R : k;
+}
+
+// ------------------------------- the contributing-cell scan -----------------------------------
+// This thread's share of the tile walk over a volume: the largest finite vote (-inf when none), the count of finite
+// votes and the count of NaN / +inf ones (-inf is a masked cell: neither).  The caller reduces the three over its
+// workgroup (vote_block_max, vote_block_count_pair).
+template <int NT>
+__device__ __forceinline__ void vote_scan_max(const float* __restrict__ votes, int P, int tpp, int tiles, float* m,
+                                              int* n_ok, int* n_bad) {
+  float vmax = -INFINITY;                   // (locals, handed out once: accumulators behind the pointers end in scratch)
+  int ok = 0, bad = 0;
+  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    int r, p;
+    if (vote_tile_cell<NT>(tile, tpp, P, &r, &p)) {
+      const float v = votes[(size_t)r * P + p];
+      if (vote_finite(v)) {
+        vmax = fmaxf(vmax, v);
+        ++ok;
+      } else if (!(v == -INFINITY)) {
+        ++bad;                              // NaN or +inf
+      }
+    }
+  }
+  *m = vmax;
+  *n_ok = ok;
+  *n_bad = bad;
+}
+
+// ------------------------------- the ground-truth cell ----------------------------------------
+// The cell nearest to a ground-truth index gt = (k, i, j) (f32 [3] on the device, or NULL): rintf on k (half to even)
+// and the mathematical modulo in the rotation, rint in double on i and j.  False when gt is NULL, not finite,
+// |k| > 2^20 or (i, j) outside [0, Ho - 1] x [0, Wo - 1]; (r, a, b) are written only with true.
+__device__ __forceinline__ bool vote_gt_cell(const float* __restrict__ gt, int R, int Ho, int Wo, int* r, int* a,
+                                             int* b) {
+  if (gt == nullptr) return false;
+  const float k = gt[0], i = gt[1], j = gt[2];
+  if (!(vote_finite(k) && vote_finite(i) && vote_finite(j))) return false;
+  if (!(fabsf(k) <= 1048576.f && (double)i >= 0.0 && (double)i <= (double)(Ho - 1) && (double)j >= 0.0 &&
+        (double)j <= (double)(Wo - 1)))
+    return false;
+  *r = vote_mod((int)rintf(k), R);
+  *a = (int)rint((double)i);                // in range: no overflow
+  *b = (int)rint((double)j);
+  return true;
 }
 
 // ------------------------------- host: the launch plan ----------------------------------------

@@ -71,19 +71,14 @@ __device__ __forceinline__ u64 cr_wave_sum(u64 v) {
   return v;
 }
 
-// The ground-truth cell's vote, NaN when the index is invalid (or the pointer NULL).
+// The ground-truth cell's vote (vote_gt_cell), NaN when the index is invalid (or the pointer NULL) or the vote is not
+// finite.
 __device__ __forceinline__ float cr_gt_vote(const float* __restrict__ votes, const float* __restrict__ gt, int R, int Ho,
                                             int Wo) {
   const float nan = __int_as_float(0x7fc00000);
-  if (gt == nullptr) return nan;
-  const float k = gt[0], i = gt[1], j = gt[2];
-  if (!(vote_finite(k) && vote_finite(i) && vote_finite(j))) return nan;
-  if (!(fabsf(k) <= 1048576.f && (double)i >= 0.0 && (double)i <= (double)(Ho - 1) && (double)j >= 0.0 &&
-        (double)j <= (double)(Wo - 1)))
-    return nan;
-  const int kk = vote_mod((int)rintf(k), R);
-  const int64_t ii = (int64_t)rint((double)i), jj = (int64_t)rint((double)j);   // round half to even; in range
-  const float v = votes[((size_t)kk * Ho + (size_t)ii) * Wo + (size_t)jj];
+  int r, a, b;
+  if (!vote_gt_cell(gt, R, Ho, Wo, &r, &a, &b)) return nan;
+  const float v = votes[((size_t)r * Ho + (size_t)a) * Wo + (size_t)b];
   return vote_finite(v) ? v : nan;
 }
 
@@ -96,20 +91,9 @@ __global__ __launch_bounds__(CR_NT) void vote_credible_max_kernel(const float* _
   __shared__ int shc[CR_WAVES][2];
   for (int i = blockIdx.x * CR_NT + threadIdx.x; i < CR_DIGITS * CR_MAX_L * CR_BINS; i += gridDim.x * CR_NT)
     gbins[i] = 0;                           // the digit passes add into them
-  float m = -INFINITY;
-  int n_ok = 0, n_bad = 0;
-  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int r, p;
-    if (vote_tile_cell<CR_NT>(tile, tpp, P, &r, &p)) {
-      const float v = votes[(size_t)r * P + p];
-      if (vote_finite(v)) {
-        m = fmaxf(m, v);
-        ++n_ok;
-      } else if (!(v == -INFINITY)) {
-        ++n_bad;                            // NaN or +inf
-      }
-    }
-  }
+  float m;
+  int n_ok, n_bad;
+  vote_scan_max<CR_NT>(votes, P, tpp, tiles, &m, &n_ok, &n_bad);
   m = vote_block_max<CR_WAVES>(m, shm);
   const int c = vote_block_count_pair<CR_WAVES>(n_ok, n_bad, shc);
   if (threadIdx.x == 0) fpart[blockIdx.x] = m;

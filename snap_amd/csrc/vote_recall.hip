@@ -76,41 +76,15 @@ __device__ __forceinline__ float rc_log_mass(double mass, double log_s) {
   return (float)(q > 0.0 ? 0.0 : q);
 }
 
-// The ground-truth cell, by vote_credible's rounding (rintf / rint: half to even, mathematical modulo in the
-// rotation): false when gt is NULL, not finite, |k| > 2^20 or (i, j) outside [0, Ho - 1] x [0, Wo - 1].
-__device__ __forceinline__ bool rc_gt_cell(const float* __restrict__ gt, int R, int Ho, int Wo, int* r, int* a, int* b) {
-  if (gt == nullptr) return false;
-  const float k = gt[0], i = gt[1], j = gt[2];
-  if (!(vote_finite(k) && vote_finite(i) && vote_finite(j))) return false;
-  if (!(fabsf(k) <= 1048576.f && (double)i >= 0.0 && (double)i <= (double)(Ho - 1) && (double)j >= 0.0 &&
-        (double)j <= (double)(Wo - 1)))
-    return false;
-  *r = vote_mod((int)rintf(k), R);
-  *a = (int)rint((double)i);
-  *b = (int)rint((double)j);
-  return true;
-}
-
 // ---- launch 1: the largest contributing vote and the counts, per workgroup
 __global__ __launch_bounds__(RC_NT) void vote_recall_max_kernel(const float* __restrict__ votes, int P, int tpp,
                                                                 int tiles, float* __restrict__ fpart,
                                                                 int32_t* __restrict__ cpart) {
   __shared__ float shm[RC_WAVES];
   __shared__ int shc[RC_WAVES][2];
-  float m = -INFINITY;
-  int n_ok = 0, n_bad = 0;
-  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    int r, p;
-    if (vote_tile_cell<RC_NT>(tile, tpp, P, &r, &p)) {
-      const float v = votes[(size_t)r * P + p];
-      if (vote_finite(v)) {
-        m = fmaxf(m, v);
-        ++n_ok;
-      } else if (!(v == -INFINITY)) {
-        ++n_bad;                            // NaN or +inf
-      }
-    }
-  }
+  float m;
+  int n_ok, n_bad;
+  vote_scan_max<RC_NT>(votes, P, tpp, tiles, &m, &n_ok, &n_bad);
   m = vote_block_max<RC_WAVES>(m, shm);
   const int c = vote_block_count_pair<RC_WAVES>(n_ok, n_bad, shc);
   if (threadIdx.x == 0) fpart[blockIdx.x] = m;
@@ -265,7 +239,7 @@ __global__ __launch_bounds__(RC_NT) void vote_recall_centres_kernel(
     out = centre_lm + (size_t)k * L + l;
     none = -INFINITY;
   } else {
-    ok = rc_gt_cell(gt, R, Ho, Wo, &r, &a, &b);
+    ok = vote_gt_cell(gt, R, Ho, Wo, &r, &a, &b);   // (vote_credible's cell: one rule)
     out = gt_lm + l;
     none = __int_as_float(0x7fc00000);
     if (l == 0 && t == 0) count[2] = ok ? 1 : 0;

@@ -283,13 +283,29 @@ def exhaustive_indices_to_tfm(indices, grid, num_rotations):
   return geometry.Transform2D(torch.where(empty, nan, angle), torch.where(empty[:, None], nan, t))
 
 
+def _check_planes(fn, volume, num_rotations, name=None):
+  """``volume`` holds one plane per rotation; with ``name`` (the track operators' wording) it is also [R, Ho, Wo]."""
+  if name is None:
+    if volume.shape[0] != num_rotations:
+      raise ValueError(f'{fn}: {volume.shape[0]} vote planes for {num_rotations} rotations')
+  elif volume.dim() != 3 or volume.shape[0] != num_rotations:
+    raise ValueError(f'{fn}: {name} [{num_rotations}, Ho, Wo], got {tuple(volume.shape)}')
+
+
+def _gt_index(m_t_q_gt, grid, num_rotations, device):
+  """A ground-truth pose (or None) -> its ``exhaustive_tfm_to_index`` as f32 [3] on ``device`` (or None)."""
+  if m_t_q_gt is None:
+    return None
+  gt = exhaustive_tfm_to_index(m_t_q_gt, grid, num_rotations).to(device=device, dtype=torch.float32)
+  return gt.reshape(3).contiguous()
+
+
 def poses_from_votes(votes, grid, num_rotations, num_peaks=16, radius_r=1, radius_xy=1):
   """The ``num_peaks`` best distinct poses of a vote volume [R, 2H-1, 2W-1] (``ops.vote_peaks``: non-maximum
   suppression over ``radius_r`` rotations, circular, and ``radius_xy`` cells) -> dict(map_t_query Transform2D [K],
   index int32 [K, 3], score f32 [K], count int32 [2] = (peaks found; NaN votes)).  Best first; rows past
   ``count[0]`` hold index -1, score -inf and a NaN transform."""
-  if votes.shape[0] != num_rotations:
-    raise ValueError(f'poses_from_votes: {votes.shape[0]} vote planes for {num_rotations} rotations')
+  _check_planes('poses_from_votes', votes, num_rotations)
   index, score, count = ops.vote_peaks(votes.contiguous(), num_peaks, radius_r, radius_xy)
   return dict(map_t_query=exhaustive_indices_to_tfm(index, grid, num_rotations), index=index, score=score,
               count=count)
@@ -309,12 +325,8 @@ def posterior_from_votes(votes, grid, num_rotations, temperature=1.0, m_t_q_gt=N
   With ``m_t_q_gt`` (a Transform2D, map corner frame): ``nll`` = -log p interpolated at ``exhaustive_tfm_to_index``
   of it (computed and read on the device) and ``nll_valid`` (bool; ``nll`` is NaN where it is False: the pose lies
   outside the volume or touches a masked cell)."""
-  if votes.shape[0] != num_rotations:
-    raise ValueError(f'posterior_from_votes: {votes.shape[0]} vote planes for {num_rotations} rotations')
-  gt = None
-  if m_t_q_gt is not None:
-    gt = exhaustive_tfm_to_index(m_t_q_gt, grid, num_rotations).to(device=votes.device, dtype=torch.float32)
-    gt = gt.reshape(3).contiguous()
+  _check_planes('posterior_from_votes', votes, num_rotations)
+  gt = _gt_index(m_t_q_gt, grid, num_rotations, votes.device)
   log_prob_xy, log_prob_r, stats, count = ops.vote_posterior(votes.contiguous(), temperature, gt)
   cell2 = float(grid.cell_size) ** 2
   out = dict(
@@ -341,12 +353,8 @@ def credible_from_votes(votes, grid, num_rotations, levels=(0.5, 0.9, 0.99), tem
   device): ``gt_credibility`` = the mass ranked strictly above the true pose's cell (uniform on [0, 1] for a calibrated
   posterior; NaN where invalid), ``gt_level`` (the smallest l whose region holds it, L = none, -1 = invalid),
   ``gt_valid`` (bool: inside the volume, on a contributing cell) and ``covered`` [L] bool."""
-  if votes.shape[0] != num_rotations:
-    raise ValueError(f'credible_from_votes: {votes.shape[0]} vote planes for {num_rotations} rotations')
-  gt = None
-  if m_t_q_gt is not None:
-    gt = exhaustive_tfm_to_index(m_t_q_gt, grid, num_rotations).to(device=votes.device, dtype=torch.float32)
-    gt = gt.reshape(3).contiguous()
+  _check_planes('credible_from_votes', votes, num_rotations)
+  gt = _gt_index(m_t_q_gt, grid, num_rotations, votes.device)
   levels = tuple(float(q) for q in levels)
   threshold, mass, table, level_xy, level_r, level_cell, gt_stats, count = ops.vote_credible(
       votes.contiguous(), levels, temperature, gt, cell_levels)
@@ -423,17 +431,13 @@ def modes_from_votes(votes, grid, num_rotations, peaks=None, num_peaks=16, radiu
   map corner frame): ``nees`` [K], the ground truth's normalised estimation error squared under each mode in index
   units with the lattice's I/12 added to the covariance (chi^2 with 3 degrees of freedom for a consistent mode:
   ``nees_table``)."""
-  if votes.shape[0] != num_rotations:
-    raise ValueError(f'modes_from_votes: {votes.shape[0]} vote planes for {num_rotations} rotations')
+  _check_planes('modes_from_votes', votes, num_rotations)
   votes = votes.contiguous()
   if peaks is None:
     peaks = poses_from_votes(votes, grid, num_rotations, num_peaks, radius_r, radius_xy)['index']
   win_r = radius_r if win_r is None else win_r
   win_xy = radius_xy if win_xy is None else win_xy
-  gt = None
-  if m_t_q_gt is not None:
-    gt = exhaustive_tfm_to_index(m_t_q_gt, grid, num_rotations).to(device=votes.device, dtype=torch.float32)
-    gt = gt.reshape(3).contiguous()
+  gt = _gt_index(m_t_q_gt, grid, num_rotations, votes.device)
   if log_z is None:
     log_z = ops.vote_posterior(votes, temperature)[2][0]
   stats, count = ops.vote_modes(votes, peaks.contiguous(), win_r, win_xy, temperature, gt)
@@ -545,13 +549,9 @@ def recall_from_votes(votes, grid, num_rotations, thresholds=RECALL_THRESHOLDS, 
   device): ``gt_recall`` [L], the probability within the thresholds of the true pose, a smooth counterpart of the
   hit / miss metric (NaN where the truth lies outside the volume).  With ``maps``: ``maps`` [L, R, 2H-1, 2W-1], the log
   of that probability for every lattice pose."""
-  if votes.shape[0] != num_rotations:
-    raise ValueError(f'recall_from_votes: {votes.shape[0]} vote planes for {num_rotations} rotations')
+  _check_planes('recall_from_votes', votes, num_rotations)
   rho2, half_r = recall_thresholds(thresholds, grid, num_rotations)
-  gt = None
-  if m_t_q_gt is not None:
-    gt = exhaustive_tfm_to_index(m_t_q_gt, grid, num_rotations).to(device=votes.device, dtype=torch.float32)
-    gt = gt.reshape(3).contiguous()
+  gt = _gt_index(m_t_q_gt, grid, num_rotations, votes.device)
   best_index, best_lm, centre_lm, gt_lm, stats, count, lm_maps = ops.vote_recall(
       votes.contiguous(), rho2.tolist(), half_r.tolist(), None if peaks is None else peaks.contiguous(), temperature,
       gt, maps)
@@ -916,13 +916,22 @@ def motion_taps(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, truncate=3
   ``ops.vote_fuse``'s own split (1 - f, f).  Entries below 2^-20 are set to 0 and the row renormalised, in float64;
   rounded to f32 once.  Built on the host (a transform on the device is read back: one synchronisation); raises
   ValueError where rho is beyond the kernel's tables (Tk <= 16, Ta, Tb <= 32)."""
+  return _motion_tables(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, truncate, device, log=False)
+
+
+def _motion_tables(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, truncate, device, log):
+  """``motion_taps`` (``log`` False) and ``motion_log_taps`` (True): ``_motion_axes``' float64 tables rounded to f32
+  once -- for ``log`` then float32(log(float64(w))), -inf for w = 0 -- and uploaded with the int32 offsets in one
+  table."""
   R = int(num_rotations)
-  angle = torch.as_tensor(cur_t_prev.angle)
   if device is None:
-    device = angle.device
+    device = torch.as_tensor(cur_t_prev.angle).device
   (wk, lk), (wa, la), (wb, lb) = _motion_axes(cur_t_prev, grid, R, sigma_xy, sigma_yaw, truncate)
   # one upload: the three f32 tables, then the int32 offsets
   f32 = np.concatenate([wk.reshape(-1), wa.reshape(-1), wb.reshape(-1)]).astype(np.float32)
+  if log:
+    with np.errstate(divide='ignore'):
+      f32 = np.log(f32.astype(np.float64)).astype(np.float32)
   off = np.stack([la, lb], -1).astype(np.int32)
   blob = ops.upload_table(np.concatenate([f32.view(np.uint8), off.reshape(-1).view(np.uint8)]), device)
   tab = blob[:f32.nbytes].view(torch.float32)
@@ -931,13 +940,17 @@ def motion_taps(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, truncate=3
           blob[f32.nbytes:].view(torch.int32).view(R, 2))
 
 
-@functools.lru_cache(maxsize=16)
-def _still_taps(R, device):
-  """One tap of weight 1 at offset 0 on every axis (the tables of a call without a predict step)."""
+@functools.lru_cache(maxsize=32)
+def _still_tables(fill, R, device):
+  """One tap of value ``fill`` at offset 0 on every axis: the tables of a call without a predict step."""
   dev = torch.device(device)
-  one = torch.ones((R, 1), dtype=torch.float32, device=dev)
-  return torch.ones((1,), dtype=torch.float32, device=dev), 0, one, one.clone(), torch.zeros((R, 2), dtype=torch.int32,
-                                                                                                device=dev)
+  tap = torch.full((R, 1), fill, dtype=torch.float32, device=dev)
+  return (torch.full((1,), fill, dtype=torch.float32, device=dev), 0, tap, tap.clone(),
+          torch.zeros((R, 2), dtype=torch.int32, device=dev))
+
+
+_still_taps = functools.partial(_still_tables, 1.0)       # weight 1: ``vote_filter``'s
+_still_log_taps = functools.partial(_still_tables, 0.0)   # log-weight 0: ``vote_viterbi``'s
 
 
 def filter_votes(belief, votes, cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0,
@@ -952,8 +965,7 @@ def filter_votes(belief, votes, cur_t_prev, grid, num_rotations, sigma_xy, sigma
   ``posterior_from_votes`` / ``refine_poses``), ``log_evidence`` (of the frame under the predicted prior),
   ``mass_kept`` (the share of the previous belief that stayed inside the volume), ``count`` int32 [4] and ``stats``
   f32 [4] (the op's raw rows)."""
-  if votes.dim() != 3 or votes.shape[0] != num_rotations:
-    raise ValueError(f'filter_votes: votes [{num_rotations}, Ho, Wo], got {tuple(votes.shape)}')
+  _check_planes('filter_votes', votes, num_rotations, 'votes')
   if belief is None:
     taps = _still_taps(int(num_rotations), str(votes.device))
   else:
@@ -976,8 +988,7 @@ def smooth_votes(belief, smoothed_next, next_t_cur, grid, num_rotations, sigma_x
   so the tables are the filter's bit for bit -> dict of device tensors: ``smoothed`` [R, 2H-1, 2W-1] (normalised
   log-probabilities of p(x_t | all frames)), ``log_norm`` (0 up to rounding where beliefs and increment belong
   together), ``mass_kept`` (the filter's, of that step), ``count`` int32 [4] and ``stats`` f32 [4] (the op's raw rows)."""
-  if belief.dim() != 3 or belief.shape[0] != num_rotations:
-    raise ValueError(f'smooth_votes: belief [{num_rotations}, Ho, Wo], got {tuple(belief.shape)}')
+  _check_planes('smooth_votes', belief, num_rotations, 'belief')
   taps = motion_taps(next_t_cur, grid, num_rotations, sigma_xy, sigma_yaw, truncate, device=belief.device)
   out, stats, count = ops.vote_smooth(belief.contiguous(), smoothed_next.contiguous(), taps, uniform_mix)
   return dict(smoothed=out, log_norm=stats[0], mass_kept=stats[1], count=count, stats=stats)
@@ -1017,8 +1028,7 @@ def pair_statistics(belief, smoothed_next, next_t_cur, grid, num_rotations, sigm
   table), ``stay`` and ``jump`` (they sum to 1: ``jump`` is the share of the step's posterior that went through the
   uniform mix, i.e. the track was lost and re-acquired), ``log_norm`` (0 up to rounding where the arguments belong
   together), ``mass_kept``, ``count`` int32 [4], ``stats`` float64 [4], and ``taps``, the tuple used."""
-  if belief.dim() != 3 or belief.shape[0] != num_rotations:
-    raise ValueError(f'pair_statistics: belief [{num_rotations}, Ho, Wo], got {tuple(belief.shape)}')
+  _check_planes('pair_statistics', belief, num_rotations, 'belief')
   taps = motion_taps(next_t_cur, grid, num_rotations, sigma_xy, sigma_yaw, truncate, device=belief.device)
   hist_k, hist_a, hist_b, stats, count = ops.vote_pairs(belief.contiguous(), smoothed_next.contiguous(), taps,
                                                         uniform_mix)
@@ -1520,8 +1530,7 @@ def sample_votes(votes, grid, num_rotations, num, seed, stream=0, temperature=1.
   [num] (the linear lattice index, -1 when no cell has mass), ``indices`` int32 [num, 3] = (r, a, b), ``m_t_q``
   (``exhaustive_indices_to_tfm`` of the indices: Transform2D [num], the cells' centre poses, no sub-cell jitter),
   ``log_prob`` f32 [num] (of the drawn cells), ``count`` int32 [2] and ``stats`` f32 [2] (the op's raw rows)."""
-  if votes.dim() != 3 or votes.shape[0] != num_rotations:
-    raise ValueError(f'sample_votes: votes [{num_rotations}, Ho, Wo], got {tuple(votes.shape)}')
+  _check_planes('sample_votes', votes, num_rotations, 'votes')
   linear, log_prob, stats, count = ops.vote_sample(votes.contiguous(), num, seed, stream, temperature)
   indices = _linear_to_indices(linear, votes.shape)
   return dict(linear=linear, indices=indices, m_t_q=exhaustive_indices_to_tfm(indices, grid, num_rotations),
@@ -1536,8 +1545,7 @@ def sample_back(belief, nxt, next_t_cur, grid, num_rotations, sigma_xy, sigma_ya
   ``smooth_votes``: the tables are the filter's bit for bit) -> dict of device tensors: ``linear`` int32 [B] (the
   chains' cells at frame t, -1 = none), ``jumped`` int32 [B] (1: the step was the uniform jump, 0: transported, -1: no
   predecessor), ``mass_kept``, ``count`` int32 [3] and ``stats`` f32 [2] (the op's raw rows)."""
-  if belief.dim() != 3 or belief.shape[0] != num_rotations:
-    raise ValueError(f'sample_back: belief [{num_rotations}, Ho, Wo], got {tuple(belief.shape)}')
+  _check_planes('sample_back', belief, num_rotations, 'belief')
   taps = motion_taps(next_t_cur, grid, num_rotations, sigma_xy, sigma_yaw, truncate, device=belief.device)
   prev, jumped, stats, count = ops.vote_sample_back(belief.contiguous(), nxt.contiguous(), taps, uniform_mix, seed,
                                                     stream)
@@ -1577,37 +1585,7 @@ def motion_log_taps(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, trunca
   rounding of every tap w to f32, then float32(log(float64(w))), -inf for w = 0 -> (ltaps_k f32 [Tk], lk int, ltaps_a
   f32 [R, Ta], ltaps_b f32 [R, Tb], offsets int32 [R, 2]) on ``device``; the offsets are ``motion_taps``' own.  Every
   entry is -inf or a finite number <= 0.  Built on the host, one upload."""
-  R = int(num_rotations)
-  angle = torch.as_tensor(cur_t_prev.angle)
-  if angle.numel() != 1:
-    raise ValueError(f'motion_log_taps: one increment, got a transform of shape {tuple(angle.shape)}')
-  if device is None:
-    device = angle.device
-  host = geometry.Transform2D(angle.detach().to('cpu', torch.float64), torch.as_tensor(cur_t_prev.t).detach().to(
-      'cpu', torch.float64))
-  dk, da, db = (v.numpy() for v in _shift_table_f64(host, grid, R))
-  cell = float(grid.cell_size)
-  wk, lk = _axis_taps(dk, float(sigma_yaw) * R / (2 * math.pi), truncate, FILTER_MAX_TAPS_K, 'rotation')
-  wa, la = _axis_taps(da[0], float(sigma_xy) / cell, truncate, FILTER_MAX_TAPS_XY, 'rows')
-  wb, lb = _axis_taps(db[0], float(sigma_xy) / cell, truncate, FILTER_MAX_TAPS_XY, 'columns')
-  f32 = np.concatenate([wk.reshape(-1), wa.reshape(-1), wb.reshape(-1)]).astype(np.float32)   # motion_taps' bits
-  with np.errstate(divide='ignore'):
-    f32 = np.log(f32.astype(np.float64)).astype(np.float32)
-  off = np.stack([la, lb], -1).astype(np.int32)
-  blob = ops.upload_table(np.concatenate([f32.view(np.uint8), off.reshape(-1).view(np.uint8)]), device)
-  tab = blob[:f32.nbytes].view(torch.float32)
-  nk, na = wk.size, wa.size
-  return (tab[:nk], int(lk[0]), tab[nk:nk + na].view(R, -1), tab[nk + na:].view(R, -1),
-          blob[f32.nbytes:].view(torch.int32).view(R, 2))
-
-
-@functools.lru_cache(maxsize=16)
-def _still_log_taps(R, device):
-  """One log-tap of 0 at offset 0 on every axis (``_still_taps`` in the log domain)."""
-  dev = torch.device(device)
-  zero = torch.zeros((R, 1), dtype=torch.float32, device=dev)
-  return (torch.zeros((1,), dtype=torch.float32, device=dev), 0, zero, zero.clone(),
-          torch.zeros((R, 2), dtype=torch.int32, device=dev))
+  return _motion_tables(cur_t_prev, grid, num_rotations, sigma_xy, sigma_yaw, truncate, device, log=True)
 
 
 def _viterbi_log_weights(uniform_mix, n):
@@ -1631,8 +1609,7 @@ def viterbi_votes(score, votes, cur_t_prev, grid, num_rotations, sigma_xy, sigma
   ``VoteViterbi.path``: ``log_taps`` (the table tuple) and ``log_weights`` = (log_stay, log_jump) as Python floats.
   The transition is max((1 - eps) T, eps / n): log_stay = float32(log1p(-eps)), log_jump = float32(log(eps) - log(n)),
   eps = ``uniform_mix``."""
-  if votes.dim() != 3 or votes.shape[0] != num_rotations:
-    raise ValueError(f'viterbi_votes: votes [{num_rotations}, Ho, Wo], got {tuple(votes.shape)}')
+  _check_planes('viterbi_votes', votes, num_rotations, 'votes')
   log_stay, log_jump = _viterbi_log_weights(uniform_mix, votes.numel())
   if score is None:
     taps = _still_log_taps(int(num_rotations), str(votes.device))

@@ -2228,6 +2228,60 @@ def template_finalize(raw, cnt, tcount, R, threshold, use_overlap=True):
   return scores
 
 
+# The argument checks of the vote-volume operators, each stated once (with ``_vote_taps`` and ``_vote_draws`` below).
+# Every message starts with the operator's name.
+def _vote_volume(op, t, name):
+  """``t`` is an f32 [R, Ho, Wo] volume on a ROCm GPU, by ``_chk``'s rules (TypeError for no tensor or another dtype,
+  RuntimeError for a CPU tensor) -> (R, Ho, Wo)."""
+  _f32(t, f'{op}: {name}')
+  if t.dim() != 3:
+    raise ValueError(f'{op}: {name} [R, Ho, Wo], got {tuple(t.shape)}')
+  return tuple(t.shape)
+
+
+def _vote_volume_arg(op, t, name, like=None):
+  """``t`` is an f32 [R, Ho, Wo] volume on a ROCm GPU -- with ``like``: of that volume's shape, on its device -- by
+  ``_arg_chk``'s rules (ValueError throughout) -> (R, Ho, Wo)."""
+  if like is None:
+    _arg_chk(t, f'{op}: {name}', (torch.float32,), (None, None, None), None,
+             f'{op}: {name} f32 [R, Ho, Wo] on a ROCm GPU')
+  else:
+    _arg_chk(t, f'{op}: {name}', (torch.float32,), tuple(like.shape), like.device,
+             f'{op}: {name} {torch.float32} {list(like.shape)} on {like.device}')
+  return tuple(t.shape)
+
+
+def _vote_scale(op, scale):
+  """float(scale) where it is > 0 and finite as the f32 the C side receives (below 2^128), else ValueError."""
+  scale = float(scale)
+  if not (scale > 0.0 and np.isfinite(ctypes.c_float(scale).value)):
+    raise ValueError(f'{op}: scale must be a finite number > 0, got {scale}')
+  return scale
+
+
+def _vote_uniform_mix(op, uniform_mix):
+  uniform_mix = float(uniform_mix)
+  if not 0.0 <= uniform_mix <= 1.0:
+    raise ValueError(f'{op}: uniform_mix must lie in [0, 1], got {uniform_mix}')
+  return uniform_mix
+
+
+def _vote_gt_index(op, gt_index, device):
+  """``gt_index`` is None or an f32 [3] tensor on ``device``."""
+  if gt_index is not None:
+    _f32(gt_index, f'{op}: gt_index')
+    if tuple(gt_index.shape) != (3,) or gt_index.device != device:
+      raise ValueError(f'{op}: gt_index f32 [3] on {device}, got {tuple(gt_index.shape)} on {gt_index.device}')
+
+
+def _vote_unsupported(op, R, Ho, Wo, taps=None):
+  """The refusal text of a workspace query: the plain-volume limits, with ``taps`` = (Tk, Ta, Tb) the tap operators'."""
+  if taps is None:
+    return f'{op}: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)'
+  return (f'{op}: unsupported R={R} Ho={Ho} Wo={Wo} Tk={taps[0]} Ta={taps[1]} Tb={taps[2]} (1 <= R <= 64, '
+          'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+
+
 def vote_peaks(votes, k, radius_r=1, radius_xy=1):
   """The ``k`` best peaks of a vote volume: votes [R, Ho, Wo] f32 -> (index int32 [k, 3] = (r, a, b), score f32 [k],
   count int32 [2] = (peaks found, clipped to k; NaN votes seen)).  A peak beats every other cell within
@@ -2235,10 +2289,7 @@ def vote_peaks(votes, k, radius_r=1, radius_xy=1):
   flat index"; the list is ordered by value descending, then flat index ascending; rows past the found count
   hold -1 / -inf (the full contract: snap_vote_peaks_f32 in include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  _f32(votes, 'votes')
-  if votes.dim() != 3:
-    raise ValueError(f'vote_peaks: votes [R, Ho, Wo], got {tuple(votes.shape)}')
-  R, Ho, Wo = votes.shape
+  R, Ho, Wo = _vote_volume('vote_peaks', votes, 'votes')
   k, radius_r, radius_xy = int(k), int(radius_r), int(radius_xy)
   words = _workspace_words(
       lib.snap_vote_peaks_workspace_bytes, (R, Ho, Wo, k, radius_r, radius_xy), votes.numel(),
@@ -2265,21 +2316,11 @@ def vote_posterior(votes, scale=1.0, gt_index=None):
   contract: snap_vote_posterior_f32 in include/snap_hip.h).  ``scale * v`` must stay below the f32 maximum for every
   finite vote (not checked: that would read the volume); beyond it the outputs are NaN.  No host synchronisation."""
   lib = _lib.load()
-  _f32(votes, 'votes')
-  if votes.dim() != 3:
-    raise ValueError(f'vote_posterior: votes [R, Ho, Wo], got {tuple(votes.shape)}')
-  R, Ho, Wo = votes.shape
-  scale = float(scale)
-  if not (scale > 0.0 and np.isfinite(scale)):
-    raise ValueError(f'vote_posterior: scale must be a finite number > 0, got {scale}')
-  if gt_index is not None:
-    _f32(gt_index, 'gt_index')
-    if tuple(gt_index.shape) != (3,) or gt_index.device != votes.device:
-      raise ValueError(f'vote_posterior: gt_index f32 [3] on {votes.device}, got {tuple(gt_index.shape)} on '
-                       f'{gt_index.device}')
-  words = _workspace_words(
-      lib.snap_vote_posterior_workspace_bytes, (R, Ho, Wo), votes.numel(),
-      f'vote_posterior: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  R, Ho, Wo = _vote_volume('vote_posterior', votes, 'votes')
+  scale = _vote_scale('vote_posterior', scale)
+  _vote_gt_index('vote_posterior', gt_index, votes.device)
+  words = _workspace_words(lib.snap_vote_posterior_workspace_bytes, (R, Ho, Wo), votes.numel(),
+                           _vote_unsupported('vote_posterior', R, Ho, Wo))
   ws = torch.empty((words,), dtype=torch.int64, device=votes.device)
   log_prob_xy = torch.empty((Ho, Wo), dtype=torch.float32, device=votes.device)
   log_prob_r = torch.empty((R,), dtype=torch.float32, device=votes.device)
@@ -2305,25 +2346,15 @@ def vote_credible(votes, levels, scale=1.0, gt_index=None, cell_levels=False):
   = (k, i, j) (``exhaustive_tfm_to_index``), rounded to the nearest cell on the device (the full contract:
   snap_vote_credible_f32 in include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  _f32(votes, 'votes')
-  if votes.dim() != 3:
-    raise ValueError(f'vote_credible: votes [R, Ho, Wo], got {tuple(votes.shape)}')
-  R, Ho, Wo = votes.shape
-  scale = float(scale)
-  if not (scale > 0.0 and np.isfinite(scale)):
-    raise ValueError(f'vote_credible: scale must be a finite number > 0, got {scale}')
+  R, Ho, Wo = _vote_volume('vote_credible', votes, 'votes')
+  scale = _vote_scale('vote_credible', scale)
   q = np.asarray(levels, dtype=np.float32).reshape(-1)
   L = int(q.size)
   if not (1 <= L <= 8 and bool(np.all(q > 0)) and bool(np.all(q < 1)) and bool(np.all(np.diff(q) > 0))):
     raise ValueError(f'vote_credible: levels must be 1 to 8 strictly increasing numbers inside (0, 1), got {levels}')
-  if gt_index is not None:
-    _f32(gt_index, 'gt_index')
-    if tuple(gt_index.shape) != (3,) or gt_index.device != votes.device:
-      raise ValueError(f'vote_credible: gt_index f32 [3] on {votes.device}, got {tuple(gt_index.shape)} on '
-                       f'{gt_index.device}')
-  words = _workspace_words(
-      lib.snap_vote_credible_workspace_bytes, (R, Ho, Wo, L), votes.numel(),
-      f'vote_credible: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  _vote_gt_index('vote_credible', gt_index, votes.device)
+  words = _workspace_words(lib.snap_vote_credible_workspace_bytes, (R, Ho, Wo, L), votes.numel(),
+                           _vote_unsupported('vote_credible', R, Ho, Wo))
   dev = votes.device
   ws = torch.empty((words,), dtype=torch.int64, device=dev)
   threshold = torch.empty((L,), dtype=torch.float32, device=dev)
@@ -2357,20 +2388,12 @@ def vote_modes(votes, peaks, win_r=1, win_xy=4, scale=1.0, gt_index=None):
   (``exhaustive_tfm_to_index``), read on the device.  An empty row or a mode without finite cells: -inf masses and NaN
   moments (the full contract: snap_vote_modes_f32 in include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  _f32(votes, 'votes')
-  if votes.dim() != 3:
-    raise ValueError(f'vote_modes: votes [R, Ho, Wo], got {tuple(votes.shape)}')
-  R, Ho, Wo = votes.shape
-  _arg_chk(peaks, 'peaks', (torch.int32,), (None, 3), votes.device, f'vote_modes: peaks int32 [K, 3] on {votes.device}')
+  R, Ho, Wo = _vote_volume('vote_modes', votes, 'votes')
+  _arg_chk(peaks, 'vote_modes: peaks', (torch.int32,), (None, 3), votes.device,
+           f'vote_modes: peaks int32 [K, 3] on {votes.device}')
   K, win_r, win_xy = int(peaks.shape[0]), int(win_r), int(win_xy)
-  scale = float(scale)
-  if not (scale > 0.0 and np.isfinite(scale)):
-    raise ValueError(f'vote_modes: scale must be a finite number > 0, got {scale}')
-  if gt_index is not None:
-    _f32(gt_index, 'gt_index')
-    if tuple(gt_index.shape) != (3,) or gt_index.device != votes.device:
-      raise ValueError(f'vote_modes: gt_index f32 [3] on {votes.device}, got {tuple(gt_index.shape)} on '
-                       f'{gt_index.device}')
+  scale = _vote_scale('vote_modes', scale)
+  _vote_gt_index('vote_modes', gt_index, votes.device)
   words = _workspace_words(
       lib.snap_vote_modes_workspace_bytes, (R, Ho, Wo, K, win_r, win_xy), votes.numel(),
       f'vote_modes: unsupported R={R} Ho={Ho} Wo={Wo} K={K} win_r={win_r} win_xy={win_xy} '
@@ -2405,14 +2428,9 @@ def vote_recall(votes, rho2, half_r, centres=None, scale=1.0, gt_index=None, map
   the same bytes either way.  Every ball mass is a sum of non-negative terms (the full contract: snap_vote_recall_f32
   in include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  _f32(votes, 'votes')
-  if votes.dim() != 3:
-    raise ValueError(f'vote_recall: votes [R, Ho, Wo], got {tuple(votes.shape)}')
-  R, Ho, Wo = votes.shape
+  R, Ho, Wo = _vote_volume('vote_recall', votes, 'votes')
   dev = votes.device
-  scale = float(scale)
-  if not (scale > 0.0 and np.isfinite(scale)):
-    raise ValueError(f'vote_recall: scale must be a finite number > 0, got {scale}')
+  scale = _vote_scale('vote_recall', scale)
   try:
     rho2_h = [operator.index(v) for v in rho2]
     half_h = [operator.index(v) for v in half_r]
@@ -2425,17 +2443,14 @@ def vote_recall(votes, rho2, half_r, centres=None, scale=1.0, gt_index=None, map
                      f'got rho2={rho2_h} half_r={half_h}')
   K = 0
   if centres is not None:
-    _arg_chk(centres, 'centres', (torch.int32,), (None, 3), dev, f'vote_recall: centres int32 [K, 3] on {dev}')
+    _arg_chk(centres, 'vote_recall: centres', (torch.int32,), (None, 3), dev,
+             f'vote_recall: centres int32 [K, 3] on {dev}')
     K = int(centres.shape[0])
     if K > 64:
       raise ValueError(f'vote_recall: at most 64 centres, got {K}')
-  if gt_index is not None:
-    _f32(gt_index, 'gt_index')
-    if tuple(gt_index.shape) != (3,) or gt_index.device != dev:
-      raise ValueError(f'vote_recall: gt_index f32 [3] on {dev}, got {tuple(gt_index.shape)} on {gt_index.device}')
-  words = _workspace_words(
-      lib.snap_vote_recall_workspace_bytes, (R, Ho, Wo, K, L), votes.numel(),
-      f'vote_recall: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  _vote_gt_index('vote_recall', gt_index, dev)
+  words = _workspace_words(lib.snap_vote_recall_workspace_bytes, (R, Ho, Wo, K, L), votes.numel(),
+                           _vote_unsupported('vote_recall', R, Ho, Wo))
   ws = torch.empty((words,), dtype=torch.int64, device=dev)
   best_index = torch.empty((L, 3), dtype=torch.int32, device=dev)
   best_log_mass = torch.empty((L,), dtype=torch.float32, device=dev)
@@ -2474,8 +2489,8 @@ def vote_odometry(prev, cur, Kr, S, shifts=None, scale_prev=1.0, scale_cur=1.0):
   cur, shift rows outside the window, finite candidates) (the full contract: snap_vote_odometry_f32 in
   include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  _f32(prev, 'prev')
-  _f32(cur, 'cur')
+  _f32(prev, 'vote_odometry: prev')
+  _f32(cur, 'vote_odometry: cur')
   if prev.dim() != 3 or prev.shape != cur.shape or prev.device != cur.device:
     raise ValueError(f'vote_odometry: prev and cur [R, Ho, Wo] on one device, got {tuple(prev.shape)} on {prev.device} '
                      f'and {tuple(cur.shape)} on {cur.device}')
@@ -2487,18 +2502,20 @@ def vote_odometry(prev, cur, Kr, S, shifts=None, scale_prev=1.0, scale_cur=1.0):
     raise ValueError(f'vote_odometry: Kr and S must be integers, got {Kr} and {S}') from None
   if not (0 <= Kr and 2 * Kr + 1 <= R and 0 <= S <= 32):
     raise ValueError(f'vote_odometry: 0 <= Kr with 2 Kr + 1 <= R={R} and 0 <= S <= 32, got Kr={Kr} S={S}')
-  scale_prev, scale_cur = float(scale_prev), float(scale_cur)
-  if not (scale_prev > 0.0 and np.isfinite(scale_prev) and scale_cur > 0.0 and np.isfinite(scale_cur)):
-    raise ValueError(f'vote_odometry: scales must be finite numbers > 0, got {scale_prev} and {scale_cur}')
+  try:
+    scale_prev, scale_cur = _vote_scale('vote_odometry', scale_prev), _vote_scale('vote_odometry', scale_cur)
+  except ValueError:
+    raise ValueError(f'vote_odometry: scales must be finite numbers > 0, got {float(scale_prev)} and '
+                     f'{float(scale_cur)}') from None
   U = 0
   if shifts is not None:
-    _arg_chk(shifts, 'shifts', (torch.int32,), (None, R, 3), dev, f'vote_odometry: shifts int32 [U, {R}, 3] on {dev}')
+    _arg_chk(shifts, 'vote_odometry: shifts', (torch.int32,), (None, R, 3), dev,
+             f'vote_odometry: shifts int32 [U, {R}, 3] on {dev}')
     U = int(shifts.shape[0])
     if U * R * 3 >= 2 ** 31:
       raise ValueError(f'vote_odometry: {U} candidates of {R} rows do not fit an int32 index')
-  words = _workspace_words(
-      lib.snap_vote_odometry_workspace_bytes, (R, Ho, Wo, Kr, S, U), prev.numel(),
-      f'vote_odometry: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  words = _workspace_words(lib.snap_vote_odometry_workspace_bytes, (R, Ho, Wo, Kr, S, U), prev.numel(),
+                           _vote_unsupported('vote_odometry', R, Ho, Wo))
   ws = torch.empty((words,), dtype=torch.int64, device=dev)
   W = 2 * S + 1
   log_table = torch.empty((2 * Kr + 1, R, W, W), dtype=torch.float32, device=dev)
@@ -2526,14 +2543,14 @@ def vote_fuse(volumes, shifts, weights=None):
   (finite cells, NaN cells) of ``fused`` (the full contract: snap_vote_fuse_f32 in include/snap_hip.h).  No host
   synchronisation."""
   lib = _lib.load()
-  _f32(volumes, 'volumes')
+  _f32(volumes, 'vote_fuse: volumes')
   if volumes.dim() != 4:
     raise ValueError(f'vote_fuse: volumes [N, R, Ho, Wo], got {tuple(volumes.shape)}')
   N, R, Ho, Wo = volumes.shape
   for t, name, shape in ((shifts, 'shifts', (N, R, 3)), (weights, 'weights', (N,))):
     if t is None and name == 'weights':
       continue
-    _arg_chk(t, name, (torch.float32,), shape, volumes.device,
+    _arg_chk(t, f'vote_fuse: {name}', (torch.float32,), shape, volumes.device,
              f'vote_fuse: {name} f32 {list(shape)} on {volumes.device}')
   words = _workspace_words(
       lib.snap_vote_fuse_workspace_bytes, (N, R, Ho, Wo), volumes.numel(),
@@ -2563,7 +2580,7 @@ def _vote_taps(op, taps, R, device):
   Tb = taps_b.shape[1] if isinstance(taps_b, torch.Tensor) and taps_b.dim() == 2 else -1
   for t, name, dtype, shape in ((taps_k, 'taps_k', torch.float32, (Tk,)), (taps_a, 'taps_a', torch.float32, (R, Ta)),
                                 (taps_b, 'taps_b', torch.float32, (R, Tb)), (offsets, 'offsets', torch.int32, (R, 2))):
-    _arg_chk(t, name, (dtype,), shape, device, f'{op}: {name} {dtype} {list(shape)} on {device}')
+    _arg_chk(t, f'{op}: {name}', (dtype,), shape, device, f'{op}: {name} {dtype} {list(shape)} on {device}')
   return taps_k, int(lk), taps_a, taps_b, offsets, Tk, Ta, Tb
 
 
@@ -2580,22 +2597,14 @@ def vote_filter(belief, votes, taps, scale=1.0, uniform_mix=0.0):
   >= 2^-20 (not checked: ``motion_taps`` guarantees it; the full contract: snap_vote_filter_f32 in
   include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  _arg_chk(votes, 'votes', (torch.float32,), (None, None, None), None,
-           'vote_filter: votes f32 [R, Ho, Wo] on a ROCm GPU')
-  R, Ho, Wo = votes.shape
+  R, Ho, Wo = _vote_volume_arg('vote_filter', votes, 'votes')
   if belief is not None:
-    _arg_chk(belief, 'belief', (torch.float32,), (R, Ho, Wo), votes.device,
-             f'vote_filter: belief {torch.float32} {[R, Ho, Wo]} on {votes.device}')
+    _vote_volume_arg('vote_filter', belief, 'belief', votes)
   taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb = _vote_taps('vote_filter', taps, R, votes.device)
-  scale, uniform_mix = float(scale), float(uniform_mix)
-  if not (scale > 0.0 and np.isfinite(np.float32(scale))):
-    raise ValueError(f'vote_filter: scale must be a finite number > 0, got {scale}')
-  if not 0.0 <= uniform_mix <= 1.0:
-    raise ValueError(f'vote_filter: uniform_mix must lie in [0, 1], got {uniform_mix}')
-  words = _workspace_words(
-      lib.snap_vote_filter_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), votes.numel(),
-      f'vote_filter: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
-      'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  scale = _vote_scale('vote_filter', scale)
+  uniform_mix = _vote_uniform_mix('vote_filter', uniform_mix)
+  words = _workspace_words(lib.snap_vote_filter_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), votes.numel(),
+                           _vote_unsupported('vote_filter', R, Ho, Wo, (Tk, Ta, Tb)))
   ws = torch.empty((words,), dtype=torch.int64, device=votes.device)
   belief_out = torch.empty((R, Ho, Wo), dtype=torch.float32, device=votes.device)
   stats = torch.empty((4,), dtype=torch.float32, device=votes.device)
@@ -2621,19 +2630,12 @@ def vote_smooth(belief, smoothed_next, taps, uniform_mix=0.0):
   smoothed, NaN / +inf cells of belief, NaN / +inf cells of smoothed_next, cells of smoothed_next with ratio mass)
   (the full contract: snap_vote_smooth_f32 in include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  _arg_chk(belief, 'belief', (torch.float32,), (None, None, None), None,
-           'vote_smooth: belief f32 [R, Ho, Wo] on a ROCm GPU')
-  R, Ho, Wo = belief.shape
-  _arg_chk(smoothed_next, 'smoothed_next', (torch.float32,), (R, Ho, Wo), belief.device,
-           f'vote_smooth: smoothed_next {torch.float32} {[R, Ho, Wo]} on {belief.device}')
+  R, Ho, Wo = _vote_volume_arg('vote_smooth', belief, 'belief')
+  _vote_volume_arg('vote_smooth', smoothed_next, 'smoothed_next', belief)
   taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb = _vote_taps('vote_smooth', taps, R, belief.device)
-  uniform_mix = float(uniform_mix)
-  if not 0.0 <= uniform_mix <= 1.0:
-    raise ValueError(f'vote_smooth: uniform_mix must lie in [0, 1], got {uniform_mix}')
-  words = _workspace_words(
-      lib.snap_vote_smooth_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), belief.numel(),
-      f'vote_smooth: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
-      'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  uniform_mix = _vote_uniform_mix('vote_smooth', uniform_mix)
+  words = _workspace_words(lib.snap_vote_smooth_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), belief.numel(),
+                           _vote_unsupported('vote_smooth', R, Ho, Wo, (Tk, Ta, Tb)))
   ws = torch.empty((words,), dtype=torch.int64, device=belief.device)
   smoothed = torch.empty((R, Ho, Wo), dtype=torch.float32, device=belief.device)
   stats = torch.empty((4,), dtype=torch.float32, device=belief.device)
@@ -2660,19 +2662,12 @@ def vote_pairs(belief, smoothed_next, taps, uniform_mix=0.0):
   mass).  Without ratio mass everything but mass_kept is 0 and log_norm -inf (the full contract: snap_vote_pairs_f32 in
   include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  _arg_chk(belief, 'belief', (torch.float32,), (None, None, None), None,
-           'vote_pairs: belief f32 [R, Ho, Wo] on a ROCm GPU')
-  R, Ho, Wo = belief.shape
-  _arg_chk(smoothed_next, 'smoothed_next', (torch.float32,), (R, Ho, Wo), belief.device,
-           f'vote_pairs: smoothed_next {torch.float32} {[R, Ho, Wo]} on {belief.device}')
+  R, Ho, Wo = _vote_volume_arg('vote_pairs', belief, 'belief')
+  _vote_volume_arg('vote_pairs', smoothed_next, 'smoothed_next', belief)
   taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb = _vote_taps('vote_pairs', taps, R, belief.device)
-  uniform_mix = float(uniform_mix)
-  if not 0.0 <= uniform_mix <= 1.0:
-    raise ValueError(f'vote_pairs: uniform_mix must lie in [0, 1], got {uniform_mix}')
-  words = _workspace_words(
-      lib.snap_vote_pairs_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), belief.numel(),
-      f'vote_pairs: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
-      'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  uniform_mix = _vote_uniform_mix('vote_pairs', uniform_mix)
+  words = _workspace_words(lib.snap_vote_pairs_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), belief.numel(),
+                           _vote_unsupported('vote_pairs', R, Ho, Wo, (Tk, Ta, Tb)))
   ws = torch.empty((words,), dtype=torch.int64, device=belief.device)
   hist_k = torch.empty((Tk,), dtype=torch.float64, device=belief.device)
   hist_a = torch.empty((R, Ta), dtype=torch.float64, device=belief.device)
@@ -2702,22 +2697,15 @@ def vote_viterbi(score_prev, votes, log_taps, scale=1.0, log_stay=0.0, log_jump=
   Only f32 additions, products and comparisons: bit for bit reproducible (the full contract: snap_vote_viterbi_f32 in
   include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  _arg_chk(votes, 'votes', (torch.float32,), (None, None, None), None,
-           'vote_viterbi: votes f32 [R, Ho, Wo] on a ROCm GPU')
-  R, Ho, Wo = votes.shape
+  R, Ho, Wo = _vote_volume_arg('vote_viterbi', votes, 'votes')
   if score_prev is not None:
-    _arg_chk(score_prev, 'score_prev', (torch.float32,), (R, Ho, Wo), votes.device,
-             f'vote_viterbi: score_prev {torch.float32} {[R, Ho, Wo]} on {votes.device}')
+    _vote_volume_arg('vote_viterbi', score_prev, 'score_prev', votes)
   taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb = _vote_taps('vote_viterbi', log_taps, R, votes.device)
-  scale, log_stay, log_jump = float(scale), float(log_stay), float(log_jump)
-  if not (scale > 0.0 and np.isfinite(np.float32(scale))):
-    raise ValueError(f'vote_viterbi: scale must be a finite number > 0, got {scale}')
+  scale, log_stay, log_jump = _vote_scale('vote_viterbi', scale), float(log_stay), float(log_jump)
   if not (log_stay <= 0.0 and log_jump <= 0.0):
     raise ValueError(f'vote_viterbi: log_stay and log_jump must be <= 0 (-inf allowed), got {log_stay}, {log_jump}')
-  words = _workspace_words(
-      lib.snap_vote_viterbi_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), votes.numel(),
-      f'vote_viterbi: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
-      'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  words = _workspace_words(lib.snap_vote_viterbi_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), votes.numel(),
+                           _vote_unsupported('vote_viterbi', R, Ho, Wo, (Tk, Ta, Tb)))
   ws = torch.empty((words,), dtype=torch.int64, device=votes.device)
   score = torch.empty((R, Ho, Wo), dtype=torch.float32, device=votes.device)
   back = torch.empty((R, Ho, Wo), dtype=torch.int32, device=votes.device)
@@ -2737,9 +2725,10 @@ def vote_backstep(back, cur):
   ``back``), cur int32 [B] linear indices on the same device -> prev int32 [B] = back.flatten()[cur], -1 where cur is
   outside [0, R Ho Wo) (a chain that has ended stays ended).  One small launch, no host synchronisation."""
   lib = _lib.load()
-  _arg_chk(back, 'back', (torch.int32,), (None, None, None), None,
+  _arg_chk(back, 'vote_backstep: back', (torch.int32,), (None, None, None), None,
            'vote_backstep: back int32 [R, Ho, Wo] on a ROCm GPU')
-  _arg_chk(cur, 'cur', (torch.int32,), (None,), back.device, f'vote_backstep: cur int32 [B] on {back.device}')
+  _arg_chk(cur, 'vote_backstep: cur', (torch.int32,), (None,), back.device,
+           f'vote_backstep: cur int32 [B] on {back.device}')
   n, B = back.numel(), cur.shape[0]
   if not (1 <= n < 2 ** 31 and 1 <= B < 2 ** 31):
     raise ValueError(f'vote_backstep: 1 <= R Ho Wo < 2^31 and 1 <= B < 2^31, got {n} cells and {B} chains')
@@ -2757,7 +2746,7 @@ def _vote_draws(op, num, seed, stream, uniforms, device):
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) < hi:
       raise ValueError(f'{op}: {name} must be an integer in [{lo}, {hi}), got {v!r}')
   if uniforms is not None:
-    _arg_chk(uniforms, 'uniforms', (torch.float64,), (int(num), 2), device,
+    _arg_chk(uniforms, f'{op}: uniforms', (torch.float64,), (int(num), 2), device,
              f'{op}: uniforms {torch.float64} {[int(num), 2]} on {device}')
   return int(num), int(seed), int(stream)
 
@@ -2773,16 +2762,11 @@ def vote_sample(votes, num, seed, stream=0, scale=1.0, uniforms=None):
   arguments give the same bytes (the full contract: snap_vote_sample_f32 in include/snap_hip.h).  No host
   synchronisation."""
   lib = _lib.load()
-  _arg_chk(votes, 'votes', (torch.float32,), (None, None, None), None,
-           'vote_sample: votes f32 [R, Ho, Wo] on a ROCm GPU')
-  R, Ho, Wo = votes.shape
+  R, Ho, Wo = _vote_volume_arg('vote_sample', votes, 'votes')
   B, seed, stream = _vote_draws('vote_sample', num, seed, stream, uniforms, votes.device)
-  scale = float(scale)
-  if not (scale > 0.0 and np.isfinite(np.float32(scale))):
-    raise ValueError(f'vote_sample: scale must be a finite number > 0, got {scale}')
-  words = _workspace_words(
-      lib.snap_vote_sample_workspace_bytes, (R, Ho, Wo), votes.numel(),
-      f'vote_sample: unsupported R={R} Ho={Ho} Wo={Wo} (1 <= R <= 64, Ho, Wo >= 1, R Ho Wo < 2^31)')
+  scale = _vote_scale('vote_sample', scale)
+  words = _workspace_words(lib.snap_vote_sample_workspace_bytes, (R, Ho, Wo), votes.numel(),
+                           _vote_unsupported('vote_sample', R, Ho, Wo))
   ws = torch.empty((words,), dtype=torch.int64, device=votes.device)
   index = torch.empty((B,), dtype=torch.int32, device=votes.device)
   log_prob = torch.empty((B,), dtype=torch.float32, device=votes.device)
@@ -2809,19 +2793,14 @@ def vote_sample_back(belief, nxt, taps, uniform_mix, seed, stream=0, uniforms=No
   counter (i, stream, 1, 0); ``uniforms`` float64 [B, 2] on the device replaces it (the full contract:
   snap_vote_sample_back_f32 in include/snap_hip.h).  No host synchronisation."""
   lib = _lib.load()
-  _arg_chk(belief, 'belief', (torch.float32,), (None, None, None), None,
-           'vote_sample_back: belief f32 [R, Ho, Wo] on a ROCm GPU')
-  R, Ho, Wo = belief.shape
-  _arg_chk(nxt, 'nxt', (torch.int32,), (None,), belief.device, f'vote_sample_back: nxt int32 [B] on {belief.device}')
+  R, Ho, Wo = _vote_volume_arg('vote_sample_back', belief, 'belief')
+  _arg_chk(nxt, 'vote_sample_back: nxt', (torch.int32,), (None,), belief.device,
+           f'vote_sample_back: nxt int32 [B] on {belief.device}')
   taps_k, lk, taps_a, taps_b, offsets, Tk, Ta, Tb = _vote_taps('vote_sample_back', taps, R, belief.device)
   B, seed, stream = _vote_draws('vote_sample_back', nxt.shape[0], seed, stream, uniforms, belief.device)
-  uniform_mix = float(uniform_mix)
-  if not 0.0 <= uniform_mix <= 1.0:
-    raise ValueError(f'vote_sample_back: uniform_mix must lie in [0, 1], got {uniform_mix}')
-  words = _workspace_words(
-      lib.snap_vote_sample_back_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), belief.numel(),
-      f'vote_sample_back: unsupported R={R} Ho={Ho} Wo={Wo} Tk={Tk} Ta={Ta} Tb={Tb} (1 <= R <= 64, '
-      'Ho, Wo >= 1, R Ho Wo < 2^31, 1 <= Tk <= 16, 1 <= Ta, Tb <= 32)')
+  uniform_mix = _vote_uniform_mix('vote_sample_back', uniform_mix)
+  words = _workspace_words(lib.snap_vote_sample_back_workspace_bytes, (R, Ho, Wo, Tk, Ta, Tb), belief.numel(),
+                           _vote_unsupported('vote_sample_back', R, Ho, Wo, (Tk, Ta, Tb)))
   ws = torch.empty((words,), dtype=torch.int64, device=belief.device)
   prev = torch.empty((B,), dtype=torch.int32, device=belief.device)
   jumped = torch.empty((B,), dtype=torch.int32, device=belief.device)
@@ -2847,15 +2826,15 @@ def plane_align_score(fq, vq, fm, vm, poses, threshold):
   snap_plane_align_score_f32 in include/snap_hip.h).  No atomics, the same bits on every call and for every grouping
   of the poses.  No host synchronisation."""
   lib = _lib.load()
-  _f32(fq, 'fq'); _f32(fm, 'fm')
+  _f32(fq, 'plane_align_score: fq'); _f32(fm, 'plane_align_score: fm')
   if fq.dim() != 3 or fm.dim() != 3 or fq.shape[-1] != fm.shape[-1]:
     raise ValueError(f'plane_align_score: fq [Hq, Wq, D] and fm [Hm, Wm, D], got {tuple(fq.shape)} / {tuple(fm.shape)}')
   Hq, Wq, D = fq.shape
   Hm, Wm = fm.shape[:2]
   for t, name, shape in ((vq, 'vq', (Hq, Wq)), (vm, 'vm', (Hm, Wm))):
-    _arg_chk(t, name, (torch.bool, torch.uint8), shape, fq.device,
+    _arg_chk(t, f'plane_align_score: {name}', (torch.bool, torch.uint8), shape, fq.device,
              f'plane_align_score: {name} bool / uint8 {list(shape)} on {fq.device}')
-  _arg_chk(poses, 'poses', (torch.float32,), (None, 4), fq.device,
+  _arg_chk(poses, 'plane_align_score: poses', (torch.float32,), (None, 4), fq.device,
            f'plane_align_score: poses f32 [P, 4] and fm on {fq.device}', also=fm.device == fq.device,
            tail=f' / {fm.device}')
   P = poses.shape[0]
