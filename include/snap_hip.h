@@ -1405,6 +1405,47 @@ int snap_vote_odometry_f32(const float* prev, const float* cur, float scale_prev
                            float* log_table, float* log_evidence, int32_t* best, float* stats, int32_t* count,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* A vote volume or belief carried into ANOTHER MAP FRAME.  Every transporting operator above composes a motion on the
+ * query side (m_t_prev = m_t_cur @ cur_t_prev: a shift per rotation); a change of map frame composes on the left,
+ * n_t_q = n_t_m @ m_t_q, which in index space is a constant circular shift in the rotation and ONE affine map of every
+ * plane (pose_exhaustive_voting.rebase_table).  The operator gathers.  src[R,Ho,Wo] f32: a log-space vote volume or
+ * belief (-inf = impossible pose); scale > 0 (the temperature); dk in [0, R) and A00, A01, A10, A11, oa, ob: the table,
+ * float64 by value; dst[R,Ho,Wo] f32 (must not overlap src); stats[4] FLOAT64; count[4] i32.
+ *   MASSES.  M = the largest finite value of src (exact).  A source cell v has the mass p = fl32(exp((double)scale *
+ *   ((double)v - (double)M))), exactly 0 for v = -inf; a NaN or +inf cell is a caller error, counted, and poisons the
+ *   cells that read it.
+ *   GATHER, float64 per destination cell (r, a, b), the expressions exactly as written (no contraction):
+ *     k = (double)r - dk, k0 = floor(k), fk = k - k0: the planes k0 mod R (mathematical modulo) and its circular successor;
+ *     sa = (A00 * a + A01 * b) + oa, sb = (A10 * a + A11 * b) + ob, each with its floor and fraction;
+ *   the axis weights are (1 - f, f) and the weight of a tap is (wk * wa) * wb.  A tap is SKIPPED when its weight is
+ *   exactly 0 or it lies outside [0, Ho) x [0, Wo): an identity or a whole-cell shift reads exactly one cell.  The cell's
+ *   mass is the float64 sum of weight * p over its taps in the order k, then a, then b, from 0, rounded to f32 once; NaN
+ *   when one of its taps is a NaN or +inf cell.  S = the float64 sum of the f32 cell masses that are not NaN.
+ *   dst = fl32(log((double)mass) - log(S)); -inf where the mass is 0; NaN stays NaN (0x7fc00000).  With S == 0 every
+ *   cell that is not NaN is -inf.
+ *   stats = { (double)scale * M + log(sum p): the log-sum-exp of scale * src over its finite cells (-inf without one);
+ *   S / sum p, the share of the mass that arrived (0 when sum p == 0); M (-inf without a finite cell); the largest dst
+ *   (NaN cells aside; -inf when there is none) }; sum p is the float64 sum of the f32 masses of the cells that are not
+ *   NaN or +inf.
+ *   count = { finite cells of dst; NaN cells of dst; NaN or +inf cells of src; cells of dst with no tap of non-zero
+ *   weight inside the volume (what the old frame did not cover) }.
+ * Four launches of 256 threads: the peak; the gather, a tile = 16 x 16 cells of one rotation's plane whose footprint in
+ * both source planes (at most 24 x 24 cells each for a rotation) is staged in LDS as masses, so exp runs once per
+ * staged cell and the 8-tap blend reads LDS (a table whose footprint is larger reads the source directly: same
+ * expressions, same result); the normalisation in place; the statistics.  No atomics: everything above the cell is
+ * float64 (counts int32) in an order fixed by (R, Ho, Wo), so two calls give the same bits.  Every element of dst, stats
+ * and count is written by every call.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31; anything else returns SNAP_ERR_BAD_SHAPE before any launch (a
+ * NULL pointer SNAP_ERR_NULL, checked first; a scale that is not a finite number > 0, a dk outside [0, R) or a table
+ * entry that is not finite SNAP_ERR_UNSUPPORTED; a short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE).
+ * workspace: snap_vote_rebase_workspace_bytes() bytes (0 = unsupported shape): the per-workgroup partials only; it needs
+ * no initialisation and no launch touches a byte beyond that size.  Asynchronous on `stream`; the caller owns every
+ * buffer. */
+size_t snap_vote_rebase_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo);
+int snap_vote_rebase_f32(const float* src, int32_t R, int32_t Ho, int32_t Wo, float scale, double dk, double A00,
+                         double A01, double A10, double A11, double oa, double ob, float* dst, double* stats,
+                         int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Most likely pose TRACK over vote volumes: one forward step of the max-product (Viterbi) recursion that goes with the
  * filter above, with back-pointers.  score_prev[R,Ho,Wo] f32 is the log score of the best path into every pose of the
  * previous frame (-inf = no path), or NULL (the first frame of a track); votes[R,Ho,Wo] f32; on the DEVICE:

@@ -15,6 +15,7 @@ c_int = ctypes.c_int32
 c_i64 = ctypes.c_int64
 c_u64 = ctypes.c_uint64
 c_float = ctypes.c_float
+c_double = ctypes.c_double
 c_size = ctypes.c_size_t
 ptr = ctypes.c_void_p
 
@@ -295,6 +296,9 @@ SIGNATURES = {
     'snap_vote_odometry_workspace_bytes': (c_size, [c_int] * 6),
     'snap_vote_odometry_f32': (
         c_int, [ptr, ptr, c_float, c_float, ptr] + [c_int] * 6 + [ptr] * 6 + [c_size, ptr]),
+    'snap_vote_rebase_workspace_bytes': (c_size, [c_int] * 3),
+    'snap_vote_rebase_f32': (
+        c_int, [ptr, c_int, c_int, c_int, c_float] + [c_double] * 7 + [ptr] * 4 + [c_size, ptr]),
     'snap_vote_viterbi_workspace_bytes': (c_size, [c_int] * 6),
     'snap_vote_viterbi_f32': (
         c_int, [ptr, ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float] * 3 + [ptr] * 5 + [c_size, ptr]),
@@ -395,7 +399,7 @@ SIGNATURES = {
     ),
 }
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _lib = None
 

@@ -979,6 +979,57 @@ def _no_motion():
   return geometry.Transform2D(torch.zeros((), dtype=torch.float64), torch.zeros(2, dtype=torch.float64))
 
 
+def rebase_table(new_t_old, grid, num_rotations):
+  """The table of ``ops.rebase_volume`` for a change of MAP frame: ``new_t_old`` is one Transform2D in corner frames, the
+  old map frame's pose in the new one, so new_t_q = new_t_old @ old_t_q -> (dk float, A float64 [2, 2], o float64 [2])
+  on the host (a transform on the device is read back: one synchronisation).
+
+  In centre frames new_t_old is (phi, sigma) with sigma = tau + (Rot(phi) - I) centre, centre = grid.extent_meters / 2.
+  Composing it in FRONT of the pose of the index (r, a, b) and reading the index back (``exhaustive_index_to_tfm`` /
+  ``exhaustive_tfm_to_index``) gives r' = (r - phi R / 2 pi) mod R and (a', b') = Rot(phi) ((a, b) - e) + e + sigma /
+  cell_size with e = extent - 1.5: the same map for every rotation (the +0.5 cell offsets cancel).  The operator
+  gathers, so the table is the inverse: the destination (r', a', b') reads the rotation r' - dk, dk = (-phi R / 2 pi)
+  mod R in [0, R), and the plane position A (a', b') + o with A = Rot(-phi), o = e - A (e + sigma / cell_size).
+  Float64 throughout; cos phi and sin phi are set to exactly 0 where their magnitude is below 2^-40, so a quarter turn
+  is an exact permutation of the lattice; negative zeros are cleared.  The identity gives dk = 0, A = I, o = 0."""
+  R = int(num_rotations)
+  angle = torch.as_tensor(new_t_old.angle)
+  if angle.numel() != 1:
+    raise ValueError(f'rebase_table: one transform, got a transform of shape {tuple(angle.shape)}')
+  phi = float(angle.detach().to('cpu', torch.float64).reshape(()))
+  tau = torch.as_tensor(new_t_old.t).detach().to('cpu', torch.float64).reshape(2).numpy()
+  if not (math.isfinite(phi) and np.isfinite(tau).all()):
+    raise ValueError(f'rebase_table: the transform ({phi}, {tau.tolist()}) is not finite')
+  cos, sin = (0.0 if abs(v) < 2.0 ** -40 else v for v in (math.cos(phi), math.sin(phi)))
+  rot = np.array([[cos, -sin], [sin, cos]])
+  centre = np.asarray(grid.extent_meters, np.float64)[:2] / 2
+  sigma = tau + (rot @ centre - centre)
+  e = np.asarray(grid.extent, np.float64)[:2] - 1.5
+  A = rot.T + 0.0
+  o = (e - A @ (e + sigma / float(grid.cell_size))) + 0.0
+  dk = math.fmod((-phi / (2 * math.pi)) * R, R)
+  if dk < 0:
+    dk += R
+  if not dk < R:                                            # (a yaw just above 0 rounds up to R)
+    dk = 0.0
+  return dk + 0.0, A, o
+
+
+def rebase_votes(volume, new_t_old, grid, num_rotations, temperature=1.0):
+  """Carry a vote volume or belief into another map frame (``ops.rebase_volume`` on ``rebase_table``): ``volume``
+  [R, 2H-1, 2W-1] holds log-scores of the poses old_t_q in the OLD map frame; ``new_t_old`` (one Transform2D, corner
+  frames) is the old frame's pose in the new one, so every pose becomes new_t_q = new_t_old @ old_t_q -- a composition
+  on the map side, where ``fuse_votes`` and the filter's predict step compose on the query side; ``temperature``
+  multiplies the volume -> dict of device tensors: ``votes`` [R, 2H-1, 2W-1] (normalised log-probabilities over the
+  new frame's lattice; again a vote volume, for every other operator of the family), ``log_z`` (the log-sum-exp of
+  temperature * volume), ``mass_kept`` (the share of the distribution that lies inside the new lattice), ``count``
+  int32 [4] and ``stats`` float64 [4] (the op's raw rows).  Cells the old lattice did not cover are -inf."""
+  _check_planes('rebase_votes', volume, num_rotations, 'volume')
+  table = rebase_table(new_t_old, grid, num_rotations)
+  out, stats, count = ops.rebase_volume(volume.contiguous(), table, temperature)
+  return dict(votes=out, log_z=stats[0], mass_kept=stats[1], count=count, stats=stats)
+
+
 def smooth_votes(belief, smoothed_next, next_t_cur, grid, num_rotations, sigma_xy, sigma_yaw, uniform_mix=1e-3,
                  truncate=3.0):
   """One backward step of the smoother that goes with ``filter_votes`` (``ops.vote_smooth`` on ``motion_taps``):
@@ -1436,6 +1487,25 @@ class VoteFilter:
     if self.belief is None:
       raise ValueError('VoteFilter.recall: no belief (at least one step)')
     return recall_from_votes(self.belief, self.grid, self.num_rotations, temperature=1.0, **kw)
+
+  def rebase(self, new_t_old, drop_history=False):
+    """Carry the belief the filter holds into another map frame (the vehicle drives onto the neighbouring map tile, or
+    the map is re-anchored): ``rebase_votes(belief, new_t_old)`` with temperature 1 (the belief is log-space and
+    normalised) -> its dict; the belief is replaced, so the track goes on where ``reset()`` would restart it from a
+    uniform prior.  Cells the old lattice did not cover come out -inf; the next ``step``'s ``uniform_mix`` re-opens
+    them.  The stored beliefs of a history are in the OLD frame and the smoother cannot mix frames: with a non-empty
+    history this raises ValueError unless ``drop_history`` is true, which restarts the history empty.  Raises
+    ValueError before the first step."""
+    if self.belief is None:
+      raise ValueError('VoteFilter.rebase: no belief (at least one step)')
+    if getattr(self, 'history', None) and not drop_history:
+      raise ValueError(f'VoteFilter.rebase: the {len(self.history)} stored beliefs are in the old map frame; '
+                       'drop_history=True restarts the history')
+    out = rebase_votes(self.belief, new_t_old, self.grid, self.num_rotations, temperature=1.0)
+    self.belief = out['votes']
+    if hasattr(self, 'history'):
+      self.history = []
+    return out
 
   def estimate_increment(self, votes, **kw):
     """``increment_from_votes(belief, votes, **kw)``: the increment since the previous step from the belief the filter

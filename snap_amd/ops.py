@@ -2534,6 +2534,47 @@ def vote_odometry(prev, cur, Kr, S, shifts=None, scale_prev=1.0, scale_cur=1.0):
   return log_table, log_evidence, best, stats, count
 
 
+def rebase_volume(volume, table, scale=1.0):
+  """The wrapper of vote_rebase.hip (its messages carry the operator's name, ``vote_rebase:``; like
+  ``plane_align_score`` of vote_refine.hip it is not named ``vote_*``: it takes a host table, not device operands, and
+  its refusals are tabled in tests/test_gpu_vote_rebase.py).  A vote volume or belief carried into another MAP frame: volume f32 [R, Ho, Wo] (log-space, -inf = impossible
+  pose), table = (dk, A, o) host numbers (``pose_exhaustive_voting.rebase_table``: dk in [0, R), A 2 x 2, o 2) ->
+  (dst f32 [R, Ho, Wo], stats float64 [4], count int32 [4]).  The destination cell (r, a, b) reads the masses
+  exp(scale * (volume - max)) at the rotation r - dk (circular) and the plane position A (a, b) + o with the trilinear
+  split, taps of weight 0 or outside the volume skipped; dst = the normalised log-probabilities, -inf where no mass
+  arrives.  stats = (log-sum-exp of scale * volume, share of the mass that arrived, largest finite volume value,
+  largest dst); count = (finite cells of dst, NaN cells of dst, NaN / +inf cells of volume, cells of dst the old frame
+  does not cover) (the full contract: snap_vote_rebase_f32 in include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  R, Ho, Wo = _vote_volume_arg('vote_rebase', volume, 'volume')
+  scale = _vote_scale('vote_rebase', scale)
+  try:
+    dk, A, o = table
+    dk = float(dk)
+    A = np.asarray(A, dtype=np.float64).reshape(2, 2)
+    o = np.asarray(o, dtype=np.float64).reshape(2)
+  except (TypeError, ValueError):
+    raise ValueError(f'vote_rebase: table = (dk, A [2, 2], o [2]) of host numbers, got {table!r}') from None
+  if not (np.isfinite(A).all() and np.isfinite(o).all()):
+    raise ValueError(f'vote_rebase: the table must be finite, got A={A.tolist()} o={o.tolist()}')
+  if not 0.0 <= dk < R:
+    raise ValueError(f'vote_rebase: dk must lie in [0, R={R}), got {dk}')
+  words = _workspace_words(lib.snap_vote_rebase_workspace_bytes, (R, Ho, Wo), volume.numel(),
+                           _vote_unsupported('vote_rebase', R, Ho, Wo))
+  dev = volume.device
+  ws = torch.empty((words,), dtype=torch.int64, device=dev)
+  dst = torch.empty((R, Ho, Wo), dtype=torch.float32, device=dev)
+  stats = torch.empty((4,), dtype=torch.float64, device=dev)
+  count = torch.empty((4,), dtype=torch.int32, device=dev)
+  # bytes the launches move (the kernel file's header): about 5 passes over the volume
+  with _region('vote_rebase', 0.0, 4.0 * volume.numel() * 5):
+    st = lib.snap_vote_rebase_f32(_p(volume), R, Ho, Wo, scale, dk, float(A[0, 0]), float(A[0, 1]), float(A[1, 0]),
+                                  float(A[1, 1]), float(o[0]), float(o[1]), _p(dst), _p(stats), _p(count), _p(ws),
+                                  ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_rebase_f32')
+  return dst, stats, count
+
+
 def vote_fuse(volumes, shifts, weights=None):
   """Multi-frame fusion of aligned vote volumes: volumes [N, R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked),
   shifts f32 [N, R, 3] = (dk, da, db) on the same device (``pose_exhaustive_voting.sequence_shift_table``), weights

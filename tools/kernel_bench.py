@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4 | vote_odometry_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4 | vote_odometry_c4 | vote_rebase_c4)
 """
 import math
 import os
@@ -633,6 +633,47 @@ def vote_odometry_c4(iters):
   emit_json(res)
 
 
+def vote_rebase_c4(iters):
+  """A change of map frame at the C4 vote volume (R = 36, 511 x 511, the low-overlap border -inf; a turn of 0.37 rad
+  about the map centre with a fractional translation: fractional dk, every tile's footprint turned): whole
+  ops.rebase_volume calls beside whole ops.vote_posterior calls on the same votes, blocks alternated, medians of single
+  calls.  One JSON line; `json=<path>` as a third argument also writes it to that file."""
+  from snap_amd.models import pose_exhaustive_voting as pev
+  from snap_amd.utils import geometry, grids
+  R, H, scale = 36, 256, 8.0
+  Ho = Wo = 2 * H - 1
+  grid = grids.Grid2D((H, H), 0.2)
+  g = torch.Generator(device='cuda').manual_seed(0)
+  votes = torch.randn((R, Ho, Wo), device='cuda', generator=g) * 0.25
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  votes = torch.where((ov[:, None] * ov[None, :] > 0.05 * H * H)[None], votes, float('-inf')).contiguous()
+  new_t_old = geometry.Transform2D(torch.tensor(0.37, dtype=torch.float64), torch.tensor([9.13, -6.47], dtype=torch.float64))
+  table = pev.rebase_table(new_t_old, grid, R)
+  dst, stats, count = ops.rebase_volume(votes, table, scale)
+  log_z = ops.vote_posterior(votes, scale)[2][0]
+  assert table[0] % 1 != 0 and abs(float(stats[0]) - float(log_z)) <= 1e-4 * abs(float(log_z))
+  assert 0.5 < float(stats[1]) < 1.05 and int(count[1]) == 0 and int(count[3]) > 0
+  assert abs(float(dst[torch.isfinite(dst)].double().exp().sum()) - 1) < 1e-5
+  rebase = lambda: ops.rebase_volume(votes, table, scale)
+  post = lambda: ops.vote_posterior(votes, scale)
+  n = max(iters, 5)
+  (r_ms, rs), (p_ms, ps) = alternated_blocks(((rebase, 5, n), (post, 5, n)))
+  by = 4.0 * votes.numel() * 5       # vote_rebase.hip's header: about 5 passes over the volume (an estimate)
+  res = dict(case='vote_rebase_c4', shape=[R, Ho, Wo], scale=scale, phi=0.37, dk=round(table[0], 6),
+             offset_cells=[round(float(v), 4) for v in table[2]], mass_kept=round(float(stats[1]), 6),
+             cells_not_covered=int(count[3]), vote_rebase_call_ms=round(r_ms, 4),
+             vote_rebase_call_ms_blocks=[round(v, 4) for v in rs], vote_posterior_call_ms=round(p_ms, 4),
+             vote_posterior_call_ms_blocks=[round(v, 4) for v in ps], ratio_to_vote_posterior=round(r_ms / p_ms, 2),
+             estimated_bytes=by, effective_bytes_per_s=round(by / (r_ms * 1e-3), 1),
+             workspace_bytes=int(ops._lib.load().snap_vote_rebase_workspace_bytes(R, Ho, Wo)),
+             timing='whole wrapper calls (torch.empty outputs and workspace, the ctypes call, the four launches) between '
+             'device events on an idle stream, NOT kernel time; median of single calls, 5 blocks of each alternated, '
+             'median block; the time is measured, the bytes are the 5 n-cell ESTIMATE of the kernel file\'s header (HBM '
+             'traffic was not measured), so effective_bytes_per_s is measured time against estimated traffic; no '
+             'threshold is set on this case')
+  emit_json(res)
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -640,4 +681,4 @@ if __name__ == '__main__':
    'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4,
    'vote_filter_c4': vote_filter_c4, 'vote_smooth_c4': vote_smooth_c4,
    'vote_refine_c4': vote_refine_c4, 'vote_modes_c4': vote_modes_c4, 'vote_recall_c4': vote_recall_c4,
-   'vote_odometry_c4': vote_odometry_c4}[which](iters)
+   'vote_odometry_c4': vote_odometry_c4, 'vote_rebase_c4': vote_rebase_c4}[which](iters)
