@@ -1446,6 +1446,47 @@ int snap_vote_rebase_f32(const float* src, int32_t R, int32_t Ho, int32_t Wo, fl
                          double A01, double A10, double A11, double oa, double ob, float* dst, double* stats,
                          int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* A vote volume's statistics over a TEMPERATURE LADDER: everything a one-parameter fit of p = softmax(s * votes) needs
+ * (the temperature that minimises the ground-truth NLL over a validation set), at S scales from ONE visit of the frame.
+ * For x = s * v: log_z(s), d log_z / d s = E_s[v], d2 log_z / d s2 = Var_s[v], and the ground-truth sample v_gt, which
+ * does not depend on s (the trilinear interpolation is linear).
+ * votes[R,Ho,Wo] f32 unnormalised log-scores, flat(r,a,b) = (r*Ho + a)*Wo + b; scales: a HOST pointer to S f32, every
+ * one finite and > 0, strictly increasing; table[S,8] FLOAT64; stats[4] FLOAT64; count[4] i32.
+ *   A cell CONTRIBUTES iff its vote is finite (snap_vote_posterior_f32's rule: -inf cells are masked silently, NaN and
+ *   +inf cells are excluded and counted).  F = the contributing set, m = max_F v (exact; the same for every scale, as
+ *   scales are > 0), d = fl32(v - m) <= 0.
+ *   Level l, s = scales[l]: x = fl32(s * d), e = expf(x) and, over F, S0 = sum e, S1 = sum fl32(e x), S2 = sum
+ *   fl32(fl32(e x) x) (the moments are summed in x: a term with e > 0 has |x| < 104, so no sum overflows);
+ *   A = log S0, mu = S1 / S0 / s (= sum e d / sum e), q = S2 / S0 / s^2 (= sum e d^2 / sum e), all float64.
+ *   table[l] = { 0: log_z = s m + A, 1: E[v] = m + mu, 2: Var[v] = max(q - mu^2, 0), 3: entropy = A - s mu,
+ *                4: log p_max = -A, 5: log_prob_gt = s v_gt - log_z, 6: dnll = E[v] - v_gt (the derivative of the
+ *                ground truth's NLL in s), 7: written as 0 }.
+ *   stats = { m, v_gt, 0, 0 }.  count = { contributing cells; NaN or +inf cells; 1 if the ground-truth sample is valid,
+ *   else 0; 0 }.
+ *   gt_index: NULL, or a DEVICE pointer to f32 [3] = (k, i, j), read by the kernel.  v_gt = the trilinear interpolation
+ *   of v (not of s v) at (k, i, j) in float64 by exactly snap_vote_posterior_f32's rule: circular in k, a tap of weight
+ *   exactly 0 is not read, valid iff k, i, j are finite, 0 <= i <= Ho-1, 0 <= j <= Wo-1 and every tap of non-zero weight
+ *   contributes.  Otherwise (and with NULL) v_gt, log_prob_gt and dnll are NaN and count[2] = 0.
+ *   F empty: m = log_z = -inf, every other column of table[l][1..6] NaN.
+ *   NO OVERFLOW CAVEAT: s * v is never formed in f32, only s * d with d <= 0 (it underflows to e = 0, which is the right
+ *   weight), and s * m is formed in float64; snap_vote_posterior_f32's condition "|scale * v| below the f32 maximum"
+ *   does not exist here, and neither does one on the spread of the votes.
+ * f32 is used for the expf and for the sums of one pixel's <= R terms (each of one sign: e >= 0, e x <= 0, e x^2 >= 0);
+ * everything above is float64 and every output is a float64 expression.  Three launches: the maximum and the counts;
+ * the tile walk, one pixel per thread with its 3 S sums in registers, ONE partial row per workgroup; the fold, one
+ * workgroup per level.  The volume is read twice (the second read follows the first through the cache), not S times.
+ * No atomics and no hand-off between workgroups: every reduction order is fixed by (R, Ho, Wo, S), so two calls give
+ * the same bits.  Every element of table, stats and count is written by every call.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31, 1 <= S <= 16; anything else returns SNAP_ERR_BAD_SHAPE before
+ * any launch (a NULL pointer other than gt_index SNAP_ERR_NULL; a ladder that is not finite, > 0 and strictly increasing
+ * SNAP_ERR_UNSUPPORTED; a short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE).  workspace:
+ * snap_vote_temper_workspace_bytes() bytes (0 = unsupported shape); it needs no initialisation and no launch touches a
+ * byte beyond that size.  Asynchronous on `stream`; the caller owns every buffer. */
+size_t snap_vote_temper_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t S);
+int snap_vote_temper_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, const float* scales, int32_t S,
+                         const float* gt_index, double* table, double* stats, int32_t* count, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* Most likely pose TRACK over vote volumes: one forward step of the max-product (Viterbi) recursion that goes with the
  * filter above, with back-pointers.  score_prev[R,Ho,Wo] f32 is the log score of the best path into every pose of the
  * previous frame (-inf = no path), or NULL (the first frame of a track); votes[R,Ho,Wo] f32; on the DEVICE:

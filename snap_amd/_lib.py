@@ -299,6 +299,8 @@ SIGNATURES = {
     'snap_vote_rebase_workspace_bytes': (c_size, [c_int] * 3),
     'snap_vote_rebase_f32': (
         c_int, [ptr, c_int, c_int, c_int, c_float] + [c_double] * 7 + [ptr] * 4 + [c_size, ptr]),
+    'snap_vote_temper_workspace_bytes': (c_size, [c_int] * 4),
+    'snap_vote_temper_f32': (c_int, [ptr, c_int, c_int, c_int, ptr, c_int] + [ptr] * 5 + [c_size, ptr]),
     'snap_vote_viterbi_workspace_bytes': (c_size, [c_int] * 6),
     'snap_vote_viterbi_f32': (
         c_int, [ptr, ptr, ptr, c_int, ptr, ptr, ptr] + [c_int] * 6 + [c_float] * 3 + [ptr] * 5 + [c_size, ptr]),
@@ -399,7 +401,7 @@ SIGNATURES = {
     ),
 }
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _lib = None
 

@@ -2575,6 +2575,47 @@ def rebase_volume(volume, table, scale=1.0):
   return dst, stats, count
 
 
+def temper_volume(votes, scales, gt_index=None):
+  """The wrapper of vote_temper.hip (its messages carry the operator's name, ``vote_temper:``; like ``rebase_volume``
+  it is not named ``vote_*``: it takes a host ladder, and its refusals are tabled in tests/test_gpu_vote_temper.py).
+  A vote volume's statistics over a temperature ladder: votes [R, Ho, Wo] f32 (unnormalised log-scores; -inf =
+  masked), ``scales`` a host sequence of 1 to 16 finite numbers > 0 whose f32 roundings increase strictly ->
+  (table float64 [S, 8], stats float64 [4], count int32 [4]) of p_s = softmax(s * votes) over the finite cells.
+  table[l] = (log_z, E[v], Var[v], entropy, log p_max, log_prob_gt, dnll = E[v] - v_gt, 0) at s = scales[l]; stats =
+  (largest finite vote, v_gt, 0, 0); count = (contributing cells, NaN or +inf cells, ground-truth sample valid, 0).
+  ``gt_index``: None or a device f32 [3] = (k, i, j) (``exhaustive_tfm_to_index``), sampled on the device by
+  ``vote_posterior``'s rule.  ``scale * v`` is never formed in f32: there is no overflow condition on the votes (the
+  full contract: snap_vote_temper_f32 in include/snap_hip.h).  No host synchronisation."""
+  lib = _lib.load()
+  R, Ho, Wo = _vote_volume('vote_temper', votes, 'votes')
+  try:
+    ladder = np.asarray(scales, dtype=np.float64).reshape(-1)
+  except (TypeError, ValueError):
+    raise ValueError(f'vote_temper: scales must be a host sequence of numbers, got {scales!r}') from None
+  with np.errstate(over='ignore'):
+    s32 = ladder.astype(np.float32)
+  S = int(s32.size)
+  if not (1 <= S <= 16 and bool(np.all(np.isfinite(s32))) and bool(np.all(s32 > 0)) and bool(np.all(np.diff(s32) > 0))):
+    raise ValueError('vote_temper: scales must be 1 to 16 finite numbers > 0, strictly increasing as f32, got '
+                     f'{ladder.tolist()}')
+  _vote_gt_index('vote_temper', gt_index, votes.device)
+  words = _workspace_words(lib.snap_vote_temper_workspace_bytes, (R, Ho, Wo, S), votes.numel(),
+                           _vote_unsupported('vote_temper', R, Ho, Wo))
+  dev = votes.device
+  ws = torch.empty((words,), dtype=torch.int64, device=dev)
+  table = torch.empty((S, 8), dtype=torch.float64, device=dev)
+  stats = torch.empty((4,), dtype=torch.float64, device=dev)
+  count = torch.empty((4,), dtype=torch.int32, device=dev)
+  host_scales = (ctypes.c_float * S)(*s32.tolist())
+  # algorithmic bytes: one read of the volume (the second launch's read of it is meant to hit in cache; the outputs are
+  # S rows)
+  with _region('vote_temper', 0.0, 4.0 * votes.numel()):
+    st = lib.snap_vote_temper_f32(_p(votes), R, Ho, Wo, host_scales, S, _p(gt_index), _p(table), _p(stats), _p(count),
+                                  _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_temper_f32')
+  return table, stats, count
+
+
 def vote_fuse(volumes, shifts, weights=None):
   """Multi-frame fusion of aligned vote volumes: volumes [N, R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked),
   shifts f32 [N, R, 3] = (dk, da, db) on the same device (``pose_exhaustive_voting.sequence_shift_table``), weights

@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4 | vote_odometry_c4 | vote_rebase_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4 | vote_odometry_c4 | vote_rebase_c4 | vote_temper_c4)
 """
 import math
 import os
@@ -674,6 +674,45 @@ def vote_rebase_c4(iters):
   emit_json(res)
 
 
+def vote_temper_c4(iters):
+  """The temperature ladder at the C4 vote volume (R = 36, 511 x 511, the low-overlap border -inf; 16 scales from 2^-2 to
+  2^2): one whole ops.temper_volume call beside the 16 whole ops.vote_posterior calls on the same votes that it replaces
+  (one per scale), blocks alternated, medians of single calls (one "call" of the second is all 16).  One JSON line;
+  `json=<path>` as a third argument also writes it to that file."""
+  R, H, S = 36, 256, 16
+  Ho = Wo = 2 * H - 1
+  g = torch.Generator(device='cuda').manual_seed(0)
+  votes = torch.randn((R, Ho, Wo), device='cuda', generator=g) * 0.25
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  votes = torch.where((ov[:, None] * ov[None, :] > 0.05 * H * H)[None], votes, float('-inf')).contiguous()
+  scales = [2.0 ** (-2 + 4 * i / (S - 1)) for i in range(S)]
+  table, stats, count = ops.temper_volume(votes, scales)
+  post = [ops.vote_posterior(votes, s)[2] for s in scales]
+  diff = max(max(abs(float(table[l, 0]) - float(post[l][0])), abs(float(table[l, 3]) - float(post[l][11])))
+             for l in range(S))
+  assert diff < 1e-3 and int(count[1]) == 0, diff
+  temper = lambda: ops.temper_volume(votes, scales)
+  def posteriors():
+    for s in scales:
+      ops.vote_posterior(votes, s)
+  n = max(iters, 5)
+  (t_ms, ts), (p_ms, ps) = alternated_blocks(((temper, 5, n), (posteriors, 5, n)))
+  by = 4.0 * votes.numel()
+  res = dict(case='vote_temper_c4', shape=[R, Ho, Wo], scales=[round(s, 6) for s in scales], S=S,
+             masked_fraction=round(1 - int(count[0]) / votes.numel(), 4), vote_temper_call_ms=round(t_ms, 4),
+             vote_temper_call_ms_blocks=[round(v, 4) for v in ts], vote_posterior_x16_ms=round(p_ms, 4),
+             vote_posterior_x16_ms_blocks=[round(v, 4) for v in ps], ratio_temper_to_posterior_x16=round(t_ms / p_ms, 4),
+             block_ranges_overlap=bool(max(ts) >= min(ps)), volume_bytes=int(by),
+             exponentials_per_s=round(S * int(count[0]) / (t_ms * 1e-3), 1),
+             max_abs_difference_to_vote_posterior=diff,
+             workspace_bytes=int(ops._lib.load().snap_vote_temper_workspace_bytes(R, Ho, Wo, S)),
+             timing='whole wrapper calls (torch.empty outputs and workspace, the ctypes call, the three launches; for '
+             'vote_posterior all of that 16 times) between device events on an idle stream, NOT kernel time; median of '
+             'single calls, 5 blocks of each alternated, median block; the 37.6 MB volume fits the 256 MB Infinity Cache, '
+             'so repeated reads need not come from HBM; no threshold is set on this case')
+  emit_json(res)
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -681,4 +720,4 @@ if __name__ == '__main__':
    'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4,
    'vote_filter_c4': vote_filter_c4, 'vote_smooth_c4': vote_smooth_c4,
    'vote_refine_c4': vote_refine_c4, 'vote_modes_c4': vote_modes_c4, 'vote_recall_c4': vote_recall_c4,
-   'vote_odometry_c4': vote_odometry_c4, 'vote_rebase_c4': vote_rebase_c4}[which](iters)
+   'vote_odometry_c4': vote_odometry_c4, 'vote_rebase_c4': vote_rebase_c4, 'vote_temper_c4': vote_temper_c4}[which](iters)
