@@ -37,7 +37,8 @@ typedef enum SnapStatus {
 } SnapStatus;
 
 /* Library / device introspection. */
-int snap_abi_version(void);                 /* bumps on any signature change */
+#define SNAP_ABI_VERSION 29   /* bump on any change to this header's prototypes, structs or constants */
+int snap_abi_version(void);                 /* SNAP_ABI_VERSION of the built library */
 const char* snap_status_string(int status);
 const char* snap_build_arch(void);          /* "gfx950" */
 

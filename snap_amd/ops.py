@@ -19,10 +19,14 @@ import torch
 
 from snap_amd import _lib
 
-PRO_NONE, PRO_AFFINE, PRO_GN_RELU, PRO_RELU_GN, PRO_RELU = 0, 1, 2, 3, 4
-EPI_BIAS, EPI_RELU, EPI_RESIDUAL, EPI_UPSAMPLE2X_ADD, EPI_ROWMASK, EPI_GELU = 1, 2, 4, 8, 16, 32
-POOLING = {'max': 0, 'sum': 1, 'mean': 2}
-SIM_CHUNK = 64
+# the header's constants (include/snap_hip.h, read by _lib) under the names the wrappers and their callers use
+PRO_NONE, PRO_AFFINE, PRO_GN_RELU, PRO_RELU_GN, PRO_RELU = (
+    _lib.SNAP_PRO_NONE, _lib.SNAP_PRO_AFFINE, _lib.SNAP_PRO_GN_RELU, _lib.SNAP_PRO_RELU_GN, _lib.SNAP_PRO_RELU)
+EPI_BIAS, EPI_RELU, EPI_RESIDUAL, EPI_UPSAMPLE2X_ADD, EPI_ROWMASK, EPI_GELU = (
+    _lib.SNAP_EPI_BIAS, _lib.SNAP_EPI_RELU, _lib.SNAP_EPI_RESIDUAL, _lib.SNAP_EPI_UPSAMPLE2X_ADD,
+    _lib.SNAP_EPI_ROWMASK, _lib.SNAP_EPI_GELU)
+POOLING = {'max': _lib.SNAP_POOL_MAX, 'sum': _lib.SNAP_POOL_SUM, 'mean': _lib.SNAP_POOL_MEAN}
+SIM_CHUNK = _lib.SNAP_SIM_CHUNK
 
 
 
@@ -711,7 +715,8 @@ def plan_conv(
   tuned = bool(T.CONV_BK or T.CONV_NO_HALO or T.CONV_RS_NSPLIT or T.CONV_NO_PLAIN)
   if tuned:
     bk_hint = int(T.CONV_BK or 0)
-    tune_flags = int(bool(T.CONV_NO_HALO)) | 8 * int(bool(T.CONV_NO_PLAIN)) | ((int(T.CONV_RS_NSPLIT) & 15) << 4)
+    tune_flags = (_lib.SNAP_TUNE_NO_HALO * int(bool(T.CONV_NO_HALO)) | _lib.SNAP_TUNE_NO_PLAIN * int(bool(T.CONV_NO_PLAIN))
+                  | ((int(T.CONV_RS_NSPLIT) & 15) << _lib.SNAP_TUNE_RS_NSPLIT_SHIFT))
   return ConvPlan(
       desc=d, out_shape=(N, Ho, Wo, Cout), out_dtype=out_dtype, engine=math if image else 'f32', family=family,
       tag='PS_' if ps else 'PS1_' if ps1 else ('', 'RS_', 'WS_', 'WS_')[kind], image=image, parts=iparts,
@@ -982,8 +987,7 @@ def pack_weights_split_root_bf16(w, parts):
   return out
 
 
-_PACK_ITEM = np.dtype([('w', np.uint64), ('out', np.uint64), ('taps', np.int32), ('Cin', np.int32),
-                       ('Cout', np.int32), ('block_begin', np.int32)])
+_PACK_ITEM = np.dtype(_lib.SnapPackItem)
 
 
 def pack_weights_split_multi(ws, math):
@@ -1319,8 +1323,7 @@ def weight_standardize(w, eps=1e-10):
   return out
 
 
-_WSTD_ITEM = np.dtype([('w', '<u8'), ('dws', '<u8'), ('out', '<u8'), ('K', '<i4'), ('Cout', '<i4'),
-                       ('block_begin', '<i4'), ('reserved', '<i4')])   # == SnapWstdItem
+_WSTD_ITEM = np.dtype(_lib.SnapWstdItem)
 
 
 def _wstd_table(ws, dwss, outs, cols=32):

@@ -34,7 +34,7 @@ def _conv_desc(x_shape, w_shape, stride, padding, prologue, in_affine, cs=None):
   ), (N, Ho, Wo, Cout)
 
 
-WGRAD_NO_WIDE, WGRAD_NO_FUSED3 = 1 << 8, 1 << 9      # SnapConvDesc.tile_hint bits (snap_hip.h)
+WGRAD_NO_WIDE, WGRAD_NO_FUSED3 = _lib.SNAP_WGRAD_NO_WIDE, _lib.SNAP_WGRAD_NO_FUSED3   # SnapConvDesc.tile_hint bits
 
 
 def conv2d_wgrad(x, dy, w_shape, *, stride=1, padding=((0, 0), (0, 0)), prologue=ops.PRO_NONE,
@@ -94,8 +94,8 @@ def conv2d_wgrad(x, dy, w_shape, *, stride=1, padding=((0, 0), (0, 0)), prologue
   kfl = 2.0 * KH * KW * Cin * Cout
   flops = kfl * M if row_count is None else (lambda: kfl * int(row_count.item()))
   bf16 = math in ops.HALF_MATH and x.shape[-1] % 4 == 0 and Cin >= 4
-  code = (2 if math == 'fp16' else 1) if bf16 else 0          # SNAP_MATH_F16 / _BF16 / _F32
-  with _region(('conv_wgrad_fp16' if code == 2 else 'conv_wgrad_bf16') if bf16 else 'conv_wgrad', flops,
+  code = (_lib.SNAP_MATH_F16 if math == 'fp16' else _lib.SNAP_MATH_BF16) if bf16 else _lib.SNAP_MATH_F32
+  with _region(('conv_wgrad_fp16' if math == 'fp16' else 'conv_wgrad_bf16') if bf16 else 'conv_wgrad', flops,
                4.0 * (x.numel() + dy.numel()),
                tag=f'M{M}_K{KH}x{KW}x{Cin}_N{Cout}_s{stride}_p{prologue}' + ('_dyh' if dy_half else '') + ('_xh' if x_half else '')):
     st = lib.snap_conv2d_wgrad_half_f32(
@@ -673,8 +673,7 @@ def masked_softmax_rows_bwd(weights, dweights):
   return dx
 
 
-_ADAM_ITEM = np.dtype([('p', np.uint64), ('g', np.uint64), ('m', np.uint64), ('v', np.uint64),
-                       ('n', np.int64), ('block_begin', np.int64)])
+_ADAM_ITEM = np.dtype(_lib.SnapAdamItem)
 
 
 def adam_update_(params, grads, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, apply_flag=None):

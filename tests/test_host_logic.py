@@ -37,12 +37,151 @@ def _header_symbols():
   return set(re.findall(r'\b(snap_[a-z0-9_]+)\s*\(', text))
 
 
-def test_abi_header_and_binding_agree():
-  assert _header_symbols() == set(_lib.SIGNATURES)
+def test_abi_binding_matches_frozen_prototypes():
+  """_lib derives SIGNATURES from the header; these rows are written out by hand and cover every type class:
+  char* / size_t / int64_t returns, both by-reference structs, double, uint64_t, pointer-to-pointer, item pointer."""
+  i32, i64, u64, f32, f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_double
+  size, ptr, P = ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER
+  frozen = {
+      'snap_status_string': (ctypes.c_char_p, [i32]),
+      'snap_abi_version': (i32, []),
+      'snap_conv2d_nhwc_ex_f32': (i32, [P(_lib.SnapConvDesc)] + [ptr] * 10 + [P(_lib.SnapConvExtras), ptr]),
+      'snap_conv2d_workspace_bytes': (size, [P(_lib.SnapConvDesc)]),
+      'snap_adam_multi_blocks': (i64, [i64]),
+      'snap_plane_fuse_match_f32': (
+          i32, [ptr, ptr, i32, i64, i32, i32, ptr, ptr, ptr, ptr, i32, i32, f32, ptr, ptr]),
+      'snap_ransac_sample_sim_f32': (
+          i32, [ptr] * 6 + [i32] * 5 + [f32, i32, i32, u64, ptr, ptr, ptr, size, ptr]),
+      'snap_vote_rebase_f32': (i32, [ptr, i32, i32, i32, f32] + [f64] * 7 + [ptr] * 4 + [size, ptr]),
+      'snap_vote_sample_back_f32': (
+          i32, [ptr, ptr, i32, ptr, ptr, ptr] + [i32] * 6 + [f32, ptr, i32, u64, i32] + [ptr] * 6 + [size, ptr]),
+      'snap_lift_pool_bwd_det_f32': (i32, [P(_lib.SnapLiftDesc)] + [ptr] * 7 + [size, ptr]),
+      'snap_conv2d_pack_weights_multi_bf16': (i32, [ptr, i32, i32, ptr]),
+  }
+  for name, want in frozen.items():
+    assert _lib.SIGNATURES[name] == want, name
+
+
+# sizeof and every field's offset; snap_amd/csrc/abi.hip pins the sizes and last offsets on the C side
+_LAYOUTS = {
+    'SnapConvDesc': (76, list(range(0, 76, 4))),
+    'SnapConvExtras': (200, [0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 80, 84, 88, 96, 104, 108, 112, 116, 120, 124, 128,
+                             132, 136, 144, 152, 160, 168, 176, 184, 192]),
+    'SnapLiftDesc': (92, list(range(0, 92, 4))),
+    'SnapPackItem': (32, [0, 8, 16, 20, 24, 28]),
+    'SnapWstdItem': (40, [0, 8, 16, 24, 28, 32, 36]),
+    'SnapAdamItem': (48, [0, 8, 16, 24, 32, 40]),
+}
+
+
+@pytest.mark.parametrize('name', sorted(_LAYOUTS))
+def test_abi_struct_layouts(name):
+  cls = getattr(_lib, name)
+  size, offsets = _LAYOUTS[name]
+  assert ctypes.sizeof(cls) == size
+  assert [getattr(cls, f).offset for f, _ in cls._fields_] == offsets
+
+
+def test_abi_descriptor_fields():
+  """Header order: the wrappers and tests construct the descriptors positionally."""
+  names = lambda cls: tuple(f for f, _ in cls._fields_)
+  assert names(_lib.SnapConvDesc) == (
+      'N', 'H', 'W', 'Cin', 'Cin_stride', 'KH', 'KW', 'stride', 'pad_t', 'pad_l', 'Ho', 'Wo', 'Cout', 'Cout_stride',
+      'prologue', 'epilogue', 'in_scale', 'in_shift', 'tile_hint')
+  assert names(_lib.SnapConvExtras) == (
+      'rows_in', 'rows_out', 'row_count', 'gn_partial', 'gn_partial_bytes', 'gn_partial_relu', 'workspace',
+      'workspace_bytes', 'w_bf16', 'w_bf16_bytes', 'w_split_parts', 'w_split_root', 'gn_partial2',
+      'gn_partial2_bytes', 'gn_partial2_done', 'x_presplit', 'ps_tile', 'ps_res_init', 'bk_hint', 'tune_flags',
+      'gn_partial_rows', 'w_half', 'x_half', 'y_half', 'gnb_x', 'gnb_mu', 'gnb_rstd', 'gnb_gamma', 'gnb_beta',
+      'gnb_mode')
+  assert names(_lib.SnapLiftDesc) == (
+      'B', 'V', 'h', 'w', 'C', 'feature_dim', 'num_bins', 'N', 'K', 'fisheye', 'out_stride', 'depth_min', 'depth_max',
+      'max_view_distance', 'weighted', 'use_variance', 'add_minmax', 'grid_y', 'grid_z', 'valid_rows_only',
+      'out_split', 'class_rows', 'tune_flags')
+  floats = {'in_scale', 'in_shift', 'depth_min', 'depth_max', 'max_view_distance'}
+  for cls in (_lib.SnapConvDesc, _lib.SnapLiftDesc):
+    assert all(t is (ctypes.c_float if f in floats else ctypes.c_int32) for f, t in cls._fields_)
+
+
+def test_abi_item_dtypes():
+  """The device tables of the multi-tensor launches are filled through numpy views of the item structs."""
+  from snap_amd import ops_bwd
+  want = {
+      'SnapPackItem': [('w', '<u8'), ('out', '<u8'), ('taps', '<i4'), ('Cin', '<i4'), ('Cout', '<i4'),
+                       ('block_begin', '<i4')],
+      'SnapWstdItem': [('w', '<u8'), ('dws', '<u8'), ('out', '<u8'), ('K', '<i4'), ('Cout', '<i4'),
+                       ('block_begin', '<i4'), ('reserved', '<i4')],
+      'SnapAdamItem': [('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('n', '<i8'), ('block_begin', '<i8')],
+  }
+  for (name, fields), used in zip(want.items(), (ops._PACK_ITEM, ops._WSTD_ITEM, ops_bwd._ADAM_ITEM)):
+    lit, got = np.dtype(fields), np.dtype(getattr(_lib, name))
+    assert used == got
+    assert got.names == lit.names and got.itemsize == lit.itemsize == _LAYOUTS[name][0]
+    for f in lit.names:
+      assert got.fields[f][0] == lit.fields[f][0] and got.fields[f][1] == lit.fields[f][1], (name, f)
+
+
+def test_abi_constants():
+  from snap_amd import ops_bwd
+  assert (ops.PRO_NONE, ops.PRO_AFFINE, ops.PRO_GN_RELU, ops.PRO_RELU_GN, ops.PRO_RELU) == (0, 1, 2, 3, 4)
+  assert (ops.EPI_BIAS, ops.EPI_RELU, ops.EPI_RESIDUAL, ops.EPI_UPSAMPLE2X_ADD, ops.EPI_ROWMASK,
+          ops.EPI_GELU) == (1, 2, 4, 8, 16, 32)
+  assert ops.POOLING == {'max': 0, 'sum': 1, 'mean': 2}
+  assert ops.SIM_CHUNK == 64
+  assert (ops_bwd.WGRAD_NO_WIDE, ops_bwd.WGRAD_NO_FUSED3) == (1 << 8, 1 << 9)
+  # ... and those the wrappers read where they use them: plan_conv's tune bits, conv2d_wgrad's math codes
+  assert (_lib.SNAP_TUNE_NO_HALO, _lib.SNAP_TUNE_NO_PLAIN, _lib.SNAP_TUNE_RS_NSPLIT_SHIFT) == (1, 8, 4)
+  assert (_lib.SNAP_MATH_F32, _lib.SNAP_MATH_BF16, _lib.SNAP_MATH_F16) == (0, 1, 2)
+  assert (_lib.SNAP_OK, _lib.SNAP_ERR_BAD_SHAPE, _lib.SNAP_ERR_WORKSPACE) == (0, -1, -5)
+  assert _lib.ABI_VERSION == 29
+
+
+@pytest.mark.parametrize('text', [
+    'int snap_foo(const quad_t* x, void* stream);',                         # unknown type
+    'int snap_foo(unsigned x);',
+    'typedef struct SnapFoo { float x[4]; } SnapFoo;',                      # array member
+    'typedef struct SnapFoo { float* a, b; } SnapFoo;',                     # member list it cannot split
+    'typedef struct SnapFoo { int32_t n : 3; } SnapFoo;',
+    'int snap_foo(float x[4]);',                                            # array parameter
+    'int snap_foo(int (*callback)(int), void* stream);',                    # function-pointer parameter
+    'int snap_foo(const SnapConvDesc* desc);',                              # pointer to a struct not declared yet
+    'static inline int snap_foo(void) { return 0; }',                       # a snap_foo( the prototype pattern does not take
+    'int (snap_foo)(void);',
+    '#define SNAP_FOO (1 + 2)',                                             # not an expression of literals, << and |
+    'enum { SNAP_FOO = SNAP_BAR };',
+])
+def test_abi_header_parser_refuses_what_it_does_not_understand(text):
+  with pytest.raises(ValueError):
+    _lib.parse_header(text)
+
+
+def test_abi_header_parser_reads_a_small_header():
+  sigs, structs, consts = _lib.parse_header('''
+      #ifndef GUARD_H_
+      #define GUARD_H_
+      #define SNAP_A 3   /* three */
+      #ifdef __cplusplus
+      extern "C" {
+      #endif
+      enum { SNAP_B = 1 << 4 | 1, SNAP_C = -2 };
+      typedef struct SnapItem { const float* p; int32_t a, b; int64_t n; } SnapItem;
+      // a by-value size, a pointer to pointer, an item array
+      size_t snap_foo(const SnapItem* items, const float* const* rows, double x, void* stream);
+      const char* snap_bar(void);
+      #ifdef __cplusplus
+      }
+      #endif
+      #endif''')
+  assert consts == {'SNAP_A': 3, 'SNAP_B': 17, 'SNAP_C': -2}
+  assert [(f, t) for f, t in structs['SnapItem']._fields_] == [
+      ('p', ctypes.c_void_p), ('a', ctypes.c_int32), ('b', ctypes.c_int32), ('n', ctypes.c_int64)]
+  assert sigs == {'snap_foo': (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p]),
+                  'snap_bar': (ctypes.c_char_p, [])}
 
 
 def test_abi_library_loads_and_exports_every_symbol():
   """No compute calls: only dlopen + dlsym + the introspection entry points."""
+  assert set(_lib.SIGNATURES) == _header_symbols()   # the binding's parser dropped no prototype
   lib = _lib.load()
   raw = ctypes.CDLL(_lib.LIB_PATH)
   for name in _header_symbols():
