@@ -37,6 +37,8 @@ typedef enum SnapStatus {
 } SnapStatus;
 
 /* Library / device introspection. */
+/* (snap_vote_prior_workspace_bytes / snap_vote_prior_f32 were ADDED at version 29 without a bump: an addition changes no
+ * existing prototype, struct or constant, and a library built without them fails to load on the missing symbol.) */
 #define SNAP_ABI_VERSION 29   /* bump on any change to this header's prototypes, structs or constants */
 int snap_abi_version(void);                 /* SNAP_ABI_VERSION of the built library */
 const char* snap_status_string(int status);
@@ -1487,6 +1489,59 @@ size_t snap_vote_temper_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32
 int snap_vote_temper_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, const float* scales, int32_t S,
                          const float* gt_index, double* table, double* stats, int32_t* count, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* A position / heading PRIOR fused into a vote volume or belief: the measurement update for a GNSS fix and a compass.
+ * The prior is a mixture of M components, each a Gaussian in the plane times a von Mises factor per rotation.  The map
+ * position of a sensor that does not sit at the query grid's centre depends on the rotation, so the Gaussian's centre
+ * is a table entry per (component, rotation); pose_exhaustive_voting.pose_prior builds the tables in float64.
+ * votes[R,Ho,Wo] f32 log-scores, flat(r,a,b) = (r*Ho + a)*Wo + b, or NULL (every cell then contributes with v = 0 and
+ * scale is ignored: the prior itself as a belief); scale: a finite float > 0 with |scale * v| below the f32 maximum for
+ * every finite v (not checked); on the DEVICE: centres[M,R,2] i32 = (n_a, n_b), planes[M,R,3] f32 = (f_a, f_b, y) and
+ * comps[M,4] f32 = (Pxx, Pxy, Pyy, log w): component m in plane k is centred at the index n + f, |f| <= 0.5, has the
+ * precision P in cells^-2 and the heading term y <= 0; log w <= 0.  PRECONDITION (not checked): every entry is finite,
+ * P is positive semi-definite and |P| times the squared distance of any cell from any centre stays below 2^120.
+ * out[R,Ho,Wo] f32 (must not overlap votes); resp[M] FLOAT64; stats[8] FLOAT64; count[4] i32.
+ *   THE LOG-PRIOR u of the cell (k, a, b), every operation ONE IEEE f32 operation (no contraction), in this order:
+ *     da = fl(float(a - n_a) - f_a), db = fl(float(b - n_b) - f_b)   (the integer difference is exact, its conversion
+ *       exact below 2^24);
+ *     q = fl(fl(fl(fl(Pxx da) da) + fl(fl(fl(2 Pxy) da) db)) + fl(fl(Pyy db) db))   (2 Pxy is exact);
+ *     term_m = fl(fl(log w_m + y_mk) - fl(0.5 q))   (0.5 q is exact);
+ *     M = 1: u = term_0, no exponential and no logarithm;
+ *     M > 1: mx = max_m term_m, s = the f32 sum over m = 0 .. M-1, in that order from 0, of expf(fl(term_m - mx)),
+ *       u = fl(mx + logf(s)).
+ *   A cell CONTRIBUTES iff its vote is finite (snap_vote_posterior_f32's rule: -inf cells are masked silently, NaN and
+ *   +inf cells are excluded and counted).  F = the contributing set.  On F: x = fl(scale v) (0 without votes),
+ *   t = fl(x + u); tmax = max_F t, xmax = max_F x, umax = the largest u of ALL R Ho Wo cells (maxima: exact).
+ *   With e = expf(fl(t - tmax)), eu = expf(fl(u - umax)), ev = expf(fl(x - xmax)) and S0 = sum_F e:
+ *   stats = { 0: log_z = tmax + log S0,
+ *             1: log_z_votes = xmax + log sum_F ev: the log-sum-exp of scale * votes over F,
+ *             2: log_z_prior = umax + log (sum of eu over ALL cells),
+ *             3: log_z_prior_F = umax + log sum_F eu (-inf where no cell of F has prior mass in f32),
+ *             4: expected_log_prior = (sum_F (double)e (double)u) / S0 = E_post[u],
+ *             5-7: written as 0 };
+ *   resp[m] = (sum_F fl(e expf(fl(term_m - u)))) / S0: the posterior responsibility of component m (M = 1: exactly 1);
+ *   out = fl32((double)t - log_z) on F, -inf elsewhere;
+ *   count = { contributing cells; NaN or +inf cells; cells of F with e == 0 (their mass underflowed); 0 }.
+ *   F empty: stats = { -inf, -inf, log_z_prior, -inf, NaN, 0, 0, 0 }, resp NaN, out all -inf.
+ *   The caller's figures: log_evidence = log_z - log_z_prior (the frame under the prior normalised on the lattice);
+ *   log_overlap = log_evidence - log_z_votes <= 0; information_gain = expected_log_prior - log_z + log_z_votes =
+ *   KL(post || votes alone) >= 0.
+ * f32 is used for the cell's expressions above and for the sums of one pixel's <= R terms of e, eu, ev and
+ * fl(e expf(..)) (each >= 0); e u enters its sum in float64 cell by cell, and everything above the pixel is float64.
+ * Four launches of 256 threads: t into out, the maxima and the counts (one pixel per thread walks its R cells; the
+ * tables sit in LDS); the sums, ONE partial row per workgroup; the fold, one workgroup; the normalisation of out in
+ * place.  The votes are read twice (the second read follows the first through the cache), out is written and then
+ * updated.  No atomics and no hand-off between workgroups: every reduction order is fixed by (R, Ho, Wo, M), so two
+ * calls give the same bits.  Every element of out, resp[0..M), stats and count is written by every call.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31, 1 <= M <= 8; anything else returns SNAP_ERR_BAD_SHAPE before
+ * any launch (a NULL pointer other than votes SNAP_ERR_NULL, checked first; with votes, a scale that is not a finite
+ * number > 0 SNAP_ERR_UNSUPPORTED; a short or not 8-byte aligned workspace SNAP_ERR_WORKSPACE).  workspace:
+ * snap_vote_prior_workspace_bytes() bytes (0 = unsupported shape); it needs no initialisation and no launch touches a
+ * byte beyond that size.  Asynchronous on `stream`; the caller owns every buffer. */
+size_t snap_vote_prior_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t M);
+int snap_vote_prior_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, float scale, int32_t M,
+                        const int32_t* centres, const float* planes, const float* comps, float* out, double* resp,
+                        double* stats, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Most likely pose TRACK over vote volumes: one forward step of the max-product (Viterbi) recursion that goes with the
  * filter above, with back-pointers.  score_prev[R,Ho,Wo] f32 is the log score of the best path into every pose of the

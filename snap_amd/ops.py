@@ -2619,6 +2619,67 @@ def temper_volume(votes, scales, gt_index=None):
   return table, stats, count
 
 
+def prior_volume(votes, table, scale=1.0, device=None):
+  """The wrapper of vote_prior.hip (its messages carry the operator's name, ``vote_prior:``; like ``rebase_volume`` and
+  ``temper_volume`` it is not named ``vote_*``: it takes a host table, and its refusals are tabled in
+  tests/test_gpu_vote_prior.py).  A position / heading prior fused into a vote volume or belief: votes [R, Ho, Wo] f32 (log-scores; -inf = masked) or
+  None (the prior itself as a belief, on ``device``), ``table`` a host table with the attributes ``shape`` = (R, Ho,
+  Wo), ``centres`` int32 [M, R, 2], ``planes`` f32 [M, R, 3] and ``comps`` f32 [M, 4], 1 <= M <= 8, as numpy arrays
+  (``pose_exhaustive_voting.pose_prior``) -> (out f32 [R, Ho, Wo], resp float64 [M], stats float64 [8], count int32
+  [4]).  With u the table's unnormalised log-prior of a cell and t = scale * votes + u over the finite cells: out = t -
+  log_z (-inf elsewhere); stats = (log_z, the log-sum-exp of scale * votes, that of u over the whole lattice, that of u
+  over the finite cells, E_post[u], 0, 0, 0); resp = the components' posterior responsibilities; count = (contributing
+  cells, NaN or +inf cells, contributing cells whose mass underflowed, 0) (the full contract: snap_vote_prior_f32 in
+  include/snap_hip.h).  The table is uploaded once per device and kept with the ``table`` object: a repeated prior
+  uploads nothing.  No host synchronisation."""
+  lib = _lib.load()
+  try:
+    shape = tuple(int(v) for v in table.shape)
+    centres, planes, comps = table.centres, table.planes, table.comps
+    M = int(comps.shape[0])
+    ok = (len(shape) == 3 and centres.dtype == np.int32 and planes.dtype == np.float32 and comps.dtype == np.float32
+          and centres.shape == (M, shape[0], 2) and planes.shape == (M, shape[0], 3) and comps.shape == (M, 4))
+  except (AttributeError, TypeError, ValueError, IndexError):
+    ok = False
+  if not ok:
+    raise ValueError('vote_prior: table with shape = (R, Ho, Wo), centres int32 [M, R, 2], planes f32 [M, R, 3] and '
+                     f'comps f32 [M, 4] as numpy arrays, got {table!r}')
+  if votes is None:
+    if device is None or torch.device(device).type != 'cuda':
+      raise ValueError(f'vote_prior: without votes a ROCm device must be named, got {device}')
+    dev = torch.device(device)
+    if dev.index is None:
+      dev = torch.device('cuda', torch.cuda.current_device())
+    scale = 1.0
+  else:
+    if _vote_volume_arg('vote_prior', votes, 'votes') != shape:
+      raise ValueError(f'vote_prior: the table was built for {shape}, votes are {tuple(votes.shape)}')
+    dev = votes.device
+    scale = _vote_scale('vote_prior', scale)
+  R, Ho, Wo = shape
+  n = R * Ho * Wo
+  words = _workspace_words(lib.snap_vote_prior_workspace_bytes, (R, Ho, Wo, M), n,
+                           _vote_unsupported('vote_prior', R, Ho, Wo)[:-1] + f', 1 <= M <= 8; M={M})')
+  from snap_amd.models import base   # (the per-device constant cache lives there; base imports this module)
+
+  def make():   # one blob: the int32 centres, then the two f32 tables
+    raw = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in (centres, planes, comps)])
+    return torch.from_numpy(raw)
+  blob = base.device_const('vote_prior_table', dev, make, owner=table)
+  nc, npl = centres.nbytes, planes.nbytes
+  ws = torch.empty((words,), dtype=torch.int64, device=dev)
+  out = torch.empty((R, Ho, Wo), dtype=torch.float32, device=dev)
+  resp = torch.empty((M,), dtype=torch.float64, device=dev)
+  stats = torch.empty((8,), dtype=torch.float64, device=dev)
+  count = torch.empty((4,), dtype=torch.int32, device=dev)
+  # algorithmic bytes: one read and one write of the volume
+  with _region('vote_prior', 0.0, 4.0 * n * (1 if votes is None else 2)):
+    st = lib.snap_vote_prior_f32(_p(votes), R, Ho, Wo, scale, M, _p(blob), _p(blob[nc:]), _p(blob[nc + npl:]), _p(out),
+                                 _p(resp), _p(stats), _p(count), _p(ws), ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_prior_f32')
+  return out, resp, stats, count
+
+
 def vote_fuse(volumes, shifts, weights=None):
   """Multi-frame fusion of aligned vote volumes: volumes [N, R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked),
   shifts f32 [N, R, 3] = (dk, da, db) on the same device (``pose_exhaustive_voting.sequence_shift_table``), weights

@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4 | vote_odometry_c4 | vote_rebase_c4 | vote_temper_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4 | vote_odometry_c4 | vote_rebase_c4 | vote_temper_c4 | vote_prior_c4)
 """
 import math
 import os
@@ -713,6 +713,65 @@ def vote_temper_c4(iters):
   emit_json(res)
 
 
+def vote_prior_c4(iters):
+  """A GNSS / compass prior fused into the C4 vote volume (R = 36, 511 x 511, the low-overlap border -inf) with M = 1 and
+  M = 8 components and a sensor off the grid centre: one whole ops.prior_volume call beside the same normalised volume
+  composed from what the library offered before (torch broadcasting for the log-prior from the same table, an add,
+  ops.vote_posterior for the normaliser, a subtraction), blocks alternated, medians of single calls.  One JSON line;
+  `json=<path>` as a third argument also writes it to that file."""
+  import numpy as np
+  from snap_amd.models import pose_exhaustive_voting as pev
+  from snap_amd.utils import grids
+  R, H, scale = 36, 256, 8.0
+  Ho = Wo = 2 * H - 1
+  grid = grids.Grid2D((H, H), 0.2)
+  g = torch.Generator(device='cuda').manual_seed(0)
+  votes = torch.randn((R, Ho, Wo), device='cuda', generator=g) * 0.25
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  votes = torch.where((ov[:, None] * ov[None, :] > 0.05 * H * H)[None], votes, float('-inf')).contiguous()
+  rng = np.random.default_rng(0)
+  res = dict(case='vote_prior_c4', shape=[R, Ho, Wo], scale=scale)
+  for M in (1, 8):
+    pos = 25.6 + rng.uniform(-8.0, 8.0, (M, 2))
+    cov = np.stack([np.array([[4.0, 1.0], [1.0, 9.0]]) * rng.uniform(0.5, 2.0) for _ in range(M)])
+    prior = pev.pose_prior(grid, R, position=pos, covariance=cov, heading=rng.uniform(-3, 3, M),
+                           concentration=np.full(M, 4.0), weights=rng.uniform(0.5, 1.0, M), sensor_q=[27.0, 24.9])
+    n = torch.tensor(prior.centres, device='cuda').float()
+    f = torch.tensor(prior.planes, device='cuda')
+    P = torch.tensor(prior.comps, device='cuda')
+    a = torch.arange(Ho, device='cuda').float()[None, None, :, None]
+    b = torch.arange(Wo, device='cuda').float()[None, None, None, :]
+
+    def composed():
+      da = (a - n[:, :, 0, None, None]) - f[:, :, 0, None, None]
+      db = (b - n[:, :, 1, None, None]) - f[:, :, 1, None, None]
+      q = (P[:, 0, None, None, None] * da * da + 2 * P[:, 1, None, None, None] * da * db
+           + P[:, 2, None, None, None] * db * db)
+      u = torch.logsumexp((P[:, 3, None] + f[:, :, 2])[:, :, None, None] - 0.5 * q, 0)
+      t = scale * votes + u
+      return t - ops.vote_posterior(t, 1.0)[2][0]
+    fused = lambda: ops.prior_volume(votes, prior, scale)
+    out, want = fused()[0], composed()
+    fin = torch.isfinite(want)
+    diff = float((out[fin] - want[fin]).abs().max())
+    assert bool((torch.isfinite(out) == fin).all()) and diff < 1e-3, diff
+    k = max(iters, 5)
+    (p_ms, ps), (c_ms, cs) = alternated_blocks(((fused, 5, k), (composed, 5, k)))
+    res[f'M{M}'] = dict(vote_prior_call_ms=round(p_ms, 4), vote_prior_call_ms_blocks=[round(v, 4) for v in ps],
+                        composed_ms=round(c_ms, 4), composed_ms_blocks=[round(v, 4) for v in cs],
+                        ratio_prior_to_composed=round(p_ms / c_ms, 4), block_ranges_overlap=bool(max(ps) >= min(cs)),
+                        max_abs_difference=diff,
+                        effective_bytes_per_s=round(8.0 * votes.numel() / (p_ms * 1e-3), 1),
+                        workspace_bytes=int(ops._lib.load().snap_vote_prior_workspace_bytes(R, Ho, Wo, M)))
+  res['timing'] = ('whole wrapper calls (torch.empty outputs and workspace, the ctypes call, the four launches; for the '
+                   'composition its torch kernels, their temporaries and one ops.vote_posterior call) between device '
+                   'events on an idle stream, NOT kernel time; median of single calls, 5 blocks of each alternated, '
+                   'median block; effective_bytes_per_s counts one read and one write of the volume against the '
+                   'measured call time (the 37.6 MB volume fits the 256 MB Infinity Cache); no threshold is set on '
+                   'this case')
+  emit_json(res)
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -720,4 +779,5 @@ if __name__ == '__main__':
    'vote_peaks_c4': vote_peaks_c4, 'vote_posterior_c4': vote_posterior_c4, 'vote_fuse_c4': vote_fuse_c4,
    'vote_filter_c4': vote_filter_c4, 'vote_smooth_c4': vote_smooth_c4,
    'vote_refine_c4': vote_refine_c4, 'vote_modes_c4': vote_modes_c4, 'vote_recall_c4': vote_recall_c4,
-   'vote_odometry_c4': vote_odometry_c4, 'vote_rebase_c4': vote_rebase_c4, 'vote_temper_c4': vote_temper_c4}[which](iters)
+   'vote_odometry_c4': vote_odometry_c4, 'vote_rebase_c4': vote_rebase_c4, 'vote_temper_c4': vote_temper_c4,
+   'vote_prior_c4': vote_prior_c4}[which](iters)
