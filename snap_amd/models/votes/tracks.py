@@ -1,0 +1,317 @@
+"""The stateful tracks: ``VoteFilter`` (the recursive filter of one vehicle on one map lattice, with its smoother,
+sampler, noise fit and the per-belief analysis) and ``VoteViterbi`` (its max-product companion), and ``viterbi_track``,
+the latter over frames held in memory."""
+import math
+
+import torch
+
+from snap_amd import ops
+from snap_amd.models.pose_exhaustive_voting import exhaustive_indices_to_tfm, exhaustive_pose_voting
+from snap_amd.models.votes.analysis import (_with_posterior, credible_from_votes, modes_from_votes, poses_from_votes,
+                                            recall_from_votes)
+from snap_amd.models.votes.frames import prior_votes, rebase_votes
+from snap_amd.models.votes.lattice import _linear_to_indices, _no_motion
+from snap_amd.models.votes.noise import NOISE_CANDIDATES, fit_motion_noise
+from snap_amd.models.votes.odometry import increment_from_votes
+from snap_amd.models.votes.sequence import (_entered_by_jump, _track_lists, filter_votes, sample_tracks, smooth_track,
+                                            viterbi_votes)
+
+
+class _Track:
+  """What ``VoteFilter`` and ``VoteViterbi`` share: the grid, the number of rotations and the five parameters of a
+  step, converted once, and the frame of ``localize``."""
+
+  def __init__(self, grid, num_rotations, sigma_xy, sigma_yaw, temperature, uniform_mix, truncate):
+    self.grid = grid
+    self.num_rotations = int(num_rotations)
+    self.sigma_xy = float(sigma_xy)
+    self.sigma_yaw = float(sigma_yaw)
+    self.temperature = float(temperature)
+    self.uniform_mix = float(uniform_mix)
+    self.truncate = float(truncate)
+
+  def _localize(self, volume, keep, plane_q, plane_map, cur_t_prev, conf_q, method, peaks):
+    """``exhaustive_pose_voting`` of the new frame, ``step``, then ``poses_from_votes(**peaks)`` of the step's
+    ``volume`` entry: that dict plus ``votes`` (the volume), ``votes_frame`` (the frame's own votes) and the step's
+    ``keep`` entries."""
+    frame = exhaustive_pose_voting(plane_q, plane_map, self.num_rotations, self.grid, conf_q=conf_q, method=method)
+    step = self.step(frame, cur_t_prev)
+    out = poses_from_votes(step[volume], self.grid, self.num_rotations, **peaks)
+    out['votes'] = step[volume]
+    out['votes_frame'] = frame
+    for name in keep:
+      out[name] = step[name]
+    return out
+
+
+class VoteFilter(_Track):
+  """A track: the recursive pose filter of one vehicle on one map lattice.  Holds the grid, the number of rotations,
+  the odometry noise (``sigma_xy`` metres, ``sigma_yaw`` radians per step), ``temperature``, ``uniform_mix``,
+  ``truncate`` (``filter_votes``) and the current ``belief`` (None before the first frame and after ``reset()``).
+  With ``keep_history`` every step's ``(belief, cur_t_prev)`` is appended to ``history`` (one volume per frame stays
+  allocated) for ``smooth()``."""
+
+  def __init__(self, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0, uniform_mix=1e-3, truncate=3.0,
+               keep_history=False):
+    # (``uniform_mix`` is not checked here, unlike in ``VoteViterbi``: ``ops.vote_filter`` rejects it at the first step)
+    super().__init__(grid, num_rotations, sigma_xy, sigma_yaw, temperature, uniform_mix, truncate)
+    self.belief = None
+    if keep_history:                                         # (without it the attribute does not exist at all)
+      self.history = []
+
+  def _belief(self, what):
+    if self.belief is None:
+      raise ValueError(f'VoteFilter.{what}: no belief (at least one step)')
+    return self.belief
+
+  def _history(self, what, least=1):
+    history = getattr(self, 'history', None) or []
+    if len(history) < least:
+      raise ValueError(f'VoteFilter.{what}: no history (keep_history=True and at least '
+                       f'{"one step" if least == 1 else "two steps"})')
+    return history
+
+  def reset(self):
+    """Drop the belief (and the history): the next ``step`` starts a track from a uniform prior."""
+    self.belief = None
+    if hasattr(self, 'history'):
+      self.history = []
+
+  def step(self, votes, cur_t_prev=None):
+    """One filter step with the new frame's ``votes`` -> ``filter_votes``' dict; the belief is kept.  ``cur_t_prev``:
+    the odometry increment since the previous step (ignored by the first step of a track); None = no motion (the
+    belief is only diffused)."""
+    # (the volume's shape against the belief's is left to the op, unlike in ``VoteViterbi.step``)
+    if self.belief is not None and cur_t_prev is None:
+      cur_t_prev = _no_motion()
+    out = filter_votes(self.belief, votes, cur_t_prev, self.grid, self.num_rotations, self.sigma_xy, self.sigma_yaw,
+                       self.temperature, self.uniform_mix, self.truncate)
+    self.belief = out['belief']
+    if hasattr(self, 'history'):
+      self.history.append((out['belief'], cur_t_prev))
+    return out
+
+  def localize(self, plane_q, plane_map, cur_t_prev=None, conf_q=None, method=None, posterior=None, **peaks):
+    """``exhaustive_pose_voting`` of the new frame, ``step``, then ``poses_from_votes(belief, **peaks)``: the dict of
+    ``localize_exhaustive`` with ``votes`` = the belief, plus ``votes_frame`` (the frame's own votes),
+    ``log_evidence`` and ``mass_kept``.  ``posterior`` as in ``localize_exhaustive``, on the belief."""
+    out = self._localize('belief', ('log_evidence', 'mass_kept'), plane_q, plane_map, cur_t_prev, conf_q, method,
+                         peaks)
+    _with_posterior(out, out['votes'], self.grid, self.num_rotations, posterior)
+    return out
+
+  def credible(self, levels=(0.5, 0.9, 0.99), m_t_q_gt=None, cell_levels=False):
+    """``credible_from_votes`` of the belief the filter holds (log-space and normalised, so the temperature is 1) ->
+    its dict.  Raises ValueError before the first step."""
+    return credible_from_votes(self._belief('credible'), self.grid, self.num_rotations, levels=levels,
+                               temperature=1.0, m_t_q_gt=m_t_q_gt, cell_levels=cell_levels)
+
+  def modes(self, **kw):
+    """``modes_from_votes(**kw)`` of the belief the filter holds (log-space and normalised, so the temperature is 1 and
+    log_z is 0) -> its dict.  Raises ValueError before the first step."""
+    return modes_from_votes(self._belief('modes'), self.grid, self.num_rotations, temperature=1.0, log_z=0.0, **kw)
+
+  def recall(self, **kw):
+    """``recall_from_votes(**kw)`` of the belief the filter holds (log-space and normalised, so the temperature is 1)
+    -> its dict.  Raises ValueError before the first step."""
+    return recall_from_votes(self._belief('recall'), self.grid, self.num_rotations, temperature=1.0, **kw)
+
+  def rebase(self, new_t_old, drop_history=False):
+    """Carry the belief the filter holds into another map frame (the vehicle drives onto the neighbouring map tile, or
+    the map is re-anchored): ``rebase_votes(belief, new_t_old)`` with temperature 1 (the belief is log-space and
+    normalised) -> its dict; the belief is replaced, so the track goes on where ``reset()`` would restart it from a
+    uniform prior.  Cells the old lattice did not cover come out -inf; the next ``step``'s ``uniform_mix`` re-opens
+    them.  The stored beliefs of a history are in the OLD frame and the smoother cannot mix frames: with a non-empty
+    history this raises ValueError unless ``drop_history`` is true, which restarts the history empty.  Raises
+    ValueError before the first step."""
+    belief = self._belief('rebase')
+    if getattr(self, 'history', None) and not drop_history:
+      raise ValueError(f'VoteFilter.rebase: the {len(self.history)} stored beliefs are in the old map frame; '
+                       'drop_history=True restarts the history')
+    out = rebase_votes(belief, new_t_old, self.grid, self.num_rotations, temperature=1.0)
+    self.belief = out['votes']
+    if hasattr(self, 'history'):
+      self.history = []
+    return out
+
+  def apply_prior(self, prior):
+    """The measurement update of the belief the filter holds with a ``pose_prior`` (a GNSS fix, a compass):
+    ``prior_votes(belief, prior)`` with temperature 1 (the belief is log-space and normalised) -> its dict; the belief
+    is replaced.  With a history the belief of its last entry is replaced as well and that entry's ``cur_t_prev`` kept:
+    a frame's stored belief is p(x_t | everything up to t), which now includes the fix.  ``step(votes)`` followed by
+    ``apply_prior`` is the prior-times-votes start of a track.  Raises ValueError before the first step."""
+    out = prior_votes(self._belief('apply_prior'), prior, self.grid, self.num_rotations, temperature=1.0)
+    self.belief = out['votes']
+    if getattr(self, 'history', None):
+      self.history[-1] = (out['votes'], self.history[-1][1])
+    return out
+
+  def estimate_increment(self, votes, **kw):
+    """``increment_from_votes(belief, votes, **kw)``: the increment since the previous step from the belief the filter
+    holds (log-space and normalised, so its temperature is 1) and the new frame's ``votes`` (the filter's
+    temperature) -> its dict.  Nothing is stepped.  Raises ValueError before the first step."""
+    return increment_from_votes(self._belief('estimate_increment'), votes, self.grid, self.num_rotations,
+                                temperature_prev=1.0, temperature_cur=self.temperature, **kw)
+
+  def step_estimated(self, votes, **kw):
+    """``step`` with the increment taken from the votes themselves: ``estimate_increment(votes, **kw)``, then
+    ``step(votes, cur_t_prev=the MAP candidate)`` -> ``step``'s dict plus ``increment`` (``estimate_increment``'s dict;
+    None for the first step of a track, which needs no increment).  Raises ValueError where no candidate has
+    evidence."""
+    if self.belief is None:
+      out = self.step(votes)
+      out['increment'] = None
+      return out
+    inc = self.estimate_increment(votes, **kw)
+    if inc['cur_t_prev'] is None:
+      raise ValueError('VoteFilter.step_estimated: no candidate increment has evidence')
+    out = self.step(votes, cur_t_prev=inc['cur_t_prev'])
+    out['increment'] = inc
+    return out
+
+  def smooth(self, posterior=None, **peaks):
+    """The backward recursion over the history (``smooth_track``; each step's taps are rebuilt by ``motion_taps``) ->
+    one dict per frame: ``poses_from_votes(smoothed, **peaks)`` plus ``votes`` (the smoothed volume; the last frame's
+    is the filter's belief itself), ``log_norm`` (None for the last frame) and, with ``posterior`` as in
+    ``localize_exhaustive``, ``posterior``.  Raises ValueError without a history."""
+    beliefs, increments = zip(*self._history('smooth'))
+    steps = smooth_track(beliefs, increments, self.grid, self.num_rotations, self.sigma_xy, self.sigma_yaw,
+                         self.uniform_mix, self.truncate, details=True)
+    frames = []
+    for belief, step in zip(beliefs, steps):
+      votes = belief if step is None else step['smoothed']
+      out = poses_from_votes(votes, self.grid, self.num_rotations, **peaks)
+      out['votes'] = votes
+      out['log_norm'] = None if step is None else step['log_norm']
+      _with_posterior(out, votes, self.grid, self.num_rotations, posterior)
+      frames.append(out)
+    return frames
+
+  def fit_noise(self, volumes=None, iterations=5, candidates=NOISE_CANDIDATES, apply=False):
+    """``fit_motion_noise`` on the history's increments, starting from this filter's ``sigma_xy``, ``sigma_yaw`` and
+    ``uniform_mix``.  The history keeps the beliefs, not the frames' own vote volumes, so ``volumes`` (the volumes the
+    steps were given, ``localize``'s ``votes_frame``, in frame order) is required -> ``fit_motion_noise``'s pair (the
+    fitted values, the per-iteration records).  The filter's parameters are left alone unless ``apply`` is true; the
+    belief and the history are never touched (they were computed with the old values).  Raises ValueError without a
+    history of at least two steps or when the volumes do not match it."""
+    history = self._history('fit_noise', least=2)
+    if volumes is None or len(volumes) != len(history):
+      raise ValueError(f'VoteFilter.fit_noise: the {len(history)} vote volumes the steps were given are needed '
+                       '(the history keeps beliefs only)')
+    increments = [h[1] for h in history]
+    fitted, records = fit_motion_noise(volumes, increments, self.grid, self.num_rotations, self.sigma_xy,
+                                       self.sigma_yaw, self.uniform_mix, self.temperature, self.truncate, iterations,
+                                       candidates)
+    if apply:
+      self.sigma_xy, self.sigma_yaw, self.uniform_mix = fitted['sigma_xy'], fitted['sigma_yaw'], fitted['uniform_mix']
+    return fitted, records
+
+  def sample(self, num, seed):
+    """``num`` whole tracks drawn from the joint posterior of the history's frames (``sample_tracks``: forward-filter /
+    backward-sample on the stored beliefs; each step's taps are rebuilt by ``motion_taps``) -> its dict.  Raises
+    ValueError without a history."""
+    beliefs, increments = zip(*self._history('sample'))
+    return sample_tracks(beliefs, increments, self.grid, self.num_rotations, self.sigma_xy, self.sigma_yaw, num, seed,
+                         self.uniform_mix, self.truncate)
+
+
+def viterbi_track(volumes, increments, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0, uniform_mix=1e-3,
+                  truncate=3.0):
+  """The jointly most likely pose sequence of a track: ``volumes`` are the N frames' vote volumes [R, 2H-1, 2W-1],
+  ``increments`` the N odometry increments as ``VoteFilter.step`` takes them (entry 0 is ignored; None = no motion).
+  ``viterbi_votes`` over the frames, then the back-pointers from the last frame's best pose (``ops.vote_backstep``)
+  -> ``VoteViterbi.path()``'s dict: ``indices`` int32 [N, 3] = (r, a, b), ``linear`` int32 [N], ``m_t_q``
+  (``exhaustive_indices_to_tfm`` of the indices), ``log_score`` (float64 scalar: the last ``top`` plus the steps'
+  ``peak_prev`` for t >= 1) and ``jumps`` bool [N] (the step into frame t was the uniform jump), all on the device.
+  One int32 volume per frame is held until the trace is done."""
+  volumes, increments = _track_lists('viterbi_track', volumes=volumes, increments=increments)
+  for v in volumes:
+    if not isinstance(v, torch.Tensor) or v.dim() != 3 or v.shape != volumes[0].shape or v.shape[0] != num_rotations:
+      raise ValueError(f'viterbi_track: every volume [{num_rotations}, Ho, Wo] of one shape, got '
+                       f'{[tuple(getattr(u, "shape", ())) for u in volumes]}')
+  track = VoteViterbi(grid, num_rotations, sigma_xy, sigma_yaw, temperature, uniform_mix, truncate)
+  for v, inc in zip(volumes, increments):
+    track.step(v, inc)
+  return track.path()
+
+
+class VoteViterbi(_Track):
+  """A track's most likely pose sequence (the max-product companion of ``VoteFilter``, same arguments): ``step`` runs
+  ``viterbi_votes`` on each new frame and keeps the current ``score`` (None before the first frame and after
+  ``reset()``); ``path`` follows the back-pointers from the current best pose.  Every step's ``back`` is appended to
+  ``history``: one int32 volume per frame stays allocated until ``reset()``."""
+
+  def __init__(self, grid, num_rotations, sigma_xy, sigma_yaw, temperature=1.0, uniform_mix=1e-3, truncate=3.0):
+    super().__init__(grid, num_rotations, sigma_xy, sigma_yaw, temperature, uniform_mix, truncate)
+    if not 0.0 <= self.uniform_mix <= 1.0:                   # (checked here; ``VoteFilter`` leaves it to its op)
+      raise ValueError(f'VoteViterbi: uniform_mix must lie in [0, 1], got {uniform_mix}')
+    self.score = None
+    self.history = []
+
+  def reset(self):
+    """Drop the score and the back-pointers: the next ``step`` starts a track."""
+    self.score = None
+    self.history = []
+
+  def step(self, votes, cur_t_prev=None):
+    """One forward step with the new frame's ``votes`` -> ``viterbi_votes``' dict; ``score`` is kept and ``back``
+    appended.  ``cur_t_prev`` as in ``VoteFilter.step``."""
+    if self.score is not None:
+      if tuple(votes.shape) != tuple(self.score.shape):      # (checked here; ``VoteFilter.step`` leaves it to its op)
+        raise ValueError(f'VoteViterbi.step: votes {tuple(votes.shape)} on a track of {tuple(self.score.shape)}')
+      if cur_t_prev is None:
+        cur_t_prev = _no_motion()
+    out = viterbi_votes(self.score, votes, cur_t_prev, self.grid, self.num_rotations, self.sigma_xy, self.sigma_yaw,
+                        self.temperature, self.uniform_mix, self.truncate)
+    self.score = out['score']
+    self.history.append(out)
+    return out
+
+  def path(self, end=None):
+    """The back-pointers followed from the last frame to the first -> dict of device tensors: ``linear`` int32 [N],
+    ``indices`` int32 [N, 3] = (r, a, b) (-1 where there is no path), ``m_t_q`` (``exhaustive_indices_to_tfm`` of the
+    indices: Transform2D [N]), ``log_score`` (float64: the end pose's score plus the steps' ``peak_prev`` for t >= 1)
+    and ``jumps`` bool [N] (the step into frame t was the uniform jump; frame 0: False).  ``end``: None = the current
+    best pose (``count[5]``), or an int32 device tensor of B linear indices of the last frame (``vote_peaks`` of the
+    score, say) to trace B alternatives at once: ``linear`` [N, B], ``indices`` [N, B, 3], ``jumps`` [N, B],
+    ``log_score`` [B], ``m_t_q`` Transform2D [N * B] (frame-major).  No host synchronisation."""
+    if not self.history:
+      raise ValueError('VoteViterbi.path: no step yet')
+    last = self.history[-1]
+    single = end is None
+    if single:
+      cur = last['count'][5:6]
+    else:
+      if (not isinstance(end, torch.Tensor) or end.dtype != torch.int32 or end.dim() != 1 or end.numel() < 1
+          or end.device != self.score.device):
+        raise ValueError(f'VoteViterbi.path: end int32 [B] on {self.score.device}, got '
+                         f'{(end.dtype, tuple(end.shape), end.device) if isinstance(end, torch.Tensor) else type(end)}')
+      cur = end.contiguous()
+    shape = tuple(self.score.shape)
+    n = self.score.numel()
+    flat = self.score.reshape(-1)
+    known = (cur >= 0) & (cur < n)
+    end_score = torch.where(known, flat[cur.clamp(0, n - 1).long()], flat.new_full((), -math.inf))
+    log_score = end_score.double()
+    linear, jumps = [cur], []
+    for step in reversed(self.history[1:]):
+      prev = ops.vote_backstep(step['back'], cur)
+      jumps.append(_entered_by_jump(cur, prev, step['count'][4], step['log_taps'], shape, *step['log_weights']))
+      log_score = log_score + step['peak_prev'].double()
+      linear.append(prev)
+      cur = prev
+    jumps.append(torch.zeros_like(cur, dtype=torch.bool))
+    linear = torch.stack(linear[::-1])                       # [N, B]
+    jumps = torch.stack(jumps[::-1])
+    indices = _linear_to_indices(linear, shape)
+    m_t_q = exhaustive_indices_to_tfm(indices.reshape(-1, 3), self.grid, self.num_rotations)
+    if single:
+      linear, jumps, indices, log_score = linear[:, 0], jumps[:, 0], indices[:, 0], log_score[0]
+    return dict(indices=indices, linear=linear, m_t_q=m_t_q, log_score=log_score, jumps=jumps)
+
+  def localize(self, plane_q, plane_map, cur_t_prev=None, conf_q=None, method=None, **peaks):
+    """``exhaustive_pose_voting`` of the new frame, ``step``, then ``poses_from_votes(score, **peaks)``: the dict of
+    ``localize_exhaustive`` with ``votes`` = the current score volume, plus ``votes_frame`` (the frame's own votes),
+    ``back``, ``peak_prev`` and ``top``."""
+    return self._localize('score', ('back', 'peak_prev', 'top'), plane_q, plane_map, cur_t_prev, conf_q, method,
+                          peaks)
