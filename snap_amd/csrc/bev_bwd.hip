@@ -16,6 +16,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
+#include "bev_common.h"
 #include "lift_common.h"
 
 namespace {
@@ -68,12 +69,6 @@ __device__ __forceinline__ float lift_bwd_dscore(float wgt, float dw, float dwba
 }
 __device__ __forceinline__ float lift_bwd_dfeat(float wgt, float f, float mean, float dmean, float dvar) {
   return wgt * dmean + 2.f * wgt * (f - mean) * dvar;
-}
-
-__device__ __forceinline__ float half_sum(float v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-  return v;
 }
 
 // MODE 0: scatter with float atomics (default fusion options only)
@@ -702,31 +697,17 @@ __global__ __launch_bounds__(256) void vertical_pool_bwd_kernel(
   float* dbase = dvol + m * Z * D;
   for (int q = hl; q < nq; q += 32) {
     const f32x4 g = *reinterpret_cast<const f32x4*>(dplane + m * D + 4 * q);
-    f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    f32x4 cnt = {0.f, 0.f, 0.f, 0.f};
-    int nvalid = 0;
-    for (int z = 0; z < Z; ++z) {
-      if (!vv[z]) continue;
-      ++nvalid;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * q);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (v[e] > best[e]) { best[e] = v[e]; cnt[e] = 1.f; }
-        else if (v[e] == best[e]) cnt[e] += 1.f;
-      }
-    }
+    const BevColumnMax cm = bev_column_max_ties(base, vv, Z, D, q);   // (whatever the pooling)
     for (int z = 0; z < Z; ++z) {
       f32x4 o = {0.f, 0.f, 0.f, 0.f};
       if (vv[z]) {
         if (pooling == SNAP_POOL_MAX) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * q);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (v[e] == best[e]) ? g[e] / cnt[e] : 0.f;
+          o = bev_share_among_holders(*reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * q), cm.best, g, cm.cnt);
         } else if (pooling == SNAP_POOL_SUM) {
           o = g;
         } else {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = g[e] / (float)nvalid;
+          for (int e = 0; e < 4; ++e) o[e] = g[e] / (float)cm.nvalid;
         }
       }
       *reinterpret_cast<f32x4*>(dbase + (int64_t)z * D + 4 * q) = o;
@@ -737,7 +718,8 @@ __global__ __launch_bounds__(256) void vertical_pool_bwd_kernel(
 // Max pooling with the forward's record of where the maximum sits (snap_vertical_pool_max_arg_f32): a level
 // receives the gradient iff it is the recorded one -- the volume is not read at all (2 x 2 GB per C3 step in
 // the kernel above).  Channels whose maximum is held by several levels (ties > 1: the gradient is shared, as
-// jnp.max's VJP does) take the two passes of the kernel above for their quad: the same values, bit for bit.
+// jnp.max's VJP does) take the two passes of the kernel above for their quad (the same two pieces of
+// bev_common.h): the same values, bit for bit.
 __global__ __launch_bounds__(256) void vertical_pool_max_bwd_arg_kernel(
     const float* __restrict__ vol, const uint8_t* __restrict__ vvalid, const uint8_t* __restrict__ argz,
     const uint8_t* __restrict__ ties, const float* __restrict__ dplane, float* __restrict__ dvol, int64_t M,
@@ -766,24 +748,11 @@ __global__ __launch_bounds__(256) void vertical_pool_max_bwd_arg_kernel(
       }
       continue;
     }
-    f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    f32x4 cnt = {0.f, 0.f, 0.f, 0.f};
-    for (int z = 0; z < Z; ++z) {
-      if (!vv[z]) continue;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * q);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (v[e] > best[e]) { best[e] = v[e]; cnt[e] = 1.f; }
-        else if (v[e] == best[e]) cnt[e] += 1.f;
-      }
-    }
+    const BevColumnMax cm = bev_column_max_ties(base, vv, Z, D, q);
     for (int z = 0; z < Z; ++z) {
       f32x4 o = {0.f, 0.f, 0.f, 0.f};
-      if (vv[z]) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (v[e] == best[e]) ? g[e] / cnt[e] : 0.f;
-      }
+      if (vv[z])
+        o = bev_share_among_holders(*reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * q), cm.best, g, cm.cnt);
       *reinterpret_cast<f32x4*>(dbase + (int64_t)z * D + 4 * q) = o;
     }
   }
@@ -791,137 +760,78 @@ __global__ __launch_bounds__(256) void vertical_pool_max_bwd_arg_kernel(
 
 // ------------------------------- fuse + matching --------------------------------
 struct FuseBwdArgs {
-  const float* planes[4];
-  const uint8_t* valids[4];
+  BevFuseHead h;
   float* dplanes[4];
-  int num_planes;
-  int64_t M;
-  int D, pooling;
-  const float* Wm;
-  const float* bm;
-  int Dm, normalize;
-  float eps;
   const float* dmatching;  // [M,Dm] or null
   const float* dfused;     // [M,D] or null
   float* dy;               // [M,Dm] grad w.r.t. the Dense output (pre-normalisation)
 };
 
-constexpr int FB_MAXQ = 2;
-
+// Both VJP kernels recompute the fused vector with bev_reduce_step<false> (fmaxf), where the forward kernels
+// step with snap_max_nan: see bev_common.h.
 __global__ __launch_bounds__(256) void plane_fuse_match_bwd_kernel(const FuseBwdArgs a) {
+  const BevFuseHead& h = a.h;
   const int hl = threadIdx.x & 31;
   const int64_t m = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
-  if (m >= a.M) return;
-  const int nq = a.D >> 2;
+  if (m >= h.M) return;
+  const int nq = h.D >> 2;
   // recompute the fused vector and the routing weights
-  f32x4 fused[FB_MAXQ], x[4][FB_MAXQ];
+  f32x4 fused[BEV_MAXQ], x[BEV_MAXQ][4];
   bool pv[4];
   int count = 0;
-  const float init = a.pooling == SNAP_POOL_MAX ? -INFINITY : 0.f;
 #pragma unroll
-  for (int i = 0; i < FB_MAXQ; ++i) fused[i] = f32x4{init, init, init, init};
+  for (int i = 0; i < BEV_MAXQ; ++i) fused[i] = bev_quad(bev_reduce_init(h.pooling));
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     pv[p] = false;
 #pragma unroll
-    for (int i = 0; i < FB_MAXQ; ++i) x[p][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (p >= a.num_planes) continue;
-    pv[p] = a.valids[p] ? (a.valids[p][m] != 0) : true;
+    for (int i = 0; i < BEV_MAXQ; ++i) x[i][p] = bev_quad(0.f);
+    if (p >= h.num_planes) continue;
+    pv[p] = h.valids[p] ? (h.valids[p][m] != 0) : true;
     if (!pv[p]) continue;
     ++count;
 #pragma unroll
-    for (int i = 0; i < FB_MAXQ; ++i) {
+    for (int i = 0; i < BEV_MAXQ; ++i) {
       const int q = hl + 32 * i;
       if (q < nq) {
-        x[p][i] = *reinterpret_cast<const f32x4*>(a.planes[p] + m * a.D + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          fused[i][e] = a.pooling == SNAP_POOL_MAX ? fmaxf(fused[i][e], x[p][i][e])
-                                                   : fused[i][e] + x[p][i][e];
+        x[i][p] = *reinterpret_cast<const f32x4*>(h.planes[p] + m * h.D + 4 * q);
+        fused[i] = bev_reduce_step<false>(fused[i], x[i][p], h.pooling);
       }
     }
   }
   const bool any = count > 0;
 #pragma unroll
-  for (int i = 0; i < FB_MAXQ; ++i) {
-    if (!any) fused[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (any && a.pooling == SNAP_POOL_MEAN) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) fused[i][e] = fused[i][e] / (float)count;
-    }
-  }
+  for (int i = 0; i < BEV_MAXQ; ++i) fused[i] = bev_reduce_finish(fused[i], h.pooling, count);
   // ---- matching head backward: dy (lane j) ----------------------------------
   const int j = hl;
   float dyj = 0.f;
   if (a.dmatching) {
-    float y = (j < a.Dm) ? a.bm[j] : 0.f;
-#pragma unroll
-    for (int i = 0; i < FB_MAXQ; ++i)
-      for (int q = 0; q < 32; ++q) {
-        const int cq = q + 32 * i;
-        if (cq >= nq) break;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float xv = __shfl(fused[i][e], q, 32);
-          if (j < a.Dm) y += xv * a.Wm[(int64_t)(4 * cq + e) * a.Dm + j];
-        }
-      }
-    const float dz = (j < a.Dm && any) ? a.dmatching[m * a.Dm + j] : 0.f;
-    if (a.normalize) {
-      const float nrm = sqrtf(half_sum((j < a.Dm) ? y * y : 0.f));
-      if (nrm >= a.eps) {
-        const float z = y / nrm;
-        const float zdz = half_sum((j < a.Dm) ? z * dz : 0.f);
-        dyj = (dz - z * zdz) / nrm;
-      }
-    } else {
-      dyj = dz;
-    }
-    if (j < a.Dm) a.dy[m * a.Dm + j] = dyj;
+    const float y = bev_head_shfl(fused, nq, h.Wm, h.bm, h.Dm, j);
+    const float dz = (j < h.Dm && any) ? a.dmatching[m * h.Dm + j] : 0.f;
+    dyj = h.normalize ? bev_l2_normalize_vjp(y, dz, j, h.Dm, h.eps) : dz;
+    if (j < h.Dm) a.dy[m * h.Dm + j] = dyj;
   }
   // ---- d fused = Wm dy (+ dfused) and routing to the planes -------------------
 #pragma unroll
-  for (int i = 0; i < FB_MAXQ; ++i) {
+  for (int i = 0; i < BEV_MAXQ; ++i) {
     const int q = hl + 32 * i;
     f32x4 df = {0.f, 0.f, 0.f, 0.f};
     if (a.dmatching) {
-      for (int jj = 0; jj < a.Dm; ++jj) {
+      for (int jj = 0; jj < h.Dm; ++jj) {
         const float dv = __shfl(dyj, jj, 32);
         if (q < nq) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) df[e] += a.Wm[(int64_t)(4 * q + e) * a.Dm + jj] * dv;
+          for (int e = 0; e < 4; ++e) df[e] += h.Wm[(int64_t)(4 * q + e) * h.Dm + jj] * dv;
         }
       }
     }
     if (q >= nq) continue;
     if (a.dfused && any) {
-      const f32x4 g = *reinterpret_cast<const f32x4*>(a.dfused + m * a.D + 4 * q);
+      const f32x4 g = *reinterpret_cast<const f32x4*>(a.dfused + m * h.D + 4 * q);
 #pragma unroll
       for (int e = 0; e < 4; ++e) df[e] += g[e];
     }
-    f32x4 ties = {0.f, 0.f, 0.f, 0.f};
-    if (a.pooling == SNAP_POOL_MAX) {
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-        if (pv[p]) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ties[e] += (x[p][i][e] == fused[i][e]) ? 1.f : 0.f;
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      if (p >= a.num_planes || !a.dplanes[p]) continue;
-      f32x4 o = {0.f, 0.f, 0.f, 0.f};
-      if (pv[p]) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (a.pooling == SNAP_POOL_MAX) o[e] = (x[p][i][e] == fused[i][e]) ? df[e] / ties[e] : 0.f;
-          else if (a.pooling == SNAP_POOL_SUM) o[e] = df[e];
-          else o[e] = df[e] / (float)count;
-        }
-      }
-      *reinterpret_cast<f32x4*>(a.dplanes[p] + m * a.D + 4 * q) = o;
-    }
+    bev_route_to_planes(x[i], pv, fused[i], df, h.pooling, count, h.num_planes, a.dplanes, m * h.D + 4 * q);
   }
 }
 
@@ -935,82 +845,54 @@ __global__ __launch_bounds__(256) void plane_fuse_match_bwd_d128_kernel(const Fu
   __shared__ __attribute__((aligned(16))) float wt[32][128];      // Wm^T, rows beyond Dm zero
   __shared__ __attribute__((aligned(16))) float sv[8][128];
   __shared__ __attribute__((aligned(16))) float sd[8][32];
+  const BevFuseHead& h = a.h;
   const int hl = threadIdx.x & 31, hw = threadIdx.x >> 5;
   const int j = hl;
   for (int i = threadIdx.x; i < 32 * 128; i += 256) {
     const int jj = i >> 7, k = i & 127;
-    wt[jj][k] = jj < a.Dm ? a.Wm[(int64_t)k * a.Dm + jj] : 0.f;
+    wt[jj][k] = jj < h.Dm ? h.Wm[(int64_t)k * h.Dm + jj] : 0.f;
   }
   float wreg[128];
-#pragma unroll
-  for (int k = 0; k < 128; ++k) wreg[k] = j < a.Dm ? a.Wm[(int64_t)k * a.Dm + j] : 0.f;
-  const float bj = j < a.Dm ? a.bm[j] : 0.f;
+  bev_head_load_column(wreg, h.Wm, h.Dm, j);
+  const float bj = j < h.Dm ? h.bm[j] : 0.f;
   __syncthreads();
-  const float init = a.pooling == SNAP_POOL_MAX ? -INFINITY : 0.f;
-  for (int64_t m = (int64_t)blockIdx.x * 8 + hw; m < a.M; m += (int64_t)gridDim.x * 8) {
-    f32x4 fused = {init, init, init, init};
+  const float init = bev_reduce_init(h.pooling);
+  for (int64_t m = (int64_t)blockIdx.x * 8 + hw; m < h.M; m += (int64_t)gridDim.x * 8) {
+    f32x4 fused = bev_quad(init);
     f32x4 x[4];
     bool pv[4];
     int count = 0;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       pv[p] = false;
-      x[p] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (p < a.num_planes) {
-        pv[p] = a.valids[p] ? (a.valids[p][m] != 0) : true;
-        if (pv[p]) x[p] = *reinterpret_cast<const f32x4*>(a.planes[p] + m * 128 + 4 * hl);
+      x[p] = bev_quad(0.f);
+      if (p < h.num_planes) {
+        pv[p] = h.valids[p] ? (h.valids[p][m] != 0) : true;
+        if (pv[p]) x[p] = *reinterpret_cast<const f32x4*>(h.planes[p] + m * 128 + 4 * hl);
       }
     }
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       if (!pv[p]) continue;
       ++count;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        fused[e] = a.pooling == SNAP_POOL_MAX ? fmaxf(fused[e], x[p][e]) : fused[e] + x[p][e];
+      fused = bev_reduce_step<false>(fused, x[p], h.pooling);
     }
     const bool any = count > 0;
-    if (!any) fused = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (any && a.pooling == SNAP_POOL_MEAN) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) fused[e] = fused[e] / (float)count;
-    }
+    fused = bev_reduce_finish(fused, h.pooling, count);
     // ---- matching head backward: dy (lane j) ----------------------------------
-    *reinterpret_cast<f32x4*>(&sv[hw][4 * hl]) = fused;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float y = bj;
-#pragma unroll
-    for (int q = 0; q < 32; ++q) {
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(&sv[hw][4 * q]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) y += xv[e] * wreg[4 * q + e];
-    }
-    float dyj = 0.f;
-    const float dz = (j < a.Dm && any) ? a.dmatching[m * a.Dm + j] : 0.f;
-    if (a.normalize) {
-      const float nrm = sqrtf(half_sum((j < a.Dm) ? y * y : 0.f));
-      if (nrm >= a.eps) {
-        const float z = y / nrm;
-        const float zdz = half_sum((j < a.Dm) ? z * dz : 0.f);
-        dyj = (dz - z * zdz) / nrm;
-      }
-    } else {
-      dyj = dz;
-    }
-    if (j < a.Dm) a.dy[m * a.Dm + j] = dyj;
+    const float y = bev_head_column(sv[hw], hl, fused, wreg, bj);
+    const float dz = (j < h.Dm && any) ? a.dmatching[m * h.Dm + j] : 0.f;
+    const float dyj = h.normalize ? bev_l2_normalize_vjp(y, dz, j, h.Dm, h.eps) : dz;
+    if (j < h.Dm) a.dy[m * h.Dm + j] = dyj;
     // ---- d fused = Wm dy (+ dfused) and routing to the planes -------------------
     sd[hw][hl] = dyj;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    bev_wave_publish();
     f32x4 df = {0.f, 0.f, 0.f, 0.f};
-    for (int j4 = 0; j4 < a.Dm; j4 += 4) {
+    for (int j4 = 0; j4 < h.Dm; j4 += 4) {
       const f32x4 dv = *reinterpret_cast<const f32x4*>(&sd[hw][j4]);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        if (j4 + u >= a.Dm) break;
+        if (j4 + u >= h.Dm) break;
         const f32x4 w = *reinterpret_cast<const f32x4*>(&wt[j4 + u][4 * hl]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) df[e] += w[e] * dv[u];
@@ -1022,29 +904,7 @@ __global__ __launch_bounds__(256) void plane_fuse_match_bwd_d128_kernel(const Fu
 #pragma unroll
       for (int e = 0; e < 4; ++e) df[e] += g[e];
     }
-    f32x4 ties = {0.f, 0.f, 0.f, 0.f};
-    if (a.pooling == SNAP_POOL_MAX) {
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-        if (pv[p]) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ties[e] += (x[p][e] == fused[e]) ? 1.f : 0.f;
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      if (p >= a.num_planes || !a.dplanes[p]) continue;
-      f32x4 o = {0.f, 0.f, 0.f, 0.f};
-      if (pv[p]) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (a.pooling == SNAP_POOL_MAX) o[e] = (x[p][e] == fused[e]) ? df[e] / ties[e] : 0.f;
-          else if (a.pooling == SNAP_POOL_SUM) o[e] = df[e];
-          else o[e] = df[e] / (float)count;
-        }
-      }
-      *reinterpret_cast<f32x4*>(a.dplanes[p] + m * 128 + 4 * hl) = o;
-    }
+    bev_route_to_planes(x, pv, fused, df, h.pooling, count, h.num_planes, a.dplanes, m * 128 + 4 * hl);
   }
 }
 
@@ -1278,6 +1138,8 @@ extern "C" int snap_lift_observations_bwd_f32(const SnapLiftDesc* desc, const fl
   return lift_det_sort_gather(dd, L, ws, a, dobs, nullptr, df_images, s);   // (the record vectors ARE d obs)
 }
 
+// (Z <= 255 and any D here, while the forward that writes the record, snap_vertical_pool_max_arg_f32, accepts
+//  Z <= 64 and D <= 128 only: an oddity kept as it is.)
 extern "C" int snap_vertical_pool_max_bwd_arg_f32(const float* vol, const uint8_t* vvalid, const uint8_t* argz,
                                                   const uint8_t* ties, const float* dplane, float* dvol,
                                                   int64_t M, int32_t Z, int32_t D, void* stream) {
@@ -1289,6 +1151,7 @@ extern "C" int snap_vertical_pool_max_bwd_arg_f32(const float* vol, const uint8_
   return SNAP_OK;
 }
 
+// (no upper bound on D, unlike the forward's D <= 256: the kernel strides over the quads.  Kept as it is.)
 extern "C" int snap_vertical_pool_bwd_f32(const float* vol, const uint8_t* vvalid,
                                           const float* dplane, float* dvol, int64_t M, int32_t Z,
                                           int32_t D, int32_t pooling, void* stream) {
@@ -1308,23 +1171,15 @@ extern "C" int snap_plane_fuse_match_bwd_f32(const float* const* planes,
                                              int32_t Dm, int32_t normalize, float eps,
                                              const float* dmatching, const float* dfused, float* dy,
                                              void* stream) {
-  if (!planes || !dplanes) return SNAP_ERR_NULL;
-  if (num_planes < 1 || num_planes > 4) return SNAP_ERR_UNSUPPORTED;
-  if (M <= 0 || D <= 0 || D % 4 != 0 || D > FB_MAXQ * 128) return SNAP_ERR_BAD_SHAPE;
-  if (pooling < SNAP_POOL_MAX || pooling > SNAP_POOL_MEAN) return SNAP_ERR_UNSUPPORTED;
-  if (dmatching && (!Wm || !bm || !dy)) return SNAP_ERR_NULL;
-  if (dmatching && (Dm < 1 || Dm > 32)) return SNAP_ERR_UNSUPPORTED;
+  if (!dplanes) return SNAP_ERR_NULL;
   FuseBwdArgs a;
-  for (int i = 0; i < 4; ++i) {
-    a.planes[i] = i < num_planes ? planes[i] : nullptr;
-    a.valids[i] = (i < num_planes && valids) ? valids[i] : nullptr;
-    a.dplanes[i] = i < num_planes ? dplanes[i] : nullptr;
-    if (i < num_planes && !a.planes[i]) return SNAP_ERR_NULL;
-  }
-  a.num_planes = num_planes; a.M = M; a.D = D; a.pooling = pooling;
-  a.Wm = Wm; a.bm = bm; a.Dm = Dm; a.normalize = normalize; a.eps = eps;
+  const bool head = dmatching != nullptr;
+  const int rc = bev_fuse_head_fill(a.h, planes, valids, num_planes, M, D, pooling, Wm, bm, Dm, normalize, eps, head,
+                                    Wm && bm && dy);
+  if (rc != SNAP_OK) return rc;
+  for (int i = 0; i < 4; ++i) a.dplanes[i] = i < num_planes ? dplanes[i] : nullptr;
   a.dmatching = dmatching; a.dfused = dfused; a.dy = dy;
-  if (dmatching && D == 128 && M >= 8192)
+  if (bev_fuse_persistent(a.h, head))
     hipLaunchKernelGGL(plane_fuse_match_bwd_d128_kernel, dim3(1024), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   else
     hipLaunchKernelGGL(plane_fuse_match_bwd_kernel, dim3((unsigned)snap_cdiv(M, 8)), dim3(256), 0,
@@ -1347,14 +1202,9 @@ __global__ __launch_bounds__(256) void confidence_head_bwd_kernel(
   const int64_t m = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
   if (m >= M) return;
   float acc = 0.f;
-  for (int c = 4 * hl; c < D; c += 128) {
-    const f32x4 x = *reinterpret_cast<const f32x4*>(f + m * D + c);
-    const f32x4 ww = *reinterpret_cast<const f32x4*>(w + c);
-    acc += ((x[0] * ww[0] + x[1] * ww[1]) + x[2] * ww[2]) + x[3] * ww[3];
-  }
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 32);
-  const float s = acc + bias[0];
+  for (int c = 4 * hl; c < D; c += 128)
+    acc += bev_dot4(*reinterpret_cast<const f32x4*>(f + m * D + c), *reinterpret_cast<const f32x4*>(w + c));
+  const float s = half_sum(acc) + bias[0];
   const bool ok = valid == nullptr || valid[m];
   const float ds = ok ? g[m] / (1.f + expf(s)) : 0.f;             // sigmoid(-s)
   for (int c = 4 * hl; c < D; c += 128) {

@@ -7,24 +7,9 @@
 // One half-wave (32 lanes x float4 = D <= 128 channels) owns one BEV column and reads its
 // Z x D voxel features ONCE (online softmax); the per-level scores live one per lane.
 // The reference materialises scores, weights and the weighted volume as separate XLA ops.
-#include "common.h"
+#include "bev_common.h"
 
 namespace {
-
-__device__ __forceinline__ float hsum(float v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-  return v;
-}
-__device__ __forceinline__ float hmax(float v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 32));
-  return v;
-}
-__device__ __forceinline__ float log_sigmoid(float x) {
-  // jax.nn.log_sigmoid = -softplus(-x) = min(x, 0) - log1p(exp(-|x|))
-  return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
-}
 
 constexpr int CP_MAXZ = 64;   // levels per column (one or two per lane)
 
@@ -44,9 +29,7 @@ __global__ __launch_bounds__(256) void conf_pool_kernel(
   const float b0 = bias[0];
   int a = 0;
   for (int z = hl; z < Z; z += 32) a |= vv[z] != 0 ? 1 : 0;
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) a |= __shfl_xor(a, o, 32);
-  const bool any = a != 0;   // some level of this column is valid (half-wave uniform)
+  const bool any = half_or(a) != 0;   // some level of this column is valid (half-wave uniform)
   // per-lane copies of the scores of levels hl and hl + 32
   float sc0 = 0.f, sc1 = 0.f;
   float run_max = 0.f, run_sum = 0.f;   // shift starts at 0 (initial=0)
@@ -54,8 +37,8 @@ __global__ __launch_bounds__(256) void conf_pool_kernel(
   for (int z = 0; z < Z; ++z) {
     const f32x4 f = lane_on ? *reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * hl)
                             : f32x4{0.f, 0.f, 0.f, 0.f};
-    float s = hsum(((f[0] * wv[0] + f[1] * wv[1]) + f[2] * wv[2]) + f[3] * wv[3]) + b0;
-    if (log_sig) s = log_sigmoid(s);
+    float s = half_sum(bev_dot4(f, wv)) + b0;
+    if (log_sig) s = bev_log_sigmoid(s);
     if ((z & 31) == hl) { if (z < 32) sc0 = s; else sc1 = s; }
     const bool use = any ? vv[z] != 0 : true;   // where = valid, or everything if none valid
     if (use) {
@@ -112,7 +95,7 @@ __global__ __launch_bounds__(256) void conf_pool_bwd_kernel(
       if (p == 0.f) continue;   // half-wave uniform (weights are per column)
       const f32x4 f = lane_on ? *reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * hl)
                               : f32x4{0.f, 0.f, 0.f, 0.f};
-      const float dp = hsum(((g[0] * f[0] + g[1] * f[1]) + g[2] * f[2]) + g[3] * f[3]);
+      const float dp = half_sum(bev_dot4(g, f));
       pdp += p * dp;
     }
     // pass 2: d f_z = p_z g + d s_z w ;  d s_z = p_z (dp_z - pdp) [* sigmoid(-s_z)]
@@ -122,10 +105,10 @@ __global__ __launch_bounds__(256) void conf_pool_bwd_kernel(
       if (p != 0.f) {
         const f32x4 f = lane_on ? *reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * hl)
                                 : f32x4{0.f, 0.f, 0.f, 0.f};
-        const float dp = hsum(((g[0] * f[0] + g[1] * f[1]) + g[2] * f[2]) + g[3] * f[3]);
+        const float dp = half_sum(bev_dot4(g, f));
         float ds = p * (dp - pdp);
         if (log_sig) {
-          const float s = hsum(((f[0] * wv[0] + f[1] * wv[1]) + f[2] * wv[2]) + f[3] * wv[3]) + b0;
+          const float s = half_sum(bev_dot4(f, wv)) + b0;
           ds *= 1.f / (1.f + expf(s));   // d log_sigmoid(s) / ds = sigmoid(-s)
         }
 #pragma unroll

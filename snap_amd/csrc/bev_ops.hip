@@ -7,11 +7,10 @@
 // A 32-lane half-wave owns one BEV cell; lane q holds channels 4q..4q+3 (one
 // 512-byte coalesced row per voxel for D = 128); per-column reductions run in
 // registers, the L2-norm over the 32 matching channels uses xor-shuffles.
-#include "common.h"
+// The pieces the kernels are built from are in bev_common.h.
+#include "bev_common.h"
 
 namespace {
-
-constexpr int MAXQ = 2;  // up to D = 256 channels (MAXQ * 32 lanes * 4)
 
 __global__ __launch_bounds__(256) void vertical_pool_kernel(
     const float* __restrict__ vol, const uint8_t* __restrict__ vvalid, float* __restrict__ plane,
@@ -22,40 +21,26 @@ __global__ __launch_bounds__(256) void vertical_pool_kernel(
   const int nq = D >> 2;
   const uint8_t* vv = vvalid + m * Z;
   const float* base = vol + m * Z * D;
-  f32x4 acc[MAXQ];
-  const float init = pooling == SNAP_POOL_MAX ? -INFINITY : 0.f;
+  f32x4 acc[BEV_MAXQ];
 #pragma unroll
-  for (int i = 0; i < MAXQ; ++i) acc[i] = f32x4{init, init, init, init};
+  for (int i = 0; i < BEV_MAXQ; ++i) acc[i] = bev_quad(bev_reduce_init(pooling));
   int count = 0;
   for (int z = 0; z < Z; ++z) {
     if (!vv[z]) continue;  // half-wave uniform
     ++count;
 #pragma unroll
-    for (int i = 0; i < MAXQ; ++i) {
+    for (int i = 0; i < BEV_MAXQ; ++i) {
       const int q = hl + 32 * i;
-      if (q < nq) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          acc[i][e] = pooling == SNAP_POOL_MAX ? snap_max_nan(acc[i][e], v[e]) : acc[i][e] + v[e];
-      }
+      if (q < nq)
+        acc[i] = bev_reduce_step<true>(acc[i], *reinterpret_cast<const f32x4*>(base + (int64_t)z * D + 4 * q), pooling);
     }
   }
-  const bool any = count > 0;
 #pragma unroll
-  for (int i = 0; i < MAXQ; ++i) {
+  for (int i = 0; i < BEV_MAXQ; ++i) {
     const int q = hl + 32 * i;
-    if (q < nq) {
-      f32x4 o = acc[i];
-      if (!any) o = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (any && pooling == SNAP_POOL_MEAN) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = o[e] / (float)count;
-      }
-      *reinterpret_cast<f32x4*>(plane + m * D + 4 * q) = o;
-    }
+    if (q < nq) *reinterpret_cast<f32x4*>(plane + m * D + 4 * q) = bev_reduce_finish(acc[i], pooling, count);
   }
-  if (hl == 0) pvalid[m] = any ? 1 : 0;
+  if (hl == 0) pvalid[m] = count > 0 ? 1 : 0;
 }
 
 // Z <= 64: ONE WAVE per column.  The validity bytes of the column become a wave-uniform 64-bit
@@ -71,58 +56,39 @@ __global__ __launch_bounds__(256) void vertical_pool_wave_kernel(
   const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= M) return;
   const int nq = D >> 2;
-  unsigned long long mask = __ballot(lane < Z && vvalid[m * Z + lane] != 0);
+  unsigned long long mask = bev_level_mask(vvalid, m, Z, lane);
   const int count = __popcll(mask);
   const float* base = vol + m * Z * D;
-  const bool is_max = pooling == SNAP_POOL_MAX;
-  f32x4 acc[MAXQ];
-  const float init = is_max ? -INFINITY : 0.f;
+  const float init = bev_reduce_init(pooling);
+  f32x4 acc[BEV_MAXQ];
 #pragma unroll
-  for (int i = 0; i < MAXQ; ++i) acc[i] = f32x4{init, init, init, init};
+  for (int i = 0; i < BEV_MAXQ; ++i) acc[i] = bev_quad(init);
   while (mask) {
-    // next four valid levels: z[0], z[2] -> half 0; z[1], z[3] -> half 1
-    int z[4];
+    int za, zb;
+    bev_next_levels(mask, half, za, zb);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      z[k] = mask ? (int)__builtin_ctzll(mask) : -1;
-      mask &= mask - 1;                    // (0 stays 0)
-    }
-    const int za = half ? z[1] : z[0], zb = half ? z[3] : z[2];
-#pragma unroll
-    for (int i = 0; i < MAXQ; ++i) {
+    for (int i = 0; i < BEV_MAXQ; ++i) {
       const int q = hl + 32 * i;
       if (q < nq) {
-        f32x4 va = f32x4{init, init, init, init}, vb = va;
+        f32x4 va = bev_quad(init), vb = va;   // (a level that is not there: the reduce's neutral element)
         if (za >= 0) va = *reinterpret_cast<const f32x4*>(base + (int64_t)za * D + 4 * q);
         if (zb >= 0) vb = *reinterpret_cast<const f32x4*>(base + (int64_t)zb * D + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          acc[i][e] = is_max ? snap_max_nan(acc[i][e], va[e]) : acc[i][e] + va[e];
-          acc[i][e] = is_max ? snap_max_nan(acc[i][e], vb[e]) : acc[i][e] + vb[e];
-        }
+        acc[i] = bev_reduce_step<true>(acc[i], va, pooling);
+        acc[i] = bev_reduce_step<true>(acc[i], vb, pooling);
       }
     }
   }
-  const bool any = count > 0;
 #pragma unroll
-  for (int i = 0; i < MAXQ; ++i) {
+  for (int i = 0; i < BEV_MAXQ; ++i) {
     const int q = hl + 32 * i;
-    f32x4 o = acc[i];
+    f32x4 other;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float other = __shfl_xor(o[e], 32);
-      o[e] = is_max ? snap_max_nan(o[e], other) : o[e] + other;
-    }
-    if (q < nq && half == 0) {
-      if (!any) o = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (any && pooling == SNAP_POOL_MEAN) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = o[e] / (float)count;
-      }
-      *reinterpret_cast<f32x4*>(plane + m * D + 4 * q) = o;
-    }
+    for (int e = 0; e < 4; ++e) other[e] = __shfl_xor(acc[i][e], 32);
+    acc[i] = bev_reduce_step<true>(acc[i], other, pooling);
+    if (q < nq && half == 0)
+      *reinterpret_cast<f32x4*>(plane + m * D + 4 * q) = bev_reduce_finish(acc[i], pooling, count);
   }
-  if (lane == 0) pvalid[m] = any ? 1 : 0;
+  if (lane == 0) pvalid[m] = count > 0 ? 1 : 0;
 }
 
 // Max pooling of a training step (Z <= 64, D <= 128: one channel quad per lane): the plane of the kernel
@@ -139,21 +105,16 @@ __global__ __launch_bounds__(256) void vertical_pool_max_arg_kernel(
   const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= M) return;
   const bool on = 4 * hl < D;
-  unsigned long long mask = __ballot(lane < Z && vvalid[m * Z + lane] != 0);
+  unsigned long long mask = bev_level_mask(vvalid, m, Z, lane);
   const bool any = mask != 0;
   const float* base = vol + m * Z * D + 4 * (on ? hl : 0);
-  f32x4 acc = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, tb = acc;
+  f32x4 acc = bev_quad(-INFINITY), tb = acc;
   int tk[4] = {255, 255, 255, 255};
 #pragma unroll 1
   while (mask) {
-    int z[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      z[k] = mask ? (int)__builtin_ctzll(mask) : -1;
-      mask &= mask - 1;
-    }
-    const int za = half ? z[1] : z[0], zb = half ? z[3] : z[2];
-    f32x4 va = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, vb = va;
+    int za, zb;
+    bev_next_levels(mask, half, za, zb);
+    f32x4 va = bev_quad(-INFINITY), vb = va;
     if (za >= 0) va = *reinterpret_cast<const f32x4*>(base + (int64_t)za * D);
     if (zb >= 0) vb = *reinterpret_cast<const f32x4*>(base + (int64_t)zb * D);
 #pragma unroll
@@ -185,7 +146,7 @@ __global__ __launch_bounds__(256) void vertical_pool_max_arg_kernel(
     pc |= (unsigned)min(c_, 255) << (8 * e);
   }
   if (on && half == 0) {
-    if (!any) o = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!any) o = bev_quad(0.f);
     *reinterpret_cast<f32x4*>(plane + m * D + 4 * hl) = o;
     *reinterpret_cast<unsigned*>(argz + m * D + 4 * hl) = pa;
     *reinterpret_cast<unsigned*>(ties + m * D + 4 * hl) = pc;
@@ -194,85 +155,48 @@ __global__ __launch_bounds__(256) void vertical_pool_max_arg_kernel(
 }
 
 struct FuseArgs {
-  const float* planes[4];
-  const uint8_t* valids[4];
-  int num_planes;
-  int64_t M;
-  int D, pooling;
+  BevFuseHead h;
   float* fused;
   uint8_t* fvalid;
-  const float* Wm;
-  const float* bm;
-  int Dm, normalize;
-  float eps;
   float* matching;
 };
 
 __global__ __launch_bounds__(256) void plane_fuse_match_kernel(const FuseArgs a) {
+  const BevFuseHead& h = a.h;
   const int hl = threadIdx.x & 31;
   const int64_t m = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
-  if (m >= a.M) return;
-  const int nq = a.D >> 2;
-  f32x4 acc[MAXQ];
-  const float init = a.pooling == SNAP_POOL_MAX ? -INFINITY : 0.f;
+  if (m >= h.M) return;
+  const int nq = h.D >> 2;
+  f32x4 acc[BEV_MAXQ];
 #pragma unroll
-  for (int i = 0; i < MAXQ; ++i) acc[i] = f32x4{init, init, init, init};
+  for (int i = 0; i < BEV_MAXQ; ++i) acc[i] = bev_quad(bev_reduce_init(h.pooling));
   int count = 0;
-  for (int p = 0; p < a.num_planes; ++p) {
-    const bool v = a.valids[p] ? (a.valids[p][m] != 0) : true;
+  for (int p = 0; p < h.num_planes; ++p) {
+    const bool v = h.valids[p] ? (h.valids[p][m] != 0) : true;
     if (!v) continue;
     ++count;
 #pragma unroll
-    for (int i = 0; i < MAXQ; ++i) {
+    for (int i = 0; i < BEV_MAXQ; ++i) {
       const int q = hl + 32 * i;
-      if (q < nq) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(a.planes[p] + m * a.D + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          acc[i][e] = a.pooling == SNAP_POOL_MAX ? snap_max_nan(acc[i][e], x[e]) : acc[i][e] + x[e];
-      }
+      if (q < nq)
+        acc[i] = bev_reduce_step<true>(acc[i], *reinterpret_cast<const f32x4*>(h.planes[p] + m * h.D + 4 * q), h.pooling);
     }
   }
   const bool any = count > 0;
 #pragma unroll
-  for (int i = 0; i < MAXQ; ++i) {
-    if (!any) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (any && a.pooling == SNAP_POOL_MEAN) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[i][e] = acc[i][e] / (float)count;
-    }
+  for (int i = 0; i < BEV_MAXQ; ++i) {
+    acc[i] = bev_reduce_finish(acc[i], h.pooling, count);
     const int q = hl + 32 * i;
-    if (q < nq && a.fused) *reinterpret_cast<f32x4*>(a.fused + m * a.D + 4 * q) = acc[i];
+    if (q < nq && a.fused) *reinterpret_cast<f32x4*>(a.fused + m * h.D + 4 * q) = acc[i];
   }
   if (hl == 0 && a.fvalid) a.fvalid[m] = any ? 1 : 0;
   if (!a.matching) return;
 
   // matching head: lane j computes output channel j (Dm <= 32).
   const int j = hl;
-  float y = (j < a.Dm) ? a.bm[j] : 0.f;
-#pragma unroll
-  for (int i = 0; i < MAXQ; ++i) {
-    for (int q = 0; q < 32; ++q) {
-      const int cq = q + 32 * i;
-      if (cq >= nq) break;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float xv = __shfl(acc[i][e], q, 32);
-        if (j < a.Dm) y += xv * a.Wm[(int64_t)(4 * cq + e) * a.Dm + j];
-      }
-    }
-  }
-  if (a.normalize) {
-    float ss = (j < a.Dm) ? y * y : 0.f;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 32);
-    const float nrm = sqrtf(ss);
-    const bool invalid = nrm < a.eps;
-    // layers.normalize: y_safe = where(invalid, eps, x); z = x / ||y_safe||.
-    const float denom = invalid ? sqrtf((float)a.Dm) * a.eps : nrm;
-    y = invalid ? 0.f : y / denom;
-  }
-  if (j < a.Dm) a.matching[m * a.Dm + j] = any ? y : 0.f;
+  float y = bev_head_shfl(acc, nq, h.Wm, h.bm, h.Dm, j);
+  if (h.normalize) y = bev_l2_normalize(y, j, h.Dm, h.eps);
+  if (j < h.Dm) a.matching[m * h.Dm + j] = any ? y : 0.f;
 }
 
 // The same kernel for D = 128 with a matching head (the bench's planes): the head is a [128] x [128, Dm]
@@ -282,17 +206,17 @@ __global__ __launch_bounds__(256) void plane_fuse_match_kernel(const FuseArgs a)
 // 16-byte reads.  Terms added in the same (ascending channel) order: the same bits.
 __global__ __launch_bounds__(256) void plane_fuse_match_d128_kernel(const FuseArgs a) {
   __shared__ __attribute__((aligned(16))) float sv[8][128];
+  const BevFuseHead& h = a.h;
   const int hl = threadIdx.x & 31, hw = threadIdx.x >> 5;
   const int j = hl;
   float wreg[128];
-#pragma unroll
-  for (int k = 0; k < 128; ++k) wreg[k] = j < a.Dm ? a.Wm[(int64_t)k * a.Dm + j] : 0.f;
-  const float bj = j < a.Dm ? a.bm[j] : 0.f;
-  const float init = a.pooling == SNAP_POOL_MAX ? -INFINITY : 0.f;
-  for (int64_t m = (int64_t)blockIdx.x * 8 + hw; m < a.M; m += (int64_t)gridDim.x * 8) {
+  bev_head_load_column(wreg, h.Wm, h.Dm, j);
+  const float bj = j < h.Dm ? h.bm[j] : 0.f;
+  const float init = bev_reduce_init(h.pooling);
+  for (int64_t m = (int64_t)blockIdx.x * 8 + hw; m < h.M; m += (int64_t)gridDim.x * 8) {
     // every plane's validity byte and row are requested before the first is looked at (one memory round
     // trip per cell instead of two per plane); a row of an invalid plane is fetched and dropped
-    f32x4 acc = {init, init, init, init};
+    f32x4 acc = bev_quad(init);
     int count = 0;
     bool pv[4];
     f32x4 px[4];
@@ -300,9 +224,9 @@ __global__ __launch_bounds__(256) void plane_fuse_match_d128_kernel(const FuseAr
     for (int p = 0; p < 4; ++p) {
       pv[p] = false;
       px[p] = acc;
-      if (p < a.num_planes) {
-        pv[p] = a.valids[p] ? (a.valids[p][m] != 0) : true;
-        px[p] = *reinterpret_cast<const f32x4*>(a.planes[p] + m * 128 + 4 * hl);
+      if (p < h.num_planes) {
+        pv[p] = h.valids[p] ? (h.valids[p][m] != 0) : true;
+        px[p] = *reinterpret_cast<const f32x4*>(h.planes[p] + m * 128 + 4 * hl);
       }
     }
 #pragma unroll
@@ -310,39 +234,17 @@ __global__ __launch_bounds__(256) void plane_fuse_match_d128_kernel(const FuseAr
       if (!pv[p]) continue;
       ++count;
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        acc[e] = a.pooling == SNAP_POOL_MAX ? snap_max_nan(acc[e], px[p][e]) : acc[e] + px[p][e];
+      for (int e = 0; e < 4; ++e)   // (the scalar step: the quad one costs this kernel 4 VGPRs, 174 -> 178)
+        acc[e] = bev_reduce_step<true>(acc[e], px[p][e], h.pooling);
     }
     const bool any = count > 0;
-    if (!any) acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (any && a.pooling == SNAP_POOL_MEAN) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = acc[e] / (float)count;
-    }
+    acc = bev_reduce_finish(acc, h.pooling, count);
     if (a.fused) *reinterpret_cast<f32x4*>(a.fused + m * 128 + 4 * hl) = acc;
     if (hl == 0 && a.fvalid) a.fvalid[m] = any ? 1 : 0;
-    *reinterpret_cast<f32x4*>(&sv[hw][4 * hl]) = acc;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float y = bj;
-#pragma unroll
-    for (int q = 0; q < 32; ++q) {
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(&sv[hw][4 * q]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) y += xv[e] * wreg[4 * q + e];
-    }
+    float y = bev_head_column(sv[hw], hl, acc, wreg, bj);
     __builtin_amdgcn_wave_barrier();       // (the row is rewritten by the next cell)
-    if (a.normalize) {
-      float ss = (j < a.Dm) ? y * y : 0.f;
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 32);
-      const float nrm = sqrtf(ss);
-      const bool invalid = nrm < a.eps;
-      const float denom = invalid ? sqrtf((float)a.Dm) * a.eps : nrm;
-      y = invalid ? 0.f : y / denom;
-    }
-    if (j < a.Dm) a.matching[m * a.Dm + j] = any ? y : 0.f;
+    if (h.normalize) y = bev_l2_normalize(y, j, h.Dm, h.eps);
+    if (j < h.Dm) a.matching[m * h.Dm + j] = any ? y : 0.f;
   }
 }
 
@@ -352,7 +254,7 @@ extern "C" int snap_vertical_pool_f32(const float* vol, const uint8_t* vvalid, f
                                       uint8_t* pvalid, int64_t M, int32_t Z, int32_t D,
                                       int32_t pooling, void* stream) {
   if (!vol || !vvalid || !plane || !pvalid) return SNAP_ERR_NULL;
-  if (M <= 0 || Z <= 0 || D <= 0 || D % 4 != 0 || D > MAXQ * 128) return SNAP_ERR_BAD_SHAPE;
+  if (M <= 0 || Z <= 0 || D <= 0 || D % 4 != 0 || D > BEV_MAXQ * 128) return SNAP_ERR_BAD_SHAPE;
   if (pooling < SNAP_POOL_MAX || pooling > SNAP_POOL_MEAN) return SNAP_ERR_UNSUPPORTED;
   if (Z <= 64) {
     hipLaunchKernelGGL(vertical_pool_wave_kernel, dim3((unsigned)snap_cdiv(M, 4)), dim3(256), 0,
@@ -367,6 +269,8 @@ extern "C" int snap_vertical_pool_f32(const float* vol, const uint8_t* vvalid, f
   return SNAP_OK;
 }
 
+// (Z <= 64, D <= 128 here, while the VJP that consumes the record, snap_vertical_pool_max_bwd_arg_f32, accepts
+//  Z <= 255 and any D: an oddity kept as it is.)
 extern "C" int snap_vertical_pool_max_arg_f32(const float* vol, const uint8_t* vvalid, float* plane,
                                               uint8_t* pvalid, uint8_t* argz, uint8_t* ties, int64_t M,
                                               int32_t Z, int32_t D, void* stream) {
@@ -384,24 +288,14 @@ extern "C" int snap_plane_fuse_match_f32(const float* const* planes, const uint8
                                          float* fused, uint8_t* fvalid, const float* Wm,
                                          const float* bm, int32_t Dm, int32_t normalize, float eps,
                                          float* matching, void* stream) {
-  if (!planes) return SNAP_ERR_NULL;
-  if (num_planes < 1 || num_planes > 4) return SNAP_ERR_UNSUPPORTED;
-  if (M <= 0 || D <= 0 || D % 4 != 0 || D > MAXQ * 128) return SNAP_ERR_BAD_SHAPE;
-  if (pooling < SNAP_POOL_MAX || pooling > SNAP_POOL_MEAN) return SNAP_ERR_UNSUPPORTED;
-  if (matching && (!Wm || !bm)) return SNAP_ERR_NULL;
-  if (matching && (Dm < 1 || Dm > 32)) return SNAP_ERR_UNSUPPORTED;
   FuseArgs a;
-  for (int i = 0; i < 4; ++i) {
-    a.planes[i] = i < num_planes ? planes[i] : nullptr;
-    a.valids[i] = (i < num_planes && valids) ? valids[i] : nullptr;
-    if (i < num_planes && !a.planes[i]) return SNAP_ERR_NULL;
-  }
-  a.num_planes = num_planes;
-  a.M = M; a.D = D; a.pooling = pooling;
+  const bool head = matching != nullptr;
+  const int rc = bev_fuse_head_fill(a.h, planes, valids, num_planes, M, D, pooling, Wm, bm, Dm, normalize, eps, head,
+                                    Wm && bm);
+  if (rc != SNAP_OK) return rc;
   a.fused = fused; a.fvalid = fvalid;
-  a.Wm = Wm; a.bm = bm; a.Dm = Dm; a.normalize = normalize; a.eps = eps;
   a.matching = matching;
-  if (matching && D == 128 && M >= 8192)
+  if (bev_fuse_persistent(a.h, head))
     hipLaunchKernelGGL(plane_fuse_match_d128_kernel, dim3(1024), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   else
     hipLaunchKernelGGL(plane_fuse_match_kernel, dim3((unsigned)snap_cdiv(M, 8)), dim3(256), 0,
@@ -425,18 +319,10 @@ __global__ __launch_bounds__(256) void confidence_head_kernel(
   const int64_t m = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
   if (m >= M) return;
   float acc = 0.f;
-  for (int c = 4 * hl; c < D; c += 128) {
-    const f32x4 x = *reinterpret_cast<const f32x4*>(f + m * D + c);
-    const f32x4 ww = *reinterpret_cast<const f32x4*>(w + c);
-    acc += ((x[0] * ww[0] + x[1] * ww[1]) + x[2] * ww[2]) + x[3] * ww[3];
-  }
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 32);
-  if (hl == 0) {
-    const float s = acc + bias[0];
-    const float ls = fminf(s, 0.f) - log1pf(expf(-fabsf(s)));
-    out[m] = (valid == nullptr || valid[m]) ? ls : 0.f;
-  }
+  for (int c = 4 * hl; c < D; c += 128)
+    acc += bev_dot4(*reinterpret_cast<const f32x4*>(f + m * D + c), *reinterpret_cast<const f32x4*>(w + c));
+  acc = half_sum(acc);
+  if (hl == 0) out[m] = (valid == nullptr || valid[m]) ? bev_log_sigmoid(acc + bias[0]) : 0.f;
 }
 }  // namespace
 
@@ -483,4 +369,3 @@ extern "C" int snap_voxel_points_f32(const float* xy, int32_t xy_batched, const 
   SNAP_CHECK_LAUNCH();
   return SNAP_OK;
 }
-

@@ -701,6 +701,35 @@ def test_vertical_pool_bwd(pooling):
   helpers.report('vpool bwd ' + pooling, got, vd.grad.float(), atol=1e-6)
 
 
+@pytest.mark.parametrize('Z,D', [(70, 256), (64, 128)])
+@pytest.mark.parametrize('pooling', ['max', 'sum', 'mean'])
+def test_vertical_pool_bwd_two_quads_and_shared_maxima(pooling, Z, D):
+  """vertical_pool_bwd at a second channel quad per lane (D = 256) and at the forward's wave-per-column limit
+  (Z = 64), 15 columns (two workgroups, the second ragged), one of them without a valid level; for max the values
+  are quantised so that many maxima are shared, and the gradient is divided among their holders as amax does."""
+  vol = rnd((3, 5, Z, D), 170 + Z)
+  if pooling == 'max':
+    vol = (vol * 2).round() / 2
+  valid = torch.rand((3, 5, Z), generator=torch.Generator().manual_seed(171 + Z)) > 0.5
+  valid[0, 0] = False
+  dplane = rnd((3, 5, D), 172 + Z)
+  vd = vol.double().requires_grad_(True)
+  anyv = valid.any(-1)
+  if pooling == 'max':
+    masked = torch.where(valid[..., None], vd, torch.full_like(vd, -math.inf))
+    out = masked.amax(-2)
+    holders = ((masked == out[..., None, :]) & valid[..., None]).sum(-2)
+    assert int((holders > 1).sum()) > 0           # (shared maxima occurred)
+    out = torch.where(anyv[..., None], out, torch.zeros_like(out))
+  else:
+    out = (vd * valid[..., None]).sum(-2)
+    if pooling == 'mean':
+      out = out / valid.sum(-1).clamp(min=1)[..., None]
+  out.backward(dplane.double())
+  got = ops_bwd.vertical_pool_bwd(G(vol), G(valid), G(dplane), pooling)
+  helpers.report('vpool bwd ' + pooling, got, vd.grad.float(), atol=1e-6)
+
+
 @pytest.mark.parametrize('Z,D,ties', [(7, 32, False), (60, 128, False), (64, 64, True), (12, 128, True)])
 def test_vertical_pool_max_bwd_from_the_forward_record(Z, D, ties):
   """Max pooling in a training step: the forward also records where every maximum sits
@@ -770,6 +799,58 @@ def test_plane_fuse_match_bwd(nplanes):
   dW = ops_bwd.conv2d_wgrad(fused_g.reshape(1, 1, M, D), dy.reshape(1, 1, M, Dm), (1, 1, D, Dm))
   helpers.report('dWm', dW.reshape(D, Dm), Wd.grad.float(), atol=1e-4, rtol=1e-4)
   helpers.report('dbm', ops_bwd.colsum(dy), bd.grad.float(), atol=1e-4, rtol=1e-4)
+
+
+@pytest.mark.parametrize('grads', ['dmatching', 'dmatching+dfused', 'dfused'])
+@pytest.mark.parametrize('normalize', [True, False])
+@pytest.mark.parametrize('Dm', [5, 32])
+@pytest.mark.parametrize('D', [132, 256])
+@pytest.mark.parametrize('pooling', ['max', 'sum', 'mean'])
+def test_plane_fuse_match_bwd_per_cell_kernel_every_pooling_two_quads(pooling, D, Dm, normalize, grads):
+  """The per-cell VJP kernel against float64 torch autograd where the other tests do not take it: sum and mean
+  pooling, a second channel quad per lane (D = 132: one live lane in it; D = 256: full), a ragged head (Dm = 5),
+  with and without normalisation, and each of d matching alone, d matching + d fused, d fused alone (then no
+  dy).  37 cells (five workgroups, the last ragged), three masked planes, a cell whose maximum two planes share
+  and a cell no plane covers."""
+  M = 37
+  planes = [rnd((M, D), 480 + i) for i in range(3)]
+  valids = [torch.rand(M, generator=torch.Generator().manual_seed(490 + i)) > 0.35 for i in range(3)]
+  planes[0][17] = planes[1][17]                 # (a cell whose maximum is shared)
+  valids[0][17] = valids[1][17] = True
+  for v in valids:
+    v[5] = False                                # (no plane covers cell 5)
+  Wm, bm = rnd((D, Dm), 485, 0.2), rnd((Dm,), 486, 0.05)
+  dmat = rnd((M, Dm), 487) if 'dmatching' in grads else None
+  dfu = rnd((M, D), 488) if 'dfused' in grads else None
+  pd = [p.double().requires_grad_(True) for p in planes]
+  vs = torch.stack(valids, -1)
+  st = torch.stack(pd, -2)
+  anyv = vs.any(-1)
+  if pooling == 'max':
+    fused = torch.where(vs[..., None], st, torch.full_like(st, -math.inf)).amax(-2)
+    fused = torch.where(anyv[:, None], fused, torch.zeros_like(fused))
+  else:
+    fused = (st * vs[..., None]).sum(-2)
+    if pooling == 'mean':
+      fused = fused / vs.sum(-1).clamp(min=1)[:, None]
+  y = fused @ Wm.double() + bm.double()
+  y.retain_grad()
+  z = y / y.norm(dim=-1, keepdim=True) if normalize else y
+  loss = 0.
+  if dmat is not None:
+    loss = loss + (z * anyv[:, None] * dmat.double()).sum()
+  if dfu is not None:
+    loss = loss + (fused * anyv[:, None] * dfu.double()).sum()
+  loss.backward()
+  dplanes, dy = ops_bwd.plane_fuse_match_bwd([G(p) for p in planes], [G(v) for v in valids], pooling, G(Wm), G(bm),
+                                             normalize, 1e-5, None if dmat is None else G(dmat),
+                                             None if dfu is None else G(dfu))
+  for i in range(3):
+    helpers.report(f'dplane{i}', dplanes[i], pd[i].grad.float(), atol=2e-5, rtol=1e-4)
+  if dmat is None:
+    assert dy is None
+  else:
+    helpers.report('dy', dy, y.grad.float(), atol=2e-5, rtol=1e-4)
 
 
 @pytest.mark.parametrize('pooling,Dm,normalize,with_dfused', [('max', 32, True, False), ('mean', 16, True, True),

@@ -1173,6 +1173,46 @@ def test_plane_fuse_match_persistent_kernel_for_128_channels(pooling, Dm, normal
   assert torch.equal(m1[:4096].view(torch.int32), m2.view(torch.int32)) and bool(v1.all())
 
 
+@pytest.mark.parametrize('Dm,normalize', [(5, True), (5, False), (32, True), (32, False), (None, True)])
+@pytest.mark.parametrize('D', [132, 256])
+@pytest.mark.parametrize('pooling', ['max', 'sum', 'mean'])
+def test_plane_fuse_match_per_cell_kernel_every_pooling_two_quads(pooling, D, Dm, normalize):
+  """The per-cell fuse + matching-head kernel against the oracle where the other tests do not take it: sum and
+  mean pooling, a second channel quad per lane (D = 132: one live lane in it; D = 256: full), a ragged head
+  (Dm = 5), with and without normalisation, without a head.  37 cells (five workgroups, the last ragged), three
+  planes.  Twice: the middle plane without a mask and a random bias; then all three masks given, one cell no
+  plane covers, and a cell whose fused vector is all zero under a zero bias (the `invalid` branch of the
+  normalisation: zero out)."""
+  M = 37
+  planes = [rnd((M, D), 370 + i) for i in range(3)]
+  masks = [torch.rand(M, generator=torch.Generator().manual_seed(380 + i)) > 0.35 for i in range(3)]
+  Wm = None if Dm is None else rnd((D, Dm), 375, 0.1)
+  for all_masks in (False, True):
+    valids = [v.clone() for v in masks]
+    bm = None if Dm is None else rnd((Dm,), 376, 0.01)
+    pl = [p.clone() for p in planes]
+    if all_masks:
+      for v in valids:
+        v[5] = False                      # (no plane covers cell 5)
+      valids[0][11] = True
+      for p in pl:
+        p[11] = 0.                        # (cell 11: covered, fused vector all zero)
+      bm = None if Dm is None else torch.zeros(Dm)
+    else:
+      valids[1] = None
+    (fg, vg, mg), (fw, vw, mw) = both('plane_fuse_match', (pl, valids, pooling, Wm, bm), {'normalize': normalize})
+    helpers.report('fuse valid', vg, vw, 0)
+    helpers.report('fused', fg, fw, atol=1e-6)
+    if all_masks:
+      assert not bool(vg[5]) and bool(vg[11]) and float(fg[5].abs().max()) == 0. and float(fg[11].abs().max()) == 0.
+    if Dm is None:
+      assert mg is None
+      continue
+    helpers.report('matching', mg, mw, atol=2e-6, rtol=1e-5)
+    if all_masks:
+      assert float(mg[5].abs().max()) == 0. and float(mg[11].abs().max()) == 0.
+
+
 def test_matching_zero_norm():
   D, Dm = 32, 8
   plane = torch.zeros(1, 4, 4, D)
