@@ -38,7 +38,8 @@ typedef enum SnapStatus {
 
 /* Library / device introspection. */
 /* (snap_vote_prior_workspace_bytes / snap_vote_prior_f32 were ADDED at version 29 without a bump: an addition changes no
- * existing prototype, struct or constant, and a library built without them fails to load on the missing symbol.) */
+ * existing prototype, struct or constant, and a library built without them fails to load on the missing symbol.
+ * snap_vote_raster_workspace_bytes / snap_vote_raster_f32 were added the same way.) */
 #define SNAP_ABI_VERSION 29   /* bump on any change to this header's prototypes, structs or constants */
 int snap_abi_version(void);                 /* SNAP_ABI_VERSION of the built library */
 const char* snap_status_string(int status);
@@ -1542,6 +1543,69 @@ size_t snap_vote_prior_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_
 int snap_vote_prior_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, float scale, int32_t M,
                         const int32_t* centres, const float* planes, const float* comps, float* out, double* resp,
                         double* stats, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* A road / lane RASTER prior fused into a vote volume or belief: the map's own constraint (the vehicle is on a drivable
+ * area and heads along the lane) as a measurement update, evaluated over a ladder of S prior strengths in one visit.
+ * votes[R,Ho,Wo] f32 log-scores, flat(r,a,b) = (r*Ho + a)*Wo + b, or NULL (every cell then has v = 0 and scale is
+ * ignored: the raster prior itself as a belief); scale: a finite float > 0 with |scale * v| below the f32 maximum for
+ * every finite v (not checked).  On the DEVICE: raster[X,Y,4] f32 = (A, C, S, valid), 16-byte aligned: the log-prior of
+ * position, kappa cos(h phi), kappa sin(h phi) of the lane heading phi, and valid = 0.0 for a cell that holds no data
+ * (any other value: valid); offsets[R,2] i32 = (n_a, n_b) and planes[R,4] f32 = (f_a, f_b, c_k, s_k): in raster index
+ * units the lattice cell (k, a, b) sits at (a, b) + n_k + f_k, 0 <= f < 1, and c_k, s_k are cos and sin of h theta_k,
+ * theta_k = -2 pi k / R (models/votes/raster.raster_prior builds them in float64).  On the HOST: strengths[S], each a
+ * finite float > 0.  outside: a float that is finite or -inf.  write: the ladder index w whose posterior is written to
+ * out; gt_index: a flat cell index, or -1.  PRECONDITION (not checked): A, C, S are finite on valid cells, and
+ * |lambda_s| (|A| + |C| + |S|) stays below the f32 maximum.
+ * out[R,Ho,Wo] f32 (must not overlap votes); table[S,4] FLOAT64; stats[4] FLOAT64; count[4] i32.
+ *   THE RASTER LOG-PRIOR g of the cell (k, a, b), every operation ONE IEEE f32 operation (no contraction), in this order:
+ *     ga = fl(1 - f_a), gb = fl(1 - f_b); the weights of the taps (0,0), (0,1), (1,0), (1,1) are fl(ga gb), fl(ga f_b),
+ *       fl(f_a gb), fl(f_a f_b): constants of the plane k.  Tap (i, j) is the raster cell (a + n_a + i, b + n_b + j)
+ *       (integer arithmetic, exact for any int32 n).
+ *     A tap whose weight is exactly 0 is neither read nor tested nor summed.  If any other tap lies off the raster or
+ *     has valid == 0, g = outside.  Otherwise, for each plane Q of A, C, S: bQ = the sum from 0 over the taps present,
+ *     in the order above, bQ = fl(bQ + fl(w Q_tap)) (one tap of weight 1: bQ = Q_tap exactly), and
+ *     g = fl(fl(bA + fl(c_k bC)) + fl(s_k bS)).
+ *   A cell CONTRIBUTES iff its vote is finite (snap_vote_posterior_f32's rule: -inf cells are masked silently, NaN and
+ *   +inf cells are excluded and counted) AND g > -inf.  F = the contributing set; V = the cells with a finite vote.
+ *   x = fl(scale v) (0 without votes); for level s, lg_s = fl(lambda_s g) and t_s = fl(x + lg_s) on F.
+ *   tmax_s = max_F t_s, gmax = the largest g of ALL R Ho Wo cells, xmax = max_V x (maxima: exact).  With
+ *   e_s = expf(fl(t_s - tmax_s)) and S0 = sum_F e_s:
+ *   table[s] = { 0: log_z_s = tmax_s + log S0,
+ *                1: log_z_prior_s = fl(lambda_s gmax) + log (sum of expf(fl(lg_s - fl(lambda_s gmax))) over ALL cells with
+ *                   g > -inf): the normaliser of the prior alone on the lattice (-inf where no cell has g > -inf),
+ *                2: E_s[g] = (sum_F (double)e_s (double)g) / S0,
+ *                3: Var_s[g] = max(0, (sum_F ((double)e_s (double)g) (double)g) / S0 - E_s[g]^2) };
+ *   stats = { 0: log_z_votes = xmax + log sum_V expf(fl(x - xmax)) (-inf where V is empty),
+ *             1: x_gt = fl(scale v) of the cell gt_index as float64 (0 without votes; -inf for a -inf vote; NaN for a NaN
+ *                or +inf vote or gt_index == -1),
+ *             2: g_gt = g of that cell (-inf for a cell the raster excludes; NaN with gt_index == -1),
+ *             3: written as 0 };
+ *   out = fl32((double)t_w - log_z_w) on F, -inf elsewhere;
+ *   count = { |V|; NaN or +inf cells; cells of V with g == -inf; cells of F with e_w == 0 (their mass underflowed) }.
+ *   F empty: log_z_s = -inf, E_s and Var_s NaN, out all -inf.
+ *   The caller's figures: log p_s(gt) = x_gt + lambda_s g_gt - log_z_s and its derivative in lambda, g_gt - E_s[g];
+ *   log_evidence_s = log_z_s - log_z_prior_s; log_overlap_s = log_evidence_s - log_z_votes; information_gain_s =
+ *   lambda_s E_s[g] - log_z_s + log_z_votes = KL(post_s || votes alone) >= 0; d log_z_s / d lambda = E_s[g] and
+ *   d2 log_z_s / d lambda^2 = Var_s[g].
+ * f32 is used for the cell's expressions above and for the sums of one pixel's <= R terms of e_s, of the prior's
+ * exponentials and of the votes' (each >= 0); e g and (e g) g enter their sums in float64 cell by cell, and everything
+ * above the pixel is float64.  Four launches of 256 threads: g into out, the maxima and the counts (one pixel per thread
+ * walks its R cells; the per-rotation table sits in LDS); the sums, ONE partial row per workgroup (g is read back from
+ * out: nothing is interpolated twice); the fold, one workgroup; out from (votes, g) in place.  No atomics and no hand-off
+ * between workgroups: every reduction order is fixed by (R, Ho, Wo, S), so two calls give the same bits.  Every element
+ * of out, table[0..S), stats and count is written by every call.
+ * Supported: 1 <= R <= 64, Ho, Wo >= 1, R*Ho*Wo < 2^31, X, Y >= 1, X*Y < 2^29, 1 <= S <= 8, 0 <= write < S, -1 <=
+ * gt_index < R*Ho*Wo; anything else returns SNAP_ERR_BAD_SHAPE before any launch (a NULL pointer other than votes
+ * SNAP_ERR_NULL, checked first; a raster that is not 16-byte aligned, with votes a scale that is not a finite number > 0,
+ * an outside that is NaN or +inf, a strength that is not a finite number > 0: SNAP_ERR_UNSUPPORTED; a short or not 8-byte
+ * aligned workspace SNAP_ERR_WORKSPACE).  workspace: snap_vote_raster_workspace_bytes() bytes (0 = unsupported shape); it
+ * needs no initialisation and no launch touches a byte beyond that size.  Asynchronous on `stream`; the caller owns
+ * every buffer. */
+size_t snap_vote_raster_workspace_bytes(int32_t R, int32_t Ho, int32_t Wo, int32_t X, int32_t Y, int32_t S);
+int snap_vote_raster_f32(const float* votes, int32_t R, int32_t Ho, int32_t Wo, float scale, const float* raster,
+                         int32_t X, int32_t Y, const int32_t* offsets, const float* planes, float outside,
+                         const float* strengths, int32_t S, int32_t write, int64_t gt_index, float* out, double* table,
+                         double* stats, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Most likely pose TRACK over vote volumes: one forward step of the max-product (Viterbi) recursion that goes with the
  * filter above, with back-pointers.  score_prev[R,Ho,Wo] f32 is the log score of the best path into every pose of the

@@ -1,6 +1,6 @@
 // Device and host pieces shared by the operators on the exhaustive vote volume (vote_peaks.hip, vote_posterior.hip,
 // vote_fuse.hip, vote_filter.hip, vote_smooth.hip, vote_pairs.hip, vote_viterbi.hip, vote_sample.hip, vote_refine.hip,
-// vote_credible.hip, vote_modes.hip, vote_recall.hip, vote_odometry.hip, vote_rebase.hip, vote_temper.hip, vote_prior.hip).  The family's
+// vote_credible.hip, vote_modes.hip, vote_recall.hip, vote_odometry.hip, vote_rebase.hip, vote_temper.hip, vote_prior.hip, vote_raster.hip).  The family's
 // contract is
 // "no floating-point atomics; every floating-point sum's order is a function of the shape alone; two calls give the
 // same bits"

@@ -316,5 +316,8 @@ from snap_amd.models.votes.frames import (  # noqa: E402,F401
     rebase_votes)
 from snap_amd.models.votes.temper import (  # noqa: E402,F401
     TemperatureFit, _hermite_root, _ladder_f32, fit_temperature, solve_temperature, temper_votes, temperature_ladder)
+from snap_amd.models.votes.raster import (  # noqa: E402,F401
+    RASTER_MAX_CONCENTRATION, RASTER_MAX_LOG_PRIOR, RASTER_MAX_OFFSET, RASTER_MAX_STRENGTHS, RasterPrior,
+    RasterStrengthFit, raster_prior, raster_prior_from_logits, raster_votes)
 from snap_amd.models.votes.tracks import VoteFilter, VoteViterbi, viterbi_track  # noqa: E402,F401
 from snap_amd.models.votes.localize import localize_exhaustive, localize_sequence  # noqa: E402,F401

@@ -8,6 +8,7 @@ every operator's kernel is a wrapper of ``snap_amd.ops``.  None of this has a co
 * ``sequence``: the stateless sequence operators (fuse, filter, smooth, pair statistics, sample, Viterbi step);
 * ``noise``: EM fit of the motion noise;  ``odometry``: the increment between two frames from their votes;
 * ``frames``: a change of map frame, and position / heading priors;  ``temper``: temperature ladders and calibration;
+* ``raster``: road / lane raster priors on the map grid, their strength ladder and its calibration;
 * ``tracks``: ``VoteFilter`` and ``VoteViterbi``, the stateful tracks over all of the above;
 * ``localize``: ``localize_exhaustive`` / ``localize_sequence``, voting followed by the analysis.
 

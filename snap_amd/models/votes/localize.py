@@ -5,12 +5,13 @@ from snap_amd.models.pose_exhaustive_voting import exhaustive_pose_voting
 from snap_amd.models.votes.analysis import (_modes_of_peaks, _with_posterior, credible_from_votes, poses_from_votes,
                                             recall_from_votes)
 from snap_amd.models.votes.frames import prior_votes
+from snap_amd.models.votes.raster import raster_votes
 from snap_amd.models.votes.refine import refine_poses
 from snap_amd.models.votes.sequence import fuse_votes
 
 
 def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, method=None, posterior=None,
-                        refine=None, credible=None, modes=None, recall=None, prior=None, **peaks):
+                        refine=None, credible=None, modes=None, recall=None, prior=None, raster=None, **peaks):
   """``exhaustive_pose_voting`` followed by ``poses_from_votes(**peaks)``: the dict of the latter plus ``votes``.
   ``['map_t_query'][0]`` is the single best pose.  ``posterior``: True, or a dict of keyword arguments of
   ``posterior_from_votes`` (``temperature``, ``m_t_q_gt``), adds its result as ``['posterior']``.  ``refine``: True,
@@ -24,18 +25,30 @@ def localize_exhaustive(plane_q, plane_map, num_rotations, grid, conf_q=None, me
   its result for the peaks already found as ``['recall']``.  ``prior``: a ``pose_prior`` (or a dict of keyword
   arguments of ``prior_votes`` with it under ``'prior'``: ``temperature``, ``m_t_q_gt``); the frame's votes then go
   through ``prior_votes`` BEFORE the peaks and everything else are taken: ``votes`` is the normalised product,
-  ``votes_frame`` the raw volume and ``['prior']`` the dict of ``prior_votes``."""
+  ``votes_frame`` the raw volume and ``['prior']`` the dict of ``prior_votes``.  ``raster``: a ``raster_prior`` (or a
+  dict of keyword arguments of ``raster_votes`` with it under ``'raster'``: ``temperature``, ``strength``,
+  ``m_t_q_gt``); the votes (the product with ``prior``, where both are given) go through ``raster_votes`` before the
+  peaks are taken: ``votes`` is the normalised product, ``votes_frame`` the raw volume and ``['raster']`` the dict of
+  ``raster_votes``."""
   votes = exhaustive_pose_voting(plane_q, plane_map, num_rotations, grid, conf_q=conf_q, method=method)
   fused = None
   if prior is not None:
     kw = dict(prior) if isinstance(prior, dict) else dict(prior=prior)
     fused = prior_votes(votes, kw.pop('prior'), grid, num_rotations, **kw)
     frame, votes = votes, fused['votes']
+  rastered = None
+  if raster is not None:
+    kw = dict(raster) if isinstance(raster, dict) else dict(raster=raster)
+    rastered = raster_votes(votes, kw.pop('raster'), grid, num_rotations, **kw)
+    frame, votes = (votes if fused is None else frame), rastered['votes']
   out = poses_from_votes(votes, grid, num_rotations, **peaks)
   out['votes'] = votes
   if fused is not None:
     out['votes_frame'] = frame
     out['prior'] = fused
+  if rastered is not None:
+    out['votes_frame'] = frame
+    out['raster'] = rastered
   _with_posterior(out, votes, grid, num_rotations, posterior)
   if refine is not None and refine is not False:
     kw = {} if refine is True else dict(refine)

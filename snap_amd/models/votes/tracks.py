@@ -13,6 +13,7 @@ from snap_amd.models.votes.frames import prior_votes, rebase_votes
 from snap_amd.models.votes.lattice import _linear_to_indices, _no_motion
 from snap_amd.models.votes.noise import NOISE_CANDIDATES, fit_motion_noise
 from snap_amd.models.votes.odometry import increment_from_votes
+from snap_amd.models.votes.raster import raster_votes
 from snap_amd.models.votes.sequence import (_entered_by_jump, _track_lists, filter_votes, sample_tracks, smooth_track,
                                             viterbi_votes)
 
@@ -141,6 +142,18 @@ class VoteFilter(_Track):
     a frame's stored belief is p(x_t | everything up to t), which now includes the fix.  ``step(votes)`` followed by
     ``apply_prior`` is the prior-times-votes start of a track.  Raises ValueError before the first step."""
     out = prior_votes(self._belief('apply_prior'), prior, self.grid, self.num_rotations, temperature=1.0)
+    self.belief = out['votes']
+    if getattr(self, 'history', None):
+      self.history[-1] = (out['votes'], self.history[-1][1])
+    return out
+
+  def apply_raster_prior(self, raster, strength=0):
+    """The measurement update of the belief the filter holds with a ``raster_prior`` (the map's drivable area and lane
+    directions): ``raster_votes(belief, raster, strength=strength)`` with temperature 1 (the belief is log-space and
+    normalised) -> its dict; the belief is replaced by the posterior at the ladder index ``strength``, and with a
+    history the belief of its last entry as well, as in ``apply_prior``.  Raises ValueError before the first step."""
+    out = raster_votes(self._belief('apply_raster_prior'), raster, self.grid, self.num_rotations, temperature=1.0,
+                       strength=strength)
     self.belief = out['votes']
     if getattr(self, 'history', None):
       self.history[-1] = (out['votes'], self.history[-1][1])

@@ -2680,6 +2680,85 @@ def prior_volume(votes, table, scale=1.0, device=None):
   return out, resp, stats, count
 
 
+def raster_volume(votes, raster, scale=1.0, write=0, gt_index=None, device=None):
+  """The wrapper of vote_raster.hip (its messages carry the operator's name, ``vote_raster:``; like ``prior_volume`` it
+  takes a host table and is not named ``vote_*``).  A road / lane raster prior fused into a vote volume or belief, over
+  a ladder of S strengths: votes [R, Ho, Wo] f32 (log-scores; -inf = masked) or None (the raster prior itself as a
+  belief, on ``device``), ``raster`` a host table with the attributes ``shape`` = (R, Ho, Wo), ``raster`` f32 [X, Y, 4] =
+  (A, C, S, valid), ``offsets`` int32 [R, 2], ``planes`` f32 [R, 4] = (f_a, f_b, cos, sin), ``outside`` (a float, finite
+  or -inf) and ``strengths`` [S] (> 0, 1 <= S <= 8) as numpy arrays (``pose_exhaustive_voting.raster_prior``);
+  ``write``: the ladder index whose posterior is returned; ``gt_index``: a flat cell index, None or -1 -> (out f32 [R,
+  Ho, Wo], table float64 [S, 4], stats float64 [4], count int32 [4]).  With g the raster's interpolated log-prior of a
+  cell and t_s = scale * votes + strengths[s] * g over the cells F with a finite vote and g > -inf: out = t_write - log_z
+  (-inf elsewhere); table[s] = (log_z_s, the log-sum-exp of strengths[s] * g over the lattice, E_s[g], Var_s[g]); stats
+  = (the log-sum-exp of scale * votes, scale * votes and g at gt_index, 0); count = (cells with a finite vote, NaN or
+  +inf cells, finite-vote cells the raster excludes, cells of F whose mass underflowed) (the full contract:
+  snap_vote_raster_f32 in include/snap_hip.h).  The table is uploaded once per device and kept with the ``raster``
+  object.  No host synchronisation."""
+  lib = _lib.load()
+  try:
+    shape = tuple(int(v) for v in raster.shape)
+    planes4, offsets, planes = raster.raster, raster.offsets, raster.planes
+    strengths = np.asarray(raster.strengths, dtype=np.float64).reshape(-1)
+    outside = float(raster.outside)
+    X, Y = int(planes4.shape[0]), int(planes4.shape[1])
+    ok = (len(shape) == 3 and planes4.dtype == np.float32 and offsets.dtype == np.int32 and planes.dtype == np.float32
+          and planes4.shape == (X, Y, 4) and X >= 1 and Y >= 1 and offsets.shape == (shape[0], 2)
+          and planes.shape == (shape[0], 4) and outside < np.inf)   # (NaN fails the comparison)
+  except (AttributeError, TypeError, ValueError, IndexError):
+    ok = False
+  if not ok:
+    raise ValueError('vote_raster: table with shape = (R, Ho, Wo), raster f32 [X, Y, 4], offsets int32 [R, 2], planes '
+                     f'f32 [R, 4], an outside that is finite or -inf and strengths [S] as numpy arrays, got {raster!r}')
+  S = int(strengths.size)
+  with np.errstate(over='ignore'):
+    lam = strengths.astype(np.float32)
+  if not (1 <= S <= 8 and bool(np.all(np.isfinite(lam))) and bool(np.all(lam > 0))):
+    raise ValueError(f'vote_raster: strengths must be 1 to 8 finite numbers > 0 as f32, got {strengths.tolist()}')
+  write = int(write)
+  if not 0 <= write < S:
+    raise ValueError(f'vote_raster: write must index the {S} strengths, got {write}')
+  if votes is None:
+    if device is None or torch.device(device).type != 'cuda':
+      raise ValueError(f'vote_raster: without votes a ROCm device must be named, got {device}')
+    dev = torch.device(device)
+    if dev.index is None:
+      dev = torch.device('cuda', torch.cuda.current_device())
+    scale = 1.0
+  else:
+    if _vote_volume_arg('vote_raster', votes, 'votes') != shape:
+      raise ValueError(f'vote_raster: the table was built for {shape}, votes are {tuple(votes.shape)}')
+    dev = votes.device
+    scale = _vote_scale('vote_raster', scale)
+  R, Ho, Wo = shape
+  n = R * Ho * Wo
+  gt = -1 if gt_index is None else int(gt_index)
+  if not -1 <= gt < n:
+    raise ValueError(f'vote_raster: gt_index must be None, -1 or a flat index below {n}, got {gt_index}')
+  words = _workspace_words(lib.snap_vote_raster_workspace_bytes, (R, Ho, Wo, X, Y, S), n,
+                           _vote_unsupported('vote_raster', R, Ho, Wo)[:-1] + f', X Y < 2^29; X={X} Y={Y})')
+  from snap_amd.models import base   # (the per-device constant cache lives there; base imports this module)
+
+  def make():   # one blob: the f32 raster (16-byte aligned at the front), the f32 planes, then the int32 offsets
+    raw = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in (planes4, planes, offsets)])
+    return torch.from_numpy(raw)
+  blob = base.device_const('vote_raster_table', dev, make, owner=raster)
+  nr, npl = planes4.nbytes, planes.nbytes
+  lam_c = (ctypes.c_float * S)(*lam.tolist())
+  ws = torch.empty((words,), dtype=torch.int64, device=dev)
+  out = torch.empty((R, Ho, Wo), dtype=torch.float32, device=dev)
+  table = torch.empty((S, 4), dtype=torch.float64, device=dev)
+  stats = torch.empty((4,), dtype=torch.float64, device=dev)
+  count = torch.empty((4,), dtype=torch.int32, device=dev)
+  # algorithmic bytes: one read and one write of the volume, one read of the raster
+  with _region('vote_raster', 0.0, 4.0 * n * (1 if votes is None else 2) + nr):
+    st = lib.snap_vote_raster_f32(_p(votes), R, Ho, Wo, scale, _p(blob), X, Y, _p(blob[nr + npl:]), _p(blob[nr:]),
+                                  outside, lam_c, S, write, gt, _p(out), _p(table), _p(stats), _p(count), _p(ws),
+                                  ws.numel() * 8, _stream())
+  _lib.check(st, 'snap_vote_raster_f32')
+  return out, table, stats, count
+
+
 def vote_fuse(volumes, shifts, weights=None):
   """Multi-frame fusion of aligned vote volumes: volumes [N, R, Ho, Wo] f32 (unnormalised log-scores; -inf = masked),
   shifts f32 [N, R, 3] = (dk, da, db) on the same device (``pose_exhaustive_voting.sequence_shift_table``), weights

@@ -1,6 +1,6 @@
 """Single-kernel micro-benchmarks at the C2 shapes (HIP-event timed; used for tuning and
 as the target of rocprofv3 --pmc passes).   python tools/kernel_bench.py pose_score [iters]
-(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4 | vote_odometry_c4 | vote_rebase_c4 | vote_temper_c4 | vote_prior_c4)
+(pose_score | pose_score_c4 | voting_c4 | vote_peaks_c4 | vote_posterior_c4 | vote_fuse_c4 | vote_filter_c4 | vote_smooth_c4 | vote_refine_c4 | vote_modes_c4 | vote_recall_c4 | vote_odometry_c4 | vote_rebase_c4 | vote_temper_c4 | vote_prior_c4 | vote_raster)
 """
 import math
 import os
@@ -772,6 +772,57 @@ def vote_prior_c4(iters):
   emit_json(res)
 
 
+def vote_raster(iters):
+  """A road / lane raster prior (256 x 256 cells) fused into the C4 vote volume (R = 36, 511 x 511, the low-overlap border
+  -inf): one whole ops.raster_volume call with S = 1 and S = 8 strengths, a centred sensor (one tap per cell) and an
+  off-centre one (four taps), each beside one whole ops.prior_volume call with M = 1 on the same volume, blocks
+  alternated, medians of single calls.  One JSON line; `json=<path>` as a third argument also writes it to that file."""
+  import numpy as np
+  from snap_amd.models import pose_exhaustive_voting as pev
+  from snap_amd.utils import grids
+  R, H, scale = 36, 256, 8.0
+  Ho = Wo = 2 * H - 1
+  grid = grids.Grid2D((H, H), 0.2)
+  g = torch.Generator(device='cuda').manual_seed(0)
+  votes = torch.randn((R, Ho, Wo), device='cuda', generator=g) * 0.25
+  ov = (H - (torch.arange(Ho, device='cuda') - (H - 1)).abs()).float()
+  votes = torch.where((ov[:, None] * ov[None, :] > 0.05 * H * H)[None], votes, float('-inf')).contiguous()
+  rng = np.random.default_rng(0)
+  gps = pev.pose_prior(grid, R, position=[27.0, 24.0], covariance=[[4.0, 1.0], [1.0, 9.0]], heading=0.3,
+                       concentration=4.0, sensor_q=[27.0, 24.9])
+  area = -6.0 * rng.random((H, H))
+  lanes = rng.uniform(-np.pi, np.pi, (H, H))
+  valid = rng.random((H, H)) > 0.02
+  ladders = {1: (1.0,), 8: tuple(2.0 ** (i - 4) for i in range(8))}
+  prior_call = lambda: ops.prior_volume(votes, gps, scale)
+  res = dict(case='vote_raster', shape=[R, Ho, Wo], raster=[H, H], scale=scale)
+  k = max(iters, 5)
+  for taps, sensor in ((1, None), (4, [27.0, 24.9])):
+    for S in (1, 8):
+      ras = pev.raster_prior(grid, R, log_area=area, valid=valid, heading=lanes, concentration=4.0, sensor_q=sensor,
+                             strengths=ladders[S])
+      assert int((ras.planes[:, :2] != 0).any(1).sum()) == (0 if taps == 1 else R)
+      call = lambda: ops.raster_volume(votes, ras, scale)
+      out, table, _, count = call()
+      lse = float(torch.logsumexp(out.double().reshape(-1), 0))
+      assert abs(lse) < 1e-3 and bool(torch.isfinite(table[:, 0]).all()), (lse, table)
+      (r_ms, rs), (p_ms, ps) = alternated_blocks(((call, 5, k), (prior_call, 5, k)))
+      nbytes = 8.0 * votes.numel() + ras.raster.nbytes
+      res[f'taps{taps}_S{S}'] = dict(
+          vote_raster_call_ms=round(r_ms, 4), vote_raster_call_ms_blocks=[round(v, 4) for v in rs],
+          vote_prior_M1_call_ms=round(p_ms, 4), vote_prior_M1_call_ms_blocks=[round(v, 4) for v in ps],
+          ratio_raster_to_prior_M1=round(r_ms / p_ms, 4), block_ranges_overlap=bool(max(ps) >= min(rs)),
+          raster_bytes_per_ms=round(nbytes / r_ms, 1), prior_bytes_per_ms=round(8.0 * votes.numel() / p_ms, 1),
+          cells_excluded_by_the_raster=int(count[2]),
+          workspace_bytes=int(ops._lib.load().snap_vote_raster_workspace_bytes(R, Ho, Wo, H, H, S)))
+  res['timing'] = ('whole wrapper calls (torch.empty outputs and workspace, the ctypes call, the four launches) between '
+                   'device events on an idle stream, NOT kernel time; median of single calls, 5 blocks of each '
+                   'alternated, median block; bytes_per_ms counts one read and one write of the volume (and one read of '
+                   'the raster) against the measured call time (the 37.6 MB volume fits the 256 MB Infinity Cache); no '
+                   'threshold is set on this case')
+  emit_json(res)
+
+
 if __name__ == '__main__':
   which = sys.argv[1] if len(sys.argv) > 1 else 'pose_score'
   iters = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -780,4 +831,4 @@ if __name__ == '__main__':
    'vote_filter_c4': vote_filter_c4, 'vote_smooth_c4': vote_smooth_c4,
    'vote_refine_c4': vote_refine_c4, 'vote_modes_c4': vote_modes_c4, 'vote_recall_c4': vote_recall_c4,
    'vote_odometry_c4': vote_odometry_c4, 'vote_rebase_c4': vote_rebase_c4, 'vote_temper_c4': vote_temper_c4,
-   'vote_prior_c4': vote_prior_c4}[which](iters)
+   'vote_prior_c4': vote_prior_c4, 'vote_raster': vote_raster}[which](iters)
