@@ -40,7 +40,7 @@ typedef enum SnapStatus {
 /* (snap_vote_prior_workspace_bytes / snap_vote_prior_f32 were ADDED at version 29 without a bump: an addition changes no
  * existing prototype, struct or constant, and a library built without them fails to load on the missing symbol.
  * snap_vote_raster_workspace_bytes / snap_vote_raster_f32 were added the same way.) */
-#define SNAP_ABI_VERSION 29   /* bump on any change to this header's prototypes, structs or constants */
+#define SNAP_ABI_VERSION 30   /* bump on any change to this header's prototypes, structs or constants */
 int snap_abi_version(void);                 /* SNAP_ABI_VERSION of the built library */
 const char* snap_status_string(int status);
 const char* snap_build_arch(void);          /* "gfx950" */
@@ -933,14 +933,16 @@ int snap_voting_fft_f32(const float* templates, const uint8_t* tvalid, const flo
 /* exhaustive_pose_voting (snap/models/pose_exhaustive_voting.py:107-124) in one call: the query plane
  * feat[H,H,D] (already multiplied by its confidence), valid[H,H], tfm[R/4,4] = (cos, sin, tx, ty) of
  * templates_t_grid for the first quadrant of rotations (:44-50), cell_size; map[Hm,Wm,D],
- * mvalid[Hm,Wm] -> scores[R, 3Hm-1-H, 3Wm-1-H] with min_overlap (0.05 in the reference).
+ * mvalid[Hm,Wm] -> scores[R, 3Hm-1-H, 3Wm-1-H]; overlap_threshold = min_overlap * H * H (0.05 in the reference)
+ * formed by the caller in double, as for snap_voting_fft_f32: an f32 min_overlap cannot carry the reference's
+ * rule (f32(0.02) * 400 < 8 = 0.02 * 400 in double: a count of 8 would pass).
  * sample_query_templates (:37-69) runs inside the first transform: template rows are interpolated on
  * the fly with the arithmetic of snap_rotate_templates_f32 (bit for bit), rotations R/4..R-1 are rot90
  * index maps; the [R,H,H,D] template tensor is never written.  R % 4 == 0, square query plane.
  * workspace: snap_voting_fft_workspace_bytes(R, H, H, D, Hm, Wm). */
 int snap_voting_fft_rotated_f32(const float* feat, const uint8_t* valid, const float* tfm,
                                 float cell_size, const float* map, const uint8_t* mvalid, int32_t R,
-                                int32_t H, int32_t D, int32_t Hm, int32_t Wm, float min_overlap,
+                                int32_t H, int32_t D, int32_t Hm, int32_t Wm, float overlap_threshold,
                                 void* workspace, size_t workspace_bytes, float* scores, void* stream);
 
 /* raw[Ho,Wo,Rp], cnt[Ho,Wo,Rp] (engine outputs) -> scores[R,Ho,Wo]:

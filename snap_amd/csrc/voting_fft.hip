@@ -179,8 +179,8 @@ extern "C" int snap_voting_fft_f32(const float* templates, const uint8_t* tvalid
 extern "C" int snap_voting_fft_rotated_f32(const float* feat, const uint8_t* valid, const float* tfm,
                                            float cell_size, const float* map, const uint8_t* mvalid,
                                            int32_t R, int32_t H, int32_t D, int32_t Hm, int32_t Wm,
-                                           float min_overlap, void* workspace, size_t workspace_bytes,
-                                           float* scores, void* stream) {
+                                           float overlap_threshold, void* workspace,
+                                           size_t workspace_bytes, float* scores, void* stream) {
   if (!feat || !valid || !tfm || !map || !mvalid || !workspace || !scores) return SNAP_ERR_NULL;
   if (R <= 0 || R % 4 != 0 || H <= 0 || D <= 0 || Hm <= 0 || Wm <= 0) return SNAP_ERR_BAD_SHAPE;
   vfft::Geometry g;
@@ -201,8 +201,7 @@ extern "C" int snap_voting_fft_rotated_f32(const float* feat, const uint8_t* val
                      tcount);
   SNAP_CHECK_LAUNCH();
   HipLaunch L{s};
-  if (!vfft::run_voting(g, nullptr, tvalid, map, mvalid, tcount, min_overlap * (float)H * (float)H, 1, ws, scores,
-                        L, &rs))
+  if (!vfft::run_voting(g, nullptr, tvalid, map, mvalid, tcount, overlap_threshold, 1, ws, scores, L, &rs))
     return SNAP_ERR_LAUNCH;
   return SNAP_OK;
 }

@@ -207,8 +207,8 @@ def template_matching(q, q_valid, m, m_valid, do_padding=True, min_overlap=0.05,
   return _match(None, cw, tcount, R, (H, W), m, m_valid, min_overlap, templates=q.contiguous())
 
 
-def exhaustive_pose_voting(plane_q, plane_map, num_rotations, grid, conf_q=None, method=None):
-  """pose_exhaustive_voting.py:107-124 -> scores [R, 2H-1, 2W-1]."""
+def exhaustive_pose_voting(plane_q, plane_map, num_rotations, grid, conf_q=None, method=None, min_overlap=0.05):
+  """pose_exhaustive_voting.py:107-124 -> scores [R, 2H-1, 2W-1] (``min_overlap``: 0.05 in the reference)."""
   feats_q = plane_q.features
   if conf_q is not None:
     feats_q = feats_q * conf_q[..., None]
@@ -224,11 +224,11 @@ def exhaustive_pose_voting(plane_q, plane_map, num_rotations, grid, conf_q=None,
     tfm = _template_transforms(num_rotations, grid, feats_q.device)[: num_rotations // 4].contiguous()
     return ops.voting_fft_rotated(feats_q.contiguous(), plane_q.valid.contiguous(), tfm, grid.cell_size,
                                   plane_map.features.contiguous(), plane_map.valid.contiguous(),
-                                  num_rotations, 0.05)
+                                  num_rotations, min_overlap)
   templates, tvalid, tw, cw, tcount = sample_query_templates(
       feats_q, plane_q.valid, num_rotations, grid, _engine=True
   )
-  return _match(tw, cw, tcount, num_rotations, (H, W), plane_map.features, plane_map.valid, 0.05,
+  return _match(tw, cw, tcount, num_rotations, (H, W), plane_map.features, plane_map.valid, min_overlap,
                 templates=templates)
 
 

@@ -2209,7 +2209,7 @@ def voting_fft_rotated(feat, valid, tfm, cell_size, m, mvalid, num_rotations, mi
   scores = torch.empty((R, 3 * Hm - 1 - H, 3 * Wm - 1 - H), dtype=torch.float32, device=feat.device)
   with _region('voting_fft', flops=0.0, nbytes=4.0 * (R * feat.numel() + m.numel() + scores.numel())):
     st = lib.snap_voting_fft_rotated_f32(
-        _p(feat), _p(valid), _p(tfm), float(cell_size), _p(m), _p(mvalid), R, H, D, Hm, Wm, float(min_overlap),
+        _p(feat), _p(valid), _p(tfm), float(cell_size), _p(m), _p(mvalid), R, H, D, Hm, Wm, float(min_overlap * H * H),
         _p(ws), nbytes, _p(scores), _stream())
   _lib.check(st, 'snap_voting_fft_rotated_f32')
   return scores

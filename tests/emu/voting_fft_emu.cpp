@@ -100,7 +100,7 @@ extern "C" int emu_voting_fft_f32(const float* templates, const uint8_t* tvalid,
 
 extern "C" int emu_voting_fft_rotated_f32(const float* feat, const uint8_t* valid, const float* tfm, float cell,
                                           const float* map, const uint8_t* mvalid, int R, int H, int D, int Hm,
-                                          int Wm, float min_overlap, void* ws_, float* scores, int nt) {
+                                          int Wm, float thr, void* ws_, float* scores, int nt) {
   vfft::Geometry g;
   if (!vfft::make_geometry(R, H, H, D, Hm, Wm, &g)) return -2;
   char* ws = static_cast<char*>(ws_);
@@ -115,6 +115,5 @@ extern "C" int emu_voting_fft_rotated_f32(const float* feat, const uint8_t* vali
       for (int k = 0; k < 4; ++k) tcount[k * RQ + r0] += 1.f;
   }
   EmuLaunch L{nt};
-  return vfft::run_voting(g, nullptr, tvalid, map, mvalid, tcount, min_overlap * (float)H * (float)H, 1, ws, scores,
-                          L, &rs) ? 0 : -4;
+  return vfft::run_voting(g, nullptr, tvalid, map, mvalid, tcount, thr, 1, ws, scores, L, &rs) ? 0 : -4;
 }

@@ -1471,12 +1471,14 @@ def test_rotate_templates_and_matching(H, R, D, method):
   assert full.shape == (R, 2 * H - 1, 2 * H - 1)
 
 
-@pytest.mark.parametrize('H,R,D', [(100, 8, 16), (86, 12, 32), (64, 4, 8)])
-def test_voting_fft_rotated_entry_equals_the_explicit_templates(H, R, D):
+@pytest.mark.parametrize('H,R,D,min_overlap', [(100, 8, 16, 0.05), (86, 12, 32, 0.05), (64, 4, 8, 0.05), (20, 8, 4, 0.02)],
+                         ids=['100-8-16', '86-12-32', '64-4-8', '20-8-4-0.02'])
+def test_voting_fft_rotated_entry_equals_the_explicit_templates(H, R, D, min_overlap):
   """The rotated entry of the frequency-domain voting (templates sampled inside the first transform, masks + counts
   from the tiled validity pass: 64 x 64 tiles, here with partial tiles and several tiles per side) against the
   explicit-template entry fed with ``sample_query_templates`` (the stand-alone rotate kernel's templates and masks):
-  the same -inf mask and the same scores."""
+  the same -inf mask and the same scores.  (0.02, 20): 0.02 x 20 x 20 = 8 in double, 7.9999995 as an f32 chain of
+  products -- both entries must hold a count of 8 below the threshold.)"""
   from snap_amd.models import pose_exhaustive_voting as pev
   from snap_amd.models import types
   from snap_amd.utils import grids
@@ -1487,8 +1489,9 @@ def test_voting_fft_rotated_entry_equals_the_explicit_templates(H, R, D):
   vm = torch.tensor(rng.random((H, H)) > 0.1).to(DEV)
   g = grids.Grid2D((H, H), 0.25)
   t, tv = pev.sample_query_templates(fq, vq, R, g)
-  want = pev.template_matching(t, tv, fm, vm, method='fft')
-  got = pev.exhaustive_pose_voting(types.FeaturePlane(fq, vq), types.FeaturePlane(fm, vm), R, g, method='fft')
+  want = pev.template_matching(t, tv, fm, vm, min_overlap=min_overlap, method='fft')
+  got = pev.exhaustive_pose_voting(types.FeaturePlane(fq, vq), types.FeaturePlane(fm, vm), R, g, method='fft',
+                                   min_overlap=min_overlap)
   fw, fg = torch.isfinite(want), torch.isfinite(got)
   assert torch.equal(fw, fg), int((fw != fg).sum())
   assert 0 < int(fw.sum()) < fw.numel()

@@ -133,7 +133,7 @@ def test_abi_constants():
   assert (_lib.SNAP_TUNE_NO_HALO, _lib.SNAP_TUNE_NO_PLAIN, _lib.SNAP_TUNE_RS_NSPLIT_SHIFT) == (1, 8, 4)
   assert (_lib.SNAP_MATH_F32, _lib.SNAP_MATH_BF16, _lib.SNAP_MATH_F16) == (0, 1, 2)
   assert (_lib.SNAP_OK, _lib.SNAP_ERR_BAD_SHAPE, _lib.SNAP_ERR_WORKSPACE) == (0, -1, -5)
-  assert _lib.ABI_VERSION == 29
+  assert _lib.ABI_VERSION == 30
 
 
 @pytest.mark.parametrize('text', [
@@ -787,7 +787,7 @@ def test_voting_fft_rotated_entry_on_the_cpu_emulation():
     out = np.full((R, 2 * H - 1, 2 * H - 1), np.nan, np.float32)
     vqb, vmb = vq.astype(np.uint8), vm.astype(np.uint8)
     rc = lib.emu_voting_fft_rotated_f32(fq.ctypes.data, vqb.ctypes.data, tfm.ctypes.data, cell, fm.ctypes.data,
-                                        vmb.ctypes.data, R, H, D, H, H, 0.05, ws.ctypes.data + off,
+                                        vmb.ctypes.data, R, H, D, H, H, 0.05 * H * H, ws.ctypes.data + off,
                                         out.ctypes.data, 32)
     assert rc == 0
     fin = np.isfinite(want)
