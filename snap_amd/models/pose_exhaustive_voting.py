@@ -72,7 +72,9 @@ def sample_query_templates(features, valid, num_rotations, grid, _engine=False):
 # Shift-stacking factor of the correlation GEMM (0 / 1 = plain direct form).  With R = 36 templates
 # the GEMM has 36 output columns -- 56 % of a 64-wide MFMA tile; stacking the S x S shifted copies
 # of every template as extra filters (and striding the correlation by S) gives R S^2 = 576 columns
-# = 9 full tiles for 2.4 % more multiply-adds: the same products, summed in the same k order.
+# = 9 full tiles for 2.4 % more multiply-adds: the same products in the same tap order, with the zero products of
+# the shifted copies in between -- the k-steps and the split-K partition fall elsewhere, so the sums agree with the
+# plain form's to rounding (both within tests/voting_direct_reference.py's bound), not bit for bit.
 STACK_SHIFT = 4
 STACK_MIN_CELLS = 64 * 64      # below this the plain form is already launch-bound
 # 'auto': the frequency-domain form from FFT_MIN_CELLS map cells on (below, the direct form is a
@@ -80,8 +82,12 @@ STACK_MIN_CELLS = 64 * 64      # below this the plain form is already launch-bou
 # Two behaviours of the frequency-domain form differ from the direct form and are why 'direct' stays
 # selectable: (1) the transforms are GLOBAL -- one NaN / Inf anywhere in the map features (valid cell or
 # not: the reference does not mask them out of the scores either) or in the query plane makes every
-# score of every rotation NaN, where the direct form poisons only the placements that overlap the bad
-# cell; (2) its workspace grows with R * D * N^2 (0.9 GB of first-axis spectra at R = 36, 256^2, D = 32):
+# score of every rotation NaN, where the direct form poisons only placements near the bad cell: on the plain route
+# (below STACK_MIN_CELLS) exactly those whose H x W window covers it; on the shift-stacked routes those whose WIDENED
+# (H + S - 1) x (W + S - 1) window, anchored at (S floor(a / S), S floor(b / S)), covers it -- up to S - 1 cells
+# further, since the stacked bank holds zeros outside each shifted copy and 0 x NaN = NaN.  A bad TEMPLATE cell
+# poisons its own rotation alone on every route; (2) its workspace grows with R * D * N^2 (0.9 GB of first-axis
+# spectra at R = 36, 256^2, D = 32):
 # 'auto' falls back to the direct form beyond FFT_WORKSPACE_BUDGET bytes.
 VOTING_METHOD = 'auto'
 FFT_MIN_CELLS = 64 * 64
@@ -108,6 +114,15 @@ def _stacked(R, q_hw):
   return S > 1 and q_hw[0] * q_hw[1] >= STACK_MIN_CELLS and (R * S * S) % 4 == 0
 
 
+def _conv_columns(x, w, R):
+  """``ops.conv2d(x, w)[0]`` for a bank of R filters.  The engines take whole column quads: explicit templates
+  with R % 4 != 0 (``rotate_templates`` never writes such a bank) get zero filters up to the next quad, cut off again."""
+  if R % 4 == 0:
+    return ops.conv2d(x, w)[0]
+  w = torch.nn.functional.pad(w, (0, -R % 4)).contiguous()
+  return ops.conv2d(x, w)[0][..., :R].contiguous()
+
+
 def _correlate(mp, tw, R, q_hw, templates=None):
   """``tw`` [H,W,D,R] and / or ``templates`` [R,H,W,D]: the same filter bank in two layouts."""
   H, W = q_hw
@@ -116,7 +131,7 @@ def _correlate(mp, tw, R, q_hw, templates=None):
   if not _stacked(R, q_hw):
     if tw is None:
       tw = templates.permute(1, 2, 3, 0).contiguous()
-    return ops.conv2d(mp[None], tw)[0]                  # [Ho, Wo, R]
+    return _conv_columns(mp[None], tw, R)               # [Ho, Wo, R]
   A4, B4 = -(-Ho // S), -(-Wo // S)
   pb = max(0, S * (A4 - 1) + (H + S - 1) - mp.shape[0])  # zero rows only cropped outputs can see
   pr = max(0, S * (B4 - 1) + (W + S - 1) - mp.shape[1])
@@ -134,7 +149,9 @@ def _correlate(mp, tw, R, q_hw, templates=None):
     # the correlation as ONE large GEMM on the pre-split engine: the map is split into its two
     # bf16 parts once (instead of once per tap and column tile inside the K loop), both operands
     # travel by LDS-DMA, 256 x 192 tiles (R S^2 = 576 = three column tiles); same products, same
-    # k order, same bits as the split engine's im2col body.  Template banks beyond the engine's
+    # k order as the split engine's im2col body (bit for bit only where that launch partitions the sum alike: at the
+    # voting's shapes -- few rows, deep K -- the two agree to rounding, tests/test_gpu_voting_direct.py).  Template
+    # banks beyond the engine's
     # 32-bit offsets (matching_dim 64 at 256^2, queries of ~360^2 cells) keep the plain-input
     # launch below, which drops to the f32 engine where the split weight image does not fit
     raw4 = ops.conv2d(ops.presplit(mp[None]), tws, stride=S, padding=((0, pb), (0, pr)), ps_tile=3)[0]
@@ -156,7 +173,7 @@ def _overlap_count(mvp, cw, R, q_hw):
   most H W < 2^24 of them, so the result is the same integers."""
   H, W = q_hw
   if not _stacked(R, q_hw) or W % 32:
-    return ops.conv2d(mvp[None, :, :, None].contiguous(), cw)[0]
+    return _conv_columns(mvp[None, :, :, None].contiguous(), cw, R)
   Hp, Wp = mvp.shape
   Ho, Wo = Hp - H + 1, Wp - W + 1
   nbq = -(-Wo // 32)                       # output column groups

@@ -401,7 +401,8 @@ def planted(g):
     vq, vm = 2.0 ** (r - 3), -(2.0 ** (2 - r)) if r % 2 else 2.0 ** (2 - r)
     q[r, i0, j0, r] = vq; m[u, v, r] = vm
     (a0, a1), (b0, b1) = span(u, Hm, i0, geo['Ho']), span(v, Wm, j0, geo['Wo'])
-    want[r, a0:a1 + 1, b0:b1 + 1] = vq * vm / PLANT_TCOUNT
+    if a1 >= a0 and b1 >= b0:       # (a template cell beyond every replica of the map cell: no placement pairs them)
+      want[r, a0:a1 + 1, b0:b1 + 1] = vq * vm / PLANT_TCOUNT
     cells.append((r, (i0, j0), (u, v)))
   return q, m, want, cells
 
